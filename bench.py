@@ -5,17 +5,19 @@ A "step" is one full sort (all D passes of the hot path) of one batch of synthet
 input already resident in HBM.  K steps sort K different pre-generated batches, so
 every timed sort sees unsorted data and generation stays outside the timed region.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--full] [--dump-outputs DIR]
   N > 1: either under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...`
   (one rank per GPU; RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment) or typed plainly: the parent
   process then starts exactly that launcher as a child BEFORE it touches the GPU, relays rank 0's JSON line and
   exits with the launcher's return code.
 
-Prints ONE JSON line on rank 0 (contract in the round prompt): `value` = Gkeys/s of the
-whole job; `roofline` = dominant kernel (rsx_sweep_kernel, one launch = one pass,
+Prints ONE JSON line on rank 0: `value` = Gkeys/s of the whole job, `ms_per_step` = ms of
+one timed step; `roofline` = dominant kernel (rsx_sweep_kernel, one launch = one pass,
 algorithmic bytes 2*n*s per launch) timed with HIP events on its own launch stream over
-the timed region; `cpu_baseline` = the oracle (thread-parallel C restatement of the
-reference, oracle/rsx_oracle.c) timed on this host's cores on a bounded sample.
+the timed region.  A plain run measures the headline workload only.  `--full` adds the
+other workloads under `extra` and `cpu_baseline` = the oracle (thread-parallel C restatement
+of the reference, oracle/rsx_oracle.c) timed on this host's cores on a bounded sample.
+`--dump-outputs DIR` writes a seeded sample of the last timed step's sorted array (dump_outputs).
 """
 from __future__ import annotations
 
@@ -81,8 +83,9 @@ def gen_id(rs, name):
             "reversed": rs.GEN_REVERSED}[name]
 
 
-def run_single(rs, torch, ctx, wl, steps, warmup, seed0=0x5EED0000, profile=True, check=True):
-    """Times `steps` sorts of `steps` different batches on the current device. Returns dict."""
+def run_single(rs, torch, ctx, wl, steps, warmup, seed0=0x5EED0000, profile=True, check=True, dump_dir=None):
+    """Times `steps` sorts of `steps` different batches on the current device. Returns dict.
+    `dump_dir`: the last timed step's output goes there (dump_outputs)."""
     t, logn, gen, param, _ = WORKLOADS[wl]
     d = digits_for(rs, t)
     n = 1 << logn
@@ -134,6 +137,8 @@ def run_single(rs, torch, ctx, wl, steps, warmup, seed0=0x5EED0000, profile=True
     ctx.verify_device(bufs[k - 1].data_ptr(), n, d, out.data_ptr(), stream)
     v = out.cpu().tolist()
     assert not check or (v[0] == 0 and v[2] == 0), f"bench output not sorted/stable: {v}"
+    if dump_dir:
+        dump_outputs(torch, dump_dir, bufs[k - 1], n, d.elem_bytes)
     del bufs, tmp
     torch.cuda.empty_cache()
     ms = total_ms / steps
@@ -168,6 +173,33 @@ def run_single(rs, torch, ctx, wl, steps, warmup, seed0=0x5EED0000, profile=True
             res["count16_ms_per_sort"] = prof_tot["hist"][0] / steps
             res["scan16_ms_per_sort"] = prof_tot["scan"][0] / steps
     return res
+
+
+DUMP_BUDGET_BYTES = 32 << 20  # all files of one --dump-outputs together
+DUMP_SEED = 0xD0D0
+
+
+def dump_outputs(torch, out_dir, buf, n, elem_bytes, prefix="", budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: the sorted array `buf` (n elements of elem_bytes bytes, on the device) as
+    `<prefix>sorted.npy`, one row per element: the element's bytes as little-endian 32-bit words in float64
+    (16-bit or 8-bit words in float32 when the element size is not a multiple of 4), so every value is exact.
+    Arrays larger than `budget` are sampled at fixed positions (DUMP_SEED; the first and the last element
+    always in); `<prefix>index.npy` (float64) holds the positions, ascending."""
+    import numpy as np
+    w = 4 if elem_bytes % 4 == 0 else 2 if elem_bytes % 2 == 0 else 1
+    wdt, fdt = {4: ("<u4", np.float64), 2: ("<u2", np.float32), 1: ("u1", np.float32)}[w]
+    row_bytes = elem_bytes // w * np.dtype(fdt).itemsize + 8  # + the position
+    m = min(n, max(2, budget // row_bytes))
+    if m == n:
+        pos = np.arange(n, dtype=np.int64)
+    else:
+        rng = np.random.default_rng(DUMP_SEED)
+        pos = np.unique(np.concatenate([[0, n - 1], rng.integers(0, n, size=m - 2, dtype=np.int64)]))
+    rows = buf.reshape(-1)[: n * elem_bytes].view(n, elem_bytes).index_select(0, torch.from_numpy(pos).to(buf.device)).cpu().numpy()
+    words = np.ascontiguousarray(rows).view(wdt).reshape(len(pos), elem_bytes // w)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, prefix + "sorted.npy"), words.astype(fdt))
+    np.save(os.path.join(out_dir, prefix + "index.npy"), pos.astype(np.float64))
 
 
 def _host_batch(np, n, es, kb, salt):
@@ -301,12 +333,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS),
                     help="default: c3-1b-u64 (configs[2], the largest single-GPU configuration) at N=1 and per GPU at N>1 (weak scaling)")
-    ap.add_argument("--extra", default=",".join(EXTRA_DEFAULT),
-                    help="comma list of further workloads measured with the same --steps/--warmup and reported under 'extra' at N=1; '' = none")
-    ap.add_argument("--extra-sharded", default="c4-slice-512m-u32",
-                    help="N>1: comma list of further per-GPU workloads reported under 'extra' (default: the configs[3] slice, "
-                         "2^29 u32 per GPU = 4B keys at N=8); '' = none")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure the --extra (N=1) or --extra-sharded (N>1) workloads and the CPU "
+                         "baseline (N=1); a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's sorted array (a seeded sample of at most 32 MB) as DIR/*.npy; "
+                         "N>1: each rank's slice, files prefixed rank<r>_")
+    ap.add_argument("--extra", default=None,
+                    help="comma list of further workloads measured with the same --steps/--warmup and reported under 'extra' at N=1 "
+                         "(default: none, with --full: %s); '' = none" % ",".join(EXTRA_DEFAULT))
+    ap.add_argument("--extra-sharded", default=None,
+                    help="N>1: comma list of further per-GPU workloads reported under 'extra' (default: none, with --full: the "
+                         "configs[3] slice c4-slice-512m-u32, 2^29 u32 per GPU = 4B keys at N=8); '' = none")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="N>1 collectives: nccl (= RCCL over xGMI, the measured path); gloo only to rehearse the N>1 code "
                          "path on a box with fewer GPUs than ranks (ranks then share devices, exchange staged through the host)")
@@ -323,8 +362,14 @@ def main():
     ap.add_argument("--cpu-ladder", action="store_true",
                     help="N=1: also time the reference's CPU ladder radix_sort0..5 (oracle restatement) on this host: extra.cpu_ladder")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.workload is None:
         args.workload = HEADLINE  # N > 1: the same configuration per GPU (weak scaling of the N = 1 line)
+    if args.extra is None:
+        args.extra = ",".join(EXTRA_DEFAULT) if args.full else ""
+    if args.extra_sharded is None:
+        args.extra_sharded = "c4-slice-512m-u32" if args.full else ""
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # typed plainly: start the N ranks as fresh children (nothing in this process has touched the GPU: no
@@ -355,7 +400,7 @@ def main():
     n = 1 << logn
 
     if world == 1:
-        res = run_single(rs, torch, ctx, args.workload, args.steps, args.warmup)
+        res = run_single(rs, torch, ctx, args.workload, args.steps, args.warmup, dump_dir=args.dump_outputs)
         ms = res["ms_per_sort"]
         line = {
             "metric": "Gkeys/sec (u32)" if t == "u32" else f"Gkeys/sec ({t})",
@@ -391,7 +436,7 @@ def main():
             extra["cpu_ladder"] = cpu_ladder()
         if extra:
             line["extra"] = extra
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(t if t in ("u32", "u64", "(u64,u64)", "(u32,u32)") else "u32", n)
         print(json.dumps(line), flush=True)
         return
@@ -409,7 +454,7 @@ def main():
     cdev = "cuda" if args.backend == "nccl" else "cpu"
     state = {"exchange": args.exchange, "note": ""}
 
-    def run_sharded(wl):
+    def run_sharded(wl, dump_dir=None):
         t, logn, gen, param, desc = WORKLOADS[wl]
         d = digits_for(rs, t)
         n = 1 << logn
@@ -476,6 +521,9 @@ def main():
         # untimed global check of the last batch (ShardedRadixSort.verify): every rank's slice in order and stable,
         # the multiset unchanged (checksums all-reduced), the last key of rank r <= the first key of rank r + 1
         sorter.verify(bufs[k - 1], d, sum_before)
+        if dump_dir:
+            dump_outputs(torch, dump_dir, bufs[k - 1], bufs[k - 1].numel() // d.elem_bytes, d.elem_bytes,
+                         prefix=f"rank{rank}_", budget=DUMP_BUDGET_BYTES // world)
         del bufs
         torch.cuda.empty_cache()
         ms = el.item() * 1e3 / args.steps
@@ -484,7 +532,7 @@ def main():
                 "gkeys_per_s": total / ms / 1e6, "algorithmic_gbps": d.key_bytes * 2 * total * d.elem_bytes / ms / 1e6,
                 "branch": sorter.last_branch + ("; " + state["note"] if state["note"] else ""), "exchange": state["exchange"]}
 
-    r = run_sharded(args.workload)
+    r = run_sharded(args.workload, dump_dir=args.dump_outputs)
     extra = {}
     for wl in [w for w in args.extra_sharded.split(",") if w and w != args.workload]:
         try:
