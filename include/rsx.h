@@ -47,13 +47,42 @@ enum {
 };
 
 /* Element descriptor: what `T: RadixDigits` means to the device.
- *   elem_bytes  size_of::<T>()            (1,2,4,8,12,16,24,32 have kernels)
+ *   elem_bytes  size_of::<T>(), 1 .. RSX_MAX_ELEM_BYTES
  *   key_offset  byte offset of the key inside the element (0 for primitives;
- *               offset_of!((K,U), 0) for tuples, radix_digits.rs:126-136)
- *   key_bytes   1,2,4,8,16 == T::NUMBER_OF_DIGITS (8-bit digits, LSB first)
+ *               offset_of!((K,U), 0) for tuples, radix_digits.rs:126-136);
+ *               key_offset + key_bytes <= elem_bytes
+ *   key_bytes   T::NUMBER_OF_DIGITS (8-bit digits, LSB first): 1 .. 16 for
+ *               RSX_KEY_UNSIGNED / RSX_KEY_SIGNED (a signed key of k bytes is the
+ *               k-byte two's-complement integer), 4 or 8 for RSX_KEY_FLOAT
  *   key_kind    RSX_KEY_*
  * Elements are moved bitwise (mod.rs:133-140 uses copy_nonoverlapping), so any
- * payload -- padding included -- is carried unchanged. */
+ * payload -- padding included -- is carried unchanged.
+ *
+ * Any layout.  Element sizes 1,2,4,8,12,16,24,32 with key widths 1,2,4,8,16 have
+ * sort kernels of their own ("direct" layouts; d_data and d_tmp aligned to the
+ * element's natural alignment: 1, 2, 4 for 4 and 12 bytes, 8 for 8 and 24, 16
+ * for 16 and 32).  rsx_sort_device, rsx_sort_host and rsx_ctx_reserve take every
+ * other layout above too and hand it to those kernels through a CANONICAL key:
+ * the key moved to offset 0 and widened to the next of 1,2,4,8,16 bytes (zero-
+ * or sign-extended).  The route (RSX_INFO_LAST_PASSES bits 28-29):
+ *   1 packed re-layout, when the canonical key plus the other elem_bytes -
+ *     key_bytes bytes fit 16: the elements are re-laid out into a workspace array
+ *     of n*s' bytes (s' that sum rounded up to 4, 8, 12 or 16), sorted there
+ *     with a second array of n*s' bytes as ping-pong, and restored into d_data;
+ *     d_tmp is not used;
+ *   2 key-index proxy, for larger elements: (canonical key, u32 position)
+ *     proxies of p = 8 (keys up to 4 bytes), 16 (up to 8) or 32 bytes are
+ *     sorted in two workspace arrays of n*p bytes, and d_data[i] =
+ *     d_tmp[proxy[i].position] after the elements were copied into d_tmp; n must
+ *     be below 2^32 (RSX_ERR_UNSUPPORTED otherwise).
+ * The workspace of a route is the context's (2*n*s' or 2*n*p bytes, each array
+ * rounded up to 256 bytes, beside the direct sort's own), made on first use or by
+ * rsx_ctx_reserve(n, layout); such layouts need only 1-byte alignment of d_data
+ * and d_tmp, may overwrite d_tmp, and leave every byte outside the n elements
+ * as it was.  Results are bit-exact with the stable sort by mapped key.  The
+ * other entry points (histogram, partition*, bounds*, splitter*, sort_sharded*)
+ * take direct layouts only; rsx_generate_device and rsx_verify_device take any. */
+#define RSX_MAX_ELEM_BYTES 32768u
 typedef struct rsx_layout {
     uint32_t elem_bytes;
     uint32_t key_offset;
@@ -141,7 +170,10 @@ enum {
                                  placement verified (status words of single-XCD chains stay in L2), bits 24-27 the
                                  path: 0 general passes, 1 one-launch sort of at most one tile, 2 middle-size bucket
                                  split, 3 one-byte counting, 4 two-byte counting, 5 wide-key hybrid (two sweeps + the
-                                 16-bit buckets in LDS; a hybrid the device refused reports 0 and its D passes) */
+                                 16-bit buckets in LDS; a hybrid the device refused reports 0 and its D passes),
+                                 bits 28-29 the route of a layout without kernels of its own: 0 direct, 1 packed
+                                 re-layout, 2 key-index proxy (bits 0-27 then describe the sort of the re-laid-out
+                                 elements / of the proxies) */
 };
 int rsx_ctx_get_info(rsx_ctx *ctx, int what, uint64_t *out);
 /* Per-launch timing with HIP events on the launch stream (measurement only).

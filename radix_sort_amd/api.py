@@ -91,8 +91,8 @@ def digits_of(dtype) -> RadixDigits:
         name0 = dt.names[0]
         kdt, koff = dt.fields[name0][0], dt.fields[name0][1]
         if kdt.kind not in _NP_KIND or kdt.itemsize not in (1, 2, 4, 8):
-            if kdt.kind == "V" and kdt.itemsize == 16:  # u128 key stored as 16 raw bytes
-                return RadixDigits(dt.itemsize, koff, 16, KEY_UNSIGNED)
+            if kdt.kind == "V" and not kdt.fields and 1 <= kdt.itemsize <= 16:  # V1..V16: unsigned key of that width
+                return RadixDigits(dt.itemsize, koff, kdt.itemsize, KEY_UNSIGNED)  # (V16: u128 stored as 16 raw bytes)
             raise TypeError(f"unsupported key field dtype {kdt}")
         return RadixDigits(dt.itemsize, koff, kdt.itemsize, _NP_KIND[kdt.kind])
     if dt.kind in _NP_KIND and dt.itemsize in (1, 2, 4, 8):
@@ -246,6 +246,23 @@ def _torch_digits(t, digits: Optional[RadixDigits]) -> RadixDigits:
     return PRIMITIVES[m[t.dtype]]
 
 
+_KERNEL_SIZES = (1, 2, 4, 8, 12, 16, 24, 32)
+
+
+def _check_element_stated(shape, itemsize: int, d: RadixDigits):
+    """Element sizes and key widths with sort kernels of their own may be read from any buffer of packed elements.
+    Any other layout (include/rsx.h, "Any layout") is sorted from an array that states its element: a dtype of
+    elem_bytes bytes (numpy structured or void dtype), or a last dimension of elem_bytes bytes ((n, elem_bytes)
+    uint8).  A flat byte buffer with such a descriptor is refused, as before those layouts could be sorted."""
+    if d.elem_bytes in _KERNEL_SIZES and d.key_bytes in (1, 2, 4, 8, 16):
+        return
+    if itemsize == d.elem_bytes or (len(shape) >= 2 and shape[-1] * itemsize == d.elem_bytes):
+        return
+    raise RsxError(_lib.ERR_UNSUPPORTED,
+                   f"{d.elem_bytes}-byte elements with {d.key_bytes}-byte keys have no kernels of their own: pass an "
+                   f"array whose dtype or last dimension is the {d.elem_bytes}-byte element")
+
+
 def radix_sort(x, digits: Optional[RadixDigits] = None, tmp=None, ctx: Optional[Context] = None):
     """`<[T]>::radix_sort(&mut self)` (mod.rs:62): sorts `x` in place and returns None.
 
@@ -254,7 +271,10 @@ def radix_sort(x, digits: Optional[RadixDigits] = None, tmp=None, ctx: Optional[
        tensor (host drop-in path: H2D -> sort -> D2H, blocking).
     digits: RadixDigits of the element type; inferred for primitive dtypes and
        numpy structured dtypes (first field = key).  When given for a byte tensor
-       (uint8), x is read as packed elements of digits.elem_bytes.
+       (uint8), x is read as packed elements of digits.elem_bytes.  Layouts without
+       kernels of their own (any other element size, keys of 3, 5-7, 9-15 bytes) need
+       an array that states the element: dtype itemsize or last dimension == elem_bytes
+       (e.g. a structured array, or a uint8 tensor of shape (n, elem_bytes)).
     tmp: optional ping-pong buffer of the same shape/dtype/device (mod.rs:71-83 `temp`).
     """
     if isinstance(x, np.ndarray):
@@ -264,6 +284,7 @@ def radix_sort(x, digits: Optional[RadixDigits] = None, tmp=None, ctx: Optional[
         n = x.nbytes // d.elem_bytes
         if x.nbytes % d.elem_bytes:
             raise ValueError("array size is not a multiple of elem_bytes")
+        _check_element_stated(x.shape, x.dtype.itemsize, d)
         c = ctx or default_context(-1)
         c.sort_host(x.ctypes.data, n, d)
         return None
@@ -277,6 +298,7 @@ def radix_sort(x, digits: Optional[RadixDigits] = None, tmp=None, ctx: Optional[
     if nbytes % d.elem_bytes:
         raise ValueError("tensor size is not a multiple of elem_bytes")
     n = nbytes // d.elem_bytes
+    _check_element_stated(tuple(x.shape), x.element_size(), d)
     if not x.is_cuda:
         c = ctx or default_context(-1)
         c.sort_host(x.data_ptr(), n, d)

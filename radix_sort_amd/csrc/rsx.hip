@@ -5,6 +5,7 @@
 // The per-element-size kernel launchers live in rsx_es.hip (one object per size).
 #include "rsx_internal.hpp"
 #include "rsx_misc_kernels.hpp"
+#include "rsx_any_kernels.hpp"
 
 #include <cmath>
 
@@ -17,6 +18,18 @@ bool layout_ok(const rsx_layout* L) {
     if (!L) return false;
     const uint32_t kb = L->key_bytes;
     if (!(kb == 1 || kb == 2 || kb == 4 || kb == 8 || kb == 16)) return false;
+    if (L->key_kind > RSX_KEY_FLOAT) return false;
+    if (L->key_kind == RSX_KEY_FLOAT && !(kb == 4 || kb == 8)) return false;
+    if (L->elem_bytes == 0 || (uint64_t)L->key_offset + kb > L->elem_bytes) return false;
+    return true;
+}
+// What rsx_sort_device / rsx_sort_host / rsx_ctx_reserve / rsx_generate_device / rsx_verify_device accept: any element
+// size and integer keys of any width up to 16 bytes.  Layouts that layout_ok + size_supported refuse reach the kernels
+// through sort_any_locked; every other entry point keeps to layout_ok.
+bool any_layout_ok(const rsx_layout* L) {
+    if (!L) return false;
+    const uint32_t kb = L->key_bytes;
+    if (kb < 1 || kb > 16) return false;
     if (L->key_kind > RSX_KEY_FLOAT) return false;
     if (L->key_kind == RSX_KEY_FLOAT && !(kb == 4 || kb == 8)) return false;
     if (L->elem_bytes == 0 || (uint64_t)L->key_offset + kb > L->elem_bytes) return false;
@@ -252,6 +265,15 @@ int check_common(rsx_ctx* ctx, const rsx_layout* L) {
     if (!size_supported(L->elem_bytes)) return fail(ctx, RSX_ERR_UNSUPPORTED, "element size has no device kernel");
     return RSX_OK;
 }
+bool direct_layout(const rsx_layout* L) { return layout_ok(L) && size_supported(L->elem_bytes); }
+// the entry points that sort any layout (sort_any_locked)
+int check_any(rsx_ctx* ctx, const rsx_layout* L) {
+    if (!ctx) return RSX_ERR_ARG;
+    if (direct_layout(L)) return RSX_OK;
+    if (!any_layout_ok(L)) return fail(ctx, RSX_ERR_ARG, "invalid rsx_layout");
+    if (L->elem_bytes > RSX_MAX_ELEM_BYTES) return fail(ctx, RSX_ERR_UNSUPPORTED, "element larger than RSX_MAX_ELEM_BYTES");
+    return RSX_OK;
+}
 
 struct DeviceGuard {
     int prev = -1;
@@ -313,6 +335,7 @@ int sort_device_locked(rsx_ctx* ctx, void* d_data, void* d_tmp, size_t n, const 
     const bool counting_path = L->elem_bytes == 1 && !(ctx->options & OPT_GENERAL_BYTES);  // no sweep follows
     ctx->last_sort_passes = 0;
     ctx->last_path = 0;
+    ctx->last_route = 0;
     // at most one tile: all D passes in one launch of one workgroup (rsx_small_kernel.hpp)
     if (!counting_path && n <= (size_t)512 * kpt_for((int)L->elem_bytes) && !(ctx->options & OPT_NO_SMALL_SORT)) {  // one 512-thread tile
         ctx->last_path = 1;
@@ -532,6 +555,169 @@ int sort_device_locked(rsx_ctx* ctx, void* d_data, void* d_tmp, size_t n, const 
     return fail(ctx, RSX_ERR_INTERNAL, "sort_device_locked: unreachable");
 }
 
+// ---- layouts without a kernel of their own (include/rsx.h, "Any layout") ----
+// Both routes sort a CANONICAL key: the key at offset 0, widened to kw = the smallest of 1, 2, 4, 8, 16 bytes that holds
+// it (unsigned keys zero-extended, signed keys sign-extended: both keep the order, so the existing kernels sort it under
+// the layout's own key kind).
+//   route 1, packed re-layout: canonical key + the other elem_bytes - key_bytes bytes in their order, c <= 16 bytes,
+//     padded to a size with kernels (a multiple of kw); re-laid out into workspace, sorted there, restored into d_data;
+//   route 2, key-index proxy: (canonical key, u32 position) proxies are sorted, then d_data[i] = copy[proxy[i].index],
+//     the copy made in d_tmp by the same kernel that made the proxies.
+struct AnyPlan {
+    uint32_t route;    // 1 or 2
+    rsx_layout inner;  // what the existing kernels sort
+    uint32_t kw;       // canonical key width
+    uint32_t idx_off;  // route 2: byte offset of the position in the proxy
+};
+uint32_t canon_width(uint32_t kb) { return kb <= 1 ? 1 : kb <= 2 ? 2 : kb <= 4 ? 4 : kb <= 8 ? 8 : 16; }
+// Route 1 while the canonical element fits 16 bytes: measured at 2^24 and 2^26, route 2 was faster from 20-byte
+// elements on ((20,0,4) 4.18 against 4.84 ms at 2^26, (28,0,4) 4.59 against 5.48) and 2.3x slower for (6,0,2)
+// (DESIGN.md section 5).
+constexpr uint32_t ANY_PACKED_MAX = 16;
+AnyPlan any_plan(const rsx_layout* L) {
+    AnyPlan P{};
+    const uint32_t kb = L->key_bytes, s = L->elem_bytes, kw = canon_width(kb);
+    const uint32_t c = kw + s - kb;
+    P.kw = kw;
+    P.route = c <= ANY_PACKED_MAX ? 1u : 2u;
+#if defined(RSX_TUNING) && defined(RSX_ANY_ROUTE)  // measurement builds: force the proxy route where both exist
+    if (RSX_ANY_ROUTE == 2) P.route = 2;
+#endif
+    if (P.route == 1) {
+        static const uint32_t sizes[] = {4, 8, 12, 16};
+        uint32_t sp = 16;
+        for (uint32_t z : sizes)
+            if (z >= c && z % (kw < 16 ? kw : 16) == 0) { sp = z; break; }
+        P.inner = rsx_layout{sp, 0, kw, L->key_kind};
+    } else {
+        const uint32_t p = kw <= 4 ? 8 : kw == 8 ? 16 : 32;  // (u32 key, u32) / (u64 key, u64) / (u128 key, u128)
+        P.idx_off = kw <= 4 ? 4 : kw;
+        P.inner = rsx_layout{p, 0, kw, L->key_kind};
+    }
+    return P;
+}
+// byte maps of the move kernel: source element -> canonical (re-layout / proxy), canonical -> source element (restore)
+AnyMap map_forward(const rsx_layout* L, const AnyPlan& P) {
+    AnyMap m{};
+    const uint32_t kb = L->key_bytes, ko = L->key_offset, kw = P.kw, c = kw + L->elem_bytes - kb;
+    m.sign_off = ko + kb - 1;
+    for (uint32_t o = 0; o < ANY_MAP_MAX; ++o) {
+        int16_t v = ANY_ZERO;
+        if (o < kb) v = (int16_t)(ko + o);
+        else if (o < kw) v = L->key_kind == RSX_KEY_SIGNED ? ANY_SIGN : ANY_ZERO;
+        else if (P.route == 1 && o < c) v = (int16_t)(o - kw < ko ? o - kw : o - kw + kb);
+        else if (P.route == 2 && o >= P.idx_off && o < P.idx_off + 4) v = (int16_t)(ANY_INDEX - (int16_t)(o - P.idx_off));
+        m.m[o] = o < P.inner.elem_bytes ? v : ANY_ZERO;
+    }
+    return m;
+}
+AnyMap map_restore(const rsx_layout* L, const AnyPlan& P) {
+    AnyMap m{};
+    const uint32_t kb = L->key_bytes, ko = L->key_offset;
+    for (uint32_t b = 0; b < ANY_MAP_MAX; ++b)
+        m.m[b] = b >= L->elem_bytes ? ANY_ZERO : (b >= ko && b < ko + kb) ? (int16_t)(b - ko) : (int16_t)(P.kw + (b < ko ? b : b - kb));
+    return m;
+}
+size_t any_half(size_t n, const AnyPlan& P) { return (n * (size_t)P.inner.elem_bytes + 255) & ~(size_t)255; }
+
+int ensure_any(rsx_ctx* ctx, size_t bytes, hipStream_t st) {
+    if (bytes <= ctx->any_bytes) return RSX_OK;
+    if (capturing(st)) return fail(ctx, RSX_ERR_WORKSPACE, "workspace too small for this layout and a stream capture is active (rsx_ctx_reserve first)");
+    if (ctx->busy) RSX_HIP(hipEventSynchronize(ctx->last_event));  // the old arrays may still be in use
+    if (ctx->any_buf) RSX_HIP(hipFree(ctx->any_buf));
+    ctx->any_buf = nullptr;
+    ctx->any_bytes = 0;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&ctx->any_buf), bytes);
+    if (e != hipSuccess) return fail(ctx, RSX_ERR_NOMEM, "workspace hipMalloc", e);
+    ctx->any_bytes = bytes;
+    return RSX_OK;
+}
+
+int reserve_any(rsx_ctx* ctx, size_t n, const rsx_layout* L, hipStream_t st) {
+    const AnyPlan P = any_plan(L);
+    int rc = ensure_workspace(ctx, n, &P.inner, st);
+    if (rc) return rc;
+    return ensure_any(ctx, 2 * any_half(n, P), st);
+}
+
+int launch_move(rsx_ctx* ctx, const void* src, uint32_t s_in, void* dst, uint32_t s_out, void* dst2, size_t n, const AnyMap& map,
+                hipStream_t st) {
+    uint32_t tile = 16384u / s_in;
+    if (tile > 4096) tile = 4096;
+    if (tile < 1) tile = 1;
+    const size_t lds = ((size_t)tile * s_in + 47) & ~(size_t)15;  // + the 16-byte chunks the tile's two ends fall into
+    uint64_t blocks = (n + tile - 1) / tile;
+    const uint64_t cap = (uint64_t)ctx->num_cu * 8;
+    if (blocks > cap) blocks = cap;
+    LaunchTimer lt(ctx, RSX_PROF_OTHER, st);
+    if (dst2) {
+        hipLaunchKernelGGL((rsx_any_move_kernel<true, true>), dim3((uint32_t)blocks), dim3(256), lds, st, static_cast<const uint8_t*>(src), s_in,
+                           static_cast<uint8_t*>(dst), s_out, static_cast<uint8_t*>(dst2), (uint64_t)n, tile, map, 1.0f / (float)s_out);
+    } else {
+        hipLaunchKernelGGL((rsx_any_move_kernel<true, false>), dim3((uint32_t)blocks), dim3(256), lds, st, static_cast<const uint8_t*>(src), s_in,
+                           static_cast<uint8_t*>(dst), s_out, static_cast<uint8_t*>(nullptr), (uint64_t)n, tile, map, 1.0f / (float)s_out);
+    }
+    RSX_HIP(hipGetLastError());
+    return RSX_OK;
+}
+
+int launch_gather(rsx_ctx* ctx, const void* src, void* dst, uint32_t s, const void* proxy, const AnyPlan& P, size_t n, hipStream_t st) {
+    const uintptr_t al = reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst) | s;
+    const uint32_t w = (al & 15) == 0 ? 16 : (al & 7) == 0 ? 8 : (al & 3) == 0 ? 4 : (al & 1) == 0 ? 2 : 1;
+    const uint32_t words = s / w;
+    uint32_t gshift = 0;
+    while (gshift < 4 && (1u << gshift) < words) ++gshift;  // lanes per row: at most 16, four rows or more per wave
+    uint64_t blocks = ((uint64_t)n << gshift) / 256 + 1;
+    const uint64_t cap = (uint64_t)ctx->num_cu * 16;
+    if (blocks > cap) blocks = cap;
+    LaunchTimer lt(ctx, RSX_PROF_OTHER, st);
+    const uint8_t* sp = static_cast<const uint8_t*>(src);
+    uint8_t* dp = static_cast<uint8_t*>(dst);
+    const uint8_t* pp = static_cast<const uint8_t*>(proxy);
+    const uint32_t p = P.inner.elem_bytes;
+    switch (w) {
+        case 16: hipLaunchKernelGGL(rsx_row_gather_kernel<uint4>, dim3((uint32_t)blocks), dim3(256), 0, st, sp, dp, words, pp, p, P.idx_off, (uint64_t)n, gshift); break;
+        case 8: hipLaunchKernelGGL(rsx_row_gather_kernel<uint2>, dim3((uint32_t)blocks), dim3(256), 0, st, sp, dp, words, pp, p, P.idx_off, (uint64_t)n, gshift); break;
+        case 4: hipLaunchKernelGGL(rsx_row_gather_kernel<uint32_t>, dim3((uint32_t)blocks), dim3(256), 0, st, sp, dp, words, pp, p, P.idx_off, (uint64_t)n, gshift); break;
+        case 2: hipLaunchKernelGGL(rsx_row_gather_kernel<uint16_t>, dim3((uint32_t)blocks), dim3(256), 0, st, sp, dp, words, pp, p, P.idx_off, (uint64_t)n, gshift); break;
+        default: hipLaunchKernelGGL(rsx_row_gather_kernel<uint8_t>, dim3((uint32_t)blocks), dim3(256), 0, st, sp, dp, words, pp, p, P.idx_off, (uint64_t)n, gshift); break;
+    }
+    RSX_HIP(hipGetLastError());
+    return RSX_OK;
+}
+
+// rsx_sort_device's body for every layout: a layout with kernels of its own goes straight to sort_device_locked (the
+// same launches as ever), any other one through route 1 or 2.  Caller holds ctx->mu and has set the device.
+int sort_any_locked(rsx_ctx* ctx, void* d_data, void* d_tmp, size_t n, const rsx_layout* L, hipStream_t st) {
+    if (direct_layout(L)) return sort_device_locked(ctx, d_data, d_tmp, n, L, st);
+    const AnyPlan P = any_plan(L);
+    if (P.route == 2 && (uint64_t)n >= (1ull << 32)) return fail(ctx, RSX_ERR_UNSUPPORTED, "2^32 or more elements wider than 32 bytes");
+    int rc = pending_error(ctx);
+    if (rc) return rc;
+    rc = reserve_any(ctx, n, L, st);
+    if (rc) return rc;
+    Enqueue enq(ctx, st);  // the workspace arrays belong to this sort from the first launch on
+    char* w0 = ctx->any_buf;
+    char* w1 = ctx->any_buf + any_half(n, P);
+    const uint32_t s = L->elem_bytes, sp = P.inner.elem_bytes;
+    if (P.route == 1) {
+        rc = launch_move(ctx, d_data, s, w0, sp, nullptr, n, map_forward(L, P), st);
+        if (rc) return rc;
+        rc = sort_device_locked(ctx, w0, w1, n, &P.inner, st);
+        if (rc) return rc;
+        rc = launch_move(ctx, w0, sp, d_data, s, nullptr, n, map_restore(L, P), st);
+    } else {
+        rc = launch_move(ctx, d_data, s, w0, sp, d_tmp, n, map_forward(L, P), st);
+        if (rc) return rc;
+        rc = sort_device_locked(ctx, w0, w1, n, &P.inner, st);
+        if (rc) return rc;
+        rc = launch_gather(ctx, d_tmp, d_data, s, w0, P, n, st);
+    }
+    if (rc) return rc;
+    ctx->last_route = P.route;
+    return RSX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -611,6 +797,7 @@ int rsx_ctx_destroy(rsx_ctx* ctx) try {
         if (ctx->part_J) (void)hipFree(ctx->part_J);
         if (ctx->ovf16) (void)hipFree(ctx->ovf16);
         if (ctx->wide_buf) (void)hipFree(ctx->wide_buf);
+        if (ctx->any_buf) (void)hipFree(ctx->any_buf);
         if (ctx->shard_q) (void)hipFree(ctx->shard_q);
         if (ctx->shard_out) (void)hipFree(ctx->shard_out);
         if (ctx->shard_hist) (void)hipFree(ctx->shard_hist);
@@ -630,10 +817,11 @@ int rsx_ctx_destroy(rsx_ctx* ctx) try {
 }
 
 int rsx_ctx_reserve(rsx_ctx* ctx, size_t n, const rsx_layout* layout) try {
-    int rc = check_common(ctx, layout);
+    int rc = check_any(ctx, layout);
     if (rc) return rc;
     std::lock_guard<std::mutex> lk(ctx->mu);
     DeviceGuard g(ctx->device);
+    if (!direct_layout(layout)) return reserve_any(ctx, n, layout, nullptr);
     return ensure_workspace(ctx, n, layout, nullptr);
 } catch (...) {
     return RSX_ERR_NOMEM;
@@ -740,7 +928,7 @@ int rsx_ctx_get_info(rsx_ctx* ctx, int what, uint64_t* out) try {
         case RSX_INFO_NUM_CU: *out = (uint64_t)ctx->num_cu; return RSX_OK;
         case RSX_INFO_DEVICE: *out = (uint64_t)ctx->device; return RSX_OK;
         case RSX_INFO_LAST_PASSES: {
-            *out = (uint64_t)ctx->last_path << 24;
+            *out = (uint64_t)ctx->last_path << 24 | (uint64_t)ctx->last_route << 28;
             if (!ctx->aux || ctx->last_sort_passes == 0) return RSX_OK;
             if (ctx->busy) RSX_HIP(hipEventSynchronize(ctx->last_event));
             uint64_t stat = 0, placed = 0;
@@ -758,7 +946,7 @@ int rsx_ctx_get_info(rsx_ctx* ctx, int what, uint64_t* out) try {
                 stat += (mode == 1u || mode == 3u) ? 1u : 0u;
                 placed += mode == 3u ? 1u : 0u;
             }
-            *out = (uint64_t)passes | (stat << 8) | (placed << 16) | ((uint64_t)path << 24);
+            *out = (uint64_t)passes | (stat << 8) | (placed << 16) | ((uint64_t)path << 24) | ((uint64_t)ctx->last_route << 28);
             return RSX_OK;
         }
         default: return fail(ctx, RSX_ERR_ARG, "unknown info id");
@@ -837,16 +1025,18 @@ int rsx_ctx_profile_read(rsx_ctx* ctx, double* ms, uint64_t* launches) try {
 }
 
 int rsx_sort_device(rsx_ctx* ctx, void* d_data, void* d_tmp, size_t n, const rsx_layout* L, void* stream) try {
-    int rc = check_common(ctx, L);
+    int rc = check_any(ctx, L);
     if (rc) return rc;
     if (n <= 1) return RSX_OK;  // reference panics on n == 0 (mod.rs:66-70,92); nothing to compare
     if (!d_data || !d_tmp) return fail(ctx, RSX_ERR_ARG, "null device pointer");
-    const uint32_t al = elem_align(L->elem_bytes);
-    if (!aligned(d_data, al) || !aligned(d_tmp, al)) return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
+    if (direct_layout(L)) {  // (the other layouts are read and written at any alignment)
+        const uint32_t al = elem_align(L->elem_bytes);
+        if (!aligned(d_data, al) || !aligned(d_tmp, al)) return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
+    }
     std::lock_guard<std::mutex> lk(ctx->mu);
     DeviceGuard g(ctx->device);
     if (!g.ok) return fail(ctx, RSX_ERR_NODEVICE, "hipSetDevice failed");
-    return sort_device_locked(ctx, d_data, d_tmp, n, L, static_cast<hipStream_t>(stream));
+    return sort_any_locked(ctx, d_data, d_tmp, n, L, static_cast<hipStream_t>(stream));
 } catch (...) {
     return RSX_ERR_HIP;
 }
@@ -919,7 +1109,7 @@ int host_pipeline(rsx_ctx* ctx, char* host, char* dev, size_t bytes, bool to_dev
 }  // namespace
 
 int rsx_sort_host(rsx_ctx* ctx, void* data, size_t n, const rsx_layout* L) try {
-    int rc = check_common(ctx, L);
+    int rc = check_any(ctx, L);
     if (rc) return rc;
     if (n <= 1) return RSX_OK;
     if (!data) return fail(ctx, RSX_ERR_ARG, "null host pointer");
@@ -944,7 +1134,7 @@ int rsx_sort_host(rsx_ctx* ctx, void* data, size_t n, const rsx_layout* L) try {
     rc = host_pipeline(ctx, static_cast<char*>(data), static_cast<char*>(ctx->host_buf[0]), bytes, true);
     if (rc) return rc;
     hipStream_t st = ctx->copy_stream[0];
-    rc = sort_device_locked(ctx, ctx->host_buf[0], ctx->host_buf[1], n, L, st);
+    rc = sort_any_locked(ctx, ctx->host_buf[0], ctx->host_buf[1], n, L, st);
     if (rc) return rc;
     RSX_HIP(hipStreamSynchronize(st));
     rc = pending_error(ctx);
@@ -1541,7 +1731,7 @@ int rsx_sort_sharded(rsx_ctx* const* ctxs, uint32_t ndev, void* const* d_slices,
 int rsx_generate_device(rsx_ctx* ctx, void* d_data, size_t n, const rsx_layout* L, int gen, uint64_t seed,
                         double param, uint64_t index_base, void* stream) try {
     if (!ctx) return RSX_ERR_ARG;
-    if (!layout_ok(L)) return fail(ctx, RSX_ERR_ARG, "invalid rsx_layout");
+    if (!any_layout_ok(L)) return fail(ctx, RSX_ERR_ARG, "invalid rsx_layout");
     if (n == 0) return RSX_OK;
     if (!d_data) return fail(ctx, RSX_ERR_ARG, "null pointer");
     const uint32_t payload_zero = (gen & RSX_GEN_PAYLOAD_ZERO) ? 1u : 0u;
@@ -1579,7 +1769,7 @@ int rsx_generate_device(rsx_ctx* ctx, void* d_data, size_t n, const rsx_layout* 
 int rsx_verify_device(rsx_ctx* ctx, const void* d_data, size_t n, const rsx_layout* L, uint64_t* d_out,
                       void* stream) try {
     if (!ctx) return RSX_ERR_ARG;
-    if (!layout_ok(L)) return fail(ctx, RSX_ERR_ARG, "invalid rsx_layout");
+    if (!any_layout_ok(L)) return fail(ctx, RSX_ERR_ARG, "invalid rsx_layout");
     if (!d_out) return fail(ctx, RSX_ERR_ARG, "null pointer");
     std::lock_guard<std::mutex> lk(ctx->mu);
     DeviceGuard g(ctx->device);

@@ -105,6 +105,9 @@ struct rsx_ctx {
     bool pass_last = true;     // no pass follows: nothing to clean
     uint32_t last_path = 0;    // 0 general passes, 1 one-launch sort, 2 middle-size bucket split, 3 / 4 one- / two-byte counting
     uint32_t last_sort_passes = 0;  // sweep passes of the last sort (RSX_INFO_LAST_PASSES)
+    uint32_t last_route = 0;   // how the last sort reached the kernels: 0 direct, 1 packed re-layout, 2 key-index proxy
+    char* any_buf = nullptr;   // routes 1 / 2: the re-laid-out elements or the proxies, and their ping-pong array
+    size_t any_bytes = 0;
     rsx::CleanList clean = {{nullptr, nullptr, nullptr}, {0, 0, 0}};  // what the next count kernel zeroes on its way (the previous sort's control block)
     uint64_t cb_used[2][2] = {{0, 0}, {0, 0}};  // per alternating block: bytes of the top-digit matrix / of count matrix 0 its last sort used
     uint32_t cb_alt = 0;       // which of the two alternating blocks the last uncaptured sort used

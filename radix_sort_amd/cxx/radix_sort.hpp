@@ -29,8 +29,12 @@
 namespace rsx {
 
 // ---- key model (radix_digits.rs) ----------------------------------------------------
+// Specialise for user types: provide layout() (and get_digit for host use).  A specialisation may name any element
+// size and any key_bytes from 1 to 16 (RSX_KEY_UNSIGNED / RSX_KEY_SIGNED; 4 or 8 for RSX_KEY_FLOAT), e.g. a packed
+// 6-byte record with a 48-bit key: layouts without kernels of their own are sorted through a canonical key
+// (include/rsx.h, "Any layout").
 template <typename T, typename Enable = void>
-struct RadixDigits;  // specialise for user types: provide layout() (and get_digit for host use)
+struct RadixDigits;
 
 namespace detail {
 template <typename T>

@@ -134,7 +134,9 @@ impl<T: RadixDigits> RadixSort<T> for [T] {
             return; // the reference panics on an empty slice (mod.rs:66-70,92): nothing to sort
         }
         match T::RSX_KEY {
-            Some(k) if matches!(core::mem::size_of::<T>(), 1 | 2 | 4 | 8 | 12 | 16 | 24 | 32) => {
+            // every layout with a mapped key goes to the device: sizes without kernels of their own and keys of
+            // 1..16 bytes through its canonical-key routes (include/rsx.h, "Any layout")
+            Some(k) => {
                 let layout = RsxLayout { elem_bytes: core::mem::size_of::<T>() as u32, key_offset: k.key_offset,
                                          key_bytes: k.key_bytes, key_kind: k.key_kind };
                 let rc = with_ctx(|ctx| unsafe {
@@ -147,8 +149,8 @@ impl<T: RadixDigits> RadixSort<T> for [T] {
     }
 }
 
-/// CPU path, for the element types the device library has no kernel for: a user key type with its own
-/// `get_digit` (`RSX_KEY == None`) or an element size outside {1, 2, 4, 8, 12, 16, 24, 32}.  Same
+/// CPU path, for the element types the device library cannot describe: a user key type with its own
+/// `get_digit` (`RSX_KEY == None`).  Same
 /// algorithm as the reference's body (`src/radix_sort/mod.rs:62-175`), restated: one chunk per hardware
 /// thread, per-chunk digit counts, digit-major / chunk-minor running sum, scatter through 96-element
 /// staging runs per digit, ping-pong between the slice and a scratch buffer, copy-back after an odd
