@@ -171,6 +171,8 @@ enum {
                                  path: 0 general passes, 1 one-launch sort of at most one tile, 2 middle-size bucket
                                  split, 3 one-byte counting, 4 two-byte counting, 5 wide-key hybrid (two sweeps + the
                                  16-bit buckets in LDS; a hybrid the device refused reports 0 and its D passes),
+                                 6 segmented sort (rsx_sort_segments_device, rsx_sort_rows_device: bits 0-7 are then
+                                 the kernels launched, one per size class, and bits 8-23 are 0),
                                  bits 28-29 the route of a layout without kernels of its own: 0 direct, 1 packed
                                  re-layout, 2 key-index proxy (bits 0-27 then describe the sort of the re-laid-out
                                  elements / of the proxies) */
@@ -204,6 +206,48 @@ int rsx_sort_device(rsx_ctx *ctx, void *d_data, void *d_tmp, size_t n, const rsx
  * blocking (mod.rs:62 is blocking too).  The copies run as a pipeline over a ring of
  * pinned chunks (the slice itself is pageable).  PCIe-bound; not the measured path. */
 int rsx_sort_host(rsx_ctx *ctx, void *data, size_t n, const rsx_layout *layout);
+
+/* -- many segments of one array ------------------------------------------ */
+/* Sorts every segment [d_offsets[i], d_offsets[i+1]) of d_data, i in [0, nseg), independently: ascending, stable,
+ * in place, by the mapped key of `layout` -- the bytes rsx_sort_device would leave if called on each segment.
+ * d_offsets: nseg + 1 uint64 ON THE DEVICE, in elements, non-decreasing, d_offsets[nseg] <= n.  Elements in front
+ * of d_offsets[0] and behind d_offsets[nseg] are not touched.  d_tmp: n * elem_bytes, caller-owned, may be
+ * overwritten.  max_seg_len: an upper bound on the segment lengths that the caller vouches for, 0 = unknown.
+ * Stream-ordered, no synchronisation, no workspace: once a context has made its first call of any kind (which
+ * creates its error word and runs its self-tests, and therefore cannot be a captured one), this call allocates
+ * nothing and can be captured into a graph without rsx_ctx_reserve.  Direct layouts only (RSX_ERR_UNSUPPORTED
+ * otherwise); nseg == 0 succeeds and launches nothing.
+ *
+ * Every segment is sorted by ONE workgroup.  Size classes by length: RSX_SEG_CLASSES classes that sort inside LDS
+ * (256 and 1024 threads; rsx_segment_caps) and one that sorts through memory (LSD passes between d_data and
+ * d_tmp by one workgroup: correct for any length below 2^32, slow for long segments).  The lengths live on the
+ * device, so one kernel per class is launched and its workgroups pick their segments from d_offsets themselves;
+ * max_seg_len drops the classes that cannot occur (a segment longer than vouched for is left unsorted or
+ * sorted, never out of bounds).  RSX_INFO_LAST_PASSES then reports path 6 and, in bits 0-7, the kernels launched.
+ *
+ * The offsets are not trusted: the host never reads them, and a segment with begin > end, end > n or 2^32 and
+ * more elements is left untouched and sets the context's error word (rsx_ctx_check and the next call report
+ * RSX_ERR_INTERNAL).  No kernel reads or writes outside the n elements of d_data and d_tmp whatever the offsets
+ * hold.  Overlapping segments cannot be detected: the contents of the overlapping segments are then undefined
+ * (still a permutation of nothing in particular, still in bounds). */
+int rsx_sort_segments_device(rsx_ctx *ctx, void *d_data, void *d_tmp, size_t n, const rsx_layout *layout,
+                             const uint64_t *d_offsets, size_t nseg, uint64_t max_seg_len, void *stream);
+/* The same for `rows` segments of `row_len` elements each, back to back (a contiguous 2-D array sorted along its
+ * last dimension): no offsets array, and the host knows the length, so exactly the launches needed are made (one).
+ * d_tmp: rows * row_len * elem_bytes.  rows == 0 and row_len <= 1 succeed and launch nothing; rows * row_len
+ * overflowing is RSX_ERR_ARG.  A row_len above the largest LDS class is sorted by one rsx_sort_device per row on
+ * its sub-range (with that sort's rules: under capture rsx_ctx_reserve(row_len, layout) first, RSX_ERR_WORKSPACE
+ * otherwise; RSX_INFO_LAST_PASSES then describes the last row's sort) -- unless there are at least as many rows
+ * as the device has CUs and row_len is at most four times that class: then one launch of the through-memory
+ * class takes them (path 6).  Per-row sorts are efficient once rows have millions of elements; rows between the
+ * LDS capacity and the middle sizes stay slow either way (a launch sequence, or one workgroup's passes through
+ * memory, per row). */
+int rsx_sort_rows_device(rsx_ctx *ctx, void *d_data, void *d_tmp, size_t rows, size_t row_len,
+                         const rsx_layout *layout, void *stream);
+/* Host-only, needs no device: caps[c] = the longest segment that size class c sorts inside LDS for this layout
+ * (ascending; RSX_SEG_CLASSES entries).  Longer segments go through memory. */
+#define RSX_SEG_CLASSES 2
+int rsx_segment_caps(const rsx_layout *layout, uint32_t *caps);
 
 /* -- per-pass building blocks (multi-GPU bucket exchange) ---------------- */
 /* 256-bin count of digit `digit` (0 = least significant) over `n` elements:

@@ -15,7 +15,9 @@ SYMBOLS = [
     "rsx_partition_device", "rsx_partition_count_device", "rsx_partition_scatter_device", "rsx_splitter_count_device",
     "rsx_splitter_pick_device", "rsx_segmented_copy_device", "rsx_bounds_device", "rsx_bounds_ranges_device", "rsx_sort_sharded",
     "rsx_sort_sharded_ex", "rsx_generate_device", "rsx_verify_device",
+    "rsx_sort_segments_device", "rsx_sort_rows_device", "rsx_segment_caps",
 ]
+SEG_CLASSES = 2  # RSX_SEG_CLASSES
 
 OK, ERR_ARG, ERR_UNSUPPORTED, ERR_HIP, ERR_NOMEM, ERR_NODEVICE, ERR_WORKSPACE, ERR_INTERNAL = 0, -1, -2, -3, -4, -5, -6, -7
 KEY_UNSIGNED, KEY_SIGNED, KEY_FLOAT = 0, 1, 2
@@ -103,6 +105,9 @@ def load():
     L.rsx_sort_sharded_ex.argtypes = [vp, u32, vp, vp, vp, lp, i]
     L.rsx_generate_device.argtypes = [vp, vp, sz, lp, i, u64, ctypes.c_double, u64, vp]
     L.rsx_verify_device.argtypes = [vp, vp, sz, lp, vp, vp]
+    L.rsx_sort_segments_device.argtypes = [vp, vp, vp, sz, lp, vp, sz, u64, vp]
+    L.rsx_sort_rows_device.argtypes = [vp, vp, vp, sz, sz, lp, vp]
+    L.rsx_segment_caps.argtypes = [lp, ctypes.POINTER(u32)]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("rsx_last_error", "rsx_strerror"):

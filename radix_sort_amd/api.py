@@ -219,6 +219,19 @@ class Context:
         lay = d.layout()
         self._check(self._L.rsx_verify_device(self._h, d_data, n, ctypes.byref(lay), d_out, stream))
 
+    def sort_segments_device(self, d_data: int, d_tmp: int, n: int, d: RadixDigits, d_offsets: int, nseg: int,
+                             max_seg_len: int = 0, stream: int = 0):
+        """rsx_sort_segments_device: every segment [offsets[i], offsets[i+1]) of the n elements sorted on its own;
+        d_offsets: nseg + 1 uint64 on the device."""
+        lay = d.layout()
+        self._check(self._L.rsx_sort_segments_device(self._h, d_data, d_tmp, n, ctypes.byref(lay), d_offsets, nseg,
+                                                     max_seg_len, stream))
+
+    def sort_rows_device(self, d_data: int, d_tmp: int, rows: int, row_len: int, d: RadixDigits, stream: int = 0):
+        """rsx_sort_rows_device: `rows` back-to-back segments of `row_len` elements each."""
+        lay = d.layout()
+        self._check(self._L.rsx_sort_rows_device(self._h, d_data, d_tmp, rows, row_len, ctypes.byref(lay), stream))
+
 
 _DEFAULT = {}
 _DEFAULT_LOCK = threading.Lock()
@@ -314,6 +327,114 @@ def radix_sort(x, digits: Optional[RadixDigits] = None, tmp=None, ctx: Optional[
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
         c.sort_device(x.data_ptr(), tmp.data_ptr(), n, d, stream)
+    return None
+
+
+def segment_caps(digits: RadixDigits):
+    """rsx_segment_caps: the longest segment each size class of a segmented sort holds in LDS (ascending); longer
+    segments are sorted through memory.  Needs no device."""
+    L = _lib.load()
+    caps = (ctypes.c_uint32 * _lib.SEG_CLASSES)()
+    lay = digits.layout()
+    rc = L.rsx_segment_caps(ctypes.byref(lay), caps)
+    if rc != 0:
+        raise RsxError(rc, L.rsx_strerror(rc).decode())
+    return [int(c) for c in caps]
+
+
+def _segment_args(x, digits, tmp):
+    """The checks radix_sort_segments and radix_sort_rows share; no context is made before they pass."""
+    import torch
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("a segmented sort takes a torch tensor on a GPU")
+    if not x.is_contiguous():
+        raise ValueError("a segmented sort needs a contiguous tensor")
+    if not x.is_cuda:
+        raise ValueError("a segmented sort takes a tensor on a GPU (host arrays: radix_sort per segment)")
+    d = _torch_digits(x, digits)
+    if d.elem_bytes not in _KERNEL_SIZES or d.key_bytes not in (1, 2, 4, 8, 16):
+        raise RsxError(_lib.ERR_UNSUPPORTED, f"{d.elem_bytes}-byte elements with {d.key_bytes}-byte keys have no kernels of their own")
+    nbytes = x.numel() * x.element_size()
+    if nbytes % d.elem_bytes:
+        raise ValueError("tensor size is not a multiple of elem_bytes")
+    if tmp is not None:
+        if not isinstance(tmp, torch.Tensor):
+            raise TypeError("tmp must be a torch tensor")
+        if tmp.device != x.device or tmp.numel() * tmp.element_size() < nbytes or not tmp.is_contiguous():
+            raise ValueError("tmp must be a contiguous buffer on the same device, at least as large as x")
+    return d, nbytes // d.elem_bytes
+
+
+def _check_offsets(offsets):
+    import torch
+    if not isinstance(offsets, torch.Tensor):
+        raise TypeError("offsets must be a torch tensor on the device of x")
+    ok = [torch.int64] + ([torch.uint64] if hasattr(torch, "uint64") else [])
+    if offsets.dtype not in ok:
+        raise TypeError(f"offsets must be int64 or uint64, not {offsets.dtype}")
+    if not offsets.is_contiguous() or offsets.dim() != 1:
+        raise ValueError("offsets must be a contiguous 1-D tensor")
+
+
+def radix_sort_segments(x, offsets, digits: Optional[RadixDigits] = None, tmp=None, ctx: Optional[Context] = None,
+                        max_seg_len: int = 0):
+    """Sorts every segment [offsets[i], offsets[i+1]) of `x` on its own, in place, ascending and stably -- what
+    radix_sort would leave if called on each segment -- in one call (rsx_sort_segments_device).  Returns None;
+    enqueued on the current stream, not synchronised.
+
+    x: a contiguous GPU tensor (dtype inferred as in radix_sort; with digits= a uint8 tensor of packed elements).
+    offsets: a contiguous GPU tensor of nseg + 1 int64 or uint64 on the same device, in elements, non-decreasing,
+       the last at most len(x).  Elements outside [offsets[0], offsets[-1]) are not touched.  The offsets are
+       checked on the device: a bad segment is left as it is and the context's next check() raises.
+    max_seg_len: an upper bound on the segment lengths, if the caller has one (0: unknown): saves the launches
+       of the size classes above it (segment_caps)."""
+    import torch
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("a segmented sort takes a torch tensor on a GPU")
+    _check_offsets(offsets)
+    d, n = _segment_args(x, digits, tmp)
+    if offsets.device != x.device:
+        raise ValueError("offsets must live on the device of x")
+    if max_seg_len < 0:
+        raise ValueError("max_seg_len must not be negative")
+    nseg = offsets.numel() - 1
+    if nseg <= 0 or n == 0:
+        return None
+    dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    c = ctx or default_context(dev)
+    if tmp is None:
+        tmp = torch.empty_like(x)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        c.sort_segments_device(x.data_ptr(), tmp.data_ptr(), n, d, offsets.data_ptr(), nseg, max_seg_len, stream)
+    return None
+
+
+def radix_sort_rows(x, digits: Optional[RadixDigits] = None, tmp=None, ctx: Optional[Context] = None):
+    """Sorts every row along the last dimension of `x` in place, ascending and stably
+    (`torch.sort(x, dim=-1, stable=True).values` written into x; rsx_sort_rows_device).  Returns None; enqueued on the
+    current stream, not synchronised.
+
+    x: a contiguous GPU tensor of at least one dimension; dtype inferred as in radix_sort.  With digits= on a uint8
+       tensor the last dimension is row_len * elem_bytes bytes."""
+    import torch
+    d, n = _segment_args(x, digits, tmp)
+    if x.dim() < 1:
+        raise ValueError("radix_sort_rows needs a tensor of at least one dimension")
+    last_bytes = x.shape[-1] * x.element_size()
+    if last_bytes % d.elem_bytes:
+        raise ValueError("the last dimension is not a multiple of elem_bytes")
+    row_len = last_bytes // d.elem_bytes
+    if row_len <= 1 or n == 0:
+        return None
+    rows = n // row_len
+    dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    c = ctx or default_context(dev)
+    if tmp is None:
+        tmp = torch.empty_like(x)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        c.sort_rows_device(x.data_ptr(), tmp.data_ptr(), rows, row_len, d, stream)
     return None
 
 

@@ -218,6 +218,11 @@ int sweep_dispatch(rsx_ctx* ctx, const void* src, void* dst, const RegionGeom& g
     RSX_DISPATCH_ES(L->elem_bytes, launch_sweep, ctx, src, dst, g, L, digit, J, jnext, jzero, xf, st)
 }
 
+int segment_dispatch(rsx_ctx* ctx, void* data, void* tmp, size_t n, const rsx_layout* L, const uint64_t* offsets, uint64_t nseg, uint64_t row_len,
+                     uint64_t max_len, uint32_t* launched, hipStream_t st) {
+    RSX_DISPATCH_ES(L->elem_bytes, launch_segment_sort, ctx, data, tmp, n, L, offsets, nseg, row_len, max_len, launched, st)
+}
+
 // the 256 digit totals of a count matrix -> d_counts
 int launch_totals(rsx_ctx* ctx, const RegionGeom& g, const unsigned long long* J, uint64_t* d_counts, hipStream_t st) {
     LaunchTimer lt(ctx, RSX_PROF_SCAN, st);
@@ -928,6 +933,10 @@ int rsx_ctx_get_info(rsx_ctx* ctx, int what, uint64_t* out) try {
         case RSX_INFO_NUM_CU: *out = (uint64_t)ctx->num_cu; return RSX_OK;
         case RSX_INFO_DEVICE: *out = (uint64_t)ctx->device; return RSX_OK;
         case RSX_INFO_LAST_PASSES: {
+            if (ctx->last_path == 6) {  // segmented: bits 0-7 are the kernels launched
+                *out = (uint64_t)(ctx->last_sort_passes & 0xFFu) | (uint64_t)6 << 24;
+                return RSX_OK;
+            }
             *out = (uint64_t)ctx->last_path << 24 | (uint64_t)ctx->last_route << 28;
             if (!ctx->aux || ctx->last_sort_passes == 0) return RSX_OK;
             if (ctx->busy) RSX_HIP(hipEventSynchronize(ctx->last_event));
@@ -1039,6 +1048,70 @@ int rsx_sort_device(rsx_ctx* ctx, void* d_data, void* d_tmp, size_t n, const rsx
     return sort_any_locked(ctx, d_data, d_tmp, n, L, static_cast<hipStream_t>(stream));
 } catch (...) {
     return RSX_ERR_HIP;
+}
+
+// Shared body of rsx_sort_segments_device (d_offsets) and rsx_sort_rows_device (d_offsets == nullptr, nseg rows of row_len).
+namespace {
+int sort_segments_common(rsx_ctx* ctx, void* d_data, void* d_tmp, size_t n, const rsx_layout* L, const uint64_t* d_offsets, size_t nseg,
+                         uint64_t row_len, uint64_t max_len, void* stream) {
+    int rc = check_common(ctx, L);
+    if (rc) return rc;
+    if (nseg == 0 || (!d_offsets && row_len <= 1)) return RSX_OK;
+    if (!d_data || !d_tmp) return fail(ctx, RSX_ERR_ARG, "null device pointer");
+    const uint32_t al = elem_align(L->elem_bytes);
+    if (!aligned(d_data, al) || !aligned(d_tmp, al) || !aligned(d_offsets, 8)) return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return fail(ctx, RSX_ERR_NODEVICE, "hipSetDevice failed");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint64_t cap = segment_cap((int)L->elem_bytes, RSX_SEG_CLASSES - 1);
+    // Rows above what a workgroup holds in LDS: the sort of one array, row by row (the context's workspace as for any sort).
+    // Only where every CU has a row of its own and the rows are short enough for one workgroup's passes through memory
+    // to beat a launch sequence per row does the through-memory class take them (measured, DESIGN section 5: 4681 rows of
+    // 28673 u32 12 ms against 121 ms; the two meet at some 10 x cap elements per row).
+    if (!d_offsets && row_len > cap && !(nseg >= (size_t)ctx->num_cu && row_len <= 4 * cap)) {
+        for (size_t i = 0; i < nseg; ++i) {
+            const size_t off = i * (size_t)row_len * L->elem_bytes;
+            rc = sort_device_locked(ctx, static_cast<char*>(d_data) + off, static_cast<char*>(d_tmp) + off, (size_t)row_len, L, st);
+            if (rc) return rc;
+        }
+        return RSX_OK;
+    }
+    rc = pending_error(ctx);
+    if (rc) return rc;
+    rc = ensure_aux(ctx, st);  // (the error word and the ranking self-test: a context's first call, never a captured one)
+    if (rc) return rc;
+    Enqueue enq(ctx, st);
+    uint32_t launched = 0;
+    rc = segment_dispatch(ctx, d_data, d_tmp, n, L, d_offsets, nseg, row_len, max_len, &launched, st);
+    ctx->last_path = 6;
+    ctx->last_route = 0;
+    ctx->last_sort_passes = launched;
+    return rc;
+}
+}  // namespace
+
+int rsx_sort_segments_device(rsx_ctx* ctx, void* d_data, void* d_tmp, size_t n, const rsx_layout* L, const uint64_t* d_offsets, size_t nseg,
+                             uint64_t max_seg_len, void* stream) try {
+    if (ctx && nseg != 0 && !d_offsets) return fail(ctx, RSX_ERR_ARG, "null device pointer");
+    return sort_segments_common(ctx, d_data, d_tmp, n, L, d_offsets, nseg, 0, max_seg_len, stream);
+} catch (...) {
+    return RSX_ERR_HIP;
+}
+
+int rsx_sort_rows_device(rsx_ctx* ctx, void* d_data, void* d_tmp, size_t rows, size_t row_len, const rsx_layout* L, void* stream) try {
+    if (ctx && rows != 0 && row_len > SIZE_MAX / rows) return fail(ctx, RSX_ERR_ARG, "rows * row_len overflows");
+    if (ctx && L && L->elem_bytes != 0 && rows != 0 && rows * row_len > SIZE_MAX / L->elem_bytes) return fail(ctx, RSX_ERR_ARG, "rows * row_len overflows");
+    return sort_segments_common(ctx, d_data, d_tmp, rows * row_len, L, nullptr, rows, row_len, 0, stream);
+} catch (...) {
+    return RSX_ERR_HIP;
+}
+
+int rsx_segment_caps(const rsx_layout* L, uint32_t* caps) {
+    if (!caps || !layout_ok(L)) return RSX_ERR_ARG;
+    if (!size_supported(L->elem_bytes)) return RSX_ERR_UNSUPPORTED;
+    for (int c = 0; c < RSX_SEG_CLASSES; ++c) caps[c] = segment_cap((int)L->elem_bytes, c);
+    return RSX_OK;
 }
 
 // Host drop-in.  The slice is pageable memory; a pageable hipMemcpy is staged by the runtime through

@@ -22,4 +22,6 @@ template int launch_sweep<RSX_ES>(rsx_ctx*, const void*, void*, const RegionGeom
 template int launch_small_sort<RSX_ES>(rsx_ctx*, void*, size_t, const rsx_layout*, hipStream_t);
 template int launch_segcopy<RSX_ES>(rsx_ctx*, const void*, void*, const uint64_t*, const uint64_t*, const uint64_t*,
                                     uint32_t, hipStream_t);
+template int launch_segment_sort<RSX_ES>(rsx_ctx*, void*, void*, size_t, const rsx_layout*, const uint64_t*, uint64_t, uint64_t, uint64_t,
+                                         uint32_t*, hipStream_t);
 }  // namespace rsxh

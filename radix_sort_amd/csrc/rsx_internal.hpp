@@ -242,6 +242,8 @@ constexpr uint32_t bucket_cape(int es, int kpt, int wg) {
     return slots < room ? slots : room;
 }
 constexpr size_t bucket_cnt_bytes(int) { return 4; }
+// the LDS size classes of a segmented sort (rsx_segment_kernels.hpp): 256 and 1024 threads x bucket_kpt_for(es) elements
+constexpr uint32_t segment_cap(int es, int cls) { return bucket_cape(es, bucket_kpt_for(es), cls == 0 ? 256 : 1024); }
 // the hybrid's buffer (ctx->wide_buf): bucket totals [65536], block totals [256], starts [65537] (u64), then its WidePlan
 constexpr size_t WIDE_PLAN_OFFSET = (65536 + 256 + 65537 + 1) * sizeof(uint64_t);
 constexpr uint32_t bucket_cap(int es) { return 1024u * (uint32_t)bucket_kpt_for(es); }
@@ -376,6 +378,10 @@ int launch_sweep(rsx_ctx* ctx, const void* src, void* dst, const RegionGeom& g, 
 // arrays of at most one tile (tile_elems(ES)): the whole sort in one launch of one workgroup, in place
 template <int ES>
 int launch_small_sort(rsx_ctx* ctx, void* data, size_t n, const rsx_layout* L, hipStream_t st);
+// every segment (offsets, or rows of row_len when offsets == nullptr) sorted by one workgroup: one launch per size class
+template <int ES>
+int launch_segment_sort(rsx_ctx* ctx, void* data, void* tmp, size_t n, const rsx_layout* L, const uint64_t* offsets, uint64_t nseg,
+                        uint64_t row_len, uint64_t max_len, uint32_t* launched, hipStream_t st);
 template <int ES>
 int launch_segcopy(rsx_ctx* ctx, const void* src, void* dst, const uint64_t* so, const uint64_t* dof,
                    const uint64_t* len, uint32_t nseg, hipStream_t st);

@@ -5,6 +5,7 @@
 #include "rsx_internal.hpp"
 #include "rsx_small_kernel.hpp"
 #include "rsx_mid_kernels.hpp"
+#include "rsx_segment_kernels.hpp"
 
 #ifndef RSX_HIST_BLOCKS_PER_CU
 #define RSX_HIST_BLOCKS_PER_CU 8
@@ -511,6 +512,82 @@ int launch_segcopy(rsx_ctx* ctx, const void* src, void* dst, const uint64_t* so,
                        static_cast<const Elem<ES>*>(src), static_cast<Elem<ES>*>(dst), so, dof, len, nseg, bps);
     RSX_HIP(hipGetLastError());
     return RSX_OK;
+}
+
+// ---- many segments of one array (rsx_segment_kernels.hpp) ------------------------------------------
+// One launch per size class that `max_len` (0: unknown) leaves possible; rows (offsets == nullptr): the one class of
+// row_len.  *launched receives the number of kernels enqueued.
+template <int ES>
+int launch_segment_sort(rsx_ctx* ctx, void* data, void* tmp, size_t n, const rsx_layout* L, const uint64_t* offsets, uint64_t nseg,
+                        uint64_t row_len, uint64_t max_len, uint32_t* launched, hipStream_t st) {
+    constexpr int KPT = bucket_kpt_for(ES);
+    constexpr uint32_t CAP0 = cape<ES, KPT, 256>(), CAP1 = cape<ES, KPT, 1024>();
+    static_assert(CAP0 == segment_cap(ES, 0) && CAP1 == segment_cap(ES, 1), "host and device agree on what a workgroup holds");
+    if (L->key_bytes > 16) return fail(ctx, RSX_ERR_INTERNAL, "launch_segment_sort: key width out of range");
+    SmallArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.passes = L->key_bytes;
+    a.rank_atomic = (ctx->rank_atomic && !(ctx->options & OPT_BALLOT_RANKS)) ? 1u : 0u;
+    a.map_load = a.map_store = L->key_kind == RSX_KEY_UNSIGNED ? 0u : 1u;
+    for (uint32_t d = 0; d < L->key_bytes; ++d) {
+        a.spec[d] = make_spec(L, d);
+        a.spec[d].flip = 0;  // the LDS forms see mapped keys: plain digits
+    }
+    a.xf = make_xform(L);
+    a.no_skip = (ctx->bucket_no_skip || L->key_bytes < 6) ? 1u : 0u;
+    a.key_offset = L->key_offset;
+    a.key_bytes = L->key_bytes;
+    SmallArgs am = a;  // through memory: the keys stay raw, every pass reads its digit through the key map
+    am.map_load = am.map_store = 0;
+    for (uint32_t d = 0; d < L->key_bytes; ++d) am.spec[d] = make_spec(L, d);
+    SegArgs s;
+    std::memset(&s, 0, sizeof s);
+    s.data = data;
+    s.tmp = tmp;
+    s.n = n;
+    s.offsets = offsets;
+    s.nseg = nseg;
+    s.row_len = row_len;
+    s.error = ctx->host_err_dev;
+    const uint64_t longest = offsets ? (max_len ? max_len : ~0ull) : row_len;
+    auto go = [&](auto wgc, auto memc, uint64_t lo, uint64_t hi) -> int {
+        constexpr int WGS = decltype(wgc)::value;
+        constexpr bool MEM = decltype(memc)::value;
+        if (longest <= lo || (!offsets && row_len > hi)) return RSX_OK;  // no segment of this class can occur
+        const size_t lds = (size_t)cape<ES, KPT, WGS>() * ES + (WGS / 64) * RADIX * bucket_cnt_bytes(ES) + 64 + 3 * RADIX * sizeof(uint32_t);
+        auto kern = rsx_segment_sort_kernel<ES, KPT, WGS, MEM>;
+        ensure_lds(ctx, reinterpret_cast<const void*>(kern), lds);
+        uint32_t per_cu = (uint32_t)((size_t)163840 / (lds + 1024));
+        if (per_cu > 1024u / WGS) per_cu = 1024u / WGS;  // (128 registers a lane: 16 waves a CU)
+        if (per_cu < 1) per_cu = 1;
+        const uint64_t full = (uint64_t)ctx->num_cu * per_cu;
+        SegArgs b = s;
+        b.lo = lo;
+        b.hi = hi;
+        b.team = 1;
+        uint64_t grid = full;
+        if (!offsets) {
+            if (grid > nseg) grid = nseg;
+        } else {  // few blocks: the workgroups of a team share a block's members
+            const uint64_t nblocks = (nseg + SEG_BLOCK - 1) / SEG_BLOCK;
+            while (b.team < SEG_BLOCK && (uint64_t)b.team < nseg && nblocks * b.team < full) b.team *= 2;
+            uint64_t teams = full / b.team;
+            if (teams < 1) teams = 1;
+            if (teams > nblocks) teams = nblocks;
+            grid = teams * b.team;
+        }
+        LaunchTimer lt(ctx, RSX_PROF_OTHER, st);
+        hipLaunchKernelGGL(kern, dim3((uint32_t)grid), dim3(WGS), lds, st, MEM ? am : a, b);
+        RSX_HIP(hipGetLastError());
+        ++*launched;
+        return RSX_OK;
+    };
+    using std::integral_constant;
+    int rc = go(integral_constant<int, 256>{}, integral_constant<bool, false>{}, 1, CAP0);
+    if (rc) return rc;
+    rc = go(integral_constant<int, 1024>{}, integral_constant<bool, false>{}, CAP0, CAP1);
+    if (rc) return rc;
+    return go(integral_constant<int, 1024>{}, integral_constant<bool, true>{}, CAP1, 0xFFFFFFFFull);
 }
 
 }  // namespace rsxh

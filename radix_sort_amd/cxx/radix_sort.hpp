@@ -156,6 +156,23 @@ void radix_sort_device(T* d_data, T* d_tmp, size_t n, void* stream = nullptr, Co
     ctx.check(rsx_sort_device(ctx.get(), d_data, d_tmp, n, &L, stream), "rsx_sort_device");
 }
 
+// Many segments of one device array in one call (rsx_sort_segments_device): segment i is elements
+// [d_offsets[i], d_offsets[i+1]) -- nseg + 1 offsets ON THE DEVICE -- sorted on its own, stably, in place.
+// T needs a layout with kernels of its own (sizes 1, 2, 4, 8, 12, 16, 24, 32).  max_seg_len: an upper bound on the
+// segment lengths if the caller has one (0: unknown).  Stream-ordered; bad offsets surface at synchronize_and_check.
+template <typename T>
+void radix_sort_segments(T* d_data, T* d_tmp, size_t n, const uint64_t* d_offsets, size_t nseg, void* stream = nullptr,
+                         uint64_t max_seg_len = 0, Context& ctx = default_context()) {
+    const rsx_layout L = RadixDigits<T>::layout();
+    ctx.check(rsx_sort_segments_device(ctx.get(), d_data, d_tmp, n, &L, d_offsets, nseg, max_seg_len, stream), "rsx_sort_segments_device");
+}
+// ... and of a contiguous rows x row_len array along its last dimension (rsx_sort_rows_device).
+template <typename T>
+void radix_sort_rows(T* d_data, T* d_tmp, size_t rows, size_t row_len, void* stream = nullptr, Context& ctx = default_context()) {
+    const rsx_layout L = RadixDigits<T>::layout();
+    ctx.check(rsx_sort_rows_device(ctx.get(), d_data, d_tmp, rows, row_len, &L, stream), "rsx_sort_rows_device");
+}
+
 // Multi-GPU, one process: slice g lives on the device of ctxs[g]; the concatenation of the slices
 // is sorted as one array (slice = the reference's "chunk", mod.rs:66-70).  Blocking.
 template <typename T>
