@@ -79,9 +79,13 @@ enum {
  * rounded up to 256 bytes, beside the direct sort's own), made on first use or by
  * rsx_ctx_reserve(n, layout); such layouts need only 1-byte alignment of d_data
  * and d_tmp, may overwrite d_tmp, and leave every byte outside the n elements
- * as it was.  Results are bit-exact with the stable sort by mapped key.  The
- * other entry points (histogram, partition*, bounds*, splitter*, sort_sharded*)
- * take direct layouts only; rsx_generate_device and rsx_verify_device take any. */
+ * as it was.  Results are bit-exact with the stable sort by mapped key.  Of the
+ * other entry points, histogram, partition*, sort_segments / sort_rows and
+ * sort_sharded* take direct layouts only (RSX_ERR_UNSUPPORTED otherwise);
+ * bounds* and splitter* read the key where it lies, so they take elements of any
+ * size (no alignment asked) whose key is 1, 2, 4, 8 or 16 bytes wide, and refuse
+ * other key widths with RSX_ERR_ARG; rsx_generate_device and rsx_verify_device
+ * take any layout. */
 #define RSX_MAX_ELEM_BYTES 32768u
 typedef struct rsx_layout {
     uint32_t elem_bytes;
@@ -361,11 +365,16 @@ int rsx_generate_device(rsx_ctx *ctx, void *d_data, size_t n, const rsx_layout *
                         uint64_t seed, double param, uint64_t index_base, void *stream);
 /* Order check + order-independent checksum, on device:
  *   out[0] = number of adjacent pairs (i, i+1) with mapped_key[i] > mapped_key[i+1]
- *   out[1] = sum over elements of hash(element bytes) mod 2^64 (multiset checksum)
- *   out[2] = number of adjacent equal-key pairs whose payload index decreases
- *            (stability violations; meaningful for rsx_generate_device payloads,
- *            elements with payload bytes only)
- * `d_out` is 3 uint64 on the device (overwritten). */
+ *   out[1] = sum over elements of hash(element bytes) mod 2^64 (multiset checksum);
+ *            hash: h = 0x243F6A8885A308D3, then for each of the elem_bytes bytes b in
+ *            order h = splitmix64(h ^ b)  (the SplitMix64 output step: h += 0x9E3779B97F4A7C15,
+ *            h = (h ^ h >> 30) * 0xBF58476D1CE4E5B9, h = (h ^ h >> 27) * 0x94D049BB133111EB, h ^ h >> 31)
+ *   out[2] = number of adjacent equal-key pairs whose payload index decreases: the first 8
+ *            bytes outside the key, read little-endian (stability violations; meaningful for
+ *            rsx_generate_device payloads; 0 for elements that are all key)
+ * `d_out` is 3 uint64 on the device (overwritten by every call, not accumulated); n == 0 writes
+ * three zeros and does not look at d_data.  tests/test_gpu_verify.py holds all three words
+ * against a numpy restatement. */
 int rsx_verify_device(rsx_ctx *ctx, const void *d_data, size_t n, const rsx_layout *layout,
                       uint64_t *d_out, void *stream);
 

@@ -25,7 +25,8 @@ bool layout_ok(const rsx_layout* L) {
 }
 // What rsx_sort_device / rsx_sort_host / rsx_ctx_reserve / rsx_generate_device / rsx_verify_device accept: any element
 // size and integer keys of any width up to 16 bytes.  Layouts that layout_ok + size_supported refuse reach the kernels
-// through sort_any_locked; every other entry point keeps to layout_ok.
+// through sort_any_locked; every other entry point keeps to layout_ok (bounds* and splitter*: layout_ok alone, any
+// element size; histogram, partition*, segments and sharded sorts: layout_ok + size_supported).
 bool any_layout_ok(const rsx_layout* L) {
     if (!L) return false;
     const uint32_t kb = L->key_bytes;

@@ -47,14 +47,18 @@ GENS = [("GEN_UNIFORM", 0.0), ("GEN_ZIPF", 1.0), ("GEN_STEP", 16.0), ("GEN_SORTE
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("t", ["u32", "u64", "(u64,u64)", "(u32,u32)", "u128", "u16", "(pay32+u32)"])
+@pytest.mark.parametrize("t", ["u32", "u64", "(u64,u64)", "(u32,u32)", "u128", "u16", "(pay32+u32)"] + util.ANY_LAYOUTS,
+                         ids=lambda t: t if isinstance(t, str) else "any%d-%d-%d" % t[:3])
 @pytest.mark.parametrize("gen,param", GENS)
 def test_device_generators_match_the_restatement(orc, t, gen, param):
+    """Seven layouts with sort kernels of their own and four without (6-, 7-, 40- and 100-byte elements, keys of 2, 6, 8
+    and 16 bytes at offsets 0, 1, 0 and 36): rsx_generate_device takes any layout."""
     import torch
     import radix_sort_amd as rs
     ctx = rs.default_context(torch.cuda.current_device())
-    d = rs.RadixDigits(*util.TYPES[t])
-    lay = _lay(orc, t)
+    tup = util.TYPES[t] if isinstance(t, str) else t
+    d = rs.RadixDigits(*tup)
+    lay = orc.Layout(*tup)
     n, base = 300007, 5_000_000_000  # index_base beyond 2^32: 64-bit indices
     for pz in (False, True):
         x = torch.empty(n * d.elem_bytes, dtype=torch.uint8, device="cuda")

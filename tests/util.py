@@ -96,3 +96,100 @@ def make_input(tname: str, n: int, dist: str, seed: int) -> np.ndarray:
 
 def layout_tuple(tname: str):
     return TYPES[tname]
+
+
+# ---------------------------------------------------------------------------------------------------------
+# The three words of rsx_verify_device (include/rsx.h), restated in numpy.  Shares no code with the library:
+# the mapped key is oracle.numpy_mapped_key_columns (byte columns, numpy only), the hash is SplitMix64's
+# finaliser (Steele, Lea, Flood 2014; Vigna's public-domain splitmix64.c) chained over the element's bytes.
+# ---------------------------------------------------------------------------------------------------------
+VERIFY_HASH_START = 0x243F6A8885A308D3  # the first 64 fraction bits of pi
+_M64 = (1 << 64) - 1
+
+
+def splitmix64_int(x: int) -> int:
+    """One SplitMix64 step on a python int (for expected values made by arithmetic)."""
+    x = (x + 0x9E3779B97F4A7C15) & _M64
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _M64
+    return x ^ (x >> 31)
+
+
+def element_hash_int(elem: bytes) -> int:
+    """hash of ONE element: h = start; for every byte b of the element in order: h = splitmix64(h ^ b)."""
+    h = VERIFY_HASH_START
+    for b in bytes(elem):
+        h = splitmix64_int(h ^ b)
+    return h
+
+
+def _splitmix64_np(x: np.ndarray) -> np.ndarray:
+    x = x + np.uint64(0x9E3779B97F4A7C15)  # uint64 arithmetic wraps mod 2^64
+    x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return x ^ (x >> np.uint64(31))
+
+
+def verify_checksum(raw: np.ndarray, elem_bytes: int) -> int:
+    """Sum mod 2^64 over the elements of the hash chain over all elem_bytes bytes (one uint64 lane per element,
+    one loop turn per byte)."""
+    n = raw.size // elem_bytes
+    if n == 0:
+        return 0
+    e = raw.reshape(n, elem_bytes)
+    h = np.full(n, VERIFY_HASH_START, dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        for b in range(elem_bytes):
+            h = _splitmix64_np(h ^ e[:, b].astype(np.uint64))
+        return int(np.add.reduce(h, dtype=np.uint64))
+
+
+def _u64_columns(cols: np.ndarray) -> np.ndarray:
+    """(n, w <= 8) little-endian byte columns -> n uint64."""
+    n, w = cols.shape
+    pad = np.zeros((n, 8), dtype=np.uint8)
+    pad[:, :w] = cols
+    return pad.view("<u8").reshape(n)
+
+
+def verify_reference(raw: np.ndarray, lay, orc) -> tuple:
+    """(descents, checksum, unstable) of include/rsx.h for the elements in `raw` (uint8, n * elem_bytes).
+    lay: (elem_bytes, key_offset, key_bytes, key_kind); orc: the oracle module (for its numpy mapped key).
+      descents  adjacent pairs whose mapped key decreases (16-byte keys compared as (hi, lo) uint64 pairs)
+      checksum  verify_checksum
+      unstable  adjacent pairs of equal mapped keys whose first 8 non-key bytes, little-endian, decrease"""
+    es, ko, kb, _kind = lay
+    raw = np.ascontiguousarray(raw, dtype=np.uint8).reshape(-1)
+    n = raw.size // es
+    checksum = verify_checksum(raw, es)
+    if n < 2:
+        return 0, checksum, 0
+    k = orc.numpy_mapped_key_columns(raw, orc.Layout(*lay))
+    lo = _u64_columns(k[:, :8])
+    hi = _u64_columns(k[:, 8:]) if kb > 8 else np.zeros(n, dtype=np.uint64)
+    down = (hi[:-1] > hi[1:]) | ((hi[:-1] == hi[1:]) & (lo[:-1] > lo[1:]))
+    same = (hi[:-1] == hi[1:]) & (lo[:-1] == lo[1:])
+    unstable = 0
+    pay = [b for b in range(es) if not ko <= b < ko + kb][:8]
+    if pay:
+        p = _u64_columns(raw.reshape(n, es)[:, pay])
+        unstable = int(np.count_nonzero(same & (p[:-1] > p[1:])))
+    return int(np.count_nonzero(down)), checksum, unstable
+
+
+# layouts without sort kernels of their own that the verifier and the generators must take as well
+ANY_LAYOUTS = [(6, 0, 2, UNSIGNED), (7, 1, 6, SIGNED), (40, 0, 8, UNSIGNED), (100, 36, 16, UNSIGNED)]
+
+
+def make_input_layout(lay, n: int, dist: str, seed: int) -> np.ndarray:
+    """make_input for a layout tuple that has no name in TYPES (no float specials: integer keys only)."""
+    es, ko, kb, _kind = lay
+    rng = np.random.default_rng(seed)
+    raw = np.zeros((n, es), dtype=np.uint8)
+    if n == 0:
+        return raw.reshape(-1)
+    raw[:, ko:ko + kb] = _key_ints(dist, n, kb, rng)
+    idx = np.arange(n, dtype=np.uint64).view(np.uint8).reshape(n, 8)
+    for j, b in enumerate([b for b in range(es) if not ko <= b < ko + kb][:8]):
+        raw[:, b] = idx[:, j]
+    return raw.reshape(-1)
