@@ -168,7 +168,7 @@ enum {
     RSX_INFO_L2_LOCAL = 2,    /* 1 if the same-XCD hand-off self-test passed on this device */
     RSX_INFO_NUM_CU = 3,
     RSX_INFO_DEVICE = 4,
-    RSX_INFO_LAST_PASSES = 5  /* which tile schedule the passes of the context's LAST sort ran with (waits for it):
+    RSX_INFO_LAST_PASSES = 5, /* which tile schedule the passes of the context's LAST sort ran with (waits for it):
                                  bits 0-7 sweep passes launched (0: one-launch or counting path), bits 8-15 of them
                                  with static tiles (the roll call succeeded), bits 16-23 of them with the XCD
                                  placement verified (status words of single-XCD chains stay in L2), bits 24-27 the
@@ -180,6 +180,9 @@ enum {
                                  bits 28-29 the route of a layout without kernels of its own: 0 direct, 1 packed
                                  re-layout, 2 key-index proxy (bits 0-27 then describe the sort of the re-laid-out
                                  elements / of the proxies) */
+    RSX_INFO_LAST_PAIRS = 6   /* how the context's last rsx_sort_pairs_device / rsx_argsort_device call ran: 0 none yet,
+                                 1 joined elements, 2 proxies and gather; bits 8-15 the size of the joined element (of
+                                 the proxy).  RSX_INFO_LAST_PASSES describes the inner sort of those elements. */
 };
 int rsx_ctx_get_info(rsx_ctx *ctx, int what, uint64_t *out);
 /* Per-launch timing with HIP events on the launch stream (measurement only).
@@ -252,6 +255,43 @@ int rsx_sort_rows_device(rsx_ctx *ctx, void *d_data, void *d_tmp, size_t rows, s
  * (ascending; RSX_SEG_CLASSES entries).  Longer segments go through memory. */
 #define RSX_SEG_CLASSES 2
 int rsx_segment_caps(const rsx_layout *layout, uint32_t *caps);
+
+/* -- separate key and value arrays ---------------------------------------- */
+/* The callers who hold a column of keys and a column of values (or want the permutation) instead of one array of
+ * elements.  Order of every call: the STABLE permutation p by mapped key (the radix_digits.rs mapping, as everywhere
+ * else: a total order on bit patterns, -NaN < -inf < ... < -0 < +0 < ... < +inf < +NaN for floats) -- ascending, or
+ * descending = larger mapped key first, equal keys still in input order (torch.sort(stable=True, descending=True)).
+ *
+ * All three are stream-ordered, do not synchronise and take no caller scratch: the joined elements live in the
+ * context's workspace (two arrays of n * s bytes, s the joined element's size, each rounded up to 256 bytes, and on
+ * route 2 a copy of the values), made on first use or by rsx_ctx_reserve_pairs; under stream capture without a
+ * sufficient reserve they return RSX_ERR_WORKSPACE and enqueue nothing.  Bad widths, kinds, orders or alignments, and
+ * null pointers with n > 0: RSX_ERR_ARG.  n of 0 or 1 succeeds without a sort.  No byte outside the n keys / n values /
+ * n indices is written.  The route is chosen from the widths alone (RSX_INFO_LAST_PAIRS):
+ *   1 joined elements: the mapped key (complemented for descending order) and the value behind it, aligned to the
+ *     value's alignment up to 4, fit an element size with sort kernels (1,2,4,8,12,16,24,32, a multiple of the key
+ *     width): a join kernel writes the elements, they are sorted as RSX_KEY_UNSIGNED, a split kernel writes the two
+ *     columns back.  Keys alone in ascending order are sorted where they lie, the workspace as ping-pong array;
+ *   2 proxies and gather, for wider values: (mapped key, u32 position) proxies are sorted, the keys written from them
+ *     and the values gathered through the copy; n must be below 2^32 (RSX_ERR_UNSUPPORTED otherwise). */
+enum { RSX_ORDER_ASCENDING = 0, RSX_ORDER_DESCENDING = 1 };
+
+/* keys: n keys of key_bytes (1, 2, 4, 8, 16; RSX_KEY_FLOAT: 4 or 8), packed, naturally aligned (16-byte keys: 16).
+ * values: n values of value_bytes (1 .. RSX_MAX_ELEM_BYTES) each, packed, moved bitwise, aligned to the largest
+ * power of two (at most 16) that divides value_bytes.  d_values == NULL and value_bytes == 0: keys only.
+ * Both arrays are sorted in place: keys[i], values[i] = keys_in[p[i]], values_in[p[i]].  Arrays whose base addresses
+ * are 16-byte aligned and values of 1, 2, 4, 8 or 16 bytes take the typed join and split kernels; anything else a
+ * slower element-by-element form. */
+int rsx_sort_pairs_device(rsx_ctx *ctx, void *d_keys, void *d_values, size_t n, uint32_t key_bytes,
+                          uint32_t key_kind, uint32_t value_bytes, int order, void *stream);
+/* d_keys is only read; d_index receives p as n integers of index_bytes (4 or 8; naturally aligned).  n == 1 writes
+ * the one 0.  Positions are joined as u32 while n < 2^32 and as u64 beyond (index_bytes 4 is then
+ * RSX_ERR_UNSUPPORTED). */
+int rsx_argsort_device(rsx_ctx *ctx, const void *d_keys, void *d_index, size_t n, uint32_t key_bytes,
+                       uint32_t key_kind, uint32_t index_bytes, int order, void *stream);
+/* Workspace for either call on up to n pairs of these widths, so that the call allocates nothing (stream capture);
+ * for rsx_argsort_device pass value_bytes = index_bytes. */
+int rsx_ctx_reserve_pairs(rsx_ctx *ctx, size_t n, uint32_t key_bytes, uint32_t value_bytes);
 
 /* -- per-pass building blocks (multi-GPU bucket exchange) ---------------- */
 /* 256-bin count of digit `digit` (0 = least significant) over `n` elements:

@@ -16,6 +16,7 @@ SYMBOLS = [
     "rsx_splitter_pick_device", "rsx_segmented_copy_device", "rsx_bounds_device", "rsx_bounds_ranges_device", "rsx_sort_sharded",
     "rsx_sort_sharded_ex", "rsx_generate_device", "rsx_verify_device",
     "rsx_sort_segments_device", "rsx_sort_rows_device", "rsx_segment_caps",
+    "rsx_sort_pairs_device", "rsx_argsort_device", "rsx_ctx_reserve_pairs",
 ]
 SEG_CLASSES = 2  # RSX_SEG_CLASSES
 
@@ -26,7 +27,8 @@ GEN_UNIFORM, GEN_ZIPF, GEN_STEP, GEN_SORTED, GEN_REVERSED, GEN_CONSTANT, GEN_GEO
 GEN_PAYLOAD_ZERO = 0x100
 (OPT_TILE_SCHEDULE, OPT_RANKING, OPT_STATUS_SCOPE, OPT_XCD_MAJOR, OPT_BYTE_COUNTING, OPT_MAX_REGIONS, OPT_HOT_LANES,
  OPT_VERBOSE, OPT_RANK_CHECK, OPT_SMALL_SORT, OPT_MID_SORT, OPT_WIDE_SORT, OPT_BUCKET_SKIP, OPT_BUCKET_GROUP) = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14
-INFO_RANK_ATOMIC, INFO_L2_LOCAL, INFO_NUM_CU, INFO_DEVICE, INFO_LAST_PASSES = 1, 2, 3, 4, 5
+INFO_RANK_ATOMIC, INFO_L2_LOCAL, INFO_NUM_CU, INFO_DEVICE, INFO_LAST_PASSES, INFO_LAST_PAIRS = 1, 2, 3, 4, 5, 6
+ORDER_ASCENDING, ORDER_DESCENDING = 0, 1
 SHARD_EXCHANGE_FIRST, SHARD_SORT_FIRST = 0, 1
 
 
@@ -108,6 +110,9 @@ def load():
     L.rsx_sort_segments_device.argtypes = [vp, vp, vp, sz, lp, vp, sz, u64, vp]
     L.rsx_sort_rows_device.argtypes = [vp, vp, vp, sz, sz, lp, vp]
     L.rsx_segment_caps.argtypes = [lp, ctypes.POINTER(u32)]
+    L.rsx_sort_pairs_device.argtypes = [vp, vp, vp, sz, u32, u32, u32, i, vp]
+    L.rsx_argsort_device.argtypes = [vp, vp, vp, sz, u32, u32, u32, i, vp]
+    L.rsx_ctx_reserve_pairs.argtypes = [vp, sz, u32, u32]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("rsx_last_error", "rsx_strerror"):

@@ -233,6 +233,25 @@ class Context:
         self._check(self._L.rsx_sort_rows_device(self._h, d_data, d_tmp, rows, row_len, ctypes.byref(lay), stream))
 
 
+    def reserve_pairs(self, n: int, key_bytes: int, value_bytes: int):
+        """rsx_ctx_reserve_pairs: workspace for sort_pairs_device / argsort_device of up to n pairs (argsort:
+        value_bytes = index_bytes), so that the call allocates nothing and can be captured into a graph."""
+        self._check(self._L.rsx_ctx_reserve_pairs(self._h, n, key_bytes, value_bytes))
+
+    def sort_pairs_device(self, d_keys: int, d_values: int, n: int, key_bytes: int, key_kind: int, value_bytes: int,
+                          descending: bool = False, stream: int = 0):
+        """rsx_sort_pairs_device: n keys and n values in separate device arrays, both sorted in place by key
+        (d_values 0 and value_bytes 0: keys only)."""
+        self._check(self._L.rsx_sort_pairs_device(self._h, d_keys, d_values or None, n, key_bytes, key_kind, value_bytes,
+                                                  1 if descending else 0, stream))
+
+    def argsort_device(self, d_keys: int, d_index: int, n: int, key_bytes: int, key_kind: int, index_bytes: int,
+                       descending: bool = False, stream: int = 0):
+        """rsx_argsort_device: the stable sorting permutation of n keys as index_bytes-wide integers; keys untouched."""
+        self._check(self._L.rsx_argsort_device(self._h, d_keys, d_index, n, key_bytes, key_kind, index_bytes,
+                                               1 if descending else 0, stream))
+
+
 _DEFAULT = {}
 _DEFAULT_LOCK = threading.Lock()
 
@@ -436,6 +455,101 @@ def radix_sort_rows(x, digits: Optional[RadixDigits] = None, tmp=None, ctx: Opti
         stream = torch.cuda.current_stream(dev).cuda_stream
         c.sort_rows_device(x.data_ptr(), tmp.data_ptr(), rows, row_len, d, stream)
     return None
+
+
+def _pairs_keys(keys, key_kind):
+    """(key_bytes, key_kind, n) of the key column of radix_sort_pairs / radix_argsort."""
+    import torch
+    if not isinstance(keys, torch.Tensor):
+        raise TypeError("keys must be a torch tensor on a GPU")
+    if not keys.is_contiguous():
+        raise ValueError("keys must be contiguous")
+    if keys.dim() == 2 and keys.dtype == torch.uint8 and keys.shape[1] == 16:  # 128-bit keys as raw bytes
+        kind = KEY_UNSIGNED if key_kind is None else key_kind
+        if kind not in (KEY_UNSIGNED, KEY_SIGNED):
+            raise ValueError("128-bit keys are KEY_UNSIGNED or KEY_SIGNED")
+        return 16, kind, keys.shape[0]
+    if keys.dim() != 1:
+        raise ValueError("keys must be 1-D (or an (n, 16) uint8 tensor of 128-bit keys)")
+    if key_kind is not None:
+        raise ValueError("key_kind= is for (n, 16) uint8 keys; other widths take it from the dtype")
+    d = _torch_digits(keys, None)
+    return d.key_bytes, d.key_kind, keys.shape[0]
+
+
+def _pairs_device(keys, other, what: str):
+    """Last of the argument checks (none of them needs a context): both tensors on one GPU."""
+    if not keys.is_cuda:
+        raise ValueError("keys must live on a GPU (host arrays: radix_sort on interleaved elements)")
+    if other is not None and other.device != keys.device:
+        raise ValueError(f"keys and {what} must live on the same device")
+
+
+def radix_sort_pairs(keys, values, descending: bool = False, ctx: Optional[Context] = None, key_kind: Optional[int] = None):
+    """Sorts `keys` and `values` in place by key and returns None (rsx_sort_pairs_device): what
+    `k, i = torch.sort(keys, stable=True, descending=descending); values = values[i]` computes, without the
+    interleaving a caller of radix_sort would have to do.  Stable in both orders: equal keys keep their input order.
+
+    keys: a contiguous 1-D GPU tensor of a dtype radix_sort knows, or an (n, 16) uint8 tensor of 128-bit keys
+       (key_kind= KEY_UNSIGNED, the default, or KEY_SIGNED).
+    values: a contiguous GPU tensor on the same device with values.shape[0] == len(keys), any dtype; one row
+       (values[i], trailing dimensions included) is one value of up to 32768 bytes, moved bitwise.  None: keys only.
+
+    The order is the reference's total order on bit patterns (radix_digits.rs), not torch.sort's: -NaN sorts below
+    -inf, +NaN above +inf, and -0.0 below +0.0.  Enqueued on the current stream, not synchronised."""
+    import torch
+    kb, kind, n = _pairs_keys(keys, key_kind)
+    vb = 0
+    if values is not None:
+        if not isinstance(values, torch.Tensor):
+            raise TypeError("values must be a torch tensor or None")
+        if not values.is_contiguous():
+            raise ValueError("values must be contiguous")
+        if values.dim() < 1 or values.shape[0] != n:
+            raise ValueError(f"values must have one row per key ({n}), not shape {tuple(values.shape)}")
+        vb = values.element_size()
+        for s in values.shape[1:]:
+            vb *= s
+        if vb == 0 or vb > 32768:
+            raise ValueError(f"one value must have 1 .. 32768 bytes, not {vb}")
+    _pairs_device(keys, values, "values")
+    if n <= 1:
+        return None
+    dev = keys.device.index if keys.device.index is not None else torch.cuda.current_device()
+    c = ctx or default_context(dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        c.sort_pairs_device(keys.data_ptr(), values.data_ptr() if values is not None else 0, n, kb, kind, vb, descending, stream)
+    return None
+
+
+def radix_argsort(keys, descending: bool = False, out=None, ctx: Optional[Context] = None, key_kind: Optional[int] = None):
+    """The stable permutation that sorts `keys` (rsx_argsort_device), like `torch.argsort(keys, stable=True,
+    descending=descending)`: returns a new int64 tensor, or fills and returns `out` (a contiguous 1-D int32 or int64
+    tensor of len(keys) on the same device).  `keys` (as in radix_sort_pairs) is not modified.
+
+    The order is the reference's total order on bit patterns (radix_digits.rs), not torch's: -NaN sorts below -inf,
+    +NaN above +inf, -0.0 below +0.0.  Enqueued on the current stream, not synchronised."""
+    import torch
+    kb, kind, n = _pairs_keys(keys, key_kind)
+    if out is not None:
+        if not isinstance(out, torch.Tensor):
+            raise TypeError("out must be a torch tensor")
+        if out.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"out must be int32 or int64, not {out.dtype}")
+        if out.dim() != 1 or out.shape[0] != n or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous 1-D tensor of {n} elements")
+    _pairs_device(keys, out, "out")
+    if out is None:
+        out = torch.empty(n, dtype=torch.int64, device=keys.device)
+    if n == 0:
+        return out
+    dev = keys.device.index if keys.device.index is not None else torch.cuda.current_device()
+    c = ctx or default_context(dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        c.argsort_device(keys.data_ptr(), out.data_ptr(), n, kb, kind, out.element_size(), descending, stream)
+    return out
 
 
 def radix_sort_sharded(slices: Sequence, digits: RadixDigits, ctxs: Optional[Sequence[Context]] = None, tmps=None,

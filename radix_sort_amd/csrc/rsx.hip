@@ -724,6 +724,101 @@ int sort_any_locked(rsx_ctx* ctx, void* d_data, void* d_tmp, size_t n, const rsx
     return RSX_OK;
 }
 
+
+// ---- separate key and value arrays (include/rsx.h: rsx_sort_pairs_device, rsx_argsort_device) ----
+// Both calls sort JOINED elements in the context's second workspace: the mapped key (complemented for descending order)
+// at offset 0, sorted as RSX_KEY_UNSIGNED by the kernels every other call uses, with
+//   route 1, joined elements: the value (or, for argsort, the element's position) behind the key, when the two fit an
+//     element size with sort kernels (rsx_pairs_kernels.hpp, pairs_elem); join, sort, split;
+//   route 2, proxies and gather: (mapped key, u32 position) proxies for wider values; the keys are written from the
+//     sorted proxies and the values gathered through a copy kept behind the two proxy arrays.
+struct PairsPlan {
+    uint32_t route;
+    uint32_t vb;       // bytes of the value inside the element (route 2: the 4-byte position)
+    rsx_layout inner;  // what the sort kernels see
+    size_t half;       // bytes of each of the two element arrays
+    size_t copy;       // route 2: bytes of the copy of the values
+};
+PairsPlan pairs_plan(size_t n, uint32_t kb, uint32_t vb) {
+    PairsPlan P{};
+    uint32_t es = pairs_elem_bytes(kb, vb);
+    P.route = es ? 1u : 2u;
+    P.vb = es ? vb : 4u;
+    if (!es) es = pairs_elem_bytes(kb, 4);
+    P.inner = rsx_layout{es, 0, kb, RSX_KEY_UNSIGNED};
+    P.half = (n * (size_t)es + 255) & ~(size_t)255;
+    P.copy = P.route == 2 ? (n * (size_t)vb + 255) & ~(size_t)255 : 0;
+    return P;
+}
+int reserve_pairs_one(rsx_ctx* ctx, size_t n, uint32_t kb, uint32_t vb, hipStream_t st) {
+    const PairsPlan P = pairs_plan(n, kb, vb);
+    int rc = ensure_workspace(ctx, n, &P.inner, st);
+    if (rc) return rc;
+    return ensure_any(ctx, 2 * P.half + P.copy, st);
+}
+bool key_widths_ok(uint32_t kb, uint32_t kind) {
+    if (!(kb == 1 || kb == 2 || kb == 4 || kb == 8 || kb == 16)) return false;
+    if (kind > RSX_KEY_FLOAT) return false;
+    return kind != RSX_KEY_FLOAT || kb == 4 || kb == 8;
+}
+uint32_t value_align(uint32_t vb) {
+    uint32_t a = 1;
+    while (a < 16 && vb % (2 * a) == 0) a *= 2;
+    return a;
+}
+
+// d_index != nullptr: argsort (d_keys only read, d_values unused, ib = index bytes); otherwise keys and values (vb == 0:
+// keys only) sorted in place.  Caller holds ctx->mu, has set the device and checked the arguments; n >= 2.
+int pairs_locked(rsx_ctx* ctx, void* d_keys, void* d_values, void* d_index, size_t n, uint32_t kb, uint32_t kind, uint32_t vb, uint32_t ib,
+                 uint32_t desc, hipStream_t st) {
+    const bool argsort = d_index != nullptr;
+    const uint32_t pw = (uint64_t)n < (1ull << 32) ? 4u : 8u;  // bytes of a position
+    if (argsort && ib < pw) return fail(ctx, RSX_ERR_UNSUPPORTED, "2^32 or more keys need 8-byte indices");
+    const PairsPlan P = pairs_plan(n, kb, argsort ? pw : vb);
+    if (P.route == 2 && (uint64_t)n >= (1ull << 32)) return fail(ctx, RSX_ERR_UNSUPPORTED, "2^32 or more pairs with values too wide to join");
+    int rc = pending_error(ctx);
+    if (rc) return rc;
+    rc = ensure_workspace(ctx, n, &P.inner, st);
+    if (rc) return rc;
+    rc = ensure_any(ctx, 2 * P.half + P.copy, st);
+    if (rc) return rc;
+    Enqueue enq(ctx, st);  // the workspace arrays belong to this call from the first launch on
+    char* w0 = ctx->any_buf;
+    char* w1 = w0 + P.half;
+    const uint32_t es = P.inner.elem_bytes;
+    if (!argsort && vb == 0 && !desc) {  // ascending keys alone: the sort of one array, the workspace as its ping-pong
+        const rsx_layout L{kb, 0, kb, kind};
+        rc = sort_device_locked(ctx, d_keys, w0, n, &L, st);
+        if (rc) return rc;
+        ctx->last_pairs = 1u | es << 8;
+        return RSX_OK;
+    }
+    if (P.route == 1) {
+        rc = launch_pairs_join(ctx, d_keys, d_values, w0, n, kb, P.vb, argsort, kind, desc, st);
+        if (rc) return rc;
+        rc = sort_device_locked(ctx, w0, w1, n, &P.inner, st);
+        if (rc) return rc;
+        if (argsort) rc = launch_pairs_split(ctx, w0, nullptr, d_index, n, kb, P.vb, 2, ib, kind, desc, st);
+        else rc = launch_pairs_split(ctx, w0, d_keys, d_values, n, kb, P.vb, 0, 0, kind, desc, st);
+    } else {
+        char* cp = w1 + P.half;
+        rc = launch_pairs_join(ctx, d_keys, nullptr, w0, n, kb, 4, true, kind, desc, st);
+        if (rc) return rc;
+        RSX_HIP(hipMemcpyAsync(cp, d_values, n * (size_t)vb, hipMemcpyDeviceToDevice, st));
+        rc = sort_device_locked(ctx, w0, w1, n, &P.inner, st);
+        if (rc) return rc;
+        rc = launch_pairs_split(ctx, w0, d_keys, nullptr, n, kb, 4, 1, 0, kind, desc, st);
+        if (rc) return rc;
+        AnyPlan G{};
+        G.inner = P.inner;
+        G.idx_off = pairs_value_offset(kb, 4);
+        rc = launch_gather(ctx, cp, d_values, vb, w0, G, n, st);
+    }
+    if (rc) return rc;
+    ctx->last_pairs = P.route | es << 8;
+    return RSX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -959,6 +1054,7 @@ int rsx_ctx_get_info(rsx_ctx* ctx, int what, uint64_t* out) try {
             *out = (uint64_t)passes | (stat << 8) | (placed << 16) | ((uint64_t)path << 24) | ((uint64_t)ctx->last_route << 28);
             return RSX_OK;
         }
+        case RSX_INFO_LAST_PAIRS: *out = (uint64_t)ctx->last_pairs; return RSX_OK;
         default: return fail(ctx, RSX_ERR_ARG, "unknown info id");
     }
 } catch (...) {
@@ -1047,6 +1143,63 @@ int rsx_sort_device(rsx_ctx* ctx, void* d_data, void* d_tmp, size_t n, const rsx
     DeviceGuard g(ctx->device);
     if (!g.ok) return fail(ctx, RSX_ERR_NODEVICE, "hipSetDevice failed");
     return sort_any_locked(ctx, d_data, d_tmp, n, L, static_cast<hipStream_t>(stream));
+} catch (...) {
+    return RSX_ERR_HIP;
+}
+
+int rsx_ctx_reserve_pairs(rsx_ctx* ctx, size_t n, uint32_t key_bytes, uint32_t value_bytes) try {
+    if (!ctx) return RSX_ERR_ARG;
+    if (!key_widths_ok(key_bytes, RSX_KEY_UNSIGNED) || value_bytes > RSX_MAX_ELEM_BYTES) return fail(ctx, RSX_ERR_ARG, "invalid key or value width");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return fail(ctx, RSX_ERR_NODEVICE, "hipSetDevice failed");
+    int rc = reserve_pairs_one(ctx, n, key_bytes, value_bytes, nullptr);
+    // an argsort with 8-byte indices joins 4-byte positions while n < 2^32: another element size
+    if (!rc && value_bytes == 8 && (uint64_t)n < (1ull << 32)) rc = reserve_pairs_one(ctx, n, key_bytes, 4, nullptr);
+    return rc;
+} catch (...) {
+    return RSX_ERR_NOMEM;
+}
+
+int rsx_sort_pairs_device(rsx_ctx* ctx, void* d_keys, void* d_values, size_t n, uint32_t key_bytes, uint32_t key_kind, uint32_t value_bytes,
+                          int order, void* stream) try {
+    if (!ctx) return RSX_ERR_ARG;
+    if (!key_widths_ok(key_bytes, key_kind)) return fail(ctx, RSX_ERR_ARG, "invalid key width or kind");
+    if (value_bytes > RSX_MAX_ELEM_BYTES) return fail(ctx, RSX_ERR_ARG, "value wider than RSX_MAX_ELEM_BYTES");
+    if (order != RSX_ORDER_ASCENDING && order != RSX_ORDER_DESCENDING) return fail(ctx, RSX_ERR_ARG, "invalid order");
+    if ((d_values == nullptr) != (value_bytes == 0) && (n > 0 || d_values != nullptr)) return fail(ctx, RSX_ERR_ARG, "d_values and value_bytes disagree");
+    if (n == 0) return RSX_OK;
+    if (!d_keys) return fail(ctx, RSX_ERR_ARG, "null device pointer");
+    if (!aligned(d_keys, key_bytes) || (value_bytes && !aligned(d_values, value_align(value_bytes)))) return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
+    if (n == 1) return RSX_OK;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return fail(ctx, RSX_ERR_NODEVICE, "hipSetDevice failed");
+    return pairs_locked(ctx, d_keys, d_values, nullptr, n, key_bytes, key_kind, value_bytes, 0, order == RSX_ORDER_DESCENDING ? 1u : 0u,
+                        static_cast<hipStream_t>(stream));
+} catch (...) {
+    return RSX_ERR_HIP;
+}
+
+int rsx_argsort_device(rsx_ctx* ctx, const void* d_keys, void* d_index, size_t n, uint32_t key_bytes, uint32_t key_kind, uint32_t index_bytes,
+                       int order, void* stream) try {
+    if (!ctx) return RSX_ERR_ARG;
+    if (!key_widths_ok(key_bytes, key_kind)) return fail(ctx, RSX_ERR_ARG, "invalid key width or kind");
+    if (index_bytes != 4 && index_bytes != 8) return fail(ctx, RSX_ERR_ARG, "index_bytes must be 4 or 8");
+    if (order != RSX_ORDER_ASCENDING && order != RSX_ORDER_DESCENDING) return fail(ctx, RSX_ERR_ARG, "invalid order");
+    if (n == 0) return RSX_OK;
+    if (!d_keys || !d_index) return fail(ctx, RSX_ERR_ARG, "null device pointer");
+    if (!aligned(d_keys, key_bytes) || !aligned(d_index, index_bytes)) return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return fail(ctx, RSX_ERR_NODEVICE, "hipSetDevice failed");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (n == 1) {  // the one position
+        RSX_HIP(hipMemsetAsync(d_index, 0, index_bytes, st));
+        return RSX_OK;
+    }
+    return pairs_locked(ctx, const_cast<void*>(d_keys), nullptr, d_index, n, key_bytes, key_kind, 0, index_bytes,
+                        order == RSX_ORDER_DESCENDING ? 1u : 0u, st);
 } catch (...) {
     return RSX_ERR_HIP;
 }

@@ -108,6 +108,7 @@ struct rsx_ctx {
     uint32_t last_route = 0;   // how the last sort reached the kernels: 0 direct, 1 packed re-layout, 2 key-index proxy
     char* any_buf = nullptr;   // routes 1 / 2: the re-laid-out elements or the proxies, and their ping-pong array
     size_t any_bytes = 0;
+    uint32_t last_pairs = 0;   // RSX_INFO_LAST_PAIRS: route of the last pairs / argsort call (1 joined, 2 proxies) | joined element size << 8
     rsx::CleanList clean = {{nullptr, nullptr, nullptr}, {0, 0, 0}};  // what the next count kernel zeroes on its way (the previous sort's control block)
     uint64_t cb_used[2][2] = {{0, 0}, {0, 0}};  // per alternating block: bytes of the top-digit matrix / of count matrix 0 its last sort used
     uint32_t cb_alt = 0;       // which of the two alternating blocks the last uncaptured sort used
@@ -385,5 +386,14 @@ int launch_segment_sort(rsx_ctx* ctx, void* data, void* tmp, size_t n, const rsx
 template <int ES>
 int launch_segcopy(rsx_ctx* ctx, const void* src, void* dst, const uint64_t* so, const uint64_t* dof,
                    const uint64_t* len, uint32_t nseg, hipStream_t st);
+
+// separate key and value arrays <-> joined elements (rsx_pairs.hip, rsx_pairs_kernels.hpp); split modes: 0 keys and
+// values, 1 keys only, 2 the position alone as ib bytes
+int launch_pairs_join(rsx_ctx* ctx, const void* keys, const void* values, void* elems, size_t n, uint32_t kb, uint32_t vb, bool gen,
+                      uint32_t kind, uint32_t desc, hipStream_t st);
+int launch_pairs_split(rsx_ctx* ctx, const void* elems, void* keys, void* values, size_t n, uint32_t kb, uint32_t vb, uint32_t mode, uint32_t ib,
+                       uint32_t kind, uint32_t desc, hipStream_t st);
+uint32_t pairs_elem_bytes(uint32_t kb, uint32_t vb);    // joined element size, 0: none (proxy route)
+uint32_t pairs_value_offset(uint32_t kb, uint32_t vb);  // of the value in the joined element
 
 }  // namespace rsxh

@@ -11,6 +11,8 @@
 //     rsx::radix_sort(T* data, size_t n)            // host slice, in place, blocking (mod.rs:62)
 //     rsx::radix_sort(std::vector<T>& v)
 //     rsx::radix_sort_device(T* d_data, T* d_tmp, size_t n, hipStream_t)   // device-resident
+//     rsx::radix_sort_pairs(K* d_keys, V* d_values, size_t n, bool descending, hipStream_t)   // separate columns
+//     rsx::radix_argsort(const K* d_keys, I* d_index, size_t n, bool descending, hipStream_t)
 // Errors: the reference panics (mod.rs:68,106); here std::runtime_error is thrown.
 // Empty and one-element slices return immediately (the reference panics on an empty
 // slice -- chunks(0), mod.rs:66-70,92 -- there is no output to differ from).
@@ -171,6 +173,37 @@ template <typename T>
 void radix_sort_rows(T* d_data, T* d_tmp, size_t rows, size_t row_len, void* stream = nullptr, Context& ctx = default_context()) {
     const rsx_layout L = RadixDigits<T>::layout();
     ctx.check(rsx_sort_rows_device(ctx.get(), d_data, d_tmp, rows, row_len, &L, stream), "rsx_sort_rows_device");
+}
+
+// Separate key and value arrays on the device (rsx_sort_pairs_device): both sorted in place by key, stably, ascending
+// or descending (larger mapped key first, equal keys in input order).  K: a type with a RadixDigits whose element IS
+// its key (the primitives); V: any trivially copyable type, moved bitwise.  Stream-ordered; the joined elements live
+// in the context's workspace (rsx_ctx_reserve_pairs before a stream capture).
+template <typename K, typename V>
+void radix_sort_pairs(K* d_keys, V* d_values, size_t n, bool descending = false, void* stream = nullptr, Context& ctx = default_context()) {
+    static_assert(std::is_trivially_copyable<V>::value, "values are moved bitwise");
+    const rsx_layout L = RadixDigits<K>::layout();
+    if (L.key_offset != 0 || L.key_bytes != L.elem_bytes) throw std::invalid_argument("radix_sort_pairs: the key type must be its own key");
+    ctx.check(rsx_sort_pairs_device(ctx.get(), d_keys, d_values, n, L.key_bytes, L.key_kind, (uint32_t)sizeof(V),
+                                    descending ? RSX_ORDER_DESCENDING : RSX_ORDER_ASCENDING, stream), "rsx_sort_pairs_device");
+}
+// ... keys alone
+template <typename K>
+void radix_sort_keys(K* d_keys, size_t n, bool descending = false, void* stream = nullptr, Context& ctx = default_context()) {
+    const rsx_layout L = RadixDigits<K>::layout();
+    if (L.key_offset != 0 || L.key_bytes != L.elem_bytes) throw std::invalid_argument("radix_sort_keys: the key type must be its own key");
+    ctx.check(rsx_sort_pairs_device(ctx.get(), d_keys, nullptr, n, L.key_bytes, L.key_kind, 0,
+                                    descending ? RSX_ORDER_DESCENDING : RSX_ORDER_ASCENDING, stream), "rsx_sort_pairs_device");
+}
+// The stable sorting permutation of d_keys (rsx_argsort_device) as uint32_t / int32_t or uint64_t / int64_t indices;
+// the keys are only read.
+template <typename K, typename I>
+void radix_argsort(const K* d_keys, I* d_index, size_t n, bool descending = false, void* stream = nullptr, Context& ctx = default_context()) {
+    static_assert(std::is_integral<I>::value && (sizeof(I) == 4 || sizeof(I) == 8), "indices are 4- or 8-byte integers");
+    const rsx_layout L = RadixDigits<K>::layout();
+    if (L.key_offset != 0 || L.key_bytes != L.elem_bytes) throw std::invalid_argument("radix_argsort: the key type must be its own key");
+    ctx.check(rsx_argsort_device(ctx.get(), d_keys, d_index, n, L.key_bytes, L.key_kind, (uint32_t)sizeof(I),
+                                 descending ? RSX_ORDER_DESCENDING : RSX_ORDER_ASCENDING, stream), "rsx_argsort_device");
 }
 
 // Multi-GPU, one process: slice g lives on the device of ctxs[g]; the concatenation of the slices

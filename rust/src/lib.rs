@@ -43,6 +43,12 @@ extern "C" {
                                     stream: *mut c_void) -> c_int;
     pub fn rsx_sort_rows_device(ctx: *mut RsxCtx, d_data: *mut c_void, d_tmp: *mut c_void, rows: usize, row_len: usize,
                                 layout: *const RsxLayout, stream: *mut c_void) -> c_int;
+    // separate key and value arrays on the device; order: 0 ascending, 1 descending (RSX_ORDER_*)
+    pub fn rsx_sort_pairs_device(ctx: *mut RsxCtx, d_keys: *mut c_void, d_values: *mut c_void, n: usize, key_bytes: u32,
+                                 key_kind: u32, value_bytes: u32, order: c_int, stream: *mut c_void) -> c_int;
+    pub fn rsx_argsort_device(ctx: *mut RsxCtx, d_keys: *const c_void, d_index: *mut c_void, n: usize, key_bytes: u32,
+                              key_kind: u32, index_bytes: u32, order: c_int, stream: *mut c_void) -> c_int;
+    pub fn rsx_ctx_reserve_pairs(ctx: *mut RsxCtx, n: usize, key_bytes: u32, value_bytes: u32) -> c_int;
     pub fn rsx_sort_sharded(ctxs: *const *mut RsxCtx, ndev: u32, d_slices: *const *mut c_void,
                             d_tmps: *const *mut c_void, n_per_dev: *const usize,
                             layout: *const RsxLayout) -> c_int;
