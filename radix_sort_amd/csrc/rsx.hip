@@ -14,31 +14,35 @@ using namespace rsxh;
 
 namespace {
 
-bool layout_ok(const rsx_layout* L) {
+// any_width: what rsx_sort_device / rsx_sort_host / rsx_ctx_reserve / rsx_generate_device / rsx_verify_device accept: any
+// element size and integer keys of any width up to 16 bytes.  Layouts that layout_ok + size_supported refuse reach the
+// kernels through sort_any_locked; every other entry point keeps to the key widths with kernels (bounds* and splitter*:
+// layout_ok alone, any element size; histogram, partition*, segments and sharded sorts: layout_ok + size_supported).
+bool layout_ok(const rsx_layout* L, bool any_width = false) {
     if (!L) return false;
     const uint32_t kb = L->key_bytes;
-    if (!(kb == 1 || kb == 2 || kb == 4 || kb == 8 || kb == 16)) return false;
+    if (any_width ? (kb < 1 || kb > 16) : !(kb == 1 || kb == 2 || kb == 4 || kb == 8 || kb == 16)) return false;
     if (L->key_kind > RSX_KEY_FLOAT) return false;
     if (L->key_kind == RSX_KEY_FLOAT && !(kb == 4 || kb == 8)) return false;
     if (L->elem_bytes == 0 || (uint64_t)L->key_offset + kb > L->elem_bytes) return false;
     return true;
 }
-// What rsx_sort_device / rsx_sort_host / rsx_ctx_reserve / rsx_generate_device / rsx_verify_device accept: any element
-// size and integer keys of any width up to 16 bytes.  Layouts that layout_ok + size_supported refuse reach the kernels
-// through sort_any_locked; every other entry point keeps to layout_ok (bounds* and splitter*: layout_ok alone, any
-// element size; histogram, partition*, segments and sharded sorts: layout_ok + size_supported).
-bool any_layout_ok(const rsx_layout* L) {
-    if (!L) return false;
-    const uint32_t kb = L->key_bytes;
-    if (kb < 1 || kb > 16) return false;
-    if (L->key_kind > RSX_KEY_FLOAT) return false;
-    if (L->key_kind == RSX_KEY_FLOAT && !(kb == 4 || kb == 8)) return false;
-    if (L->elem_bytes == 0 || (uint64_t)L->key_offset + kb > L->elem_bytes) return false;
-    return true;
+// the launchers of one element size (rsx_es.hip), looked up once per call; null: a size without kernels, which
+// check_common refuses
+const EsLaunchers* launchers_for(uint32_t es) {
+    switch (es) {
+        case 1: return &es_launchers<1>();
+        case 2: return &es_launchers<2>();
+        case 4: return &es_launchers<4>();
+        case 8: return &es_launchers<8>();
+        case 12: return &es_launchers<12>();
+        case 16: return &es_launchers<16>();
+        case 24: return &es_launchers<24>();
+        case 32: return &es_launchers<32>();
+        default: return nullptr;
+    }
 }
-bool size_supported(uint32_t es) {
-    return es == 1 || es == 2 || es == 4 || es == 8 || es == 12 || es == 16 || es == 24 || es == 32;
-}
+bool size_supported(uint32_t es) { return launchers_for(es) != nullptr; }
 uint32_t elem_align(uint32_t es) {
     switch (es) {
         case 1: return 1;
@@ -74,45 +78,12 @@ struct Enqueue {
     }
 };
 
-uint32_t bucket_cap_for(uint32_t es) {
-    switch (es) {
-        case 8: return bucket_cap(8);
-        case 12: return bucket_cap(12);
-        case 16: return bucket_cap(16);
-        case 24: return bucket_cap(24);
-        case 32: return bucket_cap(32);
-        default: return bucket_cap(4);
-    }
-}
-uint32_t wide_cap_for(uint32_t es) {  // what the hybrid's largest (1024-thread) workgroup holds
-    switch (es) {
-        case 8: return bucket_cape(8, wide_kpt_for(8), 1024);
-        case 12: return bucket_cape(12, wide_kpt_for(12), 1024);
-        case 16: return bucket_cape(16, wide_kpt_for(16), 1024);
-        case 24: return bucket_cape(24, wide_kpt_for(24), 1024);
-        case 32: return bucket_cape(32, wide_kpt_for(32), 1024);
-        default: return bucket_cape(4, wide_kpt_for(4), 1024);
-    }
-}
-uint64_t mid_max_for(uint32_t es) {
-    switch (es) {
-        case 2: return mid_max_elems(2);
-        case 4: return mid_max_elems(4);
-        case 8: return mid_max_elems(8);
-        case 12: return mid_max_elems(12);
-        case 16: return mid_max_elems(16);
-        case 24: return mid_max_elems(24);
-        case 32: return mid_max_elems(32);
-        default: return 0;
-    }
-}
-
 size_t status_bytes_for(const rsx_ctx* ctx, size_t n, uint32_t es) {
     const RegionGeom g = make_geom(ctx, n, es);
-    size_t b = (size_t)status_rows(g, es) * RADIX * (status32(g) ? 4 : 8);
-    if ((uint64_t)n <= mid_max_for(es)) {  // the bucket split of a middle-size sort has more, smaller tiles
+    size_t b = (size_t)status_rows(g) * RADIX * (status32(g) ? 4 : 8);
+    if ((uint64_t)n <= mid_max_elems((int)es)) {  // the bucket split of a middle-size sort has more, smaller tiles
         const RegionGeom gs = make_geom(ctx, n, es, true);
-        const size_t bs = (size_t)status_rows(gs, es) * RADIX * 4;
+        const size_t bs = (size_t)status_rows(gs) * RADIX * 4;
         if (bs > b) b = bs;
     }
     return b;
@@ -168,62 +139,6 @@ int ensure_workspace(rsx_ctx* ctx, size_t n, const rsx_layout* L, hipStream_t st
     return RSX_OK;
 }
 
-#define RSX_DISPATCH_ES(es, FN, ...)                           \
-    switch (es) {                                              \
-        case 1: return FN<1>(__VA_ARGS__);                     \
-        case 2: return FN<2>(__VA_ARGS__);                     \
-        case 4: return FN<4>(__VA_ARGS__);                     \
-        case 8: return FN<8>(__VA_ARGS__);                     \
-        case 12: return FN<12>(__VA_ARGS__);                   \
-        case 16: return FN<16>(__VA_ARGS__);                   \
-        case 24: return FN<24>(__VA_ARGS__);                   \
-        case 32: return FN<32>(__VA_ARGS__);                   \
-        default: return fail(ctx, RSX_ERR_UNSUPPORTED, "element size has no device kernel"); \
-    }
-
-int hist_dispatch(rsx_ctx* ctx, const void* src, const RegionGeom& g, const rsx_layout* L, uint32_t digit,
-                  unsigned long long* J, unsigned long long* jclear, bool clear_status, hipStream_t st) {
-    RSX_DISPATCH_ES(L->elem_bytes, launch_hist, ctx, src, g, L, digit, J, jclear, clear_status, st)
-}
-int hist2_dispatch(rsx_ctx* ctx, const void* src, const RegionGeom& g, const rsx_layout* L, uint32_t digit,
-                   unsigned long long* J, uint32_t digit2, unsigned long long* J2, unsigned long long* jclear, hipStream_t st) {
-    RSX_DISPATCH_ES(L->elem_bytes, launch_hist2, ctx, src, g, L, digit, J, digit2, J2, jclear, st)
-}
-int mid_split_dispatch(rsx_ctx* ctx, const void* src, void* dst, size_t n, const rsx_layout* L, hipStream_t st) {
-    RSX_DISPATCH_ES(L->elem_bytes, launch_mid_split, ctx, src, dst, n, L, st)
-}
-int bucket_dispatch(rsx_ctx* ctx, const void* src, void* dst, const RegionGeom& g, const rsx_layout* L, hipStream_t st) {
-    RSX_DISPATCH_ES(L->elem_bytes, launch_bucket_sort, ctx, src, dst, g, L, st)
-}
-int wideplan_dispatch(rsx_ctx* ctx, const void* src, size_t n, const rsx_layout* L, WidePlan* plan, hipStream_t st) {
-    RSX_DISPATCH_ES(L->elem_bytes, launch_wideplan, ctx, src, n, L, plan, st)
-}
-int count16top_dispatch(rsx_ctx* ctx, const void* src, size_t n, const rsx_layout* L, WidePlan* plan, uint32_t* P, uint32_t parts,
-                        uint32_t region_shift, uint32_t k, hipStream_t st) {
-    RSX_DISPATCH_ES(L->elem_bytes, launch_count16top, ctx, src, n, L, plan, P, parts, region_shift, k, st)
-}
-int marginal16_dispatch(rsx_ctx* ctx, const uint32_t* P, uint32_t parts, uint32_t k, const RegionGeom& g, const rsx_layout* L,
-                        unsigned long long* J, unsigned long long* jclear, hipStream_t st) {
-    RSX_DISPATCH_ES(L->elem_bytes, launch_marginal16, ctx, P, parts, k, g, J, jclear, st)
-}
-int bucket16_dispatch(rsx_ctx* ctx, void* data, void* scratch, size_t n, const rsx_layout* L, const uint64_t* starts, const WidePlan* plan,
-                      hipStream_t st) {
-    RSX_DISPATCH_ES(L->elem_bytes, launch_bucket16, ctx, data, scratch, n, L, starts, plan, st)
-}
-int small_dispatch(rsx_ctx* ctx, void* data, size_t n, const rsx_layout* L, hipStream_t st) {
-    RSX_DISPATCH_ES(L->elem_bytes, launch_small_sort, ctx, data, n, L, st)
-}
-int sweep_dispatch(rsx_ctx* ctx, const void* src, void* dst, const RegionGeom& g, const rsx_layout* L,
-                   uint32_t digit, const unsigned long long* J, unsigned long long* jnext, unsigned long long* jzero,
-                   int xf, hipStream_t st) {
-    RSX_DISPATCH_ES(L->elem_bytes, launch_sweep, ctx, src, dst, g, L, digit, J, jnext, jzero, xf, st)
-}
-
-int segment_dispatch(rsx_ctx* ctx, void* data, void* tmp, size_t n, const rsx_layout* L, const uint64_t* offsets, uint64_t nseg, uint64_t row_len,
-                     uint64_t max_len, uint32_t* launched, hipStream_t st) {
-    RSX_DISPATCH_ES(L->elem_bytes, launch_segment_sort, ctx, data, tmp, n, L, offsets, nseg, row_len, max_len, launched, st)
-}
-
 // the 256 digit totals of a count matrix -> d_counts
 int launch_totals(rsx_ctx* ctx, const RegionGeom& g, const unsigned long long* J, uint64_t* d_counts, hipStream_t st) {
     LaunchTimer lt(ctx, RSX_PROF_SCAN, st);
@@ -232,15 +147,15 @@ int launch_totals(rsx_ctx* ctx, const RegionGeom& g, const unsigned long long* J
     return RSX_OK;
 }
 
-// Picks the control block of the sort (or lone pass) being enqueued -- every pass's tickets and roll-call words, the
+// Fills `run` for the sort (or lone pass) being enqueued: picks its control block -- every pass's tickets and roll-call words, the
 // top digit's count matrix and count matrix 0, all zero -- and tells the count kernel which block to zero on its way:
 // the one the previous sort used (rsx_internal.hpp, aux layout).  A sort that is being captured into a graph uses
 // block 2 and zeroes it itself (a replay cannot alternate); so does the sort after a failed enqueue, for both blocks.
-int begin_control(rsx_ctx* ctx, hipStream_t st, const RegionGeom& g, bool uses_jt) {
-    ctx->clean = CleanList{{nullptr, nullptr, nullptr}, {0, 0, 0}};
+int begin_control(rsx_ctx* ctx, SortRun& run, hipStream_t st, const RegionGeom& g, bool uses_jt) {
+    run = SortRun{};
     const uint64_t used = (uint64_t)J_REPL * g.num_regions * RADIX * sizeof(uint64_t);  // prefix of a count matrix in use
     if (capturing(st)) {
-        ctx->cb = 2;
+        run.cb = 2;
         hipLaunchKernelGGL(rsx_zero16_kernel, dim3(64), dim3(256), 0, st, reinterpret_cast<uint4*>(cb_of(ctx, 2)), (uint64_t)(CB_BYTES / 16));
         RSX_HIP(hipGetLastError());
         return RSX_OK;
@@ -251,15 +166,15 @@ int begin_control(rsx_ctx* ctx, hipStream_t st, const RegionGeom& g, bool uses_j
     }
     const uint32_t prev = ctx->cb_alt;
     ctx->cb_alt ^= 1u;
-    ctx->cb = ctx->cb_alt;
-    ctx->clean.p[0] = reinterpret_cast<uint4*>(cb_of(ctx, prev) + CB_TICKETS);
-    ctx->clean.n16[0] = CB_JT / 16;
-    ctx->clean.p[1] = reinterpret_cast<uint4*>(cb_of(ctx, prev) + CB_JT);
-    ctx->clean.n16[1] = ctx->cb_used[prev][0] / 16;
-    ctx->clean.p[2] = reinterpret_cast<uint4*>(cb_of(ctx, prev) + CB_J0);
-    ctx->clean.n16[2] = ctx->cb_used[prev][1] / 16;
-    ctx->cb_used[ctx->cb][0] = uses_jt ? used : 0;
-    ctx->cb_used[ctx->cb][1] = used;
+    run.cb = ctx->cb_alt;
+    run.clean.p[0] = reinterpret_cast<uint4*>(cb_of(ctx, prev) + CB_TICKETS);
+    run.clean.n16[0] = CB_JT / 16;
+    run.clean.p[1] = reinterpret_cast<uint4*>(cb_of(ctx, prev) + CB_JT);
+    run.clean.n16[1] = ctx->cb_used[prev][0] / 16;
+    run.clean.p[2] = reinterpret_cast<uint4*>(cb_of(ctx, prev) + CB_J0);
+    run.clean.n16[2] = ctx->cb_used[prev][1] / 16;
+    ctx->cb_used[run.cb][0] = uses_jt ? used : 0;
+    ctx->cb_used[run.cb][1] = used;
     ctx->cb_dirty = true;  // until the enqueue has gone through (end_control)
     return RSX_OK;
 }
@@ -276,7 +191,7 @@ bool direct_layout(const rsx_layout* L) { return layout_ok(L) && size_supported(
 int check_any(rsx_ctx* ctx, const rsx_layout* L) {
     if (!ctx) return RSX_ERR_ARG;
     if (direct_layout(L)) return RSX_OK;
-    if (!any_layout_ok(L)) return fail(ctx, RSX_ERR_ARG, "invalid rsx_layout");
+    if (!layout_ok(L, true)) return fail(ctx, RSX_ERR_ARG, "invalid rsx_layout");
     if (L->elem_bytes > RSX_MAX_ELEM_BYTES) return fail(ctx, RSX_ERR_UNSUPPORTED, "element larger than RSX_MAX_ELEM_BYTES");
     return RSX_OK;
 }
@@ -295,7 +210,7 @@ struct DeviceGuard {
 
 // A kernel of this context gave up a bounded wait (the word is host-visible: no sync needed to see it).
 int pending_error(rsx_ctx* ctx) {
-    if (ctx->host_err && *reinterpret_cast<volatile uint32_t*>(ctx->host_err))
+    if (ctx->host_err && host_word(ctx, HV_ERROR))
         return fail(ctx, RSX_ERR_INTERNAL, "an earlier sort on this context gave up a device-side wait; its output is invalid (rsx_ctx_check clears the condition)");
     return RSX_OK;
 }
@@ -303,26 +218,23 @@ int pending_error(rsx_ctx* ctx) {
 // The D LSD passes of mod.rs:84-169 on the device: count phase of pass 0 (later passes are counted by the sweep before
 // them), then D sweeps with ping-pong; the prefix phase (mod.rs:110-120) is the prologue of each sweep.  mid: a
 // middle-size sort whose first sweep also reports what the top digit looks like (mid_mode 2).
-int lsd_passes(rsx_ctx* ctx, void* d_data, void* d_tmp, size_t n, const rsx_layout* L, const RegionGeom& geom, bool mid, uint32_t mid_mode,
-               hipStream_t st) {
+int lsd_passes(rsx_ctx* ctx, const EsLaunchers& K, SortRun& run, void* d_data, void* d_tmp, size_t n, const rsx_layout* L, const RegionGeom& geom,
+               bool mid, uint32_t mid_mode, hipStream_t st) {
     const uint32_t D = L->key_bytes;
     int rc;
-    if (mid) rc = hist2_dispatch(ctx, d_data, geom, L, 0, J_of(ctx, 0), D - 1, JT_of(ctx), J_of(ctx, 1), st);
-    else rc = hist_dispatch(ctx, d_data, geom, L, 0, J_of(ctx, 0), D > 1 ? J_of(ctx, 1) : nullptr, true, st);
+    if (mid) rc = K.hist2(ctx, run, d_data, geom, L, 0, J_of(ctx, run, 0), D - 1, JT_of(ctx, run), J_of(ctx, run, 1), st);
+    else rc = K.hist(ctx, run, d_data, geom, L, 0, J_of(ctx, run, 0), D > 1 ? J_of(ctx, run, 1) : nullptr, true, st);
     if (rc) return rc;
     ctx->last_sort_passes = D;
-    ctx->cb_last = ctx->cb;
+    ctx->cb_last = run.cb;
     for (uint32_t d = 0; d < D; ++d) {
         const void* src = (d % 2 == 0) ? d_data : d_tmp;
         void* dst = (d % 2 == 0) ? d_tmp : d_data;
-        unsigned long long* jnext = (d + 1 < D) ? J_of(ctx, (d + 1) % 3) : nullptr;
-        unsigned long long* jzero = (d + 2 < D) ? J_of(ctx, (d + 2) % 3) : nullptr;
+        unsigned long long* jnext = (d + 1 < D) ? J_of(ctx, run, (d + 1) % 3) : nullptr;
+        unsigned long long* jzero = (d + 2 < D) ? J_of(ctx, run, (d + 2) % 3) : nullptr;
         const int xf = (d == 0 ? 1 : 0) | (d + 1 == D ? 2 : 0);  // key map on at the first, off at the last pass
-        ctx->pass_index = d;
-        ctx->pass_last = d + 1 == D;
-        ctx->pass_mid = d == 0 ? mid_mode : 0u;  // (2: the first LSD pass also reports whether the top digit's buckets would fit)
-        rc = sweep_dispatch(ctx, src, dst, geom, L, d, J_of(ctx, d % 3), jnext, jzero, xf, st);  // mod.rs:121-168
-        ctx->pass_mid = 0;
+        const SweepPass pass{d, d + 1 == D, d == 0 ? mid_mode : 0u};  // (mid 2: the first LSD pass also reports whether the top digit's buckets would fit)
+        rc = K.sweep(ctx, run, pass, src, dst, geom, L, d, J_of(ctx, run, d % 3), jnext, jzero, xf, st);  // mod.rs:121-168
         if (rc) return rc;
     }
     if (D % 2 == 1)  // odd-D copy-back (mod.rs:170-174)
@@ -330,235 +242,256 @@ int lsd_passes(rsx_ctx* ctx, void* d_data, void* d_tmp, size_t n, const rsx_layo
     return RSX_OK;
 }
 
-// body of rsx_sort_device; caller holds ctx->mu and has set the device
-int sort_device_locked(rsx_ctx* ctx, void* d_data, void* d_tmp, size_t n, const rsx_layout* L, hipStream_t st) {
-    int rc = pending_error(ctx);
+// ---- the paths of a sort, in the order sort_device_locked tries them ----
+int ensure_ovf16(rsx_ctx* ctx, hipStream_t st) {
+    if (ctx->ovf16) return RSX_OK;
+    RSX_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->ovf16), 65536 * sizeof(uint32_t)));
+    RSX_HIP(hipMemsetAsync(ctx->ovf16, 0, 65536 * sizeof(uint32_t), st));  // kept all zero between sorts by rsx_total16_kernel
+    return RSX_OK;
+}
+
+// u16 / i16 arrays of at least 2^23 elements: the element is its two-byte key, so the 65536 counts ARE the sorted
+// array: count (one read), write the runs (one write) -- instead of D = 2 passes of each.  The count kernel's
+// per-workgroup counters (128 KiB each), the bin totals and the bin-block sums live in d_tmp.
+int sort_counting16(rsx_ctx* ctx, void* d_data, void* d_tmp, size_t n, const rsx_layout* L, hipStream_t st) {
+    int rc = ensure_ovf16(ctx, st);
     if (rc) return rc;
-    rc = ensure_workspace(ctx, n, L, st);
-    if (rc) return rc;
-    Enqueue enq(ctx, st);
-    const uint32_t D = L->key_bytes;  // T::NUMBER_OF_DIGITS
-    const bool counting_path = L->elem_bytes == 1 && !(ctx->options & OPT_GENERAL_BYTES);  // no sweep follows
-    ctx->last_sort_passes = 0;
-    ctx->last_path = 0;
-    ctx->last_route = 0;
-    // at most one tile: all D passes in one launch of one workgroup (rsx_small_kernel.hpp)
-    if (!counting_path && n <= (size_t)512 * kpt_for((int)L->elem_bytes) && !(ctx->options & OPT_NO_SMALL_SORT)) {  // one 512-thread tile
-        ctx->last_path = 1;
-        return small_dispatch(ctx, d_data, n, L, st);
-    }
-    // u16 / i16 arrays of at least 2^23 elements: the element is its two-byte key, so the 65536 counts ARE the sorted
-    // array: count (one read), write the runs (one write) -- instead of D = 2 passes of each.  The count kernel's
-    // per-workgroup counters (128 KiB each), the bin totals and the bin-block sums live in d_tmp.
-    if (L->elem_bytes == 2 && L->key_bytes == 2 && n >= ((size_t)1 << 23) && !(ctx->options & OPT_GENERAL_BYTES) &&
-        (ctx->ovf16 != nullptr || !capturing(st))) {
-        if (!ctx->ovf16) {
-            RSX_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->ovf16), 65536 * sizeof(uint32_t)));
-            RSX_HIP(hipMemsetAsync(ctx->ovf16, 0, 65536 * sizeof(uint32_t), st));  // kept all zero between sorts by rsx_total16_kernel
-        }
-        const size_t tail = 65536 * sizeof(uint64_t) + 256 * sizeof(uint64_t);
-        size_t parts = (n * 2 - tail) / (32768 * sizeof(uint32_t));
-        if (parts > (size_t)ctx->num_cu) parts = (size_t)ctx->num_cu;
-        uint32_t* P = static_cast<uint32_t*>(d_tmp);
-        uint64_t* tot = reinterpret_cast<uint64_t*>(static_cast<char*>(d_tmp) + parts * 32768 * sizeof(uint32_t));
-        uint64_t* BT = tot + 65536;
-        const uint32_t xor_mask = L->key_kind == RSX_KEY_SIGNED ? 0x8000u : 0u;
-        ensure_lds(ctx, reinterpret_cast<const void*>(rsx_count16_kernel), 131072);
-        {
-            LaunchTimer lt(ctx, RSX_PROF_HIST, st);
-            hipLaunchKernelGGL(rsx_count16_kernel, dim3((uint32_t)parts), dim3(1024), 131072, st, static_cast<const uint16_t*>(d_data),
-                               (uint64_t)n, xor_mask, P, ctx->ovf16);
-            RSX_HIP(hipGetLastError());
-        }
-        {
-            LaunchTimer lt(ctx, RSX_PROF_SCAN, st);
-            hipLaunchKernelGGL(rsx_total16_kernel, dim3(256), dim3(256), 0, st, P, (uint32_t)parts, ctx->ovf16, tot, BT);
-            RSX_HIP(hipGetLastError());
-        }
-        LaunchTimer lt(ctx, RSX_PROF_OTHER, st);
-        hipLaunchKernelGGL(rsx_expand16_kernel, dim3((uint32_t)ctx->num_cu * 8), dim3(256), 0, st, static_cast<uint16_t*>(d_data), (uint64_t)n, tot,
-                           BT, xor_mask);
+    const size_t tail = 65536 * sizeof(uint64_t) + 256 * sizeof(uint64_t);
+    size_t parts = (n * 2 - tail) / (32768 * sizeof(uint32_t));
+    if (parts > (size_t)ctx->num_cu) parts = (size_t)ctx->num_cu;
+    uint32_t* P = static_cast<uint32_t*>(d_tmp);
+    uint64_t* tot = reinterpret_cast<uint64_t*>(static_cast<char*>(d_tmp) + parts * 32768 * sizeof(uint32_t));
+    uint64_t* BT = tot + 65536;
+    const uint32_t xor_mask = L->key_kind == RSX_KEY_SIGNED ? 0x8000u : 0u;
+    ensure_lds(ctx, reinterpret_cast<const void*>(rsx_count16_kernel), 131072);
+    {
+        LaunchTimer lt(ctx, RSX_PROF_HIST, st);
+        hipLaunchKernelGGL(rsx_count16_kernel, dim3((uint32_t)parts), dim3(1024), 131072, st, static_cast<const uint16_t*>(d_data),
+                           (uint64_t)n, xor_mask, P, ctx->ovf16);
         RSX_HIP(hipGetLastError());
-        ctx->last_path = 4;
-        return RSX_OK;
     }
-    // Wide keys, large arrays (rsx_mid_kernels.hpp): two passes through memory for the top 16 bits, the rest in LDS --
-    // when the count of those 16 bits says that every bucket fits a workgroup.  That is known on the device only, so
-    // BOTH kernel sequences are enqueued, gated on the verdict word rsx_scan16_kernel writes (a launch that returns at
-    // once costs ~5 us: nothing beside milliseconds).  A refused try costs its count (one read of the array): the
-    // verdict is also written host-visibly, and after a refusal the context goes 15 sorts without trying.
-    const uint32_t es = L->elem_bytes;
+    {
+        LaunchTimer lt(ctx, RSX_PROF_SCAN, st);
+        hipLaunchKernelGGL(rsx_total16_kernel, dim3(256), dim3(256), 0, st, P, (uint32_t)parts, ctx->ovf16, tot, BT);
+        RSX_HIP(hipGetLastError());
+    }
+    LaunchTimer lt(ctx, RSX_PROF_OTHER, st);
+    hipLaunchKernelGGL(rsx_expand16_kernel, dim3((uint32_t)ctx->num_cu * 8), dim3(256), 0, st, static_cast<uint16_t*>(d_data), (uint64_t)n, tot,
+                       BT, xor_mask);
+    RSX_HIP(hipGetLastError());
+    ctx->last_path = 4;
+    return RSX_OK;
+}
+
+// Wide keys, large arrays (rsx_mid_kernels.hpp): two passes through memory for the top 16 bits, the rest in LDS --
+// when the count of those 16 bits says that every bucket fits a workgroup.  That is known on the device only, so
+// BOTH kernel sequences are enqueued, gated on the verdict word rsx_scan16_kernel writes (a launch that returns at
+// once costs ~5 us: nothing beside milliseconds).  A refused try costs its count (one read of the array): the
+// verdict is also written host-visibly, and after a refusal the context goes 15 sorts without trying.
+// what the hybrid's largest (1024-thread) workgroup holds
+uint32_t wide_cap(uint32_t es) { return bucket_cape((int)es, wide_kpt_for((int)es), 1024); }
+// whether this sort is to try it
+bool wide_forecast(rsx_ctx* ctx, size_t n, const rsx_layout* L, hipStream_t st) {
+    const uint32_t es = L->elem_bytes, D = L->key_bytes;
     // Where it pays (measured, uniform keys, LSD passes / hybrid): keys of 8 and 16 bytes everywhere above the middle
     // sizes -- u64 2^23 x1.34, 2^26 x1.29, 2^28 x1.9; (u64,u64) 2^22 x1.3, 2^26 x1.9; u128 2^22 x2.4, 2^26 x3.8 (small
     // buckets are sorted in groups, rsx_bucket16_kernel) --; 4-byte keys in 8-byte and wider elements (two of four passes
     // in LDS) x1.2 from 2 GiB on; (u32,u32) x1.09 at 1 GiB already (2^27: 1.99 -> 1.83 ms), x0.88 at 2^26.
     const bool wide_type = es >= 8 && D >= 4;
     const size_t wide_floor = D >= 8 ? 0 : es == 8 ? ((size_t)1 << 30) : ((size_t)2 << 30);
-    const bool wide_size = wide_type && (uint64_t)n > mid_max_for(es);
+    const bool wide_size = wide_type && (uint64_t)n > mid_max_elems((int)es);
     bool wide = false;
     if (ctx->wide_mode == 2) {
         wide = wide_type && n >= 65536;
     } else if (((ctx->wide_mode == 1 && n * (size_t)es >= wide_floor) || ctx->wide_mode == 3) && wide_size &&
-               (uint64_t)n / 65536u < (uint64_t)wide_cap_for(es)) {  // (the real test is the device's, on the actual counts)
+               (uint64_t)n / 65536u < (uint64_t)wide_cap(es)) {  // (the real test is the device's, on the actual counts)
         // the last try's verdict (1 taken, 2 refused) counts for arrays like the one it was given on: same layout, n
         // within a factor of two (the multi-GPU drivers sort value ranges of slightly different lengths)
-        volatile uint32_t* hint = reinterpret_cast<volatile uint32_t*>(ctx->host_err) + 9;
+        volatile uint32_t& hint = host_word(ctx, HV_WIDE_HINT);
         const uint64_t sig = 1ull | (uint64_t)(63 - __builtin_clzll((unsigned long long)n)) << 8 | (uint64_t)es << 16 | (uint64_t)L->key_offset << 24 |
                              (uint64_t)D << 32 | (uint64_t)L->key_kind << 40;
         if (ctx->wide_skip > 0 && sig == ctx->wide_refused_sig) {
             --ctx->wide_skip;
-        } else if (*hint == 2u && sig == ctx->wide_tried_sig) {
-            *hint = 0;
+        } else if (hint == 2u && sig == ctx->wide_tried_sig) {
+            hint = 0;
             ctx->wide_skip = 15;
             ctx->wide_refused_sig = sig;
         } else {
-            if (*hint == 2u) *hint = 0;
+            if (hint == 2u) hint = 0;
             wide = true;
             ctx->wide_tried_sig = sig;
         }
     }
-    if (wide && (ctx->ovf16 == nullptr || ctx->wide_buf == nullptr) && capturing(st)) wide = false;
-    if (wide) {
-        if (!ctx->ovf16) {
-            RSX_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->ovf16), 65536 * sizeof(uint32_t)));
-            RSX_HIP(hipMemsetAsync(ctx->ovf16, 0, 65536 * sizeof(uint32_t), st));
-        }
-        if (!ctx->wide_buf) {
-            RSX_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->wide_buf), WIDE_PLAN_OFFSET + sizeof(WidePlan)));
-            RSX_HIP(hipMemsetAsync(reinterpret_cast<char*>(ctx->wide_buf) + WIDE_PLAN_OFFSET, 0, sizeof(WidePlan), st));  // (plan_or, plan_done)
-        }
-        uint64_t* tot = reinterpret_cast<uint64_t*>(ctx->wide_buf);
-        uint64_t* BT = tot + 65536;
-        uint64_t* starts = BT + 256;
-        WidePlan* plan = reinterpret_cast<WidePlan*>(reinterpret_cast<char*>(ctx->wide_buf) + WIDE_PLAN_OFFSET);
-        const uint32_t* verdict = &plan->verdict;
-        const RegionGeom geom = make_geom(ctx, n, es);
-        // the count's workgroups: k per region of the sweeps' geometry where the scratch array holds their counters
-        // (128 KiB each) -- then the first sweep's count matrix is a marginal of those counters -- and no counter can
-        // overflow when the hybrid is taken (the device's verdict: every bucket fits LDS, so fewer than 0x8000 elements);
-        // else flat shares, and a count kernel of its own for that sweep
-        size_t parts = n * (size_t)es / (32768 * sizeof(uint32_t));
-        if (parts > (size_t)ctx->num_cu) parts = (size_t)ctx->num_cu;
-        static_assert(bucket_cape(8, wide_kpt_for(8), 1024) < 0x8000u && bucket_cape(4, wide_kpt_for(4), 1024) < 0x8000u, "a bucket that fits LDS must not overflow a 16-bit counter");
-        uint32_t k = ctx->wide_mode == 2 ? 0u : (uint32_t)(parts / geom.num_regions);
-        if (k > 0) parts = (size_t)k * geom.num_regions;
-        rc = wideplan_dispatch(ctx, d_data, n, L, plan, st);
-        if (rc) return rc;
-        rc = count16top_dispatch(ctx, d_data, n, L, plan, static_cast<uint32_t*>(d_tmp), (uint32_t)parts, geom.region_shift, k, st);  // partial counts in d_tmp
-        if (rc) return rc;
-        {
-            LaunchTimer lt(ctx, RSX_PROF_SCAN, st);
-            hipLaunchKernelGGL(rsx_total16_kernel, dim3(256), dim3(256), 0, st, static_cast<const uint32_t*>(d_tmp), (uint32_t)parts, ctx->ovf16, tot, BT);
-            RSX_HIP(hipGetLastError());
-            // which form of the bucket kernel runs is the device's choice too (launch_bucket16 enqueues them all):
-            // groups of small buckets are on offer when the AVERAGE bucket is small (keys of at least 8 bytes)
-            const uint64_t cap1024 = wide_big_form((int)es, n) ? wide_cap_for(es) : bucket_cap_for(es), cap512 = bucket_cap_for(es) / 2, avg = (uint64_t)n / 65536u;
-            uint32_t gs = 0;
-            if (D >= 8 && ctx->bucket_group)
-                while (gs < 6 && (avg << (gs + 1)) <= cap512 * 3 / 4) ++gs;
-            hipLaunchKernelGGL(rsx_scan16_kernel, dim3(256), dim3(256), 0, st, tot, BT, starts, cap512 / 2, cap512, cap1024, gs >= 2 ? gs : 0u,
-                               ctx->wide_mode == 2 ? 1u : 0u, (uint64_t)bucket_cape((int)es, medium_kpt_for((int)es), 1024) * 150u, (uint64_t)n / 64u, plan, ctx->host_err_dev + 9);
-            RSX_HIP(hipGetLastError());
-        }
-        rc = begin_control(ctx, st, geom, false);
-        if (rc) return rc;
-        const CleanList clean = ctx->clean;  // whichever count kernel runs does the cleaning
-        ctx->cb_last = ctx->cb;
-        // sequence 1 (verdict 1): LSD passes on digits D-2 and D-1, then every 16-bit bucket in LDS
-        ctx->gate = Gate{verdict, VERDICT_PATH_MASK, VERDICT_HYBRID};
-        if (k > 0) {
-            rc = marginal16_dispatch(ctx, static_cast<const uint32_t*>(d_tmp), (uint32_t)parts, k, geom, L, J_of(ctx, 0), J_of(ctx, 1), st);
-        } else {  // (forced mode: counters may have overflowed; a count kernel of its own, its digit from the plan)
-            ctx->spec_dev = &plan->specs[0];
-            rc = hist_dispatch(ctx, d_data, geom, L, D - 2, J_of(ctx, 0), J_of(ctx, 1), true, st);
-            ctx->spec_dev = nullptr;
-        }
-        if (rc == RSX_OK) {  // (the two digits of the window come from the plan, not from the digit index given here)
-            ctx->pass_index = 0;
-            ctx->pass_last = false;
-            ctx->spec_dev = &plan->specs[0];
-            rc = sweep_dispatch(ctx, d_data, d_tmp, geom, L, D - 2, J_of(ctx, 0), J_of(ctx, 1), nullptr, 1, st);  // keys mapped on load
-        }
-        if (rc == RSX_OK) {
-            ctx->pass_index = 1;
-            ctx->pass_last = true;
-            ctx->spec_dev = &plan->specs[1];
-            rc = sweep_dispatch(ctx, d_tmp, d_data, geom, L, D - 1, J_of(ctx, 1), nullptr, nullptr, 0, st);  // ... and stay mapped
-        }
-        ctx->spec_dev = nullptr;
-        if (rc == RSX_OK) rc = bucket16_dispatch(ctx, d_data, d_tmp, n, L, starts, plan, st);
-        // sequence 2 (verdict 2): the D LSD passes
-        if (rc == RSX_OK) {
-            ctx->gate = Gate{verdict, VERDICT_PATH_MASK, VERDICT_LSD};
-            ctx->clean = clean;
-            rc = lsd_passes(ctx, d_data, d_tmp, n, L, geom, false, 0, st);
-        }
-        ctx->gate = Gate{nullptr, 0u, 0u};
-        if (rc) return rc;
-        ctx->last_sort_passes = D;
-        ctx->last_path = 5;
-        end_control(ctx);
-        return RSX_OK;
-    }
-    // Middle sizes (more than one tile, up to mid_max_elems): the count kernel also counts the MOST significant digit.
-    // If that digit spreads the array over its 256 buckets so that each fits a workgroup's LDS, one sweep makes the
-    // buckets and rsx_bucket_sort_kernel sorts each by the remaining digits: 4 launches and two trips through memory
-    // instead of D + 2 and D.  Whether it does is known on the device only, and a launch costs ~4 us even when it
-    // returns at once, so the host FORECASTS from what the previous middle-size sort reported (a host-visible word,
-    // read without synchronising: it may lag, and either way the result is right -- a bucket that does not fit after
-    // all is sorted through memory by its one workgroup, slowly, after which the context keeps to LSD passes for a while).
-    const bool mid = !counting_path && D >= 2 && (uint64_t)n <= mid_max_for(L->elem_bytes) && !(ctx->options & OPT_NO_MID_SORT);
-    uint32_t mid_mode = 0;
-    if (mid) {
-        const uint32_t hint = reinterpret_cast<volatile uint32_t*>(ctx->host_err)[8];  // 0 nothing yet, 1 / 3 fits (a small / a large workgroup), 2 does not
-        if (ctx->mid_choice == 1 && hint == 2 && ctx->mid_cooldown == 0) ctx->mid_cooldown = 8;  // a split met a skewed input
-        if (ctx->mid_cooldown > 0) {
-            --ctx->mid_cooldown;
-            mid_mode = 2;
-        } else {
-            mid_mode = hint == 2 ? 2u : 1u;
-        }
-        if (ctx->mid_force) mid_mode = ctx->mid_force;
-        ctx->mid_choice = mid_mode;
-        ctx->bucket_small = hint == 1 && (uint64_t)n <= 256ull * 2048ull;
-    }
-    if (mid_mode == 1) {  // bucket split (count, scan, scatter: rsx_mid_kernels.hpp), then every bucket sorted in LDS
-        const RegionGeom gs = make_geom(ctx, n, L->elem_bytes, true);
-        rc = mid_split_dispatch(ctx, d_data, d_tmp, n, L, st);  // the buckets are made in d_tmp (keys stay mapped) ...
-        if (rc) return rc;
-        rc = bucket_dispatch(ctx, d_tmp, d_data, gs, L, st);    // ... sorted, they land in d_data
-        if (rc) return rc;
-        ctx->last_path = 2;
-        return RSX_OK;
-    }
-    const RegionGeom geom = make_geom(ctx, n, L->elem_bytes);
-    rc = begin_control(ctx, st, geom, mid);
+    return wide && !((ctx->ovf16 == nullptr || ctx->wide_buf == nullptr) && capturing(st));
+}
+int sort_wide(rsx_ctx* ctx, const EsLaunchers& K, void* d_data, void* d_tmp, size_t n, const rsx_layout* L, hipStream_t st) {
+    const uint32_t es = L->elem_bytes, D = L->key_bytes;
+    int rc = ensure_ovf16(ctx, st);
     if (rc) return rc;
-    if (!counting_path) {
-        rc = lsd_passes(ctx, d_data, d_tmp, n, L, geom, mid, mid_mode, st);
-        if (rc) return rc;
-        end_control(ctx);
-        return RSX_OK;
+    if (!ctx->wide_buf) {
+        RSX_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->wide_buf), WIDE_PLAN_OFFSET + sizeof(WidePlan)));
+        RSX_HIP(hipMemsetAsync(reinterpret_cast<char*>(ctx->wide_buf) + WIDE_PLAN_OFFSET, 0, sizeof(WidePlan), st));  // (plan_or, plan_done)
     }
-    // count phase of the one pass (mod.rs:90-109)
-    rc = hist_dispatch(ctx, d_data, geom, L, 0, J_of(ctx, 0), nullptr, false, st);
+    uint64_t* tot = reinterpret_cast<uint64_t*>(ctx->wide_buf);
+    uint64_t* BT = tot + 65536;
+    uint64_t* starts = BT + 256;
+    WidePlan* plan = reinterpret_cast<WidePlan*>(reinterpret_cast<char*>(ctx->wide_buf) + WIDE_PLAN_OFFSET);
+    const uint32_t* verdict = &plan->verdict;
+    const RegionGeom geom = make_geom(ctx, n, es);
+    // the count's workgroups: k per region of the sweeps' geometry where the scratch array holds their counters
+    // (128 KiB each) -- then the first sweep's count matrix is a marginal of those counters -- and no counter can
+    // overflow when the hybrid is taken (the device's verdict: every bucket fits LDS, so fewer than 0x8000 elements);
+    // else flat shares, and a count kernel of its own for that sweep
+    size_t parts = n * (size_t)es / (32768 * sizeof(uint32_t));
+    if (parts > (size_t)ctx->num_cu) parts = (size_t)ctx->num_cu;
+    static_assert(bucket_cape(8, wide_kpt_for(8), 1024) < 0x8000u && bucket_cape(4, wide_kpt_for(4), 1024) < 0x8000u, "a bucket that fits LDS must not overflow a 16-bit counter");
+    uint32_t k = ctx->wide_mode == 2 ? 0u : (uint32_t)(parts / geom.num_regions);
+    if (k > 0) parts = (size_t)k * geom.num_regions;
+    rc = K.wideplan(ctx, d_data, n, L, plan, st);
     if (rc) return rc;
-    if (counting_path) {
-        // u8 / i8: the element is its digit, so the 256 counts ARE the sorted array (same bytes as
-        // the pass + copy-back of mod.rs:121-174 would leave): write the runs, skip scatter and copy
-        LaunchTimer lt(ctx, RSX_PROF_OTHER, st);
-        const uint64_t steps = ((n + 15) / 16 + 255) / 256;  // a block writes 256 chunks of 16 bytes per step
-        uint64_t blocks = steps;
-        if (blocks > (uint64_t)ctx->num_cu * 16) blocks = (uint64_t)ctx->num_cu * 16;
-        hipLaunchKernelGGL(rsx_expand_bytes_kernel, dim3((uint32_t)blocks), dim3(256), 0, st, static_cast<uint8_t*>(d_data),
-                           (uint64_t)n, J_of(ctx, 0), geom.num_regions, status32(geom) ? 1u : 0u,
-                           L->key_kind == RSX_KEY_SIGNED ? 0x80u : 0u);
+    rc = K.count16top(ctx, d_data, n, L, plan, static_cast<uint32_t*>(d_tmp), (uint32_t)parts, geom.region_shift, k, st);  // partial counts in d_tmp
+    if (rc) return rc;
+    {
+        LaunchTimer lt(ctx, RSX_PROF_SCAN, st);
+        hipLaunchKernelGGL(rsx_total16_kernel, dim3(256), dim3(256), 0, st, static_cast<const uint32_t*>(d_tmp), (uint32_t)parts, ctx->ovf16, tot, BT);
         RSX_HIP(hipGetLastError());
-        end_control(ctx);
-        ctx->last_path = 3;
-        return RSX_OK;
+        // which form of the bucket kernel runs is the device's choice too (launch_bucket16 enqueues them all):
+        // groups of small buckets are on offer when the AVERAGE bucket is small (group_shift)
+        const uint64_t cap1024 = wide_big_form((int)es, n) ? wide_cap(es) : bucket_cap((int)es), cap512 = bucket_cap((int)es) / 2;
+        hipLaunchKernelGGL(rsx_scan16_kernel, dim3(256), dim3(256), 0, st, tot, BT, starts, cap512 / 2, cap512, cap1024, group_shift(ctx, n, L),
+                           ctx->wide_mode == 2 ? 1u : 0u, (uint64_t)bucket_cape((int)es, medium_kpt_for((int)es), 1024) * 150u, (uint64_t)n / 64u, plan,
+                           ctx->host_err_dev + HV_WIDE_HINT);
+        RSX_HIP(hipGetLastError());
     }
-    return fail(ctx, RSX_ERR_INTERNAL, "sort_device_locked: unreachable");
+    SortRun lsd;
+    rc = begin_control(ctx, lsd, st, geom, false);
+    if (rc) return rc;
+    ctx->cb_last = lsd.cb;
+    // Two runs on one control block, each with the clean list: whichever sequence's count kernel runs does the cleaning.
+    // sequence 1 (verdict 1): LSD passes on digits D-2 and D-1, then every 16-bit bucket in LDS
+    SortRun hyb = lsd;
+    hyb.gate = Gate{verdict, VERDICT_PATH_MASK, VERDICT_HYBRID};
+    hyb.spec_dev = &plan->specs[0];  // (the two digits of the window come from the plan, not from the digit index given here)
+    if (k > 0) {
+        rc = K.marginal16(ctx, hyb, static_cast<const uint32_t*>(d_tmp), (uint32_t)parts, k, geom, J_of(ctx, hyb, 0), J_of(ctx, hyb, 1), st);
+    } else {  // (forced mode: counters may have overflowed; a count kernel of its own, its digit from the plan)
+        rc = K.hist(ctx, hyb, d_data, geom, L, D - 2, J_of(ctx, hyb, 0), J_of(ctx, hyb, 1), true, st);
+    }
+    if (rc) return rc;
+    rc = K.sweep(ctx, hyb, SweepPass{0, false, 0}, d_data, d_tmp, geom, L, D - 2, J_of(ctx, hyb, 0), J_of(ctx, hyb, 1), nullptr, 1, st);  // keys mapped on load
+    if (rc) return rc;
+    hyb.spec_dev = &plan->specs[1];
+    rc = K.sweep(ctx, hyb, SweepPass{1, true, 0}, d_tmp, d_data, geom, L, D - 1, J_of(ctx, hyb, 1), nullptr, nullptr, 0, st);  // ... and stay mapped
+    if (rc) return rc;
+    rc = K.bucket16(ctx, hyb, d_data, d_tmp, n, L, starts, plan, st);
+    if (rc) return rc;
+    // sequence 2 (verdict 2): the D LSD passes
+    lsd.gate = Gate{verdict, VERDICT_PATH_MASK, VERDICT_LSD};
+    rc = lsd_passes(ctx, K, lsd, d_data, d_tmp, n, L, geom, false, 0, st);
+    if (rc) return rc;
+    ctx->last_sort_passes = D;
+    ctx->last_path = 5;
+    end_control(ctx);
+    return RSX_OK;
+}
+
+// Middle sizes (more than one tile, up to mid_max_elems): the count kernel also counts the MOST significant digit.
+// If that digit spreads the array over its 256 buckets so that each fits a workgroup's LDS, one sweep makes the
+// buckets and rsx_bucket_sort_kernel sorts each by the remaining digits: 4 launches and two trips through memory
+// instead of D + 2 and D.  Whether it does is known on the device only, and a launch costs ~4 us even when it
+// returns at once, so the host FORECASTS from what the previous middle-size sort reported (a host-visible word,
+// read without synchronising: it may lag, and either way the result is right -- a bucket that does not fit after
+// all is sorted through memory by its one workgroup, slowly, after which the context keeps to LSD passes for a while).
+// Returns how this sort is enqueued: 1 bucket split (*bucket_small: by 256-thread workgroups), 2 LSD passes.
+uint32_t mid_forecast(rsx_ctx* ctx, size_t n, bool* bucket_small) {
+    const uint32_t hint = host_word(ctx, HV_MID_HINT);  // 0 nothing yet, 1 / 3 fits (a small / a large workgroup), 2 does not
+    uint32_t mid_mode;
+    if (ctx->mid_choice == 1 && hint == 2 && ctx->mid_cooldown == 0) ctx->mid_cooldown = 8;  // a split met a skewed input
+    if (ctx->mid_cooldown > 0) {
+        --ctx->mid_cooldown;
+        mid_mode = 2;
+    } else {
+        mid_mode = hint == 2 ? 2u : 1u;
+    }
+    if (ctx->mid_force) mid_mode = ctx->mid_force;
+    ctx->mid_choice = mid_mode;
+    *bucket_small = hint == 1 && (uint64_t)n <= 256ull * 2048ull;
+    return mid_mode;
+}
+// bucket split (count, scan, scatter: rsx_mid_kernels.hpp), then every bucket sorted in LDS
+int sort_mid_split(rsx_ctx* ctx, const EsLaunchers& K, void* d_data, void* d_tmp, size_t n, const rsx_layout* L, bool bucket_small, hipStream_t st) {
+    int rc = K.mid_split(ctx, d_data, d_tmp, n, L, st);  // the buckets are made in d_tmp (keys stay mapped) ...
+    if (rc) return rc;
+    rc = K.bucket_sort(ctx, d_tmp, d_data, L, bucket_small, st);  // ... sorted, they land in d_data
+    if (rc) return rc;
+    ctx->last_path = 2;
+    return RSX_OK;
+}
+
+// the general path; mid: a middle-size sort that the forecast gave to LSD passes (mid_mode 2)
+int sort_lsd(rsx_ctx* ctx, const EsLaunchers& K, void* d_data, void* d_tmp, size_t n, const rsx_layout* L, bool mid, uint32_t mid_mode,
+             hipStream_t st) {
+    const RegionGeom geom = make_geom(ctx, n, L->elem_bytes);
+    SortRun run;
+    int rc = begin_control(ctx, run, st, geom, mid);
+    if (rc) return rc;
+    rc = lsd_passes(ctx, K, run, d_data, d_tmp, n, L, geom, mid, mid_mode, st);
+    if (rc) return rc;
+    end_control(ctx);
+    return RSX_OK;
+}
+
+// u8 / i8: the element is its digit, so the 256 counts ARE the sorted array (same bytes as the pass + copy-back of
+// mod.rs:121-174 would leave): count (mod.rs:90-109), write the runs, skip scatter and copy
+int sort_counting8(rsx_ctx* ctx, const EsLaunchers& K, void* d_data, size_t n, const rsx_layout* L, hipStream_t st) {
+    const RegionGeom geom = make_geom(ctx, n, L->elem_bytes);
+    SortRun run;
+    int rc = begin_control(ctx, run, st, geom, false);
+    if (rc) return rc;
+    rc = K.hist(ctx, run, d_data, geom, L, 0, J_of(ctx, run, 0), nullptr, false, st);
+    if (rc) return rc;
+    LaunchTimer lt(ctx, RSX_PROF_OTHER, st);
+    const uint64_t steps = ((n + 15) / 16 + 255) / 256;  // a block writes 256 chunks of 16 bytes per step
+    uint64_t blocks = steps;
+    if (blocks > (uint64_t)ctx->num_cu * 16) blocks = (uint64_t)ctx->num_cu * 16;
+    hipLaunchKernelGGL(rsx_expand_bytes_kernel, dim3((uint32_t)blocks), dim3(256), 0, st, static_cast<uint8_t*>(d_data),
+                       (uint64_t)n, J_of(ctx, run, 0), geom.num_regions, status32(geom) ? 1u : 0u,
+                       L->key_kind == RSX_KEY_SIGNED ? 0x80u : 0u);
+    RSX_HIP(hipGetLastError());
+    end_control(ctx);
+    ctx->last_path = 3;
+    return RSX_OK;
+}
+
+// body of rsx_sort_device; caller holds ctx->mu and has set the device
+int sort_device_locked(rsx_ctx* ctx, void* d_data, void* d_tmp, size_t n, const rsx_layout* L, hipStream_t st) {
+    const EsLaunchers* K = launchers_for(L->elem_bytes);
+    if (!K) return fail(ctx, RSX_ERR_UNSUPPORTED, "element size has no device kernel");
+    int rc = pending_error(ctx);
+    if (rc) return rc;
+    rc = ensure_workspace(ctx, n, L, st);
+    if (rc) return rc;
+    Enqueue enq(ctx, st);
+    const uint32_t D = L->key_bytes;  // T::NUMBER_OF_DIGITS
+    const bool general_bytes = (ctx->options & OPT_GENERAL_BYTES) != 0;
+    const bool counting8 = L->elem_bytes == 1 && !general_bytes;  // no sweep follows
+    ctx->last_sort_passes = 0;
+    ctx->last_path = 0;
+    ctx->last_route = 0;
+    // at most one tile: all D passes in one launch of one workgroup (rsx_small_kernel.hpp)
+    if (!counting8 && n <= (size_t)512 * kpt_for((int)L->elem_bytes) && !(ctx->options & OPT_NO_SMALL_SORT)) {  // one 512-thread tile
+        ctx->last_path = 1;
+        return K->small_sort(ctx, d_data, n, L, st);
+    }
+    if (L->elem_bytes == 2 && D == 2 && n >= ((size_t)1 << 23) && !general_bytes && (ctx->ovf16 != nullptr || !capturing(st)))
+        return sort_counting16(ctx, d_data, d_tmp, n, L, st);
+    if (wide_forecast(ctx, n, L, st)) return sort_wide(ctx, *K, d_data, d_tmp, n, L, st);
+    const bool mid = !counting8 && D >= 2 && (uint64_t)n <= mid_max_elems((int)L->elem_bytes) && !(ctx->options & OPT_NO_MID_SORT);
+    bool bucket_small = false;
+    const uint32_t mid_mode = mid ? mid_forecast(ctx, n, &bucket_small) : 0u;
+    if (mid_mode == 1) return sort_mid_split(ctx, *K, d_data, d_tmp, n, L, bucket_small, st);
+    if (counting8) return sort_counting8(ctx, *K, d_data, n, L, st);
+    return sort_lsd(ctx, *K, d_data, d_tmp, n, L, mid, mid_mode, st);
 }
 
 // ---- layouts without a kernel of their own (include/rsx.h, "Any layout") ----
@@ -667,7 +600,8 @@ int launch_move(rsx_ctx* ctx, const void* src, uint32_t s_in, void* dst, uint32_
     return RSX_OK;
 }
 
-int launch_gather(rsx_ctx* ctx, const void* src, void* dst, uint32_t s, const void* proxy, const AnyPlan& P, size_t n, hipStream_t st) {
+// dst[i] = src[position in proxy i]: rows of s bytes; proxies of p bytes with the u32 position at byte idx_off
+int launch_gather(rsx_ctx* ctx, const void* src, void* dst, uint32_t s, const void* proxy, uint32_t p, uint32_t idx_off, size_t n, hipStream_t st) {
     const uintptr_t al = reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst) | s;
     const uint32_t w = (al & 15) == 0 ? 16 : (al & 7) == 0 ? 8 : (al & 3) == 0 ? 4 : (al & 1) == 0 ? 2 : 1;
     const uint32_t words = s / w;
@@ -680,13 +614,12 @@ int launch_gather(rsx_ctx* ctx, const void* src, void* dst, uint32_t s, const vo
     const uint8_t* sp = static_cast<const uint8_t*>(src);
     uint8_t* dp = static_cast<uint8_t*>(dst);
     const uint8_t* pp = static_cast<const uint8_t*>(proxy);
-    const uint32_t p = P.inner.elem_bytes;
     switch (w) {
-        case 16: hipLaunchKernelGGL(rsx_row_gather_kernel<uint4>, dim3((uint32_t)blocks), dim3(256), 0, st, sp, dp, words, pp, p, P.idx_off, (uint64_t)n, gshift); break;
-        case 8: hipLaunchKernelGGL(rsx_row_gather_kernel<uint2>, dim3((uint32_t)blocks), dim3(256), 0, st, sp, dp, words, pp, p, P.idx_off, (uint64_t)n, gshift); break;
-        case 4: hipLaunchKernelGGL(rsx_row_gather_kernel<uint32_t>, dim3((uint32_t)blocks), dim3(256), 0, st, sp, dp, words, pp, p, P.idx_off, (uint64_t)n, gshift); break;
-        case 2: hipLaunchKernelGGL(rsx_row_gather_kernel<uint16_t>, dim3((uint32_t)blocks), dim3(256), 0, st, sp, dp, words, pp, p, P.idx_off, (uint64_t)n, gshift); break;
-        default: hipLaunchKernelGGL(rsx_row_gather_kernel<uint8_t>, dim3((uint32_t)blocks), dim3(256), 0, st, sp, dp, words, pp, p, P.idx_off, (uint64_t)n, gshift); break;
+        case 16: hipLaunchKernelGGL(rsx_row_gather_kernel<uint4>, dim3((uint32_t)blocks), dim3(256), 0, st, sp, dp, words, pp, p, idx_off, (uint64_t)n, gshift); break;
+        case 8: hipLaunchKernelGGL(rsx_row_gather_kernel<uint2>, dim3((uint32_t)blocks), dim3(256), 0, st, sp, dp, words, pp, p, idx_off, (uint64_t)n, gshift); break;
+        case 4: hipLaunchKernelGGL(rsx_row_gather_kernel<uint32_t>, dim3((uint32_t)blocks), dim3(256), 0, st, sp, dp, words, pp, p, idx_off, (uint64_t)n, gshift); break;
+        case 2: hipLaunchKernelGGL(rsx_row_gather_kernel<uint16_t>, dim3((uint32_t)blocks), dim3(256), 0, st, sp, dp, words, pp, p, idx_off, (uint64_t)n, gshift); break;
+        default: hipLaunchKernelGGL(rsx_row_gather_kernel<uint8_t>, dim3((uint32_t)blocks), dim3(256), 0, st, sp, dp, words, pp, p, idx_off, (uint64_t)n, gshift); break;
     }
     RSX_HIP(hipGetLastError());
     return RSX_OK;
@@ -717,7 +650,7 @@ int sort_any_locked(rsx_ctx* ctx, void* d_data, void* d_tmp, size_t n, const rsx
         if (rc) return rc;
         rc = sort_device_locked(ctx, w0, w1, n, &P.inner, st);
         if (rc) return rc;
-        rc = launch_gather(ctx, d_tmp, d_data, s, w0, P, n, st);
+        rc = launch_gather(ctx, d_tmp, d_data, s, w0, sp, P.idx_off, n, st);
     }
     if (rc) return rc;
     ctx->last_route = P.route;
@@ -756,10 +689,9 @@ int reserve_pairs_one(rsx_ctx* ctx, size_t n, uint32_t kb, uint32_t vb, hipStrea
     if (rc) return rc;
     return ensure_any(ctx, 2 * P.half + P.copy, st);
 }
-bool key_widths_ok(uint32_t kb, uint32_t kind) {
-    if (!(kb == 1 || kb == 2 || kb == 4 || kb == 8 || kb == 16)) return false;
-    if (kind > RSX_KEY_FLOAT) return false;
-    return kind != RSX_KEY_FLOAT || kb == 4 || kb == 8;
+bool key_widths_ok(uint32_t kb, uint32_t kind) {  // the key array as a layout of its own
+    const rsx_layout L{kb, 0, kb, kind};
+    return layout_ok(&L);
 }
 uint32_t value_align(uint32_t vb) {
     uint32_t a = 1;
@@ -778,9 +710,7 @@ int pairs_locked(rsx_ctx* ctx, void* d_keys, void* d_values, void* d_index, size
     if (P.route == 2 && (uint64_t)n >= (1ull << 32)) return fail(ctx, RSX_ERR_UNSUPPORTED, "2^32 or more pairs with values too wide to join");
     int rc = pending_error(ctx);
     if (rc) return rc;
-    rc = ensure_workspace(ctx, n, &P.inner, st);
-    if (rc) return rc;
-    rc = ensure_any(ctx, 2 * P.half + P.copy, st);
+    rc = reserve_pairs_one(ctx, n, kb, argsort ? pw : vb, st);
     if (rc) return rc;
     Enqueue enq(ctx, st);  // the workspace arrays belong to this call from the first launch on
     char* w0 = ctx->any_buf;
@@ -809,10 +739,7 @@ int pairs_locked(rsx_ctx* ctx, void* d_keys, void* d_values, void* d_index, size
         if (rc) return rc;
         rc = launch_pairs_split(ctx, w0, d_keys, nullptr, n, kb, 4, 1, 0, kind, desc, st);
         if (rc) return rc;
-        AnyPlan G{};
-        G.inner = P.inner;
-        G.idx_off = pairs_value_offset(kb, 4);
-        rc = launch_gather(ctx, cp, d_values, vb, w0, G, n, st);
+        rc = launch_gather(ctx, cp, d_values, vb, w0, es, pairs_value_offset(kb, 4), n, st);
     }
     if (rc) return rc;
     ctx->last_pairs = P.route | es << 8;
@@ -891,8 +818,7 @@ int rsx_ctx_destroy(rsx_ctx* ctx) try {
             if (p) (void)hipFree(p);
         for (void* p : ctx->pinned)
             if (p) (void)hipHostFree(p);
-        for (hipStream_t s : ctx->copy_stream)
-            if (s) (void)hipStreamDestroy(s);
+        if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
         for (hipEvent_t e : ctx->copy_event)
             if (e) (void)hipEventDestroy(e);
         if (ctx->part_J) (void)hipFree(ctx->part_J);
@@ -934,10 +860,9 @@ int rsx_ctx_check(rsx_ctx* ctx, void* stream) try {
     DeviceGuard g(ctx->device);
     RSX_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
     if (!ctx->host_err) return RSX_OK;
-    volatile uint32_t* e = reinterpret_cast<volatile uint32_t*>(ctx->host_err);
-    if (*e) {
+    if (host_word(ctx, HV_ERROR)) {
         if (ctx->busy) (void)hipEventSynchronize(ctx->last_event);  // nothing of this context may still be running
-        *e = 0;
+        host_word(ctx, HV_ERROR) = 0;
         return fail(ctx, RSX_ERR_INTERNAL, "look-back spin gave up, or an atomic rank failed its cross-check (device protocol error)");
     }
     return RSX_OK;
@@ -993,7 +918,7 @@ int rsx_ctx_set_option(rsx_ctx* ctx, int option, uint64_t value) try {
             if (value > 3) return fail(ctx, RSX_ERR_ARG, "RSX_OPT_WIDE_SORT: 0 (off), 1 (auto), 2 (always) or 3 (auto from 2^22 elements on)");
             ctx->wide_mode = (uint32_t)value;
             ctx->wide_skip = 0;  // setting the option forgets an earlier refusal
-            if (ctx->host_err) reinterpret_cast<volatile uint32_t*>(ctx->host_err)[9] = 0;
+            if (ctx->host_err) host_word(ctx, HV_WIDE_HINT) = 0;
             return RSX_OK;
         case RSX_OPT_BUCKET_SKIP:
             if (value > 1) return fail(ctx, RSX_ERR_ARG, "RSX_OPT_BUCKET_SKIP: 0 or 1");
@@ -1237,7 +1162,7 @@ int sort_segments_common(rsx_ctx* ctx, void* d_data, void* d_tmp, size_t n, cons
     if (rc) return rc;
     Enqueue enq(ctx, st);
     uint32_t launched = 0;
-    rc = segment_dispatch(ctx, d_data, d_tmp, n, L, d_offsets, nseg, row_len, max_len, &launched, st);
+    rc = launchers_for(L->elem_bytes)->segment_sort(ctx, d_data, d_tmp, n, L, d_offsets, nseg, row_len, max_len, &launched, st);
     ctx->last_path = 6;
     ctx->last_route = 0;
     ctx->last_sort_passes = launched;
@@ -1299,8 +1224,8 @@ int host_pipeline(rsx_ctx* ctx, char* host, char* dev, size_t bytes, bool to_dev
         if (!ctx->pinned[i]) RSX_HIP(hipHostMalloc(&ctx->pinned[i], HOST_CHUNK, hipHostMallocDefault));
         if (!ctx->copy_event[i]) RSX_HIP(hipEventCreateWithFlags(&ctx->copy_event[i], hipEventDisableTiming));
     }
-    if (!ctx->copy_stream[0]) RSX_HIP(hipStreamCreateWithFlags(&ctx->copy_stream[0], hipStreamNonBlocking));
-    hipStream_t cs = ctx->copy_stream[0];
+    if (!ctx->copy_stream) RSX_HIP(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
+    hipStream_t cs = ctx->copy_stream;
     const int threads = (int)std::min<unsigned>(8u, std::max(1u, std::thread::hardware_concurrency() / 2));
     const size_t chunks = (bytes + HOST_CHUNK - 1) / HOST_CHUNK;
     if (to_device) {
@@ -1360,13 +1285,13 @@ int rsx_sort_host(rsx_ctx* ctx, void* data, size_t n, const rsx_layout* L) try {
     if (ctx->busy) RSX_HIP(hipEventSynchronize(ctx->last_event));  // an earlier device sort may still use the workspace
     rc = host_pipeline(ctx, static_cast<char*>(data), static_cast<char*>(ctx->host_buf[0]), bytes, true);
     if (rc) return rc;
-    hipStream_t st = ctx->copy_stream[0];
+    hipStream_t st = ctx->copy_stream;
     rc = sort_any_locked(ctx, ctx->host_buf[0], ctx->host_buf[1], n, L, st);
     if (rc) return rc;
     RSX_HIP(hipStreamSynchronize(st));
     rc = pending_error(ctx);
     if (rc) {
-        *reinterpret_cast<volatile uint32_t*>(ctx->host_err) = 0;
+        host_word(ctx, HV_ERROR) = 0;
         return fail(ctx, RSX_ERR_INTERNAL, "look-back spin gave up (device protocol error)");
     }
     return host_pipeline(ctx, static_cast<char*>(data), static_cast<char*>(ctx->host_buf[0]), bytes, false);
@@ -1391,11 +1316,12 @@ int rsx_histogram_device(rsx_ctx* ctx, const void* d_src, size_t n, const rsx_la
     if (rc) return rc;
     Enqueue enq(ctx, st);
     const RegionGeom geom = make_geom(ctx, n, L->elem_bytes);
-    rc = begin_control(ctx, st, geom, false);
+    SortRun run;
+    rc = begin_control(ctx, run, st, geom, false);
     if (rc) return rc;
-    rc = hist_dispatch(ctx, d_src, geom, L, digit, J_of(ctx, 0), nullptr, false, st);
+    rc = launchers_for(L->elem_bytes)->hist(ctx, run, d_src, geom, L, digit, J_of(ctx, run, 0), nullptr, false, st);
     if (rc) return rc;
-    rc = launch_totals(ctx, geom, J_of(ctx, 0), d_hist, st);  // column sums -> d_hist
+    rc = launch_totals(ctx, geom, J_of(ctx, run, 0), d_hist, st);  // column sums -> d_hist
     if (rc == RSX_OK) end_control(ctx);
     return rc;
 } catch (...) {
@@ -1411,17 +1337,17 @@ int partition_locked(rsx_ctx* ctx, const void* d_src, void* d_dst, size_t n, con
     if (rc) return rc;
     Enqueue enq(ctx, st);
     const RegionGeom geom = make_geom(ctx, n, L->elem_bytes);
-    rc = begin_control(ctx, st, geom, false);
+    const EsLaunchers& K = *launchers_for(L->elem_bytes);
+    SortRun run;
+    rc = begin_control(ctx, run, st, geom, false);
     if (rc) return rc;
-    rc = hist_dispatch(ctx, d_src, geom, L, digit, J_of(ctx, 0), nullptr, true, st);
+    rc = K.hist(ctx, run, d_src, geom, L, digit, J_of(ctx, run, 0), nullptr, true, st);
     if (rc) return rc;
     if (d_hist) {
-        rc = launch_totals(ctx, geom, J_of(ctx, 0), d_hist, st);
+        rc = launch_totals(ctx, geom, J_of(ctx, run, 0), d_hist, st);
         if (rc) return rc;
     }
-    ctx->pass_index = 0;
-    ctx->pass_last = true;
-    rc = sweep_dispatch(ctx, d_src, d_dst, geom, L, digit, J_of(ctx, 0), nullptr, nullptr, 3, st);  // a lone pass maps and unmaps
+    rc = K.sweep(ctx, run, SweepPass{0, true, 0}, d_src, d_dst, geom, L, digit, J_of(ctx, run, 0), nullptr, nullptr, 3, st);  // a lone pass maps and unmaps
     if (rc == RSX_OK) end_control(ctx);
     return rc;
 }
@@ -1469,6 +1395,8 @@ int rsx_partition_count_device(rsx_ctx* ctx, const void* d_src, size_t n, const 
     }
     Enqueue enq(ctx, st);
     RSX_HIP(hipMemsetAsync(ctx->part_J, 0, (size_t)nsub * J_BYTES, st));
+    const EsLaunchers& K = *launchers_for(L->elem_bytes);
+    SortRun run;  // no control block, nothing to clean: the counts go to matrices of their own
     for (uint32_t k = 0; k < nsub; ++k) {
         const uint64_t beg = sub_start(n, nsub, k), nk = sub_start(n, nsub, k + 1) - beg;
         if (nk == 0) {
@@ -1477,7 +1405,7 @@ int rsx_partition_count_device(rsx_ctx* ctx, const void* d_src, size_t n, const 
         }
         const RegionGeom geom = make_geom(ctx, nk, L->elem_bytes);
         unsigned long long* Jk = ctx->part_J + (size_t)k * (J_BYTES / sizeof(unsigned long long));
-        rc = hist_dispatch(ctx, static_cast<const char*>(d_src) + beg * L->elem_bytes, geom, L, digit, Jk, nullptr, false, st);
+        rc = K.hist(ctx, run, static_cast<const char*>(d_src) + beg * L->elem_bytes, geom, L, digit, Jk, nullptr, false, st);
         if (rc) return rc;
         rc = launch_totals(ctx, geom, Jk, d_hist + (size_t)k * RADIX, st);
         if (rc) return rc;
@@ -1510,15 +1438,11 @@ int rsx_partition_scatter_device(rsx_ctx* ctx, const void* d_src, void* d_dst, s
     // what the count kernel of a whole sort clears on its way: this pass's control words and status words
     RSX_HIP(hipMemsetAsync(part_tickets_of(ctx), 0, TICKET_WORDS * sizeof(uint32_t), st));
     RSX_HIP(hipMemsetAsync(ctx->status, 0, status_bytes_for(ctx, nk, L->elem_bytes), st));
-    ctx->pass_index = 0;
-    ctx->pass_last = true;
-    ctx->pass_mid = 0;
-    ctx->tickets_override = part_tickets_of(ctx);  // outside the alternating control blocks
+    SortRun run;
+    run.tickets_override = part_tickets_of(ctx);  // outside the alternating control blocks
     const size_t off = beg * (size_t)L->elem_bytes;
-    rc = sweep_dispatch(ctx, static_cast<const char*>(d_src) + off, static_cast<char*>(d_dst) + off, geom, L, digit,
-                        ctx->part_J + (size_t)k * (J_BYTES / sizeof(unsigned long long)), nullptr, nullptr, 3, st);
-    ctx->tickets_override = nullptr;
-    return rc;
+    return launchers_for(L->elem_bytes)->sweep(ctx, run, SweepPass{0, true, 0}, static_cast<const char*>(d_src) + off, static_cast<char*>(d_dst) + off, geom, L,
+                                               digit, ctx->part_J + (size_t)k * (J_BYTES / sizeof(unsigned long long)), nullptr, nullptr, 3, st);
 } catch (...) {
     return RSX_ERR_HIP;
 }
@@ -1565,7 +1489,7 @@ int rsx_segmented_copy_device(rsx_ctx* ctx, const void* d_src, void* d_dst, uint
     std::lock_guard<std::mutex> lk(ctx->mu);
     DeviceGuard g(ctx->device);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    RSX_DISPATCH_ES(elem_bytes, launch_segcopy, ctx, d_src, d_dst, d_src_off, d_dst_off, d_len, nseg, st)
+    return launchers_for(elem_bytes)->segcopy(ctx, d_src, d_dst, d_src_off, d_dst_off, d_len, nseg, st);
 } catch (...) {
     return RSX_ERR_HIP;
 }
@@ -1657,7 +1581,7 @@ int sync_all(rsx_ctx* ctx, const std::vector<Shard>& sh) {
         std::lock_guard<std::mutex> lk(sh[g].c->mu);
         int rc = pending_error(sh[g].c);
         if (rc) {
-            *reinterpret_cast<volatile uint32_t*>(sh[g].c->host_err) = 0;
+            host_word(sh[g].c, HV_ERROR) = 0;
             return fail(ctx, RSX_ERR_INTERNAL, "look-back spin gave up on one of the slices");
         }
     }
@@ -1958,7 +1882,7 @@ int rsx_sort_sharded(rsx_ctx* const* ctxs, uint32_t ndev, void* const* d_slices,
 int rsx_generate_device(rsx_ctx* ctx, void* d_data, size_t n, const rsx_layout* L, int gen, uint64_t seed,
                         double param, uint64_t index_base, void* stream) try {
     if (!ctx) return RSX_ERR_ARG;
-    if (!any_layout_ok(L)) return fail(ctx, RSX_ERR_ARG, "invalid rsx_layout");
+    if (!layout_ok(L, true)) return fail(ctx, RSX_ERR_ARG, "invalid rsx_layout");
     if (n == 0) return RSX_OK;
     if (!d_data) return fail(ctx, RSX_ERR_ARG, "null pointer");
     const uint32_t payload_zero = (gen & RSX_GEN_PAYLOAD_ZERO) ? 1u : 0u;
@@ -1996,7 +1920,7 @@ int rsx_generate_device(rsx_ctx* ctx, void* d_data, size_t n, const rsx_layout* 
 int rsx_verify_device(rsx_ctx* ctx, const void* d_data, size_t n, const rsx_layout* L, uint64_t* d_out,
                       void* stream) try {
     if (!ctx) return RSX_ERR_ARG;
-    if (!any_layout_ok(L)) return fail(ctx, RSX_ERR_ARG, "invalid rsx_layout");
+    if (!layout_ok(L, true)) return fail(ctx, RSX_ERR_ARG, "invalid rsx_layout");
     if (!d_out) return fail(ctx, RSX_ERR_ARG, "null pointer");
     std::lock_guard<std::mutex> lk(ctx->mu);
     DeviceGuard g(ctx->device);

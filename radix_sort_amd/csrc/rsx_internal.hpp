@@ -1,7 +1,7 @@
 // rsx_internal.hpp -- host-side state and helpers shared by the translation units of librsx.so:
 //   rsx.hip     the C-ABI of include/rsx.h (context, pass loop, multi-GPU driver, harness)
 //   rsx_es.hip  the kernel launchers of ONE element size (compiled once per size with -DRSX_ES=n,
-//               so the eight sizes build in parallel)
+//               so the eight sizes build in parallel), reached through that size's EsLaunchers table
 #pragma once
 #include "rsx_device.hpp"
 
@@ -50,6 +50,9 @@ constexpr size_t OFF_BASE = OFF_PART_TICKETS + ((TICKET_WORDS * 4 + 255) / 256) 
 constexpr size_t OFF_FLAGS = OFF_BASE + 4096;                                    // self-test verdicts
 constexpr size_t OFF_DBG = OFF_FLAGS + 256;                                      // 16 waves x 8 diagnostic counters
 constexpr size_t AUX_BYTES = OFF_DBG + 1024;
+// words of the host-visible block (rsx_ctx::host_err, 64 bytes): a kernel that gives up a bounded wait sets the first; the
+// second word group holds what the last middle-size sort and the last wide-key try reported, for the host's forecasts
+constexpr uint32_t HV_ERROR = 0, HV_MID_HINT = 8, HV_WIDE_HINT = 9;
 
 // option bits (rsx_ctx_set_option): alternative kernel paths, all bit-exact
 enum : uint32_t {
@@ -79,21 +82,19 @@ struct rsx_ctx {
     // staging for rsx_sort_host
     void* host_buf[2] = {nullptr, nullptr};
     size_t host_bytes = 0;
-    hipStream_t copy_stream[2] = {nullptr, nullptr};
+    hipStream_t copy_stream = nullptr;
     void* pinned[4] = {nullptr, nullptr, nullptr, nullptr};  // ring of pinned bounce chunks
     hipEvent_t copy_event[4] = {nullptr, nullptr, nullptr, nullptr};
-    // multi-GPU driver (rsx_sort_sharded): per-slice stream and splitter-search scratch, made once
-    rsx::Gate gate = {nullptr, 0, 0};  // set around the launches of a gated kernel sequence (wide keys)
     uint32_t wide_skip = 0;     // sorts to go without trying the wide-key hybrid (the last try was refused on the device)
     char* wide_buf = nullptr;   // wide-key hybrid: bin totals [65536] u64, bin-block sums [256] u64, bucket starts [65537] u64, verdict u32
     uint32_t wide_mode = 1;     // RSX_OPT_WIDE_SORT: 0 off, 1 auto, 2 always, 3 auto without the size floor
     std::vector<const void*> lds_attr;  // kernels whose dynamic-LDS limit was raised on this context's device (ensure_lds)
-    const rsx::DigitSpec* spec_dev = nullptr;  // the hybrid's sweeps read their digits from the device's plan (WidePlan::specs)
     uint64_t wide_tried_sig = 0, wide_refused_sig = 0;  // (layout, n) of the last hybrid try / of the last refusal
     uint32_t bucket_no_skip = 0;  // RSX_OPT_BUCKET_SKIP == 0
     uint32_t bucket_group = 1;    // RSX_OPT_BUCKET_GROUP: small buckets of the hybrid are sorted in groups
     uint32_t* ovf16 = nullptr;  // u16 / i16 counting path: 65536 overflow counters, all zero between sorts
     unsigned long long* part_J = nullptr;  // rsx_partition_count_device: one count matrix per sub-range (PART_MAX_SUB x J_BYTES)
+    // multi-GPU driver (rsx_sort_sharded): per-slice stream and splitter-search scratch, made once
     hipStream_t shard_stream = nullptr;
     uint64_t* shard_q = nullptr;     // device: queries (lo, hi) + ranges (begin, end)
     uint64_t* shard_out = nullptr;   // device: answers
@@ -101,24 +102,17 @@ struct rsx_ctx {
     uint64_t* shard_host = nullptr;  // pinned: answers, then the 256 counts
     std::vector<uint64_t> shard_stage;
     int num_cu = 256;
-    uint32_t pass_index = 0;   // of the sweep being launched within its sort (selects the status half, J rotation)
-    bool pass_last = true;     // no pass follows: nothing to clean
     uint32_t last_path = 0;    // 0 general passes, 1 one-launch sort, 2 middle-size bucket split, 3 / 4 one- / two-byte counting
     uint32_t last_sort_passes = 0;  // sweep passes of the last sort (RSX_INFO_LAST_PASSES)
     uint32_t last_route = 0;   // how the last sort reached the kernels: 0 direct, 1 packed re-layout, 2 key-index proxy
     char* any_buf = nullptr;   // routes 1 / 2: the re-laid-out elements or the proxies, and their ping-pong array
     size_t any_bytes = 0;
     uint32_t last_pairs = 0;   // RSX_INFO_LAST_PAIRS: route of the last pairs / argsort call (1 joined, 2 proxies) | joined element size << 8
-    rsx::CleanList clean = {{nullptr, nullptr, nullptr}, {0, 0, 0}};  // what the next count kernel zeroes on its way (the previous sort's control block)
     uint64_t cb_used[2][2] = {{0, 0}, {0, 0}};  // per alternating block: bytes of the top-digit matrix / of count matrix 0 its last sort used
     uint32_t cb_alt = 0;       // which of the two alternating blocks the last uncaptured sort used
-    uint32_t* tickets_override = nullptr;  // rsx_partition_scatter_device: control words outside the blocks
-    uint32_t cb = 0;           // control block of the sort being enqueued (aux layout above)
-    uint32_t cb_last = 0;      // ... of the last sort that ran sweeps (RSX_INFO_LAST_PASSES)
+    uint32_t cb_last = 0;      // control block of the last sort that ran sweeps (RSX_INFO_LAST_PASSES)
     bool cb_dirty = false;     // an enqueue failed half way: both alternating blocks are zeroed by memset before the next sort
-    uint32_t pass_mid = 0;     // middle-size sort, first sweep (MID instantiation): 1 = bucket split by the top digit, 2 = first LSD pass
     uint32_t mid_choice = 0;   // what the last middle-size sort was enqueued as (1 / 2)
-    bool bucket_small = false; // the bucket kernel being launched: 256-thread workgroups
     uint32_t mid_force = 0;    // RSX_OPT_MID_SORT 2 / 3: always split (1) / always LSD passes (2)
     uint32_t mid_cooldown = 0; // sorts to go by LSD passes after a bucket split met a skewed input
     bool rank_atomic = false;  // LDS atomic ordering self-test passed (set when the workspace is first made)
@@ -141,6 +135,22 @@ struct rsx_ctx {
 };
 
 namespace rsxh {
+
+// What belongs to ONE sort (or lone pass) while it is being enqueued: made on the stack by the entry point's body and
+// handed down to the launchers, so that nothing of one call is left behind on the context for the next.
+struct SortRun {
+    uint32_t cb = 0;  // control block of this sort (aux layout above)
+    CleanList clean = {{nullptr, nullptr, nullptr}, {0, 0, 0}};  // what the first count kernel zeroes on its way (the previous sort's control block)
+    Gate gate = {nullptr, 0, 0};  // of a gated kernel sequence (wide keys)
+    const DigitSpec* spec_dev = nullptr;  // the hybrid's sweeps read their digits from the device's plan (WidePlan::specs)
+    uint32_t* tickets_override = nullptr;  // rsx_partition_scatter_device: control words outside the blocks
+};
+// ... and to one sweep within it
+struct SweepPass {
+    uint32_t index;  // of the sweep within its sort (selects the status half, the ticket words)
+    bool last;       // no pass follows: nothing to clean
+    uint32_t mid;    // middle-size sort, first sweep (MID instantiation): 1 = bucket split by the top digit, 2 = first LSD pass
+};
 
 inline int fail(rsx_ctx* c, int code, const char* what, hipError_t e = hipSuccess) {
     if (c) {
@@ -242,7 +252,7 @@ constexpr uint32_t bucket_cape(int es, int kpt, int wg) {
     const uint32_t room = ((163840u - 1024u - (uint32_t)(wg / 64) * 256u * 4u - 64u - 3u * 256u * 4u) / (uint32_t)es) & ~3u;
     return slots < room ? slots : room;
 }
-constexpr size_t bucket_cnt_bytes(int) { return 4; }
+constexpr size_t bucket_cnt_bytes() { return 4; }
 // the LDS size classes of a segmented sort (rsx_segment_kernels.hpp): 256 and 1024 threads x bucket_kpt_for(es) elements
 constexpr uint32_t segment_cap(int es, int cls) { return bucket_cape(es, bucket_kpt_for(es), cls == 0 ? 256 : 1024); }
 // the hybrid's buffer (ctx->wide_buf): bucket totals [65536], block totals [256], starts [65537] (u64), then its WidePlan
@@ -253,7 +263,8 @@ constexpr uint32_t bucket_cap(int es) { return 1024u * (uint32_t)bucket_kpt_for(
 // go up to 2^22 as well (the general path needs 275 us there, this one 90): the average bucket is then 16384 of 17408,
 // eight standard deviations of a uniform top digit below the capacity; a bucket that overflows all the same is sorted
 // through memory by its workgroup, which costs about what the general path would have.
-constexpr uint64_t mid_max_elems(int es) { return es == 8 ? (1ull << 22) : (uint64_t)bucket_cap(es) * 256u * 4u / 7u; }
+// One-byte elements have no such path (their one digit is counted, never split): 0.
+constexpr uint64_t mid_max_elems(int es) { return es == 1 ? 0 : es == 8 ? (1ull << 22) : (uint64_t)bucket_cap(es) * 256u * 4u / 7u; }
 constexpr int kpt_for(int es) { return es <= 2 ? RSX_KPT2 : es <= 4 ? RSX_KPT4 : es == 8 ? RSX_KPT8 : es == 12 ? RSX_KPT12 : es == 16 ? RSX_KPT16 : es == 24 ? RSX_KPT24 : RSX_KPT32; }
 constexpr int wg_for(int es) { return es <= 4 ? RSX_WG4 : es == 8 ? RSX_WG8 : 512; }
 constexpr uint32_t tile_elems(int es) { return wg_for(es) * kpt_for(es); }
@@ -287,11 +298,11 @@ inline RegionGeom make_geom(const rsx_ctx* ctx, uint64_t n, uint32_t es, bool sm
     if (g.num_regions == 0) g.num_regions = 1;
     return g;
 }
-inline uint64_t tiles_per_region(const RegionGeom& g, uint32_t) {
+inline uint64_t tiles_per_region(const RegionGeom& g) {
     return ((1ull << g.region_shift) + g.tile - 1) / g.tile;
 }
-inline uint64_t status_rows(const RegionGeom& g, uint32_t es) {
-    return (uint64_t)g.num_regions * tiles_per_region(g, es);
+inline uint64_t status_rows(const RegionGeom& g) {
+    return (uint64_t)g.num_regions * tiles_per_region(g);
 }
 // chain prefixes are relative to the region: 30 value bits suffice up to 2^30-element regions
 inline bool status32(const RegionGeom& g) { return g.region_shift <= 30; }
@@ -327,65 +338,70 @@ inline DigitSpec make_spec(const rsx_layout* L, uint32_t digit) {
 // the three count matrices rotate: pass d reads J_of(d % 3), accumulates the next pass's into
 // J_of((d + 1) % 3) and zeroes J_of((d + 2) % 3) for the pass after
 inline char* cb_of(rsx_ctx* c, uint32_t which) { return c->aux + (size_t)which * CB_BYTES; }
-inline unsigned long long* J_of(rsx_ctx* c, uint32_t which) {
-    char* p = which == 0 ? cb_of(c, c->cb) + CB_J0 : which == 1 ? c->aux + OFF_J1 : c->aux + OFF_J2;
+inline unsigned long long* J_of(rsx_ctx* c, const SortRun& run, uint32_t which) {
+    char* p = which == 0 ? cb_of(c, run.cb) + CB_J0 : which == 1 ? c->aux + OFF_J1 : c->aux + OFF_J2;
     return reinterpret_cast<unsigned long long*>(p);
 }
-inline unsigned long long* JT_of(rsx_ctx* c) { return reinterpret_cast<unsigned long long*>(cb_of(c, c->cb) + CB_JT); }
-inline uint64_t* base_of(rsx_ctx* c) { return reinterpret_cast<uint64_t*>(c->aux + OFF_BASE); }
-inline uint32_t* tickets_of(rsx_ctx* c, uint32_t pass) {
-    return reinterpret_cast<uint32_t*>(cb_of(c, c->cb) + CB_TICKETS) + (size_t)pass * TICKET_WORDS;
+inline unsigned long long* JT_of(rsx_ctx* c, const SortRun& run) { return reinterpret_cast<unsigned long long*>(cb_of(c, run.cb) + CB_JT); }
+inline uint32_t* tickets_of(rsx_ctx* c, const SortRun& run, uint32_t pass) {
+    return reinterpret_cast<uint32_t*>(cb_of(c, run.cb) + CB_TICKETS) + (size_t)pass * TICKET_WORDS;
 }
 inline uint32_t* part_tickets_of(rsx_ctx* c) { return reinterpret_cast<uint32_t*>(c->aux + OFF_PART_TICKETS); }
 inline uint32_t* flags_of(rsx_ctx* c) { return reinterpret_cast<uint32_t*>(c->aux + OFF_FLAGS); }
+inline volatile uint32_t& host_word(rsx_ctx* c, uint32_t w) { return reinterpret_cast<volatile uint32_t*>(c->host_err)[w]; }  // HV_*
 
-// ---- per-element-size launchers (defined in rsx_launch_impl.hpp, instantiated in rsx_es.hip) ----
-// count phase of a first pass: J[rep][r][v] for `digit` over the input regions (J zeroed by the caller);
-// jclear: a second count matrix to clear on the way (or null); clear_status: zero the tile status words of
-// the sweep that follows (first half of the workspace)
-template <int ES>
-int launch_hist(rsx_ctx* ctx, const void* src, const RegionGeom& g, const rsx_layout* L, uint32_t digit,
-                unsigned long long* J, unsigned long long* jclear, bool clear_status, hipStream_t st);
-// the same counting a second digit (`digit2` into `J2`) on the same read (middle-size path)
-template <int ES>
-int launch_hist2(rsx_ctx* ctx, const void* src, const RegionGeom& g, const rsx_layout* L, uint32_t digit,
-                 unsigned long long* J, uint32_t digit2, unsigned long long* J2, unsigned long long* jclear, hipStream_t st);
-// first half of a middle-size sort: stable split of `src` into `dst` by the most significant digit (three launches)
-template <int ES>
-int launch_mid_split(rsx_ctx* ctx, const void* src, void* dst, size_t n, const rsx_layout* L, hipStream_t st);
-// wide keys, large arrays: the top 16 bits of the mapped key counted per workgroup (P[parts][32768]); the 65536
-// buckets (starts[65537]) sorted by the lower digits in LDS, in place
-template <int ES>
-int launch_wideplan(rsx_ctx* ctx, const void* src, size_t n, const rsx_layout* L, WidePlan* plan, hipStream_t st);
-template <int ES>
-int launch_count16top(rsx_ctx* ctx, const void* src, size_t n, const rsx_layout* L, WidePlan* plan, uint32_t* P, uint32_t parts,
-                      uint32_t region_shift, uint32_t k, hipStream_t st);
-template <int ES>
-int launch_marginal16(rsx_ctx* ctx, const uint32_t* P, uint32_t parts, uint32_t k, const RegionGeom& g, unsigned long long* J,
-                      unsigned long long* jclear, hipStream_t st);
-template <int ES>
-int launch_bucket16(rsx_ctx* ctx, void* data, void* scratch, size_t n, const rsx_layout* L, const uint64_t* starts, const WidePlan* plan,
-                    hipStream_t st);
-// second half of a middle-size sort: the 256 top-digit buckets of `src` sorted by the lower digits into `dst`
-template <int ES>
-int launch_bucket_sort(rsx_ctx* ctx, const void* src, void* dst, const RegionGeom& g, const rsx_layout* L, hipStream_t st);
-// one sweep pass.  J: this pass's count matrix; jnext: accumulated for the next pass (or null);
-// jzero: matrix to clear for the pass after next (or null); xf: bit 0 = map signed/float keys on
-// load (first pass), bit 1 = map back on store (last pass)
-template <int ES>
-int launch_sweep(rsx_ctx* ctx, const void* src, void* dst, const RegionGeom& g, const rsx_layout* L, uint32_t digit,
-                 const unsigned long long* J, unsigned long long* jnext, unsigned long long* jzero, int xf,
-                 hipStream_t st);
-// arrays of at most one tile (tile_elems(ES)): the whole sort in one launch of one workgroup, in place
-template <int ES>
-int launch_small_sort(rsx_ctx* ctx, void* data, size_t n, const rsx_layout* L, hipStream_t st);
-// every segment (offsets, or rows of row_len when offsets == nullptr) sorted by one workgroup: one launch per size class
-template <int ES>
-int launch_segment_sort(rsx_ctx* ctx, void* data, void* tmp, size_t n, const rsx_layout* L, const uint64_t* offsets, uint64_t nseg,
+// The wide-key hybrid sorts its small buckets in groups of 2^gs (0: none), about 3/4 of what a 512-thread workgroup of the
+// bucket kernel holds (keys of at least 8 bytes): rsx_scan16_kernel is offered this shift and launch_bucket16 enqueues the
+// form that goes with it, so both ask here.
+inline uint32_t group_shift(const rsx_ctx* ctx, size_t n, const rsx_layout* L) {
+    const uint64_t avg = (uint64_t)n / 65536u;
+    uint32_t gs = 0;
+    if (L->key_bytes >= 8 && ctx->bucket_group)
+        while (gs < 6 && (avg << (gs + 1)) <= (uint64_t)512 * bucket_kpt_for((int)L->elem_bytes) * 3 / 4) ++gs;
+    return gs >= 2 ? gs : 0;
+}
+
+// ---- per-element-size launchers: defined in rsx_launch_impl.hpp; rsx_es.hip fills ONE size's table with them (which
+// instantiates them), rsx.hip looks the table up by element size once per call (launchers_for).  A unit's kernels are emitted
+// in the order of the members here: keeping it keeps the code objects comparable from one build to the next. ----
+struct EsLaunchers {
+    // every segment (offsets, or rows of row_len when offsets == nullptr) sorted by one workgroup: one launch per size class
+    int (*segment_sort)(rsx_ctx* ctx, void* data, void* tmp, size_t n, const rsx_layout* L, const uint64_t* offsets, uint64_t nseg,
                         uint64_t row_len, uint64_t max_len, uint32_t* launched, hipStream_t st);
+    // count phase of a first pass: J[rep][r][v] for `digit` over the input regions (J zeroed by the caller);
+    // jclear: a second count matrix to clear on the way (or null); clear_status: zero the tile status words of
+    // the sweep that follows (first half of the workspace).  Like every count launcher it hands run.clean to its kernel
+    // and empties it: done once per sort.
+    int (*hist)(rsx_ctx* ctx, SortRun& run, const void* src, const RegionGeom& g, const rsx_layout* L, uint32_t digit,
+                unsigned long long* J, unsigned long long* jclear, bool clear_status, hipStream_t st);
+    // the same counting a second digit (`digit2` into `J2`) on the same read (middle-size path)
+    int (*hist2)(rsx_ctx* ctx, SortRun& run, const void* src, const RegionGeom& g, const rsx_layout* L, uint32_t digit,
+                 unsigned long long* J, uint32_t digit2, unsigned long long* J2, unsigned long long* jclear, hipStream_t st);
+    // wide keys, large arrays: the top 16 bits of the mapped key counted per workgroup (P[parts][32768]); the 65536
+    // buckets (starts[65537]) sorted by the lower digits in LDS, in place
+    int (*wideplan)(rsx_ctx* ctx, const void* src, size_t n, const rsx_layout* L, WidePlan* plan, hipStream_t st);
+    int (*count16top)(rsx_ctx* ctx, const void* src, size_t n, const rsx_layout* L, WidePlan* plan, uint32_t* P, uint32_t parts,
+                      uint32_t region_shift, uint32_t k, hipStream_t st);
+    int (*marginal16)(rsx_ctx* ctx, SortRun& run, const uint32_t* P, uint32_t parts, uint32_t k, const RegionGeom& g, unsigned long long* J,
+                      unsigned long long* jclear, hipStream_t st);
+    int (*bucket16)(rsx_ctx* ctx, const SortRun& run, void* data, void* scratch, size_t n, const rsx_layout* L, const uint64_t* starts,
+                    const WidePlan* plan, hipStream_t st);
+    // first half of a middle-size sort: stable split of `src` into `dst` by the most significant digit (three launches)
+    int (*mid_split)(rsx_ctx* ctx, const void* src, void* dst, size_t n, const rsx_layout* L, hipStream_t st);
+    // second half: the 256 top-digit buckets of `src` sorted by the lower digits into `dst`; small: 256-thread workgroups
+    int (*bucket_sort)(rsx_ctx* ctx, const void* src, void* dst, const rsx_layout* L, bool small, hipStream_t st);
+    // one sweep pass.  J: this pass's count matrix; jnext: accumulated for the next pass (or null);
+    // jzero: matrix to clear for the pass after next (or null); xf: bit 0 = map signed/float keys on
+    // load (first pass), bit 1 = map back on store (last pass)
+    int (*sweep)(rsx_ctx* ctx, const SortRun& run, const SweepPass& pass, const void* src, void* dst, const RegionGeom& g, const rsx_layout* L,
+                 uint32_t digit, const unsigned long long* J, unsigned long long* jnext, unsigned long long* jzero, int xf, hipStream_t st);
+    // arrays of at most one tile (tile_elems(ES)): the whole sort in one launch of one workgroup, in place
+    int (*small_sort)(rsx_ctx* ctx, void* data, size_t n, const rsx_layout* L, hipStream_t st);
+    int (*segcopy)(rsx_ctx* ctx, const void* src, void* dst, const uint64_t* so, const uint64_t* dof, const uint64_t* len, uint32_t nseg,
+                   hipStream_t st);
+};
 template <int ES>
-int launch_segcopy(rsx_ctx* ctx, const void* src, void* dst, const uint64_t* so, const uint64_t* dof,
-                   const uint64_t* len, uint32_t nseg, hipStream_t st);
+const EsLaunchers& es_launchers();  // specialised in rsx_es.hip
 
 // separate key and value arrays <-> joined elements (rsx_pairs.hip, rsx_pairs_kernels.hpp); split modes: 0 keys and
 // values, 1 keys only, 2 the position alone as ib bytes

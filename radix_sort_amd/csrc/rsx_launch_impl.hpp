@@ -1,5 +1,5 @@
-// rsx_launch_impl.hpp -- definitions of the per-element-size launchers declared in
-// rsx_internal.hpp.  Included only by rsx_es.hip, which instantiates them for ONE element size.
+// rsx_launch_impl.hpp -- definitions of the per-element-size launchers behind EsLaunchers
+// (rsx_internal.hpp).  Included only by rsx_es.hip, which instantiates them for ONE element size.
 #pragma once
 #include <cstdlib>
 #include "rsx_internal.hpp"
@@ -13,54 +13,57 @@
 
 namespace rsxh {
 
+inline uint32_t rank_atomic_of(const rsx_ctx* ctx) { return (ctx->rank_atomic && !(ctx->options & OPT_BALLOT_RANKS)) ? 1u : 0u; }
+constexpr CleanList CLEAN_NONE = {{nullptr, nullptr, nullptr}, {0, 0, 0}};
+
 // ---- count phase of a first pass: J[r][v] for `digit` over the input regions ------------------
-template <int ES, bool FLT>
-int launch_hist_t(rsx_ctx* ctx, const void* src, const RegionGeom& g, const rsx_layout* L, uint32_t digit,
-                  unsigned long long* J, unsigned long long* jclear, bool clear_status, hipStream_t st) {
+// the count kernels' grid: workgroups per region, each region cut into blocks of 512 x 16 elements
+inline uint64_t hist_blocks_per_region(const rsx_ctx* ctx, const RegionGeom& g) {
     const uint64_t per_block = 512ull * 16;
-    // the status words of the sweep that follows (its first half of the workspace) are zeroed by this kernel
-    const uint64_t zero16_n = clear_status ? status_rows(g, ES) * RADIX * (status32(g) ? 4u : 8u) / 16u : 0u;
     uint64_t bpr = ((1ull << g.region_shift) + per_block - 1) / per_block;
     const uint64_t cap = ((uint64_t)ctx->num_cu * RSX_HIST_BLOCKS_PER_CU + g.num_regions - 1) / g.num_regions;
     if (bpr > cap) bpr = cap;
-    if (bpr == 0) bpr = 1;
+    return bpr == 0 ? 1 : bpr;
+}
+template <int ES, bool FLT>
+int launch_hist_t(rsx_ctx* ctx, SortRun& run, const void* src, const RegionGeom& g, const rsx_layout* L, uint32_t digit,
+                  unsigned long long* J, unsigned long long* jclear, bool clear_status, hipStream_t st) {
+    // the status words of the sweep that follows (its first half of the workspace) are zeroed by this kernel
+    const uint64_t zero16_n = clear_status ? status_rows(g) * RADIX * (status32(g) ? 4u : 8u) / 16u : 0u;
+    const uint64_t bpr = hist_blocks_per_region(ctx, g);
     LaunchTimer lt(ctx, RSX_PROF_HIST, st);
     hipLaunchKernelGGL((rsx_hist_kernel<ES, FLT>), dim3((uint32_t)(bpr * g.num_regions)), dim3(512), 0, st,
                        static_cast<const Elem<ES>*>(src), g, make_spec(L, digit), (uint32_t)bpr, J, jclear, status32(g) ? 1u : 0u,
-                       static_cast<uint4*>(ctx->status), zero16_n, ctx->clean, ctx->gate, DigitSpec{}, nullptr, ctx->spec_dev);
+                       static_cast<uint4*>(ctx->status), zero16_n, run.clean, run.gate, DigitSpec{}, nullptr, run.spec_dev);
     RSX_HIP(hipGetLastError());
-    ctx->clean = CleanList{{nullptr, nullptr, nullptr}, {0, 0, 0}};  // done once per sort
+    run.clean = CLEAN_NONE;  // done once per sort
     return RSX_OK;
 }
 template <int ES>
-int launch_hist(rsx_ctx* ctx, const void* src, const RegionGeom& g, const rsx_layout* L, uint32_t digit,
+int launch_hist(rsx_ctx* ctx, SortRun& run, const void* src, const RegionGeom& g, const rsx_layout* L, uint32_t digit,
                 unsigned long long* J, unsigned long long* jclear, bool clear_status, hipStream_t st) {
-    if (L->key_kind == RSX_KEY_FLOAT || (L->key_kind == RSX_KEY_SIGNED && (digit + 1 == L->key_bytes || ctx->spec_dev != nullptr)))
-        return launch_hist_t<ES, true>(ctx, src, g, L, digit, J, jclear, clear_status, st);
-    return launch_hist_t<ES, false>(ctx, src, g, L, digit, J, jclear, clear_status, st);
+    if (L->key_kind == RSX_KEY_FLOAT || (L->key_kind == RSX_KEY_SIGNED && (digit + 1 == L->key_bytes || run.spec_dev != nullptr)))
+        return launch_hist_t<ES, true>(ctx, run, src, g, L, digit, J, jclear, clear_status, st);
+    return launch_hist_t<ES, false>(ctx, run, src, g, L, digit, J, jclear, clear_status, st);
 }
 
 template <int ES>
-int launch_hist2(rsx_ctx* ctx, const void* src, const RegionGeom& g, const rsx_layout* L, uint32_t digit,
+int launch_hist2(rsx_ctx* ctx, SortRun& run, const void* src, const RegionGeom& g, const rsx_layout* L, uint32_t digit,
                  unsigned long long* J, uint32_t digit2, unsigned long long* J2, unsigned long long* jclear, hipStream_t st) {
-    const uint64_t per_block = 512ull * 16;
-    const uint64_t zero16_n = status_rows(g, ES) * RADIX * (status32(g) ? 4u : 8u) / 16u;
-    uint64_t bpr = ((1ull << g.region_shift) + per_block - 1) / per_block;
-    const uint64_t cap = ((uint64_t)ctx->num_cu * RSX_HIST_BLOCKS_PER_CU + g.num_regions - 1) / g.num_regions;
-    if (bpr > cap) bpr = cap;
-    if (bpr == 0) bpr = 1;
+    const uint64_t zero16_n = status_rows(g) * RADIX * (status32(g) ? 4u : 8u) / 16u;
+    const uint64_t bpr = hist_blocks_per_region(ctx, g);
     LaunchTimer lt(ctx, RSX_PROF_HIST, st);
     // one instantiation per key kind class: the general digit map is the identity for unsigned keys' specs
     if (L->key_kind != RSX_KEY_UNSIGNED)
         hipLaunchKernelGGL((rsx_hist_kernel<ES, true, true>), dim3((uint32_t)(bpr * g.num_regions)), dim3(512), 0, st,
                            static_cast<const Elem<ES>*>(src), g, make_spec(L, digit), (uint32_t)bpr, J, jclear, status32(g) ? 1u : 0u,
-                           static_cast<uint4*>(ctx->status), zero16_n, ctx->clean, ctx->gate, make_spec(L, digit2), J2);
+                           static_cast<uint4*>(ctx->status), zero16_n, run.clean, run.gate, make_spec(L, digit2), J2);
     else
         hipLaunchKernelGGL((rsx_hist_kernel<ES, false, true>), dim3((uint32_t)(bpr * g.num_regions)), dim3(512), 0, st,
                            static_cast<const Elem<ES>*>(src), g, make_spec(L, digit), (uint32_t)bpr, J, jclear, status32(g) ? 1u : 0u,
-                           static_cast<uint4*>(ctx->status), zero16_n, ctx->clean, ctx->gate, make_spec(L, digit2), J2);
+                           static_cast<uint4*>(ctx->status), zero16_n, run.clean, run.gate, make_spec(L, digit2), J2);
     RSX_HIP(hipGetLastError());
-    ctx->clean = CleanList{{nullptr, nullptr, nullptr}, {0, 0, 0}};
+    run.clean = CLEAN_NONE;
     return RSX_OK;
 }
 
@@ -86,28 +89,26 @@ inline KeyXform make_xform(const rsx_layout* L) {
 }
 
 template <int ES, typename S, int XF, bool NEXT, bool MID = false, bool STR = false>
-int launch_sweep_t(rsx_ctx* ctx, const void* src, void* dst, const RegionGeom& g, const rsx_layout* L,
+int launch_sweep_t(rsx_ctx* ctx, const SortRun& run, const SweepPass& pass, const void* src, void* dst, const RegionGeom& g, const rsx_layout* L,
                    uint32_t digit, const unsigned long long* J, unsigned long long* jnext, unsigned long long* jzero,
                    hipStream_t st) {
     constexpr int KPT = kpt_for(ES);
     if (g.tile != (uint32_t)(wg_for(ES) * KPT)) return fail(ctx, RSX_ERR_INTERNAL, "launch_sweep: geometry of another tile size");
     constexpr int SWEEP_WG = wg_for(ES);
     constexpr int TILE = SWEEP_WG * KPT;
-    const uint64_t rows = status_rows(g, ES);
     // Status words alternate between the two halves of the workspace.  The first half is zeroed by the
     // count kernel that precedes the first sweep; every pass zeroes, tile by tile, the half of the next.
     char* const half[2] = {static_cast<char*>(ctx->status), static_cast<char*>(ctx->status) + ctx->status_bytes};
-    const uint32_t which = ctx->pass_index & 1u;
-    (void)rows;
+    const uint32_t which = pass.index & 1u;
     SweepArgs a;
-    a.status_clean = ctx->pass_last ? nullptr : half[which ^ 1u];
+    a.status_clean = pass.last ? nullptr : half[which ^ 1u];
     a.src = src;
     a.dst = dst;
     a.g = g;
     a.J = J;
     a.status = half[which];
-    a.tickets = ctx->tickets_override ? ctx->tickets_override : tickets_of(ctx, ctx->pass_index);
-    a.prev_mode = ctx->pass_index ? tickets_of(ctx, ctx->pass_index - 1) + ROLL_SHARDS + 1 : nullptr;
+    a.tickets = run.tickets_override ? run.tickets_override : tickets_of(ctx, run, pass.index);
+    a.prev_mode = pass.index ? tickets_of(ctx, run, pass.index - 1) + ROLL_SHARDS + 1 : nullptr;
     a.jnext = jnext;
     a.jzero = jzero;
     a.error = ctx->host_err_dev;
@@ -115,7 +116,7 @@ int launch_sweep_t(rsx_ctx* ctx, const void* src, void* dst, const RegionGeom& g
     a.next = make_spec(L, NEXT ? digit + 1 : digit);
     a.spec.flip = a.next.flip = 0;  // the sweep sees mapped keys: plain digits
     a.xf = make_xform(L);
-    a.tiles_per_region = (uint32_t)tiles_per_region(g, ES);
+    a.tiles_per_region = (uint32_t)tiles_per_region(g);
     a.opts = ((ctx->options & OPT_DYNAMIC_TILES) ? SWEEP_OPT_DYNAMIC : 0u) |
              ((ctx->options & OPT_NO_XCD_MAJOR) ? SWEEP_OPT_NO_XCD_MAJOR : 0u) |
              ((ctx->options & OPT_AGENT_STATUS) || !ctx->l2_local ? SWEEP_OPT_AGENT_STATUS : 0u) |
@@ -125,17 +126,17 @@ int launch_sweep_t(rsx_ctx* ctx, const void* src, void* dst, const RegionGeom& g
     a.mid_J = nullptr;
     a.mid_spec = a.spec;
     a.mid_cap = 0;
-    a.gate = ctx->gate;
-    a.spec_dev = ctx->spec_dev;
-    a.mid_mode = ctx->pass_mid;
-    a.mid_hint = ctx->host_err_dev + 8;  // second word group of the host-visible block
+    a.gate = run.gate;
+    a.spec_dev = run.spec_dev;
+    a.mid_mode = pass.mid;
+    a.mid_hint = ctx->host_err_dev + HV_MID_HINT;
     if constexpr (MID) {
-        a.mid_J = JT_of(ctx);
+        a.mid_J = JT_of(ctx, run);
         a.mid_spec = make_spec(L, L->key_bytes - 1);
         a.mid_spec.flip = 0;
         a.mid_cap = bucket_cap(ES);
     }
-    a.rank_atomic = (ctx->rank_atomic && !(ctx->options & OPT_BALLOT_RANKS)) ? 1u : 0u;
+    a.rank_atomic = rank_atomic_of(ctx);
     a.hot_lanes = (ctx->options & OPT_ATOMIC_RANKS) ? 65u : ctx->hot_lanes;
     a.dbg_cnt = reinterpret_cast<unsigned long long*>(ctx->aux + OFF_DBG);
     const size_t lds = (size_t)TILE * ES + (SWEEP_WG / WAVE) * RADIX * ((RSX_WIDE_CNT && ES <= 4 && KPT >= 16 && SWEEP_WG <= 512) ? sizeof(uint32_t) : sizeof(uint16_t)) +
@@ -204,45 +205,67 @@ int launch_sweep_t(rsx_ctx* ctx, const void* src, void* dst, const RegionGeom& g
 }
 
 template <int ES, typename S, int XF>
-int launch_sweep_n(rsx_ctx* ctx, const void* src, void* dst, const RegionGeom& g, const rsx_layout* L,
+int launch_sweep_n(rsx_ctx* ctx, const SortRun& run, const SweepPass& pass, const void* src, void* dst, const RegionGeom& g, const rsx_layout* L,
                    uint32_t digit, const unsigned long long* J, unsigned long long* jnext, unsigned long long* jzero,
                    hipStream_t st) {
-    if (ctx->spec_dev != nullptr) {  // the hybrid's two sweeps: window digits at any bit offset (the STR instantiation)
+    if (run.spec_dev != nullptr) {  // the hybrid's two sweeps: window digits at any bit offset (the STR instantiation)
         if constexpr (ES >= 8 && (XF & 2) == 0) {
-            if (jnext) return launch_sweep_t<ES, S, XF, true, false, true>(ctx, src, dst, g, L, digit, J, jnext, jzero, st);
-            if constexpr (XF == 0) return launch_sweep_t<ES, S, 0, false, false, true>(ctx, src, dst, g, L, digit, J, nullptr, jzero, st);
+            if (jnext) return launch_sweep_t<ES, S, XF, true, false, true>(ctx, run, pass, src, dst, g, L, digit, J, jnext, jzero, st);
+            if constexpr (XF == 0) return launch_sweep_t<ES, S, 0, false, false, true>(ctx, run, pass, src, dst, g, L, digit, J, nullptr, jzero, st);
         }
         return fail(ctx, RSX_ERR_INTERNAL, "launch_sweep: no kernel for this pass of the hybrid");
     }
     if constexpr ((XF & 2) == 0) {  // a pass that maps the keys back is a last pass: nothing to count for
         if constexpr (sizeof(S) == 4 && ES != 1) {  // the first sweep of a middle-size sort (regions of <= 2^30 elements by far)
-            if (jnext && ctx->pass_mid != 0) return launch_sweep_t<ES, S, XF, true, true>(ctx, src, dst, g, L, digit, J, jnext, jzero, st);
+            if (jnext && pass.mid != 0) return launch_sweep_t<ES, S, XF, true, true>(ctx, run, pass, src, dst, g, L, digit, J, jnext, jzero, st);
         }
-        if (jnext) return launch_sweep_t<ES, S, XF, true>(ctx, src, dst, g, L, digit, J, jnext, jzero, st);
+        if (jnext) return launch_sweep_t<ES, S, XF, true>(ctx, run, pass, src, dst, g, L, digit, J, jnext, jzero, st);
     } else if (jnext) {
         return fail(ctx, RSX_ERR_ARG, "a last pass cannot count for a next one");
     }
-    return launch_sweep_t<ES, S, XF, false>(ctx, src, dst, g, L, digit, J, nullptr, jzero, st);
+    return launch_sweep_t<ES, S, XF, false>(ctx, run, pass, src, dst, g, L, digit, J, nullptr, jzero, st);
 }
 
 template <int ES, typename S>
-int launch_sweep_x(rsx_ctx* ctx, const void* src, void* dst, const RegionGeom& g, const rsx_layout* L,
+int launch_sweep_x(rsx_ctx* ctx, const SortRun& run, const SweepPass& pass, const void* src, void* dst, const RegionGeom& g, const rsx_layout* L,
                    uint32_t digit, const unsigned long long* J, unsigned long long* jnext, unsigned long long* jzero,
                    int xf, hipStream_t st) {
     switch (L->key_kind == RSX_KEY_UNSIGNED ? 0 : xf) {
-        case 1: return launch_sweep_n<ES, S, 1>(ctx, src, dst, g, L, digit, J, jnext, jzero, st);
-        case 2: return launch_sweep_n<ES, S, 2>(ctx, src, dst, g, L, digit, J, jnext, jzero, st);
-        case 3: return launch_sweep_n<ES, S, 3>(ctx, src, dst, g, L, digit, J, jnext, jzero, st);
-        default: return launch_sweep_n<ES, S, 0>(ctx, src, dst, g, L, digit, J, jnext, jzero, st);
+        case 1: return launch_sweep_n<ES, S, 1>(ctx, run, pass, src, dst, g, L, digit, J, jnext, jzero, st);
+        case 2: return launch_sweep_n<ES, S, 2>(ctx, run, pass, src, dst, g, L, digit, J, jnext, jzero, st);
+        case 3: return launch_sweep_n<ES, S, 3>(ctx, run, pass, src, dst, g, L, digit, J, jnext, jzero, st);
+        default: return launch_sweep_n<ES, S, 0>(ctx, run, pass, src, dst, g, L, digit, J, jnext, jzero, st);
     }
 }
 
 template <int ES>
-int launch_sweep(rsx_ctx* ctx, const void* src, void* dst, const RegionGeom& g, const rsx_layout* L, uint32_t digit,
-                 const unsigned long long* J, unsigned long long* jnext, unsigned long long* jzero, int xf,
-                 hipStream_t st) {
-    if (status32(g)) return launch_sweep_x<ES, uint32_t>(ctx, src, dst, g, L, digit, J, jnext, jzero, xf, st);
-    return launch_sweep_x<ES, uint64_t>(ctx, src, dst, g, L, digit, J, jnext, jzero, xf, st);
+int launch_sweep(rsx_ctx* ctx, const SortRun& run, const SweepPass& pass, const void* src, void* dst, const RegionGeom& g, const rsx_layout* L,
+                 uint32_t digit, const unsigned long long* J, unsigned long long* jnext, unsigned long long* jzero, int xf, hipStream_t st) {
+    if (status32(g)) return launch_sweep_x<ES, uint32_t>(ctx, run, pass, src, dst, g, L, digit, J, jnext, jzero, xf, st);
+    return launch_sweep_x<ES, uint64_t>(ctx, run, pass, src, dst, g, L, digit, J, jnext, jzero, xf, st);
+}
+
+// ---- sorts of one workgroup in LDS (rsx_small_kernel.hpp) ------------------------------------------
+// What their SmallArgs share: `passes` digits to sort by, the digits `nspec` of them are described for, and whether the
+// keys arrive raw (map_load) or mapped by an earlier sweep.  The bucket kernels start their LDS passes at the digit their
+// bucket's size allows (RSX_OPT_BUCKET_SKIP, first_digit_for) and compare neighbours on the key bytes from there up: they
+// build their compare masks from key_offset / key_bytes.
+inline SmallArgs small_args(const rsx_ctx* ctx, const rsx_layout* L, uint32_t passes, uint32_t nspec, bool map_load) {
+    SmallArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.passes = passes;
+    a.rank_atomic = rank_atomic_of(ctx);
+    a.map_store = L->key_kind == RSX_KEY_UNSIGNED ? 0u : 1u;
+    a.map_load = map_load ? a.map_store : 0u;
+    for (uint32_t d = 0; d < nspec; ++d) {
+        a.spec[d] = make_spec(L, d);
+        a.spec[d].flip = 0;  // the kernel sees mapped keys: plain digits
+    }
+    a.xf = make_xform(L);
+    a.no_skip = ctx->bucket_no_skip;
+    a.key_offset = L->key_offset;
+    a.key_bytes = L->key_bytes;
+    return a;
 }
 
 // ---- arrays of at most one tile: all passes in one launch of one workgroup ----------------------
@@ -250,19 +273,10 @@ template <int ES>
 int launch_small_sort(rsx_ctx* ctx, void* data, size_t n, const rsx_layout* L, hipStream_t st) {
     constexpr int KPT = kpt_for(ES);
     if (n == 0 || n > (size_t)512 * KPT || L->key_bytes > 16) return fail(ctx, RSX_ERR_INTERNAL, "launch_small_sort: size out of range");
-    SmallArgs a;
-    std::memset(&a, 0, sizeof a);
+    SmallArgs a = small_args(ctx, L, L->key_bytes, L->key_bytes, true);
     a.src = data;
     a.data = data;
     a.n = (uint32_t)n;
-    a.passes = L->key_bytes;
-    a.rank_atomic = (ctx->rank_atomic && !(ctx->options & OPT_BALLOT_RANKS)) ? 1u : 0u;
-    a.map_load = a.map_store = L->key_kind == RSX_KEY_UNSIGNED ? 0u : 1u;
-    for (uint32_t d = 0; d < L->key_bytes; ++d) {
-        a.spec[d] = make_spec(L, d);
-        a.spec[d].flip = 0;  // the kernel sees mapped keys: plain digits
-    }
-    a.xf = make_xform(L);
     const size_t lds = (size_t)512 * KPT * ES + 8 * RADIX * sizeof(uint32_t) + 64;
     auto kern = rsx_small_sort_kernel<ES, KPT>;
     LaunchTimer lt(ctx, RSX_PROF_OTHER, st);
@@ -293,7 +307,7 @@ int launch_mid_split(rsx_ctx* ctx, const void* src, void* dst, size_t n, const r
         a.spec = make_spec(L, L->key_bytes - 1);  // count: the raw key's top byte through the digit map
         a.xf = make_xform(L);
         a.map_keys = L->key_kind == RSX_KEY_UNSIGNED ? 0u : 1u;
-        a.rank_atomic = (ctx->rank_atomic && !(ctx->options & OPT_BALLOT_RANKS)) ? 1u : 0u;
+        a.rank_atomic = rank_atomic_of(ctx);
         {
             LaunchTimer lt(ctx, RSX_PROF_HIST, st);
             if (L->key_kind != RSX_KEY_UNSIGNED) hipLaunchKernelGGL((rsx_tilecount_kernel<ES, KPT, true>), dim3(a.tiles), dim3(512), 0, st, a);
@@ -315,45 +329,25 @@ int launch_mid_split(rsx_ctx* ctx, const void* src, void* dst, size_t n, const r
 }
 
 // ---- ... then the 256 buckets, each sorted by one workgroup --------------------------------------
-// the bucket kernels start their LDS passes at the digit their bucket's size allows (RSX_OPT_BUCKET_SKIP, first_digit_for)
-// and compare neighbours on the key bytes from there up
-inline void set_skip_mask(rsx_ctx* ctx, SmallArgs& a, const rsx_layout* L) {
-    a.no_skip = ctx->bucket_no_skip;
-    a.key_offset = L->key_offset;  // (the kernel builds its compare masks from these)
-    a.key_bytes = L->key_bytes;
-}
-
 template <int ES>
-int launch_bucket_sort(rsx_ctx* ctx, const void* src, void* dst, const RegionGeom& g, const rsx_layout* L, hipStream_t st) {
+int launch_bucket_sort(rsx_ctx* ctx, const void* src, void* dst, const rsx_layout* L, bool small, hipStream_t st) {
     if constexpr (ES == 1) {
         return fail(ctx, RSX_ERR_INTERNAL, "launch_bucket_sort: one-byte elements");
     } else {
         constexpr int KPT = bucket_kpt_for(ES);
         if (L->key_bytes < 2 || L->key_bytes > 16) return fail(ctx, RSX_ERR_INTERNAL, "launch_bucket_sort: key width out of range");
-        SmallArgs a;
-        std::memset(&a, 0, sizeof a);
+        SmallArgs a = small_args(ctx, L, L->key_bytes - 1, L->key_bytes - 1, false);  // (the split mapped the keys)
         a.src = src;
         a.data = dst;
-        a.passes = L->key_bytes - 1;
-        a.rank_atomic = (ctx->rank_atomic && !(ctx->options & OPT_BALLOT_RANKS)) ? 1u : 0u;
-        a.map_load = 0;  // the first sweep mapped the keys
-        a.map_store = L->key_kind == RSX_KEY_UNSIGNED ? 0u : 1u;
-        for (uint32_t d = 0; d + 1 < L->key_bytes; ++d) {
-            a.spec[d] = make_spec(L, d);
-            a.spec[d].flip = 0;
-        }
-        a.xf = make_xform(L);
-        (void)g;
         a.top_tot = mid_totals_of(ctx);
         a.cap = bucket_cap(ES);
-        a.hint = ctx->host_err_dev + 8;
-        set_skip_mask(ctx, a, L);
+        a.hint = ctx->host_err_dev + HV_MID_HINT;
         LaunchTimer lt(ctx, RSX_PROF_OTHER, st);
-        if (ctx->bucket_small) {  // small buckets, all known to fit: 256 threads each
-            const size_t lds = (size_t)cape<ES, KPT, 256>() * ES + 4 * RADIX * bucket_cnt_bytes(ES) + 64 + 3 * RADIX * sizeof(uint32_t);
+        if (small) {  // small buckets, all known to fit: 256 threads each
+            const size_t lds = (size_t)cape<ES, KPT, 256>() * ES + 4 * RADIX * bucket_cnt_bytes() + 64 + 3 * RADIX * sizeof(uint32_t);
             hipLaunchKernelGGL((rsx_bucket_sort_kernel<ES, KPT, 256>), dim3(RADIX), dim3(256), lds, st, a);
         } else {
-            const size_t lds = (size_t)cape<ES, KPT, 1024>() * ES + 16 * RADIX * bucket_cnt_bytes(ES) + 64 + 3 * RADIX * sizeof(uint32_t);
+            const size_t lds = (size_t)cape<ES, KPT, 1024>() * ES + 16 * RADIX * bucket_cnt_bytes() + 64 + 3 * RADIX * sizeof(uint32_t);
             auto kern = rsx_bucket_sort_kernel<ES, KPT, 1024>;
             ensure_lds(ctx, reinterpret_cast<const void*>(kern), lds);
             hipLaunchKernelGGL(kern, dim3(RADIX), dim3(1024), lds, st, a);
@@ -407,56 +401,33 @@ int launch_count16top(rsx_ctx* ctx, const void* src, size_t n, const rsx_layout*
 
 // the first sweep's count matrix from the counters of launch_count16top (k chunks per region), + the side jobs of launch_hist
 template <int ES>
-int launch_marginal16(rsx_ctx* ctx, const uint32_t* P, uint32_t parts, uint32_t k, const RegionGeom& g, unsigned long long* J,
+int launch_marginal16(rsx_ctx* ctx, SortRun& run, const uint32_t* P, uint32_t parts, uint32_t k, const RegionGeom& g, unsigned long long* J,
                       unsigned long long* jclear, hipStream_t st) {
-    const uint64_t zero16_n = status_rows(g, ES) * RADIX * (status32(g) ? 4u : 8u) / 16u;
+    const uint64_t zero16_n = status_rows(g) * RADIX * (status32(g) ? 4u : 8u) / 16u;
     uint32_t grid = (uint32_t)ctx->num_cu * 8u;
     if (grid < parts) grid = parts;
     LaunchTimer lt(ctx, RSX_PROF_HIST, st);
     hipLaunchKernelGGL(rsx_marginal16_kernel<ES>, dim3(grid), dim3(256), 0, st, P, parts, k, g, J, jclear, status32(g) ? 1u : 0u,
-                       static_cast<uint4*>(ctx->status), zero16_n, ctx->clean, ctx->gate);
+                       static_cast<uint4*>(ctx->status), zero16_n, run.clean, run.gate);
     RSX_HIP(hipGetLastError());
-    ctx->clean = CleanList{{nullptr, nullptr, nullptr}, {0, 0, 0}};
+    run.clean = CLEAN_NONE;
     return RSX_OK;
 }
 
-// groups of 2^gs small buckets (0: none): about 3/4 of what a 512-thread workgroup of the bucket kernel holds
 template <int ES>
-uint32_t bucket16_group_shift(rsx_ctx* ctx, size_t n, const rsx_layout* L) {
-    constexpr int KPT = bucket_kpt_for(ES);
-    const uint64_t avg = (uint64_t)n / 65536u;
-    uint32_t gs = 0;
-    if (L->key_bytes >= 8 && ctx->bucket_group)
-        while (gs < 6 && (avg << (gs + 1)) <= (uint64_t)512 * KPT * 3 / 4) ++gs;
-    return gs >= 2 ? gs : 0;
-}
-
-template <int ES>
-int launch_bucket16(rsx_ctx* ctx, void* data, void* scratch, size_t n, const rsx_layout* L, const uint64_t* starts, const WidePlan* plan,
-                    hipStream_t st) {
+int launch_bucket16(rsx_ctx* ctx, const SortRun& run, void* data, void* scratch, size_t n, const rsx_layout* L, const uint64_t* starts,
+                    const WidePlan* plan, hipStream_t st) {
     if constexpr (ES < 4) {
         return fail(ctx, RSX_ERR_INTERNAL, "launch_bucket16: narrow elements");
     } else {
         constexpr int KPT = bucket_kpt_for(ES);
         if (L->key_bytes < 4) return fail(ctx, RSX_ERR_INTERNAL, "launch_bucket16: key width out of range");
-        SmallArgs a;
-        std::memset(&a, 0, sizeof a);
+        // passes: what the sort THROUGH MEMORY of an oversized bucket runs: an even number, every digit the LDS passes could
+        // need; the LDS passes themselves follow the device's plan.  The first sweep mapped the keys.
+        SmallArgs a = small_args(ctx, L, L->key_bytes - 2, L->key_bytes, false);
         a.src = data;
         a.data = data;
-        a.passes = L->key_bytes - 2;  // (what the sort THROUGH MEMORY of an oversized bucket runs: an even number, every digit the
-                                      // LDS passes could need; the LDS passes themselves follow the device's plan)
-        a.rank_atomic = (ctx->rank_atomic && !(ctx->options & OPT_BALLOT_RANKS)) ? 1u : 0u;
-        a.map_load = 0;  // the first sweep mapped the keys
-        a.map_store = L->key_kind == RSX_KEY_UNSIGNED ? 0u : 1u;
-        for (uint32_t d = 0; d < L->key_bytes; ++d) {
-            a.spec[d] = make_spec(L, d);
-            a.spec[d].flip = 0;
-        }
-        a.xf = make_xform(L);
         a.cap = bucket_cap(ES);
-        a.no_skip = ctx->bucket_no_skip;
-        a.key_offset = L->key_offset;
-        a.key_bytes = L->key_bytes;
         LaunchTimer lt(ctx, RSX_PROF_OTHER, st);
         // Every form the device's verdict can name is enqueued behind its own gate (rsx_scan16_kernel picks the smallest
         // workgroup that holds all but a handful of THIS input's buckets; a form whose workgroup cannot even hold the
@@ -464,8 +435,8 @@ int launch_bucket16(rsx_ctx* ctx, void* data, void* scratch, size_t n, const rsx
         // registers allow (3, 2, 1); small buckets in groups of 2^gs, about 3/4 of what a 512-thread workgroup holds,
         // sorted by all digits up to the window's top (keys of at least 8 bytes).
         const uint64_t avg = (uint64_t)n / 65536u;
-        const uint32_t gs = bucket16_group_shift<ES>(ctx, n, L);
-        const Gate base = ctx->gate;  // (null word: no gates -- never the case for this kernel)
+        const uint32_t gs = group_shift(ctx, n, L);
+        const Gate base = run.gate;  // (null word: no gates -- never the case for this kernel)
         auto go = [&](auto wgc, auto kc, uint32_t form, uint32_t group_shift) {
             constexpr int WGS = decltype(wgc)::value;
             constexpr int K = decltype(kc)::value;
@@ -473,7 +444,7 @@ int launch_bucket16(rsx_ctx* ctx, void* data, void* scratch, size_t n, const rsx
             b.group_shift = group_shift;
             if (group_shift) b.passes = L->key_bytes;
             static_assert(cape<ES, K, WGS>() == bucket_cape(ES, K, WGS), "host and device agree on what a workgroup holds");
-            const size_t lds = (size_t)cape<ES, K, WGS>() * ES + (WGS / 64) * RADIX * bucket_cnt_bytes(ES) + 64 + 3 * RADIX * sizeof(uint32_t);
+            const size_t lds = (size_t)cape<ES, K, WGS>() * ES + (WGS / 64) * RADIX * bucket_cnt_bytes() + 64 + 3 * RADIX * sizeof(uint32_t);
             auto kern = rsx_bucket16_kernel<ES, K, WGS>;
             ensure_lds(ctx, reinterpret_cast<const void*>(kern), lds);
             int per_cu = (int)((size_t)163840 / lds);
@@ -492,7 +463,7 @@ int launch_bucket16(rsx_ctx* ctx, void* data, void* scratch, size_t n, const rsx
         else go(integral_constant<int, 1024>{}, integral_constant<int, KPT>{}, VERDICT_WG1024, 0);
         {   // the buckets above the chosen form's workgroup (VERDICT_MEDIUM): one workgroup of the largest kind each
             constexpr int KMED = medium_kpt_for(ES);
-            const size_t lds = (size_t)cape<ES, KMED, 1024>() * ES + 16 * RADIX * bucket_cnt_bytes(ES) + 64 + 3 * RADIX * sizeof(uint32_t);
+            const size_t lds = (size_t)cape<ES, KMED, 1024>() * ES + 16 * RADIX * bucket_cnt_bytes() + 64 + 3 * RADIX * sizeof(uint32_t);
             auto kern = rsx_bucket16_medium_kernel<ES, KMED, 1024>;
             ensure_lds(ctx, reinterpret_cast<const void*>(kern), lds);
             const Gate g{base.word, VERDICT_PATH_MASK | VERDICT_MEDIUM, VERDICT_HYBRID | VERDICT_MEDIUM};
@@ -524,19 +495,8 @@ int launch_segment_sort(rsx_ctx* ctx, void* data, void* tmp, size_t n, const rsx
     constexpr uint32_t CAP0 = cape<ES, KPT, 256>(), CAP1 = cape<ES, KPT, 1024>();
     static_assert(CAP0 == segment_cap(ES, 0) && CAP1 == segment_cap(ES, 1), "host and device agree on what a workgroup holds");
     if (L->key_bytes > 16) return fail(ctx, RSX_ERR_INTERNAL, "launch_segment_sort: key width out of range");
-    SmallArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.passes = L->key_bytes;
-    a.rank_atomic = (ctx->rank_atomic && !(ctx->options & OPT_BALLOT_RANKS)) ? 1u : 0u;
-    a.map_load = a.map_store = L->key_kind == RSX_KEY_UNSIGNED ? 0u : 1u;
-    for (uint32_t d = 0; d < L->key_bytes; ++d) {
-        a.spec[d] = make_spec(L, d);
-        a.spec[d].flip = 0;  // the LDS forms see mapped keys: plain digits
-    }
-    a.xf = make_xform(L);
-    a.no_skip = (ctx->bucket_no_skip || L->key_bytes < 6) ? 1u : 0u;
-    a.key_offset = L->key_offset;
-    a.key_bytes = L->key_bytes;
+    SmallArgs a = small_args(ctx, L, L->key_bytes, L->key_bytes, true);  // the LDS forms
+    if (L->key_bytes < 6) a.no_skip = 1u;
     SmallArgs am = a;  // through memory: the keys stay raw, every pass reads its digit through the key map
     am.map_load = am.map_store = 0;
     for (uint32_t d = 0; d < L->key_bytes; ++d) am.spec[d] = make_spec(L, d);
@@ -554,7 +514,7 @@ int launch_segment_sort(rsx_ctx* ctx, void* data, void* tmp, size_t n, const rsx
         constexpr int WGS = decltype(wgc)::value;
         constexpr bool MEM = decltype(memc)::value;
         if (longest <= lo || (!offsets && row_len > hi)) return RSX_OK;  // no segment of this class can occur
-        const size_t lds = (size_t)cape<ES, KPT, WGS>() * ES + (WGS / 64) * RADIX * bucket_cnt_bytes(ES) + 64 + 3 * RADIX * sizeof(uint32_t);
+        const size_t lds = (size_t)cape<ES, KPT, WGS>() * ES + (WGS / 64) * RADIX * bucket_cnt_bytes() + 64 + 3 * RADIX * sizeof(uint32_t);
         auto kern = rsx_segment_sort_kernel<ES, KPT, WGS, MEM>;
         ensure_lds(ctx, reinterpret_cast<const void*>(kern), lds);
         uint32_t per_cu = (uint32_t)((size_t)163840 / (lds + 1024));

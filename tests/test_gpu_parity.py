@@ -1075,6 +1075,81 @@ def test_one_context_two_streams(rs, torch, orc):
     c.close()
 
 
+def test_entry_points_leave_nothing_behind_for_one_another(rs, torch, orc):
+    """Every entry point enqueues from its own arguments alone: on ONE context, a forced wide-key hybrid sort (both gated
+    sequences, the device's digit plan), a lone partition pass, a middle-size sort, sub-range counts and scatters (ticket
+    words outside the control blocks), LSD passes over 12-byte elements above the middle sizes, a pairs sort and an argsort
+    -- then the same calls in reverse order.  Each result against the oracle (tests/pairs_ref.py for the last two)."""
+    from pairs_ref import pairs_reference
+    c = rs.Context(torch.cuda.current_device())
+
+    def sort(t, n, dist, seed):
+        raw = util.make_input(t, n, dist, seed=seed)
+        x = torch.from_numpy(raw.copy()).cuda()
+        rs.radix_sort(x, digits=_digits(rs, t), ctx=c)
+        c.check()
+        assert np.array_equal(x.cpu().numpy(), orc.sort_parallel(raw, orc.Layout(*util.TYPES[t]), 8)), (t, n, dist)
+
+    def hybrid():
+        c.set_option(rs.OPT_WIDE_SORT, 2)
+        sort("i64", 200003, "uniform", 801)
+        assert (c.get_info(rs.INFO_LAST_PASSES) >> 24) & 15 == 5  # both sequences were enqueued, the hybrid ran
+        c.set_option(rs.OPT_WIDE_SORT, 1)
+
+    def partition():
+        t, n = "u32", 70001
+        raw = util.make_input(t, n, "zipf", seed=802)
+        src = torch.from_numpy(raw.copy()).cuda()
+        dst = torch.empty_like(src)
+        hist = torch.zeros(256, dtype=torch.int64, device="cuda")
+        c.partition_device(src.data_ptr(), dst.data_ptr(), n, _digits(rs, t), 3, hist.data_ptr())
+        c.check()
+        exp, exp_hist = orc.partition_pass(raw, orc.Layout(*util.TYPES[t]), 3)
+        assert np.array_equal(dst.cpu().numpy(), exp)
+        assert np.array_equal(hist.cpu().numpy().astype(np.uint64), exp_hist)
+
+    def sub_ranges():
+        t, n, nsub, digit = "u64", 70001, 2, 7
+        es = util.TYPES[t][0]
+        raw = util.make_input(t, n, "uniform", seed=803)
+        src = torch.from_numpy(raw.copy()).cuda()
+        dst = torch.zeros_like(src)
+        hist = torch.full((nsub * 256,), -1, dtype=torch.int64, device="cuda")
+        c.partition_count_device(src.data_ptr(), n, _digits(rs, t), digit, nsub, hist.data_ptr())
+        for k in range(nsub):
+            c.partition_scatter_device(src.data_ptr(), dst.data_ptr(), n, _digits(rs, t), digit, nsub, k)
+        c.check()
+        got, got_hist = dst.cpu().numpy(), hist.cpu().numpy().view(np.uint64).reshape(nsub, 256)
+        for k in range(nsub):
+            b, e = n * k // nsub * es, n * (k + 1) // nsub * es
+            exp, exp_hist = orc.partition_pass(np.ascontiguousarray(raw[b:e]), orc.Layout(*util.TYPES[t]), digit)
+            assert np.array_equal(got[b:e], exp) and np.array_equal(got_hist[k], exp_hist), k
+
+    def pairs():
+        n = 100003
+        keys_raw = util.make_input("u32", n, "zipf", seed=804)
+        keys = torch.from_numpy(keys_raw.copy()).cuda().view(torch.int32).view(torch.uint32)
+        vals = torch.arange(n, dtype=torch.int64, device="cuda")
+        rs.radix_sort_pairs(keys, vals, descending=True, ctx=c)
+        c.check()
+        want_keys, _v, perm = pairs_reference(keys_raw, None, 4, util.UNSIGNED, 0, True)
+        assert np.array_equal(keys.view(torch.int32).cpu().numpy().view(np.uint8), want_keys) and np.array_equal(vals.cpu().numpy(), perm)
+
+    def argsort():
+        n = 100003
+        keys_raw = util.make_input("i64", n, "step16", seed=805)
+        out = rs.radix_argsort(torch.from_numpy(keys_raw.copy()).cuda().view(torch.int64), ctx=c)
+        c.check()
+        assert np.array_equal(out.cpu().numpy(), pairs_reference(keys_raw, None, 8, util.SIGNED, 0, False)[2])
+
+    assert 1500001 > _mid_max(12)
+    steps = [hybrid, partition, lambda: sort("u32", 300001, "uniform", 806), sub_ranges,
+             lambda: sort("(u32,[u8;8])", 1500001, "uniform", 807), pairs, argsort]
+    for step in steps + steps[::-1]:
+        step()
+    c.close()
+
+
 def test_unreserved_sort_under_capture_reports_workspace(rs, torch):
     """A sort that would have to allocate while its stream is being captured returns RSX_ERR_WORKSPACE
     instead of calling hipMalloc mid-capture."""
