@@ -182,7 +182,10 @@ enum {
                                  elements / of the proxies) */
     RSX_INFO_LAST_PAIRS = 6   /* how the context's last rsx_sort_pairs_device / rsx_argsort_device call ran: 0 none yet,
                                  1 joined elements, 2 proxies and gather; bits 8-15 the size of the joined element (of
-                                 the proxy).  RSX_INFO_LAST_PASSES describes the inner sort of those elements. */
+                                 the proxy).  RSX_INFO_LAST_PASSES describes the inner sort of those elements.
+                                 The segmented key / value calls report 3, fused per segment (the joined elements exist
+                                 in registers and LDS only), or 4, fused per segment on (key, position) proxies followed
+                                 by a gather of the values; bits 8-15 as above, RSX_INFO_LAST_PASSES path 6. */
 };
 int rsx_ctx_get_info(rsx_ctx *ctx, int what, uint64_t *out);
 /* Per-launch timing with HIP events on the launch stream (measurement only).
@@ -292,6 +295,49 @@ int rsx_argsort_device(rsx_ctx *ctx, const void *d_keys, void *d_index, size_t n
 /* Workspace for either call on up to n pairs of these widths, so that the call allocates nothing (stream capture);
  * for rsx_argsort_device pass value_bytes = index_bytes. */
 int rsx_ctx_reserve_pairs(rsx_ctx *ctx, size_t n, uint32_t key_bytes, uint32_t value_bytes);
+
+/* -- many segments of separate key and value arrays ------------------------ */
+/* The segmented calls and the key / value calls combined: every segment [d_offsets[i], d_offsets[i+1]) (every row of
+ * row_len) of the key column gets the stable permutation by mapped key that rsx_sort_pairs_device / rsx_argsort_device
+ * would leave on that segment alone, ascending or descending, and the value column (1 .. RSX_MAX_ELEM_BYTES bytes a
+ * value; d_values == NULL with value_bytes == 0: keys only, which is how plain keys are sorted in descending order per
+ * segment) moves with it.  The argsort forms only read d_keys; d_index[i] receives the position INSIDE its segment,
+ * 0 .. len-1, as index_bytes (4 or 8) wide integers: torch.sort(dim=-1).indices.  Key widths, kinds and alignments
+ * are those of rsx_sort_pairs_device; the offsets follow the rules of rsx_sort_segments_device (on the device, never
+ * read by the host, a bad segment left untouched with the error word set, nothing outside the n keys / values /
+ * indices read or written, whatever lies outside [offsets[0], offsets[nseg]) as it was).  Index slots of segments of
+ * length 0 are untouched, a segment of length 1 gets its one 0.
+ *
+ * Routes (RSX_INFO_LAST_PAIRS; RSX_INFO_LAST_PASSES reports path 6 and the kernels launched):
+ *   3 fused per segment: values of 0, 1, 2, 4, 8 or 16 bytes, and positions.  One workgroup per segment reads its part
+ *     of the two columns, sorts the joined (mapped key, value) elements in LDS and writes the columns back; one launch
+ *     per size class of the JOINED element size (rsx_segment_pairs_caps).  The LDS classes touch no workspace and can be
+ *     captured once the context has made its first call.  Segments above the largest LDS class are joined into the
+ *     context's pairs workspace (the shape of rsx_ctx_reserve_pairs: for the argsort forms pass value_bytes = 4 or 8),
+ *     sorted through memory by their workgroup and split back; that class is launched only when such a segment can
+ *     occur (max_seg_len unknown or above the cap, row_len above the cap), and under capture without a sufficient
+ *     reserve the call then returns RSX_ERR_WORKSPACE and enqueues nothing.
+ *   4 wider values: the values are copied into the workspace, the fused kernels sort (key, u32 position in the array),
+ *     write the keys in place and the positions into a workspace array, and a gather moves the values.  n must be
+ *     below 2^32 (RSX_ERR_UNSUPPORTED otherwise).
+ * Rows longer than the largest LDS class follow the rule of rsx_sort_rows_device: at least as many rows as the device
+ * has CUs and row_len at most four times that class go through memory in one launch; otherwise rsx_sort_pairs_device /
+ * rsx_argsort_device runs once per row on its sub-range (RSX_INFO_LAST_PAIRS then describes the last row's call).
+ * Very short rows are the weak spot they are for rsx_sort_rows_device: one workgroup per row. */
+int rsx_sort_segments_pairs_device(rsx_ctx *ctx, void *d_keys, void *d_values, size_t n, uint32_t key_bytes,
+                                   uint32_t key_kind, uint32_t value_bytes, int order, const uint64_t *d_offsets,
+                                   size_t nseg, uint64_t max_seg_len, void *stream);
+int rsx_argsort_segments_device(rsx_ctx *ctx, const void *d_keys, void *d_index, size_t n, uint32_t key_bytes,
+                                uint32_t key_kind, uint32_t index_bytes, int order, const uint64_t *d_offsets,
+                                size_t nseg, uint64_t max_seg_len, void *stream);
+int rsx_sort_rows_pairs_device(rsx_ctx *ctx, void *d_keys, void *d_values, size_t rows, size_t row_len,
+                               uint32_t key_bytes, uint32_t key_kind, uint32_t value_bytes, int order, void *stream);
+int rsx_argsort_rows_device(rsx_ctx *ctx, const void *d_keys, void *d_index, size_t rows, size_t row_len,
+                            uint32_t key_bytes, uint32_t key_kind, uint32_t index_bytes, int order, void *stream);
+/* Host-only, needs no device: caps[c] = the longest segment that size class c of the calls above sorts inside LDS for
+ * these widths (RSX_SEG_CLASSES entries): rsx_segment_caps of the joined element, which for values without a fused
+ * kernel -- and for the argsort forms, whatever index_bytes: pass value_bytes = 4 -- is the (key, u32 position) proxy. */
+int rsx_segment_pairs_caps(uint32_t key_bytes, uint32_t value_bytes, uint32_t *caps);
 
 /* -- per-pass building blocks (multi-GPU bucket exchange) ---------------- */
 /* 256-bin count of digit `digit` (0 = least significant) over `n` elements:

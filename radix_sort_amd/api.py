@@ -235,7 +235,10 @@ class Context:
 
     def reserve_pairs(self, n: int, key_bytes: int, value_bytes: int):
         """rsx_ctx_reserve_pairs: workspace for sort_pairs_device / argsort_device of up to n pairs (argsort:
-        value_bytes = index_bytes), so that the call allocates nothing and can be captured into a graph."""
+        value_bytes = index_bytes), so that the call allocates nothing and can be captured into a graph.  The segmented
+        and row forms (radix_sort_rows_pairs, radix_argsort_rows, radix_sort_segments_pairs, radix_argsort_segments)
+        need it only where a segment can exceed segment_pairs_caps(...)[-1] or the values are wider than 16 bytes; n is
+        then the length of the whole key column."""
         self._check(self._L.rsx_ctx_reserve_pairs(self._h, n, key_bytes, value_bytes))
 
     def sort_pairs_device(self, d_keys: int, d_values: int, n: int, key_bytes: int, key_kind: int, value_bytes: int,
@@ -250,6 +253,31 @@ class Context:
         """rsx_argsort_device: the stable sorting permutation of n keys as index_bytes-wide integers; keys untouched."""
         self._check(self._L.rsx_argsort_device(self._h, d_keys, d_index, n, key_bytes, key_kind, index_bytes,
                                                1 if descending else 0, stream))
+
+    def sort_segments_pairs_device(self, d_keys: int, d_values: int, n: int, key_bytes: int, key_kind: int, value_bytes: int,
+                                   d_offsets: int, nseg: int, descending: bool = False, max_seg_len: int = 0, stream: int = 0):
+        """rsx_sort_segments_pairs_device: every segment of the key column sorted on its own, the value column with it
+        (d_values 0 and value_bytes 0: keys only)."""
+        self._check(self._L.rsx_sort_segments_pairs_device(self._h, d_keys, d_values or None, n, key_bytes, key_kind, value_bytes,
+                                                           1 if descending else 0, d_offsets, nseg, max_seg_len, stream))
+
+    def argsort_segments_device(self, d_keys: int, d_index: int, n: int, key_bytes: int, key_kind: int, index_bytes: int,
+                                d_offsets: int, nseg: int, descending: bool = False, max_seg_len: int = 0, stream: int = 0):
+        """rsx_argsort_segments_device: every segment's stable sorting permutation as positions inside the segment."""
+        self._check(self._L.rsx_argsort_segments_device(self._h, d_keys, d_index, n, key_bytes, key_kind, index_bytes,
+                                                        1 if descending else 0, d_offsets, nseg, max_seg_len, stream))
+
+    def sort_rows_pairs_device(self, d_keys: int, d_values: int, rows: int, row_len: int, key_bytes: int, key_kind: int,
+                               value_bytes: int, descending: bool = False, stream: int = 0):
+        """rsx_sort_rows_pairs_device: `rows` back-to-back segments of `row_len` keys (and values) each."""
+        self._check(self._L.rsx_sort_rows_pairs_device(self._h, d_keys, d_values or None, rows, row_len, key_bytes, key_kind,
+                                                       value_bytes, 1 if descending else 0, stream))
+
+    def argsort_rows_device(self, d_keys: int, d_index: int, rows: int, row_len: int, key_bytes: int, key_kind: int,
+                            index_bytes: int, descending: bool = False, stream: int = 0):
+        """rsx_argsort_rows_device: torch.sort(dim=-1).indices of a (rows, row_len) key array."""
+        self._check(self._L.rsx_argsort_rows_device(self._h, d_keys, d_index, rows, row_len, key_bytes, key_kind, index_bytes,
+                                                    1 if descending else 0, stream))
 
 
 _DEFAULT = {}
@@ -549,6 +577,172 @@ def radix_argsort(keys, descending: bool = False, out=None, ctx: Optional[Contex
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
         c.argsort_device(keys.data_ptr(), out.data_ptr(), n, kb, kind, out.element_size(), descending, stream)
+    return out
+
+
+def segment_pairs_caps(key_bytes: int, value_bytes: int):
+    """rsx_segment_pairs_caps: the longest segment each LDS size class of the segmented key / value sorts holds for
+    these widths (argsort: value_bytes = 4).  Needs no device."""
+    L = _lib.load()
+    caps = (ctypes.c_uint32 * _lib.SEG_CLASSES)()
+    rc = L.rsx_segment_pairs_caps(key_bytes, value_bytes, caps)
+    if rc != 0:
+        raise RsxError(rc, L.rsx_strerror(rc).decode())
+    return [int(c) for c in caps]
+
+
+def _value_bytes(values, lead, what: str) -> int:
+    """Bytes of one value of `values`, whose leading shape must be `lead`; None: keys only (0)."""
+    import torch
+    if values is None:
+        return 0
+    if not isinstance(values, torch.Tensor):
+        raise TypeError("values must be a torch tensor or None")
+    if not values.is_contiguous():
+        raise ValueError("values must be contiguous")
+    if values.dim() < len(lead) or tuple(values.shape[:len(lead)]) != tuple(lead):
+        raise ValueError(f"values must have the leading shape of {what} {tuple(lead)}, not shape {tuple(values.shape)}")
+    vb = values.element_size()
+    for s in values.shape[len(lead):]:
+        vb *= s
+    if vb == 0 or vb > 32768:
+        raise ValueError(f"one value must have 1 .. 32768 bytes, not {vb}")
+    return vb
+
+
+def _index_out(out, shape, what: str):
+    import torch
+    if out is None:
+        return
+    if not isinstance(out, torch.Tensor):
+        raise TypeError("out must be a torch tensor")
+    if out.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"out must be int32 or int64, not {out.dtype}")
+    if tuple(out.shape) != tuple(shape) or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous tensor of shape {tuple(shape)} like {what}")
+
+
+def _rows_keys(keys):
+    """(key_bytes, key_kind, rows, row_len) of a key tensor sorted along its last dimension."""
+    import torch
+    if not isinstance(keys, torch.Tensor):
+        raise TypeError("keys must be a torch tensor on a GPU")
+    if not keys.is_contiguous():
+        raise ValueError("keys must be contiguous")
+    if keys.dim() < 1:
+        raise ValueError("keys must have at least one dimension")
+    d = _torch_digits(keys, None)
+    row_len = keys.shape[-1]
+    return d.key_bytes, d.key_kind, (keys.numel() // row_len if row_len else 0), row_len
+
+
+def radix_sort_rows_pairs(keys, values, descending: bool = False, ctx: Optional[Context] = None):
+    """Sorts every row along the last dimension of `keys` in place and moves `values` with it
+    (rsx_sort_rows_pairs_device): `k, i = torch.sort(keys, dim=-1, stable=True, descending=descending)`,
+    `values = values.gather(-1, i)`, fused into one kernel per row.  Returns None; enqueued on the current stream.
+
+    keys: a contiguous GPU tensor of at least one dimension, of a dtype radix_sort knows.
+    values: a contiguous GPU tensor on the same device whose leading shape is keys.shape; one value is values[..., j]
+       (a scalar) or values[..., j, :] with its trailing dimensions, 1 .. 32768 bytes, moved bitwise.  None: keys only,
+       which is how rows of plain keys are sorted in descending order.
+    The order is radix_sort_pairs' (a total order on bit patterns, stable in both directions).  Values of 1, 2, 4, 8 or 16
+    bytes stay in registers and LDS with their keys; wider ones are gathered through a copy in the context's workspace.
+    Rows above segment_pairs_caps(key_bytes, value_bytes)[-1] are sorted through memory or row by row: slow."""
+    import torch
+    kb, kind, rows, row_len = _rows_keys(keys)
+    vb = _value_bytes(values, keys.shape, "keys")
+    _pairs_device(keys, values, "values")
+    if rows == 0 or row_len <= 1:
+        return None
+    dev = keys.device.index if keys.device.index is not None else torch.cuda.current_device()
+    c = ctx or default_context(dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        c.sort_rows_pairs_device(keys.data_ptr(), values.data_ptr() if values is not None else 0, rows, row_len, kb, kind, vb,
+                                 descending, stream)
+    return None
+
+
+def radix_argsort_rows(keys, descending: bool = False, out=None, ctx: Optional[Context] = None):
+    """`torch.sort(keys, dim=-1, stable=True, descending=descending).indices` (rsx_argsort_rows_device): returns a new
+    int64 tensor of keys.shape, or fills and returns `out` (contiguous, int32 or int64, keys.shape, same device).  `keys`
+    is not modified.  The order is radix_argsort's.  Enqueued on the current stream, not synchronised."""
+    import torch
+    kb, kind, rows, row_len = _rows_keys(keys)
+    _index_out(out, keys.shape, "keys")
+    _pairs_device(keys, out, "out")
+    if out is None:
+        out = torch.empty(keys.shape, dtype=torch.int64, device=keys.device)
+    if rows == 0 or row_len == 0:
+        return out
+    dev = keys.device.index if keys.device.index is not None else torch.cuda.current_device()
+    c = ctx or default_context(dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        c.argsort_rows_device(keys.data_ptr(), out.data_ptr(), rows, row_len, kb, kind, out.element_size(), descending, stream)
+    return out
+
+
+def _segments_common(keys, offsets, max_seg_len):
+    import torch
+    if not isinstance(keys, torch.Tensor):
+        raise TypeError("keys must be a torch tensor on a GPU")
+    _check_offsets(offsets)
+    kb, kind, n = _pairs_keys(keys, None)
+    if max_seg_len < 0:
+        raise ValueError("max_seg_len must not be negative")
+    return kb, kind, n
+
+
+def radix_sort_segments_pairs(keys, values, offsets, descending: bool = False, max_seg_len: int = 0,
+                              ctx: Optional[Context] = None):
+    """Sorts every segment [offsets[i], offsets[i+1]) of `keys` on its own, in place, and moves `values` with it
+    (rsx_sort_segments_pairs_device): what radix_sort_pairs would leave if called on each segment.  Returns None.
+
+    keys: as in radix_sort_pairs (1-D, or (n, 16) uint8 for unsigned 128-bit keys).  values: one row per key, or None.
+    offsets, max_seg_len: as in radix_sort_segments; keys and values outside [offsets[0], offsets[-1]) are not touched,
+    a bad segment is left as it is and the context's next check() raises."""
+    import torch
+    kb, kind, n = _segments_common(keys, offsets, max_seg_len)
+    vb = _value_bytes(values, (n,), "one row per key,")
+    _pairs_device(keys, values, "values")
+    if offsets.device != keys.device:
+        raise ValueError("offsets must live on the device of keys")
+    nseg = offsets.numel() - 1
+    if nseg <= 0 or n == 0:
+        return None
+    dev = keys.device.index if keys.device.index is not None else torch.cuda.current_device()
+    c = ctx or default_context(dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        c.sort_segments_pairs_device(keys.data_ptr(), values.data_ptr() if values is not None else 0, n, kb, kind, vb,
+                                     offsets.data_ptr(), nseg, descending, max_seg_len, stream)
+    return None
+
+
+def radix_argsort_segments(keys, offsets, descending: bool = False, out=None, max_seg_len: int = 0,
+                           ctx: Optional[Context] = None):
+    """The stable sorting permutation of every segment of `keys`, as positions INSIDE the segment (0 .. len-1;
+    rsx_argsort_segments_device).  Returns a new int64 tensor of len(keys), zero-filled so that the slots no segment
+    covers are defined, or fills and returns `out` (contiguous 1-D int32 or int64, len(keys)), whose slots outside every
+    segment, and those of bad segments, stay as they were.  `keys` is not modified."""
+    import torch
+    kb, kind, n = _segments_common(keys, offsets, max_seg_len)
+    _index_out(out, (n,), "one index per key,")
+    _pairs_device(keys, out, "out")
+    if offsets.device != keys.device:
+        raise ValueError("offsets must live on the device of keys")
+    if out is None:
+        out = torch.zeros(n, dtype=torch.int64, device=keys.device)
+    nseg = offsets.numel() - 1
+    if nseg <= 0 or n == 0:
+        return out
+    dev = keys.device.index if keys.device.index is not None else torch.cuda.current_device()
+    c = ctx or default_context(dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        c.argsort_segments_device(keys.data_ptr(), out.data_ptr(), n, kb, kind, out.element_size(), offsets.data_ptr(), nseg,
+                                  descending, max_seg_len, stream)
     return out
 
 

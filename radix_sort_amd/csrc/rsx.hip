@@ -693,6 +693,17 @@ bool key_widths_ok(uint32_t kb, uint32_t kind) {  // the key array as a layout o
     const rsx_layout L{kb, 0, kb, kind};
     return layout_ok(&L);
 }
+// ---- the segmented forms of those calls (rsx_segment_pairs_kernels.hpp): values with a fused kernel, or positions ----
+bool typed_value_width(uint32_t vb) { return vb == 0 || vb == 1 || vb == 2 || vb == 4 || vb == 8 || vb == 16; }
+// the joined element the fused kernels sort: the value itself, or a four-byte position (argsort; values too wide to join)
+uint32_t segment_pairs_elem(uint32_t kb, uint32_t vb, bool argsort) {
+    return pairs_elem_bytes(kb, (!argsort && typed_value_width(vb)) ? vb : 4u);
+}
+// route B's workspace: two arrays of proxies and the copy of the values
+size_t segment_pairs_wide_bytes(size_t n, uint32_t kb, uint32_t vb) {
+    const size_t half = (n * (size_t)pairs_elem_bytes(kb, 4) + 255) & ~(size_t)255;
+    return 2 * half + ((n * (size_t)vb + 255) & ~(size_t)255);
+}
 uint32_t value_align(uint32_t vb) {
     uint32_t a = 1;
     while (a < 16 && vb % (2 * a) == 0) a *= 2;
@@ -1081,6 +1092,8 @@ int rsx_ctx_reserve_pairs(rsx_ctx* ctx, size_t n, uint32_t key_bytes, uint32_t v
     int rc = reserve_pairs_one(ctx, n, key_bytes, value_bytes, nullptr);
     // an argsort with 8-byte indices joins 4-byte positions while n < 2^32: another element size
     if (!rc && value_bytes == 8 && (uint64_t)n < (1ull << 32)) rc = reserve_pairs_one(ctx, n, key_bytes, 4, nullptr);
+    // the segmented calls keep values without a fused kernel behind four-byte positions, whatever their width
+    if (!rc && !typed_value_width(value_bytes)) rc = ensure_any(ctx, segment_pairs_wide_bytes(n, key_bytes, value_bytes), nullptr);
     return rc;
 } catch (...) {
     return RSX_ERR_NOMEM;
@@ -1184,6 +1197,153 @@ int rsx_sort_rows_device(rsx_ctx* ctx, void* d_data, void* d_tmp, size_t rows, s
     return sort_segments_common(ctx, d_data, d_tmp, rows * row_len, L, nullptr, rows, row_len, 0, stream);
 } catch (...) {
     return RSX_ERR_HIP;
+}
+
+// ---- many segments of separate key and value columns (include/rsx.h) ----
+// Shared body of rsx_sort_segments_pairs_device / rsx_argsort_segments_device (d_offsets) and their row forms (d_offsets ==
+// nullptr, nseg rows of row_len).  d_index != nullptr: argsort.
+namespace {
+
+int segments_pairs_common(rsx_ctx* ctx, void* d_keys, void* d_values, void* d_index, bool argsort, size_t n, uint32_t kb, uint32_t kind, uint32_t vb,
+                          uint32_t ib, int order, const uint64_t* d_offsets, bool rows, size_t nseg, uint64_t row_len, uint64_t max_len, void* stream) {
+    if (!ctx) return RSX_ERR_ARG;
+    if (!key_widths_ok(kb, kind)) return fail(ctx, RSX_ERR_ARG, "invalid key width or kind");
+    if (argsort && ib != 4 && ib != 8) return fail(ctx, RSX_ERR_ARG, "index_bytes must be 4 or 8");
+    if (!argsort && vb > RSX_MAX_ELEM_BYTES) return fail(ctx, RSX_ERR_ARG, "value wider than RSX_MAX_ELEM_BYTES");
+    if (order != RSX_ORDER_ASCENDING && order != RSX_ORDER_DESCENDING) return fail(ctx, RSX_ERR_ARG, "invalid order");
+    if (!argsort && (d_values == nullptr) != (vb == 0)) return fail(ctx, RSX_ERR_ARG, "d_values and value_bytes disagree");
+    if (nseg == 0 || n == 0 || (rows && row_len == 0)) return RSX_OK;
+    if (rows && row_len == 1 && !argsort) return RSX_OK;
+    if (!rows && !d_offsets) return fail(ctx, RSX_ERR_ARG, "null device pointer");
+    if (!d_keys || (argsort && !d_index)) return fail(ctx, RSX_ERR_ARG, "null device pointer");
+    if (!aligned(d_keys, kb) || (argsort && !aligned(d_index, ib)) || (vb && !aligned(d_values, value_align(vb))) || !aligned(d_offsets, 8))
+        return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return fail(ctx, RSX_ERR_NODEVICE, "hipSetDevice failed");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint32_t desc = order == RSX_ORDER_DESCENDING ? 1u : 0u;
+    if (rows && row_len == 1) {  // argsort: every row's one position
+        RSX_HIP(hipMemsetAsync(d_index, 0, n * (size_t)ib, st));
+        return RSX_OK;
+    }
+    const bool wide = !argsort && !typed_value_width(vb);  // route B: positions and a gather
+    const uint32_t es = segment_pairs_elem(kb, vb, argsort);
+    if (es == 0 || !launchers_for(es)) return fail(ctx, RSX_ERR_INTERNAL, "no joined element for these widths");
+    if (wide && (uint64_t)n >= (1ull << 32)) return fail(ctx, RSX_ERR_UNSUPPORTED, "2^32 or more pairs with values too wide to join");
+    const uint64_t cap = segment_cap((int)es, RSX_SEG_CLASSES - 1);
+    int rc;
+    // Rows above what a workgroup holds in LDS: the rule of rsx_sort_rows_device -- the whole-array call row by row, unless
+    // every CU has a row of its own and the rows are short enough for one workgroup's passes through memory.
+    if (rows && row_len > cap && !(nseg >= (size_t)ctx->num_cu && row_len <= 4 * cap)) {
+        for (size_t i = 0; i < nseg; ++i) {
+            const size_t off = i * (size_t)row_len;
+            char* k = static_cast<char*>(d_keys) + off * kb;
+            if (argsort) rc = pairs_locked(ctx, k, nullptr, static_cast<char*>(d_index) + off * ib, (size_t)row_len, kb, kind, 0, ib, desc, st);
+            else rc = pairs_locked(ctx, k, vb ? static_cast<char*>(d_values) + off * vb : nullptr, nullptr, (size_t)row_len, kb, kind, vb, 0, desc, st);
+            if (rc) return rc;
+        }
+        return RSX_OK;
+    }
+    rc = pending_error(ctx);
+    if (rc) return rc;
+    const bool mem = segment_pairs_mem(es, d_offsets, row_len, max_len);
+    if (wide) {
+        rc = ensure_aux(ctx, st);
+        if (!rc) rc = ensure_any(ctx, segment_pairs_wide_bytes(n, kb, vb), st);
+    } else if (mem) {
+        rc = reserve_pairs_one(ctx, n, kb, argsort ? 4u : vb, st);  // (two arrays of n joined elements)
+    } else {
+        rc = ensure_aux(ctx, st);  // (the error word and the ranking self-test: a context's first call, never a captured one)
+    }
+    if (rc) return rc;
+    Enqueue enq(ctx, st);
+    const size_t half = (n * (size_t)es + 255) & ~(size_t)255;
+    char* w0 = (wide || mem) ? ctx->any_buf : nullptr;
+    char* w1 = w0 ? w0 + half : nullptr;
+    SegPairsCall c{};
+    c.keys = d_keys;
+    c.values = argsort ? d_index : wide ? static_cast<void*>(w0) : d_values;
+    c.w0 = w0;
+    c.w1 = w1;
+    c.n = n;
+    c.kb = kb;
+    c.vb = (argsort || wide) ? 4u : vb;
+    c.kind = kind;
+    c.desc = desc;
+    c.mode = argsort ? SEGP_LOCAL : wide ? SEGP_GLOBAL : SEGP_VALUES;
+    c.ib = ib;
+    c.offsets = d_offsets;
+    c.nseg = nseg;
+    c.row_len = row_len;
+    c.max_len = max_len;
+    char* cp = nullptr;
+    if (wide) {  // every element's own position first: what no segment covers, and what a bad one holds, stays where it is
+        cp = w1 + half;
+        rc = launch_pairs_join(ctx, d_keys, nullptr, w0, n, kb, 4, true, kind, desc, st);
+        if (rc) return rc;
+        RSX_HIP(hipMemcpyAsync(cp, d_values, n * (size_t)vb, hipMemcpyDeviceToDevice, st));
+    }
+    uint32_t launched = 0;
+    rc = launchers_for(es)->segment_pairs(ctx, c, &launched, st);
+    if (rc) return rc;
+    if (wide) {
+        rc = launch_gather(ctx, cp, d_values, vb, w0, es, pairs_value_offset(kb, 4), n, st);
+        if (rc) return rc;
+    }
+    ctx->last_path = 6;
+    ctx->last_route = 0;
+    ctx->last_sort_passes = launched;
+    ctx->last_pairs = (wide ? 4u : 3u) | es << 8;
+    return RSX_OK;
+}
+bool rows_overflow(size_t rows, size_t row_len, uint32_t widest) {
+    if (rows == 0 || row_len == 0) return false;
+    if (row_len > SIZE_MAX / rows) return true;
+    return widest != 0 && rows * row_len > SIZE_MAX / widest;
+}
+}  // namespace
+
+int rsx_sort_segments_pairs_device(rsx_ctx* ctx, void* d_keys, void* d_values, size_t n, uint32_t key_bytes, uint32_t key_kind, uint32_t value_bytes,
+                                   int order, const uint64_t* d_offsets, size_t nseg, uint64_t max_seg_len, void* stream) try {
+    return segments_pairs_common(ctx, d_keys, d_values, nullptr, false, n, key_bytes, key_kind, value_bytes, 0, order, d_offsets, false, nseg, 0,
+                                 max_seg_len, stream);
+} catch (...) {
+    return RSX_ERR_HIP;
+}
+
+int rsx_argsort_segments_device(rsx_ctx* ctx, const void* d_keys, void* d_index, size_t n, uint32_t key_bytes, uint32_t key_kind, uint32_t index_bytes,
+                                int order, const uint64_t* d_offsets, size_t nseg, uint64_t max_seg_len, void* stream) try {
+    return segments_pairs_common(ctx, const_cast<void*>(d_keys), nullptr, d_index, true, n, key_bytes, key_kind, 0, index_bytes, order, d_offsets, false,
+                                 nseg, 0, max_seg_len, stream);
+} catch (...) {
+    return RSX_ERR_HIP;
+}
+
+int rsx_sort_rows_pairs_device(rsx_ctx* ctx, void* d_keys, void* d_values, size_t rows, size_t row_len, uint32_t key_bytes, uint32_t key_kind,
+                               uint32_t value_bytes, int order, void* stream) try {
+    if (ctx && rows_overflow(rows, row_len, key_bytes > value_bytes ? key_bytes : value_bytes)) return fail(ctx, RSX_ERR_ARG, "rows * row_len overflows");
+    return segments_pairs_common(ctx, d_keys, d_values, nullptr, false, rows * row_len, key_bytes, key_kind, value_bytes, 0, order, nullptr, true, rows,
+                                 row_len, 0, stream);
+} catch (...) {
+    return RSX_ERR_HIP;
+}
+
+int rsx_argsort_rows_device(rsx_ctx* ctx, const void* d_keys, void* d_index, size_t rows, size_t row_len, uint32_t key_bytes, uint32_t key_kind,
+                            uint32_t index_bytes, int order, void* stream) try {
+    if (ctx && rows_overflow(rows, row_len, key_bytes > 8 ? key_bytes : 8)) return fail(ctx, RSX_ERR_ARG, "rows * row_len overflows");
+    return segments_pairs_common(ctx, const_cast<void*>(d_keys), nullptr, d_index, true, rows * row_len, key_bytes, key_kind, 0, index_bytes, order,
+                                 nullptr, true, rows, row_len, 0, stream);
+} catch (...) {
+    return RSX_ERR_HIP;
+}
+
+int rsx_segment_pairs_caps(uint32_t key_bytes, uint32_t value_bytes, uint32_t* caps) {
+    if (!caps || !key_widths_ok(key_bytes, RSX_KEY_UNSIGNED) || value_bytes > RSX_MAX_ELEM_BYTES) return RSX_ERR_ARG;
+    const uint32_t es = segment_pairs_elem(key_bytes, value_bytes, false);
+    if (es == 0) return RSX_ERR_UNSUPPORTED;
+    for (int c = 0; c < RSX_SEG_CLASSES; ++c) caps[c] = segment_cap((int)es, c);
+    return RSX_OK;
 }
 
 int rsx_segment_caps(const rsx_layout* L, uint32_t* caps) {

@@ -1583,4 +1583,11 @@ __global__ __launch_bounds__(256) void rsx_segcopy_kernel(const Elem<ES>* __rest
         dst[dof + i] = src[so + i];
 }
 
+// what the value of a fused segmented key / value sort is (rsx_segment_pairs_kernels.hpp; the host names it in SegPairsCall)
+enum : uint32_t {
+    SEGP_VALUES = 0,  // the value column is read and written (VB == 0: keys only)
+    SEGP_LOCAL = 1,   // argsort: the value is the position inside the segment; only the index column is written
+    SEGP_GLOBAL = 2,  // wider values: the value is the position in the array; keys in place, positions into the proxies
+};
+
 }  // namespace rsx

@@ -361,6 +361,26 @@ inline uint32_t group_shift(const rsx_ctx* ctx, size_t n, const rsx_layout* L) {
     return gs >= 2 ? gs : 0;
 }
 
+// What one fused segmented key / value sort is asked to do (rsx.hip -> launch_segment_pairs of the joined element size).
+struct SegPairsCall {
+    void* keys;               // n keys of kb bytes (mode 1: only read)
+    void* values;             // mode 0: n values of vb bytes (vb 0: none); mode 1: n indices of ib bytes; mode 2: n proxies (w0)
+    void* w0;                 // the two workspace arrays of n joined elements (through-memory class only)
+    void* w1;
+    size_t n;
+    uint32_t kb, vb;          // widths inside the joined element (modes 1 and 2: vb 4, the position)
+    uint32_t kind, desc;
+    uint32_t mode;            // rsx::SEGP_VALUES / SEGP_LOCAL / SEGP_GLOBAL
+    uint32_t ib;
+    const uint64_t* offsets;  // or nullptr: nseg rows of row_len
+    uint64_t nseg, row_len, max_len;
+};
+// whether a segment above the largest LDS class can occur (the through-memory class is launched, its workspace needed)
+inline bool segment_pairs_mem(uint32_t es, const uint64_t* offsets, uint64_t row_len, uint64_t max_len) {
+    const uint64_t cap = segment_cap((int)es, 1);
+    return offsets ? (max_len == 0 || max_len > cap) : row_len > cap;
+}
+
 // ---- per-element-size launchers: defined in rsx_launch_impl.hpp; rsx_es.hip fills ONE size's table with them (which
 // instantiates them), rsx.hip looks the table up by element size once per call (launchers_for).  A unit's kernels are emitted
 // in the order of the members here: keeping it keeps the code objects comparable from one build to the next. ----
@@ -399,6 +419,9 @@ struct EsLaunchers {
     int (*small_sort)(rsx_ctx* ctx, void* data, size_t n, const rsx_layout* L, hipStream_t st);
     int (*segcopy)(rsx_ctx* ctx, const void* src, void* dst, const uint64_t* so, const uint64_t* dof, const uint64_t* len, uint32_t nseg,
                    hipStream_t st);
+    // every segment of separate key and value columns sorted by one workgroup (rsx_segment_pairs_kernels.hpp), for the
+    // joined element size of this table: one launch per size class
+    int (*segment_pairs)(rsx_ctx* ctx, const SegPairsCall& call, uint32_t* launched, hipStream_t st);
 };
 template <int ES>
 const EsLaunchers& es_launchers();  // specialised in rsx_es.hip

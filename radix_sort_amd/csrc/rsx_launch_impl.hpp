@@ -6,6 +6,7 @@
 #include "rsx_small_kernel.hpp"
 #include "rsx_mid_kernels.hpp"
 #include "rsx_segment_kernels.hpp"
+#include "rsx_segment_pairs_kernels.hpp"
 
 #ifndef RSX_HIST_BLOCKS_PER_CU
 #define RSX_HIST_BLOCKS_PER_CU 8
@@ -548,6 +549,102 @@ int launch_segment_sort(rsx_ctx* ctx, void* data, void* tmp, size_t n, const rsx
     rc = go(integral_constant<int, 1024>{}, integral_constant<bool, false>{}, CAP0, CAP1);
     if (rc) return rc;
     return go(integral_constant<int, 1024>{}, integral_constant<bool, true>{}, CAP1, 0xFFFFFFFFull);
+}
+
+// ---- many segments of separate key and value columns (rsx_segment_pairs_kernels.hpp) ----------------------
+// One launch per size class of the JOINED element size ES that `max_len` (0: unknown) leaves possible; rows: the one
+// class of row_len.  The kernel is typed on the widths (KB, VB) with pairs_elem(KB, VB) == ES.
+template <int ES, int KB, int VB>
+int launch_segment_pairs_kv(rsx_ctx* ctx, const SegPairsCall& c, uint32_t* launched, hipStream_t st) {
+    constexpr int KPT = bucket_kpt_for(ES);
+    constexpr uint32_t CAP0 = cape<ES, KPT, 256>(), CAP1 = cape<ES, KPT, 1024>();
+    static_assert(CAP0 == segment_cap(ES, 0) && CAP1 == segment_cap(ES, 1), "host and device agree on what a workgroup holds");
+    const rsx_layout L{(uint32_t)ES, 0, (uint32_t)KB, RSX_KEY_UNSIGNED};  // what the passes see: the mapped key in front
+    SmallArgs a = small_args(ctx, &L, KB, KB, false);
+    if (KB < 6) a.no_skip = 1u;
+    SegPairsArgs s;
+    std::memset(&s, 0, sizeof s);
+    s.keys = static_cast<uint8_t*>(c.keys);
+    s.values = static_cast<uint8_t*>(c.values);
+    s.w0 = c.w0;
+    s.w1 = c.w1;
+    s.n = c.n;
+    s.offsets = c.offsets;
+    s.nseg = c.nseg;
+    s.row_len = c.row_len;
+    s.error = ctx->host_err_dev;
+    s.kind = c.kind;
+    s.desc = c.desc;
+    s.mode = c.mode;
+    s.ib = c.ib;
+    const uint64_t longest = c.offsets ? (c.max_len ? c.max_len : ~0ull) : c.row_len;
+    auto go = [&](auto wgc, auto memc, uint64_t lo, uint64_t hi) -> int {
+        constexpr int WGS = decltype(wgc)::value;
+        constexpr bool MEM = decltype(memc)::value;
+        if (longest <= lo || (!c.offsets && c.row_len > hi)) return RSX_OK;  // no segment of this class can occur
+        if (MEM && (!c.w0 || !c.w1)) return fail(ctx, RSX_ERR_INTERNAL, "launch_segment_pairs: no workspace for the through-memory class");
+        const size_t lds = (size_t)cape<ES, KPT, WGS>() * ES + (WGS / 64) * RADIX * bucket_cnt_bytes() + 64 + 3 * RADIX * sizeof(uint32_t);
+        auto kern = rsx_segment_pairs_kernel<ES, KB, VB, KPT, WGS, MEM>;
+        ensure_lds(ctx, reinterpret_cast<const void*>(kern), lds);
+        uint32_t per_cu = (uint32_t)((size_t)163840 / (lds + 1024));
+        if (per_cu > 1024u / WGS) per_cu = 1024u / WGS;  // (128 registers a lane: 16 waves a CU)
+        if (per_cu < 1) per_cu = 1;
+        const uint64_t full = (uint64_t)ctx->num_cu * per_cu;
+        SegPairsArgs b = s;
+        b.lo = lo;
+        b.hi = hi;
+        b.team = 1;
+        uint64_t grid = full;
+        if (!c.offsets) {
+            if (grid > c.nseg) grid = c.nseg;
+        } else {  // few blocks: the workgroups of a team share a block's members
+            const uint64_t nblocks = (c.nseg + SEG_BLOCK - 1) / SEG_BLOCK;
+            while (b.team < SEG_BLOCK && (uint64_t)b.team < c.nseg && nblocks * b.team < full) b.team *= 2;
+            uint64_t teams = full / b.team;
+            if (teams < 1) teams = 1;
+            if (teams > nblocks) teams = nblocks;
+            grid = teams * b.team;
+        }
+        LaunchTimer lt(ctx, RSX_PROF_OTHER, st);
+        hipLaunchKernelGGL(kern, dim3((uint32_t)grid), dim3(WGS), lds, st, a, b);
+        RSX_HIP(hipGetLastError());
+        ++*launched;
+        return RSX_OK;
+    };
+    using std::integral_constant;
+    // (argsort: a segment of one element gets its one 0, so the first class starts at length 1)
+    int rc = go(integral_constant<int, 256>{}, integral_constant<bool, false>{}, c.mode == SEGP_LOCAL ? 0 : 1, CAP0);
+    if (rc) return rc;
+    rc = go(integral_constant<int, 1024>{}, integral_constant<bool, false>{}, CAP0, CAP1);
+    if (rc) return rc;
+    return go(integral_constant<int, 1024>{}, integral_constant<bool, true>{}, CAP1, 0xFFFFFFFFull);
+}
+
+template <int ES, int KB, int VB>
+bool segment_pairs_try(rsx_ctx* ctx, const SegPairsCall& c, uint32_t* launched, hipStream_t st, int& rc) {
+    if constexpr (pairs_elem(KB, VB) == (uint32_t)ES) {
+        if (c.kb == (uint32_t)KB && c.vb == (uint32_t)VB) {
+            rc = launch_segment_pairs_kv<ES, KB, VB>(ctx, c, launched, st);
+            return true;
+        }
+    }
+    return false;
+}
+template <int ES, int KB>
+bool segment_pairs_try_kb(rsx_ctx* ctx, const SegPairsCall& c, uint32_t* launched, hipStream_t st, int& rc) {
+    return segment_pairs_try<ES, KB, 0>(ctx, c, launched, st, rc) || segment_pairs_try<ES, KB, 1>(ctx, c, launched, st, rc) ||
+           segment_pairs_try<ES, KB, 2>(ctx, c, launched, st, rc) || segment_pairs_try<ES, KB, 4>(ctx, c, launched, st, rc) ||
+           segment_pairs_try<ES, KB, 8>(ctx, c, launched, st, rc) || segment_pairs_try<ES, KB, 16>(ctx, c, launched, st, rc);
+}
+template <int ES>
+int launch_segment_pairs(rsx_ctx* ctx, const SegPairsCall& c, uint32_t* launched, hipStream_t st) {
+    int rc = RSX_OK;
+    if (c.mode != SEGP_VALUES && c.vb != 4) return fail(ctx, RSX_ERR_INTERNAL, "launch_segment_pairs: positions are four bytes");
+    if (segment_pairs_try_kb<ES, 1>(ctx, c, launched, st, rc) || segment_pairs_try_kb<ES, 2>(ctx, c, launched, st, rc) ||
+        segment_pairs_try_kb<ES, 4>(ctx, c, launched, st, rc) || segment_pairs_try_kb<ES, 8>(ctx, c, launched, st, rc) ||
+        segment_pairs_try_kb<ES, 16>(ctx, c, launched, st, rc))
+        return rc;
+    return fail(ctx, RSX_ERR_INTERNAL, "launch_segment_pairs: widths without a kernel of this element size");
 }
 
 }  // namespace rsxh

@@ -206,6 +206,51 @@ void radix_argsort(const K* d_keys, I* d_index, size_t n, bool descending = fals
                                  descending ? RSX_ORDER_DESCENDING : RSX_ORDER_ASCENDING, stream), "rsx_argsort_device");
 }
 
+// The segmented forms of the three calls above (rsx_sort_segments_pairs_device, rsx_argsort_segments_device and their
+// row forms): every segment [d_offsets[i], d_offsets[i+1]) -- nseg + 1 offsets ON THE DEVICE -- or every row of row_len
+// keys gets the stable permutation by key on its own; d_values == nullptr sorts the keys alone.  Values of 1, 2, 4, 8 or
+// 16 bytes are sorted with their keys inside LDS, one workgroup per segment; the indices of the argsort forms are
+// positions INSIDE the segment (torch.sort(dim=-1).indices).  Stream-ordered; bad offsets surface at
+// synchronize_and_check.  Segments above rsx_segment_pairs_caps use the context's workspace (rsx_ctx_reserve_pairs).
+template <typename K, typename V>
+void radix_sort_segments_pairs(K* d_keys, V* d_values, size_t n, const uint64_t* d_offsets, size_t nseg, bool descending = false,
+                               void* stream = nullptr, uint64_t max_seg_len = 0, Context& ctx = default_context()) {
+    static_assert(std::is_trivially_copyable<V>::value, "values are moved bitwise");
+    const rsx_layout L = RadixDigits<K>::layout();
+    if (L.key_offset != 0 || L.key_bytes != L.elem_bytes) throw std::invalid_argument("radix_sort_segments_pairs: the key type must be its own key");
+    ctx.check(rsx_sort_segments_pairs_device(ctx.get(), d_keys, d_values, n, L.key_bytes, L.key_kind, d_values ? (uint32_t)sizeof(V) : 0u,
+                                             descending ? RSX_ORDER_DESCENDING : RSX_ORDER_ASCENDING, d_offsets, nseg, max_seg_len, stream),
+              "rsx_sort_segments_pairs_device");
+}
+template <typename K, typename I>
+void radix_argsort_segments(const K* d_keys, I* d_index, size_t n, const uint64_t* d_offsets, size_t nseg, bool descending = false,
+                            void* stream = nullptr, uint64_t max_seg_len = 0, Context& ctx = default_context()) {
+    static_assert(std::is_integral<I>::value && (sizeof(I) == 4 || sizeof(I) == 8), "indices are 4- or 8-byte integers");
+    const rsx_layout L = RadixDigits<K>::layout();
+    if (L.key_offset != 0 || L.key_bytes != L.elem_bytes) throw std::invalid_argument("radix_argsort_segments: the key type must be its own key");
+    ctx.check(rsx_argsort_segments_device(ctx.get(), d_keys, d_index, n, L.key_bytes, L.key_kind, (uint32_t)sizeof(I),
+                                          descending ? RSX_ORDER_DESCENDING : RSX_ORDER_ASCENDING, d_offsets, nseg, max_seg_len, stream),
+              "rsx_argsort_segments_device");
+}
+template <typename K, typename V>
+void radix_sort_rows_pairs(K* d_keys, V* d_values, size_t rows, size_t row_len, bool descending = false, void* stream = nullptr,
+                           Context& ctx = default_context()) {
+    static_assert(std::is_trivially_copyable<V>::value, "values are moved bitwise");
+    const rsx_layout L = RadixDigits<K>::layout();
+    if (L.key_offset != 0 || L.key_bytes != L.elem_bytes) throw std::invalid_argument("radix_sort_rows_pairs: the key type must be its own key");
+    ctx.check(rsx_sort_rows_pairs_device(ctx.get(), d_keys, d_values, rows, row_len, L.key_bytes, L.key_kind, d_values ? (uint32_t)sizeof(V) : 0u,
+                                         descending ? RSX_ORDER_DESCENDING : RSX_ORDER_ASCENDING, stream), "rsx_sort_rows_pairs_device");
+}
+template <typename K, typename I>
+void radix_argsort_rows(const K* d_keys, I* d_index, size_t rows, size_t row_len, bool descending = false, void* stream = nullptr,
+                        Context& ctx = default_context()) {
+    static_assert(std::is_integral<I>::value && (sizeof(I) == 4 || sizeof(I) == 8), "indices are 4- or 8-byte integers");
+    const rsx_layout L = RadixDigits<K>::layout();
+    if (L.key_offset != 0 || L.key_bytes != L.elem_bytes) throw std::invalid_argument("radix_argsort_rows: the key type must be its own key");
+    ctx.check(rsx_argsort_rows_device(ctx.get(), d_keys, d_index, rows, row_len, L.key_bytes, L.key_kind, (uint32_t)sizeof(I),
+                                      descending ? RSX_ORDER_DESCENDING : RSX_ORDER_ASCENDING, stream), "rsx_argsort_rows_device");
+}
+
 // Multi-GPU, one process: slice g lives on the device of ctxs[g]; the concatenation of the slices
 // is sorted as one array (slice = the reference's "chunk", mod.rs:66-70).  Blocking.
 template <typename T>
