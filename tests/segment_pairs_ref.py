@@ -2,12 +2,15 @@
 row forms), numpy only; a helper, no tests.
 
 Every good segment gets what pairs_ref.pairs_reference leaves on that segment alone; a bad segment (begin > end, or
-end > n) and everything no segment covers stays as it was.  Index slots no good segment of length >= 1 covers are -1."""
+end > n) and everything no segment covers stays as it was.  Index slots no good segment of length >= 1 covers are -1.
+
+segments_reference is the reference; segments_reference_fast computes the same for good offsets without a Python loop
+and is held equal to it by tests/test_segment_pairs_ref.py."""
 from __future__ import annotations
 
 import numpy as np
 
-from pairs_ref import pairs_reference
+from pairs_ref import mapped_columns, pairs_reference
 
 GUARD = 64  # bytes of 0xA5 on each side of every array the GPU tests hand to the library
 
@@ -36,9 +39,47 @@ def segments_reference(keys_raw, values_raw, key_bytes: int, kind: int, value_by
     return keys, values, local
 
 
-def with_guards(raw: np.ndarray) -> np.ndarray:
+def segments_reference_fast(keys_raw, values_raw, key_bytes: int, kind: int, value_bytes: int, descending: bool, offsets):
+    """segments_reference without the Python loop, for calls of many thousand segments: one np.lexsort over (mapped key
+    low word, mapped key high word, segment id) of the elements in [offsets[0], offsets[-1]).  lexsort is stable and the
+    segment id is the primary key, so every segment keeps its own range and inside it the order is pairs_reference's.
+
+    Only for good offsets: non-decreasing and within [0, n] (anything else raises).  tests/test_segment_pairs_ref.py holds
+    the two forms equal on the CPU; a GPU test may use this form only with widths and kinds that test covers."""
+    keys_raw = np.ascontiguousarray(keys_raw, dtype=np.uint8).reshape(-1)
+    n = keys_raw.size // key_bytes
+    offs = np.asarray(offsets, dtype=np.int64).reshape(-1)
+    if offs.size < 2 or offs[0] < 0 or offs[-1] > n or np.any(np.diff(offs) < 0):
+        raise ValueError("segments_reference_fast takes non-decreasing offsets within [0, n]")
+    keys = keys_raw.copy()
+    values = None
+    if value_bytes:
+        values_raw = np.ascontiguousarray(values_raw, dtype=np.uint8).reshape(-1)
+        values = values_raw.copy()
+    local = np.full(n, -1, dtype=np.int64)
+    b0, e0 = int(offs[0]), int(offs[-1])
+    m = e0 - b0
+    if m == 0:
+        return keys, values, local
+    cols = mapped_columns(keys_raw[b0 * key_bytes:e0 * key_bytes], key_bytes, kind, descending)
+    pad = np.zeros((m, 16), dtype=np.uint8)
+    pad[:, :key_bytes] = cols
+    lo = np.ascontiguousarray(pad[:, :8]).view("<u8").reshape(m)
+    hi = np.ascontiguousarray(pad[:, 8:]).view("<u8").reshape(m)
+    # the segment of every covered element: the last i with offsets[i] <= position (empty segments never win)
+    sid = np.searchsorted(offs, np.arange(b0, e0, dtype=np.int64), side="right") - 1
+    perm = np.lexsort((lo, hi, sid)).astype(np.int64)  # the last key is the primary one
+    keys[b0 * key_bytes:e0 * key_bytes] = keys_raw.reshape(n, key_bytes)[b0 + perm].reshape(-1)
+    if value_bytes:
+        values[b0 * value_bytes:e0 * value_bytes] = values_raw.reshape(n, value_bytes)[b0 + perm].reshape(-1)
+    local[b0:e0] = b0 + perm - offs[sid]  # (sid is sorted, so sid[i] is also the segment of OUTPUT position i)
+    return keys, values, local
+
+
+def with_guards(raw: np.ndarray, shift: int = 0) -> np.ndarray:
+    """What segment_pairs_gpu.guarded(raw, shift) allocates: GUARD + shift bytes of 0xA5, the array, GUARD bytes."""
     g = np.full(GUARD, 0xA5, dtype=np.uint8)
-    return np.concatenate([g, np.ascontiguousarray(raw).view(np.uint8).reshape(-1), g])
+    return np.concatenate([g, np.full(shift, 0xA5, dtype=np.uint8), np.ascontiguousarray(raw).view(np.uint8).reshape(-1), g])
 
 
 def expected_index(local: np.ndarray, index_bytes: int) -> np.ndarray:
