@@ -177,6 +177,8 @@ enum {
                                  16-bit buckets in LDS; a hybrid the device refused reports 0 and its D passes),
                                  6 segmented sort (rsx_sort_segments_device, rsx_sort_rows_device: bits 0-7 are then
                                  the kernels launched, one per size class, and bits 8-23 are 0),
+                                 7 top-k (rsx_topk_rows_device: bits 0-7 are then the kernels launched, one per round
+                                 of the selection, and bits 8-23 are 0),
                                  bits 28-29 the route of a layout without kernels of its own: 0 direct, 1 packed
                                  re-layout, 2 key-index proxy (bits 0-27 then describe the sort of the re-laid-out
                                  elements / of the proxies) */
@@ -338,6 +340,38 @@ int rsx_argsort_rows_device(rsx_ctx *ctx, const void *d_keys, void *d_index, siz
  * these widths (RSX_SEG_CLASSES entries): rsx_segment_caps of the joined element, which for values without a fused
  * kernel -- and for the argsort forms, whatever index_bytes: pass value_bytes = 4 -- is the (key, u32 position) proxy. */
 int rsx_segment_pairs_caps(uint32_t key_bytes, uint32_t value_bytes, uint32_t *caps);
+
+/* -- the first k of every row --------------------------------------------- */
+/* Top-k along the rows of a (rows, row_len) key array without sorting the rows.  One definition: let p_r be the stable
+ * permutation of row r that rsx_argsort_rows_device produces in `order` (ascending or descending by mapped key, equal
+ * keys in input order, floats by the total order on bit patterns); then, for i in [0, k),
+ *     d_out_keys[r*k + i] = d_keys[r*row_len + p_r[i]],    d_out_index[r*k + i] = p_r[i]
+ * -- the first k columns of the full sort, byte for byte: sorted output, and ties at the threshold go to the lowest
+ * positions.  d_keys is only read.  Key widths, kinds and alignments are those of rsx_argsort_rows_device; index_bytes
+ * is 4 or 8; either output pointer may be NULL (that output is not produced), not both.  A flat array is rows == 1.
+ * RSX_ERR_ARG: k > row_len, rows * row_len overflowing, bad widths, kinds, orders or alignments, both outputs NULL.
+ * rows == 0 or k == 0 succeeds, launches nothing and looks at no pointer.  row_len >= 2^32 is RSX_ERR_UNSUPPORTED.  Stream-ordered, no
+ * synchronisation; nothing outside the rows*k output keys and rows*k indices is written.
+ *
+ * One workgroup selects inside LDS: a most-significant-digit-first radix select over the joined (mapped key, u32
+ * position) elements (at most key_bytes counting passes that move nothing), a compaction in position order, and the
+ * stable sort of the k chosen elements.  Rows of at most caps[last] elements (rsx_topk_caps) take ONE launch, one
+ * workgroup per row, and no workspace: once the context has made its first call of any kind the call can be captured.
+ * Longer rows are a tournament: the row is cut into chunks of caps[last], every chunk leaves its min(k, length) best as
+ * joined candidates, and the candidates of a row are the row of the next round until it fits one chunk (one launch per
+ * round).  That needs k <= max_k (RSX_ERR_UNSUPPORTED otherwise: sort the row) and two workspace arrays of the first
+ * round's candidates in the context, made on first use or by rsx_ctx_reserve_topk; under capture without a sufficient
+ * reserve the call returns RSX_ERR_WORKSPACE and enqueues nothing.  RSX_INFO_LAST_PASSES reports path 7 and the rounds. */
+int rsx_topk_rows_device(rsx_ctx *ctx, const void *d_keys, void *d_out_keys, void *d_out_index, size_t rows,
+                         size_t row_len, size_t k, uint32_t key_bytes, uint32_t key_kind, uint32_t index_bytes,
+                         int order, void *stream);
+/* Workspace (and the context's first-call set-up) for rsx_topk_rows_device of this shape, so that the call allocates
+ * nothing.  The argument rules are the call's. */
+int rsx_ctx_reserve_topk(rsx_ctx *ctx, size_t rows, size_t row_len, size_t k, uint32_t key_bytes);
+/* Host-only, needs no device: caps[c] = the longest row that size class c (256 and 1024 threads) selects inside LDS
+ * for this key width (RSX_SEG_CLASSES entries, ascending: the classes of the joined (key, u32 position) element);
+ * *max_k = the largest k accepted for rows longer than caps[last] (half of it). */
+int rsx_topk_caps(uint32_t key_bytes, uint32_t *caps, uint32_t *max_k);
 
 /* -- per-pass building blocks (multi-GPU bucket exchange) ---------------- */
 /* 256-bin count of digit `digit` (0 = least significant) over `n` elements:

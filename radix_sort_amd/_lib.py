@@ -19,6 +19,7 @@ SYMBOLS = [
     "rsx_sort_pairs_device", "rsx_argsort_device", "rsx_ctx_reserve_pairs",
     "rsx_sort_segments_pairs_device", "rsx_argsort_segments_device", "rsx_sort_rows_pairs_device", "rsx_argsort_rows_device",
     "rsx_segment_pairs_caps",
+    "rsx_topk_rows_device", "rsx_ctx_reserve_topk", "rsx_topk_caps",
 ]
 SEG_CLASSES = 2  # RSX_SEG_CLASSES
 
@@ -120,6 +121,9 @@ def load():
     L.rsx_sort_rows_pairs_device.argtypes = [vp, vp, vp, sz, sz, u32, u32, u32, i, vp]
     L.rsx_argsort_rows_device.argtypes = [vp, vp, vp, sz, sz, u32, u32, u32, i, vp]
     L.rsx_segment_pairs_caps.argtypes = [u32, u32, ctypes.POINTER(u32)]
+    L.rsx_topk_rows_device.argtypes = [vp, vp, vp, vp, sz, sz, sz, u32, u32, u32, i, vp]
+    L.rsx_ctx_reserve_topk.argtypes = [vp, sz, sz, sz, u32]
+    L.rsx_topk_caps.argtypes = [u32, ctypes.POINTER(u32), ctypes.POINTER(u32)]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("rsx_last_error", "rsx_strerror"):

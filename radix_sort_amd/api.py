@@ -13,6 +13,7 @@ torch is used for device memory and streams only.
 from __future__ import annotations
 
 import ctypes
+import operator
 import threading
 from dataclasses import dataclass
 from typing import Optional, Sequence
@@ -278,6 +279,19 @@ class Context:
         """rsx_argsort_rows_device: torch.sort(dim=-1).indices of a (rows, row_len) key array."""
         self._check(self._L.rsx_argsort_rows_device(self._h, d_keys, d_index, rows, row_len, key_bytes, key_kind, index_bytes,
                                                     1 if descending else 0, stream))
+
+
+    def reserve_topk(self, rows: int, row_len: int, k: int, key_bytes: int):
+        """rsx_ctx_reserve_topk: the context's first-call set-up and, for rows above topk_caps(key_bytes)[0][-1], the two
+        candidate arrays of topk_rows_device for this shape, so that the call allocates nothing and can be captured."""
+        self._check(self._L.rsx_ctx_reserve_topk(self._h, rows, row_len, k, key_bytes))
+
+    def topk_rows_device(self, d_keys: int, d_out_keys: int, d_out_index: int, rows: int, row_len: int, k: int, key_bytes: int,
+                         key_kind: int, index_bytes: int, descending: bool = False, stream: int = 0):
+        """rsx_topk_rows_device: the first k columns of every row's stable sort -- the keys into d_out_keys and their
+        positions in the row into d_out_index (either may be 0: not produced); d_keys is only read."""
+        self._check(self._L.rsx_topk_rows_device(self._h, d_keys, d_out_keys or None, d_out_index or None, rows, row_len, k, key_bytes,
+                                                 key_kind, index_bytes, 1 if descending else 0, stream))
 
 
 _DEFAULT = {}
@@ -681,6 +695,70 @@ def radix_argsort_rows(keys, descending: bool = False, out=None, ctx: Optional[C
         stream = torch.cuda.current_stream(dev).cuda_stream
         c.argsort_rows_device(keys.data_ptr(), out.data_ptr(), rows, row_len, kb, kind, out.element_size(), descending, stream)
     return out
+
+
+def topk_caps(key_bytes: int):
+    """rsx_topk_caps -> (caps, max_k): the longest row each LDS size class of the top-k selects in one launch for this
+    key width, and the largest k taken for longer rows.  Needs no device."""
+    L = _lib.load()
+    caps = (ctypes.c_uint32 * _lib.SEG_CLASSES)()
+    max_k = ctypes.c_uint32()
+    rc = L.rsx_topk_caps(key_bytes, caps, ctypes.byref(max_k))
+    if rc != 0:
+        raise RsxError(rc, L.rsx_strerror(rc).decode())
+    return [int(c) for c in caps], int(max_k.value)
+
+
+# Shapes radix_topk hands to the full sort although rsx_topk_rows_device takes them: (no entry: none measured slower)
+def _topk_by_sort(rows: int, row_len: int, k: int, key_bytes: int) -> bool:
+    return False
+
+
+def radix_topk(keys, k: int, largest: bool = True, index_dtype=None, ctx: Optional[Context] = None):
+    """(values, indices) of the k largest (largest=False: smallest) keys along the last dimension, sorted, like
+    `torch.topk(keys, k, largest=largest, sorted=True)` -- with the tie order specified: the result is the first k
+    columns of the stable sort `radix_argsort_rows(keys, descending=largest)` and of the keys gathered through it, byte
+    for byte, so equal keys appear in input order and ties at the threshold go to the lowest positions
+    (rsx_topk_rows_device: a radix select in LDS and a sort of k elements, not a sort of the row).
+
+    keys: a contiguous GPU tensor of at least one dimension, of a dtype radix_sort knows; it is not modified.
+    Returns new tensors of shape keys.shape[:-1] + (k,): values of keys.dtype and indices of index_dtype (torch.int64,
+    the default, or torch.int32).  The order is radix_argsort's total order on bit patterns (+NaN is the largest float).
+    Enqueued on the current stream, not synchronised.
+
+    Total: where the C call is unsupported (rows longer than topk_caps(key_bytes)[0][-1] with k above its max_k), the
+    rows are sorted by radix_argsort_rows and the first k columns gathered -- the same bytes, at the cost of the sort."""
+    import torch
+    kb, kind, rows, row_len = _rows_keys(keys)
+    k = operator.index(k)
+    if k < 0 or k > row_len:
+        raise ValueError(f"k must be in 0 .. {row_len} (the last dimension), not {k}")
+    if index_dtype is None:
+        index_dtype = torch.int64
+    if index_dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"index_dtype must be torch.int32 or torch.int64, not {index_dtype}")
+    _pairs_device(keys, None, "")
+    shape = tuple(keys.shape[:-1]) + (k,)
+    values = torch.empty(shape, dtype=keys.dtype, device=keys.device)
+    indices = torch.empty(shape, dtype=index_dtype, device=keys.device)
+    if rows == 0 or k == 0:
+        return values, indices
+    dev = keys.device.index if keys.device.index is not None else torch.cuda.current_device()
+    c = ctx or default_context(dev)
+    caps, max_k = topk_caps(kb)
+    if (row_len > caps[-1] and k > max_k) or _topk_by_sort(rows, row_len, k, kb):
+        full = radix_argsort_rows(keys, descending=largest, ctx=c)
+        first = full[..., :k]
+        indices.copy_(first)
+        # (a gather of the raw bits: dtypes torch cannot index, uint32 / uint64, go as their signed twins)
+        bits = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[kb]
+        values.view(bits).copy_(torch.gather(keys.view(bits), -1, first))
+        return values, indices
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        c.topk_rows_device(keys.data_ptr(), values.data_ptr(), indices.data_ptr(), rows, row_len, k, kb, kind,
+                           indices.element_size(), largest, stream)
+    return values, indices
 
 
 def _segments_common(keys, offsets, max_seg_len):

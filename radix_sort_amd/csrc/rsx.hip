@@ -965,8 +965,8 @@ int rsx_ctx_get_info(rsx_ctx* ctx, int what, uint64_t* out) try {
         case RSX_INFO_NUM_CU: *out = (uint64_t)ctx->num_cu; return RSX_OK;
         case RSX_INFO_DEVICE: *out = (uint64_t)ctx->device; return RSX_OK;
         case RSX_INFO_LAST_PASSES: {
-            if (ctx->last_path == 6) {  // segmented: bits 0-7 are the kernels launched
-                *out = (uint64_t)(ctx->last_sort_passes & 0xFFu) | (uint64_t)6 << 24;
+            if (ctx->last_path == 6 || ctx->last_path == 7) {  // segmented, top-k: bits 0-7 are the kernels launched
+                *out = (uint64_t)(ctx->last_sort_passes & 0xFFu) | (uint64_t)ctx->last_path << 24;
                 return RSX_OK;
             }
             *out = (uint64_t)ctx->last_path << 24 | (uint64_t)ctx->last_route << 28;
@@ -1343,6 +1343,97 @@ int rsx_segment_pairs_caps(uint32_t key_bytes, uint32_t value_bytes, uint32_t* c
     const uint32_t es = segment_pairs_elem(key_bytes, value_bytes, false);
     if (es == 0) return RSX_ERR_UNSUPPORTED;
     for (int c = 0; c < RSX_SEG_CLASSES; ++c) caps[c] = segment_cap((int)es, c);
+    return RSX_OK;
+}
+
+// ---- the first k of every row (rsx_topk_kernels.hpp, include/rsx.h) ----
+namespace {
+// the checks rsx_topk_rows_device and rsx_ctx_reserve_topk share; *es: the joined (key, u32 position) element
+int topk_shape(rsx_ctx* ctx, size_t rows, size_t row_len, size_t k, uint32_t kb, uint32_t* es) {
+    if (k > row_len) return fail(ctx, RSX_ERR_ARG, "k above row_len");
+    if (rows_overflow(rows, row_len, kb > 8 ? kb : 8)) return fail(ctx, RSX_ERR_ARG, "rows * row_len overflows");
+    *es = pairs_elem_bytes(kb, 4);
+    if (*es == 0 || !launchers_for(*es)) return fail(ctx, RSX_ERR_INTERNAL, "no joined element for this key width");
+    if (rows == 0 || k == 0) return RSX_OK;
+    if ((uint64_t)row_len >= (1ull << 32)) return fail(ctx, RSX_ERR_UNSUPPORTED, "rows of 2^32 or more keys");
+    if ((uint64_t)row_len > segment_cap((int)*es, RSX_SEG_CLASSES - 1) && (uint64_t)k > topk_max_k(*es))
+        return fail(ctx, RSX_ERR_UNSUPPORTED, "k above rsx_topk_caps' max_k for rows longer than the largest LDS class");
+    return RSX_OK;
+}
+}  // namespace
+
+int rsx_topk_rows_device(rsx_ctx* ctx, const void* d_keys, void* d_out_keys, void* d_out_index, size_t rows, size_t row_len, size_t k,
+                         uint32_t key_bytes, uint32_t key_kind, uint32_t index_bytes, int order, void* stream) try {
+    if (!ctx) return RSX_ERR_ARG;
+    if (!key_widths_ok(key_bytes, key_kind)) return fail(ctx, RSX_ERR_ARG, "invalid key width or kind");
+    if (index_bytes != 4 && index_bytes != 8) return fail(ctx, RSX_ERR_ARG, "index_bytes must be 4 or 8");
+    if (order != RSX_ORDER_ASCENDING && order != RSX_ORDER_DESCENDING) return fail(ctx, RSX_ERR_ARG, "invalid order");
+    uint32_t es = 0;
+    int rc = topk_shape(ctx, rows, row_len, k, key_bytes, &es);
+    if (rc) return rc;
+    if (rows == 0 || k == 0) return RSX_OK;  // (empty outputs: no pointer is looked at)
+    if (!d_out_keys && !d_out_index) return fail(ctx, RSX_ERR_ARG, "both output pointers are null");
+    if (!d_keys) return fail(ctx, RSX_ERR_ARG, "null device pointer");
+    if (!aligned(d_keys, key_bytes) || !aligned(d_out_keys, key_bytes) || !aligned(d_out_index, index_bytes))
+        return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return fail(ctx, RSX_ERR_NODEVICE, "hipSetDevice failed");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    rc = pending_error(ctx);
+    if (rc) return rc;
+    rc = ensure_aux(ctx, st);  // (the error word and the ranking self-test: a context's first call, never a captured one)
+    const size_t half = topk_workspace_half(es, rows, row_len, k);
+    if (!rc && half) rc = ensure_any(ctx, 2 * half, st);
+    if (rc) return rc;
+    Enqueue enq(ctx, st);
+    TopkCall c{};
+    c.keys = d_keys;
+    c.out_keys = d_out_keys;
+    c.out_index = d_out_index;
+    c.w0 = half ? ctx->any_buf : nullptr;
+    c.w1 = half ? ctx->any_buf + half : nullptr;
+    c.rows = rows;
+    c.row_len = row_len;
+    c.k = k;
+    c.kb = key_bytes;
+    c.kind = key_kind;
+    c.desc = order == RSX_ORDER_DESCENDING ? 1u : 0u;
+    c.ib = index_bytes;
+    uint32_t launched = 0;
+    rc = launchers_for(es)->topk(ctx, c, &launched, st);
+    if (rc) return rc;
+    ctx->last_path = 7;
+    ctx->last_route = 0;
+    ctx->last_sort_passes = launched;
+    return RSX_OK;
+} catch (...) {
+    return RSX_ERR_HIP;
+}
+
+int rsx_ctx_reserve_topk(rsx_ctx* ctx, size_t rows, size_t row_len, size_t k, uint32_t key_bytes) try {
+    if (!ctx) return RSX_ERR_ARG;
+    if (!key_widths_ok(key_bytes, RSX_KEY_UNSIGNED)) return fail(ctx, RSX_ERR_ARG, "invalid key width");
+    uint32_t es = 0;
+    int rc = topk_shape(ctx, rows, row_len, k, key_bytes, &es);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return fail(ctx, RSX_ERR_NODEVICE, "hipSetDevice failed");
+    rc = ensure_aux(ctx, nullptr);
+    const size_t half = (rows == 0 || k == 0) ? 0 : topk_workspace_half(es, rows, row_len, k);
+    if (!rc && half) rc = ensure_any(ctx, 2 * half, nullptr);
+    return rc;
+} catch (...) {
+    return RSX_ERR_NOMEM;
+}
+
+int rsx_topk_caps(uint32_t key_bytes, uint32_t* caps, uint32_t* max_k) {
+    if (!caps || !max_k || !key_widths_ok(key_bytes, RSX_KEY_UNSIGNED)) return RSX_ERR_ARG;
+    const uint32_t es = pairs_elem_bytes(key_bytes, 4);
+    if (es == 0) return RSX_ERR_UNSUPPORTED;
+    for (int c = 0; c < RSX_SEG_CLASSES; ++c) caps[c] = segment_cap((int)es, c);
+    *max_k = topk_max_k(es);
     return RSX_OK;
 }
 

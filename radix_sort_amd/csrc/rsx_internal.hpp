@@ -381,6 +381,27 @@ inline bool segment_pairs_mem(uint32_t es, const uint64_t* offsets, uint64_t row
     return offsets ? (max_len == 0 || max_len > cap) : row_len > cap;
 }
 
+// What one rsx_topk_rows_device call is asked to do (rsx.hip -> launch_topk of the joined (key, u32 position) element size).
+struct TopkCall {
+    const void* keys;         // rows x row_len keys of kb bytes, only read
+    void* out_keys;           // rows x k keys, or nullptr
+    void* out_index;          // rows x k positions of ib bytes, or nullptr
+    void* w0;                 // rows longer than the largest LDS class: the two candidate arrays (topk_workspace_half bytes each)
+    void* w1;
+    uint64_t rows, row_len, k;
+    uint32_t kb, kind, desc, ib;
+};
+// the largest k a row above the largest LDS class is selected with: every round of the tournament then shrinks the row
+inline uint32_t topk_max_k(uint32_t es) { return segment_cap((int)es, 1) / 2u; }
+// bytes of ONE candidate array: what the first round leaves, min(k, length) joined elements per chunk (0: no round needs one)
+inline size_t topk_workspace_half(uint32_t es, uint64_t rows, uint64_t row_len, uint64_t k) {
+    const uint64_t L = segment_cap((int)es, 1);
+    if (row_len <= L) return 0;
+    const uint64_t cpr = (row_len + L - 1) / L, last = row_len - (cpr - 1) * L;
+    const uint64_t m1 = (cpr - 1) * k + (k < last ? k : last);
+    return ((size_t)(rows * m1) * es + 255) & ~(size_t)255;
+}
+
 // ---- per-element-size launchers: defined in rsx_launch_impl.hpp; rsx_es.hip fills ONE size's table with them (which
 // instantiates them), rsx.hip looks the table up by element size once per call (launchers_for).  A unit's kernels are emitted
 // in the order of the members here: keeping it keeps the code objects comparable from one build to the next. ----
@@ -422,6 +443,9 @@ struct EsLaunchers {
     // every segment of separate key and value columns sorted by one workgroup (rsx_segment_pairs_kernels.hpp), for the
     // joined element size of this table: one launch per size class
     int (*segment_pairs)(rsx_ctx* ctx, const SegPairsCall& call, uint32_t* launched, hipStream_t st);
+    // the first k of every row's stable sort (rsx_topk_kernels.hpp), for the joined (key, u32 position) element size of
+    // this table (8, 16, 32): one launch per round, *launched receives their number
+    int (*topk)(rsx_ctx* ctx, const TopkCall& call, uint32_t* launched, hipStream_t st);
 };
 template <int ES>
 const EsLaunchers& es_launchers();  // specialised in rsx_es.hip

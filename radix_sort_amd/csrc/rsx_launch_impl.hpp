@@ -7,6 +7,7 @@
 #include "rsx_mid_kernels.hpp"
 #include "rsx_segment_kernels.hpp"
 #include "rsx_segment_pairs_kernels.hpp"
+#include "rsx_topk_kernels.hpp"
 
 #ifndef RSX_HIST_BLOCKS_PER_CU
 #define RSX_HIST_BLOCKS_PER_CU 8
@@ -645,6 +646,80 @@ int launch_segment_pairs(rsx_ctx* ctx, const SegPairsCall& c, uint32_t* launched
         segment_pairs_try_kb<ES, 16>(ctx, c, launched, st, rc))
         return rc;
     return fail(ctx, RSX_ERR_INTERNAL, "launch_segment_pairs: widths without a kernel of this element size");
+}
+
+// ---- the first k of every row (rsx_topk_kernels.hpp) ------------------------------------------------
+// Rows of at most CAP1 elements: one launch, one workgroup per row, of the class of row_len.  Longer rows: a tournament --
+// the row is cut into chunks of CAP1, every chunk leaves its min(k, length) best as joined candidates in a workspace array,
+// and the candidates of a row are the row of the next round (k <= CAP1 / 2: every round shrinks the row) until it fits one
+// chunk, whose launch writes the outputs.
+template <int ES, int KB>
+int launch_topk_kb(rsx_ctx* ctx, const TopkCall& c, uint32_t* launched, hipStream_t st) {
+    constexpr int KPT = bucket_kpt_for(ES);
+    constexpr uint32_t CAP0 = cape<ES, KPT, 256>(), CAP1 = cape<ES, KPT, 1024>();
+    static_assert(CAP0 == segment_cap(ES, 0) && CAP1 == segment_cap(ES, 1), "host and device agree on what a workgroup holds");
+    const rsx_layout L{(uint32_t)ES, 0, (uint32_t)KB, RSX_KEY_UNSIGNED};  // what the passes see: the mapped key in front
+    SmallArgs a = small_args(ctx, &L, KB, KB, false);
+    if (KB < 6) a.no_skip = 1u;
+    if (c.row_len > CAP1 && (c.k > topk_max_k(ES) || !c.w0 || !c.w1)) return fail(ctx, RSX_ERR_INTERNAL, "launch_topk: long rows without their workspace");
+    TopkArgs t;
+    std::memset(&t, 0, sizeof t);
+    t.rows = c.rows;
+    t.row_len = c.row_len;
+    t.chunk = CAP1;
+    t.k = (uint32_t)c.k;
+    t.kind = c.kind;
+    t.desc = c.desc;
+    t.ib = c.ib;
+    auto go = [&](auto wgc) -> int {
+        constexpr int WGS = decltype(wgc)::value;
+        const size_t lds = (size_t)cape<ES, KPT, WGS>() * ES + (WGS / 64) * RADIX * bucket_cnt_bytes() + 64 + 3 * RADIX * sizeof(uint32_t);
+        auto kern = rsx_topk_kernel<ES, KB, KPT, WGS>;
+        ensure_lds(ctx, reinterpret_cast<const void*>(kern), lds);
+        uint32_t per_cu = (uint32_t)((size_t)163840 / (lds + 1024));
+        if (per_cu > 1024u / WGS) per_cu = 1024u / WGS;  // (128 registers a lane: 16 waves a CU)
+        if (per_cu < 1) per_cu = 1;
+        uint64_t grid = (uint64_t)ctx->num_cu * per_cu;
+        const uint64_t total = t.rows * t.cpr;
+        if (grid > total) grid = total;
+        LaunchTimer lt(ctx, RSX_PROF_OTHER, st);
+        hipLaunchKernelGGL(kern, dim3((uint32_t)grid), dim3(WGS), lds, st, a, t);
+        RSX_HIP(hipGetLastError());
+        ++*launched;
+        return RSX_OK;
+    };
+    uint64_t m = c.row_len;
+    void* bufs[2] = {c.w0, c.w1};
+    for (uint32_t round = 0;; ++round) {
+        const uint64_t cpr = (m + CAP1 - 1) / CAP1, last = m - (cpr - 1) * CAP1;
+        const bool final = cpr == 1;
+        t.keys = round == 0 ? static_cast<const uint8_t*>(c.keys) : nullptr;
+        t.cand_in = round == 0 ? nullptr : bufs[(round - 1) & 1u];
+        t.cand_out = final ? nullptr : bufs[round & 1u];
+        t.out_keys = final ? static_cast<uint8_t*>(c.out_keys) : nullptr;
+        t.out_index = final ? static_cast<uint8_t*>(c.out_index) : nullptr;
+        t.m = (uint32_t)m;
+        t.cpr = (uint32_t)cpr;
+        t.m_next = (uint32_t)((cpr - 1) * c.k + (c.k < last ? c.k : last));
+        const int rc = (final && m <= CAP0) ? go(std::integral_constant<int, 256>{}) : go(std::integral_constant<int, 1024>{});
+        if (rc) return rc;
+        if (final) return RSX_OK;
+        m = t.m_next;
+    }
+}
+
+template <int ES>
+int launch_topk(rsx_ctx* ctx, const TopkCall& c, uint32_t* launched, hipStream_t st) {
+    if constexpr (ES == 8) {
+        if (c.kb == 1) return launch_topk_kb<ES, 1>(ctx, c, launched, st);
+        if (c.kb == 2) return launch_topk_kb<ES, 2>(ctx, c, launched, st);
+        if (c.kb == 4) return launch_topk_kb<ES, 4>(ctx, c, launched, st);
+    } else if constexpr (ES == 16) {
+        if (c.kb == 8) return launch_topk_kb<ES, 8>(ctx, c, launched, st);
+    } else if constexpr (ES == 32) {
+        if (c.kb == 16) return launch_topk_kb<ES, 16>(ctx, c, launched, st);
+    }
+    return fail(ctx, RSX_ERR_INTERNAL, "launch_topk: no (key, u32 position) element of this size for the key width");
 }
 
 }  // namespace rsxh
