@@ -179,6 +179,8 @@ enum {
                                  the kernels launched, one per size class, and bits 8-23 are 0),
                                  7 top-k (rsx_topk_rows_device: bits 0-7 are then the kernels launched, one per round
                                  of the selection, and bits 8-23 are 0),
+                                 8 groups of equal keys (rsx_unique_device: bits 0-7 are then the kernels launched
+                                 after the sort of the joined elements, and bits 8-23 are 0),
                                  bits 28-29 the route of a layout without kernels of its own: 0 direct, 1 packed
                                  re-layout, 2 key-index proxy (bits 0-27 then describe the sort of the re-laid-out
                                  elements / of the proxies) */
@@ -372,6 +374,48 @@ int rsx_ctx_reserve_topk(rsx_ctx *ctx, size_t rows, size_t row_len, size_t k, ui
  * for this key width (RSX_SEG_CLASSES entries, ascending: the classes of the joined (key, u32 position) element);
  * *max_k = the largest k accepted for rows longer than caps[last] (half of it). */
 int rsx_topk_caps(uint32_t key_bytes, uint32_t *caps, uint32_t *max_k);
+
+/* -- groups of equal keys -------------------------------------------------- */
+/* What most callers do after a sort: which keys are equal, and where each group starts.  One definition: let p be the
+ * stable permutation of the n keys that rsx_argsort_device produces in `order` (ascending or descending by mapped key,
+ * equal keys in input order, floats by the total order on bit patterns), s[i] = d_keys[p[i]], and call position i a
+ * HEAD when i == 0 or s[i] and s[i-1] differ in any bit (-0.0 and +0.0 are two keys, NaNs of different payloads are
+ * different keys; the mapping is a bijection, so this is equality of mapped keys).  With the heads h[0] < ... < h[m-1]
+ * and h[m] = n, every output optional through a NULL pointer but d_out_num:
+ *     d_out_keys[j]    = s[h[j]], j < m: the distinct keys in order, as raw keys        (n entries of key_bytes)
+ *     d_out_offsets[j] = h[j], j <= m: CSR offsets of the groups inside p, uint64; the counts are their differences --
+ *                        the d_offsets of every rsx_*_segments* call, made on the device             (n + 1 entries)
+ *     d_out_perm[i]    = p[i]: d_out_perm[h[j] .. h[j+1]) are the input positions of group j in input order, the first
+ *                        of them its first occurrence                                (n entries of index_bytes)
+ *     d_out_inverse[q] = the j with d_keys[q] == d_out_keys[j], for every input position q      (n entries of index_bytes)
+ *     d_out_num[0]     = m, uint64
+ * Entries of d_out_keys at m and beyond and of d_out_offsets beyond m are not written; nothing outside these arrays
+ * and the context's workspace is written; d_keys is only read.  Key widths, kinds and alignments are those of
+ * rsx_argsort_device; the outputs are naturally aligned (offsets and num: 8 bytes); index_bytes is 4 or 8 and looked at
+ * only when d_out_perm or d_out_inverse is given.  RSX_ERR_ARG: bad widths, kinds, orders or alignments, d_out_num NULL,
+ * d_keys NULL with n > 0.  n >= 2^32 is RSX_ERR_UNSUPPORTED.  n == 0 writes d_out_num[0] = 0 and d_out_offsets[0] = 0 with
+ * stream-ordered memsets and launches nothing.  Stream-ordered, no synchronisation, no caller scratch: the host never
+ * reads m.
+ *
+ * Two routes, chosen from the pointers alone.  Keys only (d_out_perm and d_out_inverse NULL): the mapped keys,
+ * complemented for descending order, are sorted as elements of key_bytes.  With positions: (mapped key, u32 position)
+ * elements of 8 bytes (keys of 1, 2 and 4 bytes), 16 (8-byte keys) or 32 (16-byte keys), the join of
+ * rsx_argsort_device.  Either way the elements are sorted in the context's pairs workspace and three run kernels follow
+ * instead of the split kernel: heads per tile, one workgroup's exclusive sum over the tiles (it writes m and
+ * d_out_offsets[m]), and the write of the outputs.  No kernel waits for another workgroup.  d_out_inverse is a scatter by
+ * input position, the one uncoalesced stream of the call.  The workspace -- the two element arrays and two per-tile
+ * arrays -- is made on first use or by rsx_ctx_reserve_unique; under capture without a sufficient reserve the call
+ * returns RSX_ERR_WORKSPACE and enqueues nothing.  RSX_INFO_LAST_PASSES reports path 8 and, in bits 0-7, the kernels
+ * launched after the sort; RSX_INFO_LAST_PAIRS route 1 and the joined element's size. */
+int rsx_unique_device(rsx_ctx *ctx, const void *d_keys, size_t n, uint32_t key_bytes, uint32_t key_kind, int order,
+                      void *d_out_keys, uint64_t *d_out_offsets, void *d_out_perm, void *d_out_inverse,
+                      uint32_t index_bytes, uint64_t *d_out_num, void *stream);
+/* Workspace (and the context's first-call set-up) for rsx_unique_device on up to n keys of this width by the route
+ * with positions (with_positions != 0) or keys only, so that the call allocates nothing (stream capture). */
+int rsx_ctx_reserve_unique(rsx_ctx *ctx, size_t n, uint32_t key_bytes, int with_positions);
+/* Host-only, needs no device: *tile = the elements one workgroup of the run kernels takes for this key width and
+ * route, *scan_span = the tiles one sweep of the scan kernel's loop sums. */
+int rsx_unique_caps(uint32_t key_bytes, int with_positions, uint32_t *tile, uint32_t *scan_span);
 
 /* -- per-pass building blocks (multi-GPU bucket exchange) ---------------- */
 /* 256-bin count of digit `digit` (0 = least significant) over `n` elements:

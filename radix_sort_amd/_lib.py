@@ -20,6 +20,7 @@ SYMBOLS = [
     "rsx_sort_segments_pairs_device", "rsx_argsort_segments_device", "rsx_sort_rows_pairs_device", "rsx_argsort_rows_device",
     "rsx_segment_pairs_caps",
     "rsx_topk_rows_device", "rsx_ctx_reserve_topk", "rsx_topk_caps",
+    "rsx_unique_device", "rsx_ctx_reserve_unique", "rsx_unique_caps",
 ]
 SEG_CLASSES = 2  # RSX_SEG_CLASSES
 
@@ -124,6 +125,9 @@ def load():
     L.rsx_topk_rows_device.argtypes = [vp, vp, vp, vp, sz, sz, sz, u32, u32, u32, i, vp]
     L.rsx_ctx_reserve_topk.argtypes = [vp, sz, sz, sz, u32]
     L.rsx_topk_caps.argtypes = [u32, ctypes.POINTER(u32), ctypes.POINTER(u32)]
+    L.rsx_unique_device.argtypes = [vp, vp, sz, u32, u32, i, vp, vp, vp, vp, u32, vp, vp]
+    L.rsx_ctx_reserve_unique.argtypes = [vp, sz, u32, i]
+    L.rsx_unique_caps.argtypes = [u32, i, ctypes.POINTER(u32), ctypes.POINTER(u32)]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("rsx_last_error", "rsx_strerror"):

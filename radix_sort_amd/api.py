@@ -15,6 +15,7 @@ from __future__ import annotations
 import ctypes
 import operator
 import threading
+from collections import namedtuple
 from dataclasses import dataclass
 from typing import Optional, Sequence
 
@@ -292,6 +293,21 @@ class Context:
         positions in the row into d_out_index (either may be 0: not produced); d_keys is only read."""
         self._check(self._L.rsx_topk_rows_device(self._h, d_keys, d_out_keys or None, d_out_index or None, rows, row_len, k, key_bytes,
                                                  key_kind, index_bytes, 1 if descending else 0, stream))
+
+    def reserve_unique(self, n: int, key_bytes: int, with_positions: bool = True):
+        """rsx_ctx_reserve_unique: the context's first-call set-up and the workspace of unique_device on up to n keys of this
+        width, by the route with positions (perm or inverse asked for) or keys only, so that the call allocates nothing and
+        can be captured."""
+        self._check(self._L.rsx_ctx_reserve_unique(self._h, n, key_bytes, 1 if with_positions else 0))
+
+    def unique_device(self, d_keys: int, n: int, key_bytes: int, key_kind: int, d_out_keys: int, d_out_offsets: int, d_out_perm: int,
+                      d_out_inverse: int, index_bytes: int, d_out_num: int, descending: bool = False, stream: int = 0):
+        """rsx_unique_device: the groups of equal keys of the stable sort of n keys -- the distinct keys, the CSR offsets of
+        the groups, the sorting permutation, the group of every input position (each output may be 0: not produced) and
+        their number m into d_out_num; d_keys is only read."""
+        self._check(self._L.rsx_unique_device(self._h, d_keys or None, n, key_bytes, key_kind, 1 if descending else 0, d_out_keys or None,
+                                              d_out_offsets or None, d_out_perm or None, d_out_inverse or None, index_bytes,
+                                              d_out_num or None, stream))
 
 
 _DEFAULT = {}
@@ -759,6 +775,79 @@ def radix_topk(keys, k: int, largest: bool = True, index_dtype=None, ctx: Option
         c.topk_rows_device(keys.data_ptr(), values.data_ptr(), indices.data_ptr(), rows, row_len, k, kb, kind,
                            indices.element_size(), largest, stream)
     return values, indices
+
+
+def unique_caps(key_bytes: int, with_positions: bool = True):
+    """rsx_unique_caps -> (tile, scan_span): the elements one workgroup of the run kernels of radix_group takes for this key
+    width and route, and the tiles one sweep of their scan kernel sums.  Needs no device."""
+    L = _lib.load()
+    tile, span = ctypes.c_uint32(), ctypes.c_uint32()
+    rc = L.rsx_unique_caps(key_bytes, 1 if with_positions else 0, ctypes.byref(tile), ctypes.byref(span))
+    if rc != 0:
+        raise RsxError(rc, L.rsx_strerror(rc).decode())
+    return int(tile.value), int(span.value)
+
+
+Group = namedtuple("Group", ["num", "keys", "offsets", "perm", "inverse"])
+
+
+def radix_group(keys, descending: bool = False, perm: bool = True, inverse: bool = False, index_dtype=None,
+                ctx: Optional[Context] = None, key_kind: Optional[int] = None):
+    """Groups equal keys (rsx_unique_device) and returns Group(num, keys, offsets, perm, inverse) without synchronising:
+
+    num      a 0-d int64 device tensor: m, the number of distinct keys.
+    keys     the distinct keys in sorted order in its first m entries (a tensor like `keys`; the rest is not written).
+    offsets  int64, len(keys) + 1: offsets[j], j <= m, is where group j starts in the stable sort of the keys (the rest is
+             not written); the counts are the differences, and offsets[: m + 1] is the `offsets` of radix_sort_segments and
+             its siblings, made on the device.
+    perm     the stable sorting permutation (radix_argsort): perm[offsets[j] : offsets[j + 1]] are the input positions of
+             group j in input order, the first of them its first occurrence.  None unless perm=True.
+    inverse  for every input position the j of its group.  None unless inverse=True.
+
+    `keys` follows the rules of radix_argsort (1-D of a supported dtype, or (n, 16) uint8 128-bit keys with key_kind=) and
+    is not modified; perm and inverse are of index_dtype (torch.int64, the default, or torch.int32).  Equality is
+    bit-pattern equality and the order radix_argsort's total order on bit patterns: -0.0 and +0.0 are two groups, NaNs
+    of different payloads too.  With perm=False and inverse=False the keys are sorted alone, without positions."""
+    import torch
+    kb, kind, n = _pairs_keys(keys, key_kind)
+    if index_dtype is None:
+        index_dtype = torch.int64
+    if index_dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"index_dtype must be torch.int32 or torch.int64, not {index_dtype}")
+    _pairs_device(keys, None, "")
+    if n >= 1 << 32:
+        raise ValueError("radix_group takes fewer than 2^32 keys")
+    num = torch.empty((), dtype=torch.int64, device=keys.device)
+    out_keys = torch.empty_like(keys)
+    offsets = torch.empty(n + 1, dtype=torch.int64, device=keys.device)
+    out_perm = torch.empty(n, dtype=index_dtype, device=keys.device) if perm else None
+    out_inverse = torch.empty(n, dtype=index_dtype, device=keys.device) if inverse else None
+    dev = keys.device.index if keys.device.index is not None else torch.cuda.current_device()
+    c = ctx or default_context(dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        c.unique_device(keys.data_ptr(), n, kb, kind, out_keys.data_ptr(), offsets.data_ptr(),
+                        out_perm.data_ptr() if perm else 0, out_inverse.data_ptr() if inverse else 0,
+                        8 if index_dtype == torch.int64 else 4, num.data_ptr(), descending, stream)
+    return Group(num, out_keys, offsets, out_perm, out_inverse)
+
+
+def radix_unique(keys, return_inverse: bool = False, return_counts: bool = False, descending: bool = False,
+                 ctx: Optional[Context] = None, key_kind: Optional[int] = None):
+    """`torch.unique(keys, sorted=True, return_inverse=..., return_counts=...)` through radix_group: the distinct keys in
+    sorted order and, where asked for, the int64 index of every key's group and the int64 counts, as a tuple in that
+    order (the keys alone when neither is asked for).  Reads the number of groups once, which synchronises, as torch does.
+
+    Floats differ from torch: the order is radix_argsort's total order on bit patterns (-NaN first, -0.0 below +0.0, +NaN
+    last) and equality is bit-pattern equality, so -0.0 and +0.0 are two keys and every NaN payload is a key of its own."""
+    g = radix_group(keys, descending=descending, perm=False, inverse=return_inverse, ctx=ctx, key_kind=key_kind)
+    m = int(g.num)
+    out = (g.keys[:m],)
+    if return_inverse:
+        out += (g.inverse,)
+    if return_counts:
+        out += (g.offsets[1:m + 1] - g.offsets[:m],)
+    return out if len(out) > 1 else out[0]
 
 
 def _segments_common(keys, offsets, max_seg_len):

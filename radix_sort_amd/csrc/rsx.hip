@@ -965,7 +965,7 @@ int rsx_ctx_get_info(rsx_ctx* ctx, int what, uint64_t* out) try {
         case RSX_INFO_NUM_CU: *out = (uint64_t)ctx->num_cu; return RSX_OK;
         case RSX_INFO_DEVICE: *out = (uint64_t)ctx->device; return RSX_OK;
         case RSX_INFO_LAST_PASSES: {
-            if (ctx->last_path == 6 || ctx->last_path == 7) {  // segmented, top-k: bits 0-7 are the kernels launched
+            if (ctx->last_path == 6 || ctx->last_path == 7 || ctx->last_path == 8) {  // segmented, top-k, groups: bits 0-7 are the kernels launched
                 *out = (uint64_t)(ctx->last_sort_passes & 0xFFu) | (uint64_t)ctx->last_path << 24;
                 return RSX_OK;
             }
@@ -1434,6 +1434,127 @@ int rsx_topk_caps(uint32_t key_bytes, uint32_t* caps, uint32_t* max_k) {
     if (es == 0) return RSX_ERR_UNSUPPORTED;
     for (int c = 0; c < RSX_SEG_CLASSES; ++c) caps[c] = segment_cap((int)es, c);
     *max_k = topk_max_k(es);
+    return RSX_OK;
+}
+
+// ---- groups of equal keys (rsx_unique_kernels.hpp, include/rsx.h) ----
+namespace {
+// The workspace of one rsx_unique_device call: the two arrays of joined elements (the shape of pairs_plan) and, behind
+// them, the per-tile arrays of the run kernels.
+struct UniquePlan {
+    rsx_layout inner;  // what the sort kernels see
+    size_t half;       // bytes of each of the two element arrays
+    size_t tiles;
+    size_t heads_off;  // tile_heads [tiles] u32
+    size_t base_off;   // tile_base [tiles] u64
+    size_t bytes;
+};
+UniquePlan unique_plan(size_t n, uint32_t kb, bool pos) {
+    UniquePlan P{};
+    const uint32_t es = pairs_elem_bytes(kb, pos ? 4u : 0u);
+    const uint32_t tile = unique_tile_elems(kb, pos);
+    P.inner = rsx_layout{es, 0, kb, RSX_KEY_UNSIGNED};
+    P.half = (n * (size_t)es + 255) & ~(size_t)255;
+    P.tiles = (n + tile - 1) / tile;
+    P.heads_off = 2 * P.half;
+    P.base_off = P.heads_off + ((P.tiles * sizeof(uint32_t) + 255) & ~(size_t)255);
+    P.bytes = P.base_off + ((P.tiles * sizeof(uint64_t) + 255) & ~(size_t)255);
+    return P;
+}
+int reserve_unique_one(rsx_ctx* ctx, const UniquePlan& P, size_t n, hipStream_t st) {
+    int rc = ensure_workspace(ctx, n, &P.inner, st);
+    if (rc) return rc;
+    return ensure_any(ctx, P.bytes, st);
+}
+bool unique_size_ok(size_t n) { return (uint64_t)n < (1ull << 32); }
+}  // namespace
+
+int rsx_unique_device(rsx_ctx* ctx, const void* d_keys, size_t n, uint32_t key_bytes, uint32_t key_kind, int order, void* d_out_keys,
+                      uint64_t* d_out_offsets, void* d_out_perm, void* d_out_inverse, uint32_t index_bytes, uint64_t* d_out_num,
+                      void* stream) try {
+    if (!ctx) return RSX_ERR_ARG;
+    if (!key_widths_ok(key_bytes, key_kind)) return fail(ctx, RSX_ERR_ARG, "invalid key width or kind");
+    if (order != RSX_ORDER_ASCENDING && order != RSX_ORDER_DESCENDING) return fail(ctx, RSX_ERR_ARG, "invalid order");
+    if (!d_out_num) return fail(ctx, RSX_ERR_ARG, "d_out_num is null");
+    const bool pos = d_out_perm != nullptr || d_out_inverse != nullptr;
+    if (pos && index_bytes != 4 && index_bytes != 8) return fail(ctx, RSX_ERR_ARG, "index_bytes must be 4 or 8");
+    if (n > 0 && !d_keys) return fail(ctx, RSX_ERR_ARG, "null device pointer");
+    if (!aligned(d_keys, key_bytes) || !aligned(d_out_keys, key_bytes) || !aligned(d_out_offsets, 8) || !aligned(d_out_num, 8) ||
+        (pos && (!aligned(d_out_perm, index_bytes) || !aligned(d_out_inverse, index_bytes))))
+        return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
+    if (!unique_size_ok(n)) return fail(ctx, RSX_ERR_UNSUPPORTED, "2^32 or more keys");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return fail(ctx, RSX_ERR_NODEVICE, "hipSetDevice failed");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (n == 0) {  // no group: two memsets, no kernel
+        RSX_HIP(hipMemsetAsync(d_out_num, 0, sizeof(uint64_t), st));
+        if (d_out_offsets) RSX_HIP(hipMemsetAsync(d_out_offsets, 0, sizeof(uint64_t), st));
+        ctx->last_path = 8;
+        ctx->last_route = 0;
+        ctx->last_sort_passes = 0;
+        return RSX_OK;
+    }
+    const UniquePlan P = unique_plan(n, key_bytes, pos);
+    if (P.inner.elem_bytes == 0 || !launchers_for(P.inner.elem_bytes)) return fail(ctx, RSX_ERR_INTERNAL, "no joined element for this key width");
+    int rc = pending_error(ctx);
+    if (rc) return rc;
+    rc = reserve_unique_one(ctx, P, n, st);
+    if (rc) return rc;
+    Enqueue enq(ctx, st);  // the workspace arrays belong to this call from the first launch on
+    char* w0 = ctx->any_buf;
+    char* w1 = w0 + P.half;
+    const uint32_t desc = order == RSX_ORDER_DESCENDING ? 1u : 0u;
+    // the join of rsx_argsort_device (mapped key, u32 position), or of keys alone in descending order (the mapped key)
+    rc = launch_pairs_join(ctx, d_keys, nullptr, w0, n, key_bytes, pos ? 4u : 0u, pos, key_kind, desc, st);
+    if (rc) return rc;
+    if (n > 1) {
+        rc = sort_device_locked(ctx, w0, w1, n, &P.inner, st);
+        if (rc) return rc;
+    }
+    UniqueCall c{};
+    c.elems = w0;
+    c.tile_heads = reinterpret_cast<uint32_t*>(w0 + P.heads_off);
+    c.tile_base = reinterpret_cast<uint64_t*>(w0 + P.base_off);
+    c.n = n;
+    c.kb = key_bytes;
+    c.kind = key_kind;
+    c.desc = desc;
+    c.pos = pos;
+    c.ib = index_bytes;
+    c.out_keys = d_out_keys;
+    c.out_offsets = d_out_offsets;
+    c.out_perm = d_out_perm;
+    c.out_inverse = d_out_inverse;
+    c.out_num = d_out_num;
+    uint32_t launched = 0;
+    rc = launch_unique(ctx, c, &launched, st);
+    if (rc) return rc;
+    ctx->last_pairs = 1u | P.inner.elem_bytes << 8;
+    ctx->last_path = 8;
+    ctx->last_route = 0;
+    ctx->last_sort_passes = launched;
+    return RSX_OK;
+} catch (...) {
+    return RSX_ERR_HIP;
+}
+
+int rsx_ctx_reserve_unique(rsx_ctx* ctx, size_t n, uint32_t key_bytes, int with_positions) try {
+    if (!ctx) return RSX_ERR_ARG;
+    if (!key_widths_ok(key_bytes, RSX_KEY_UNSIGNED)) return fail(ctx, RSX_ERR_ARG, "invalid key width");
+    if (!unique_size_ok(n)) return fail(ctx, RSX_ERR_UNSUPPORTED, "2^32 or more keys");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return fail(ctx, RSX_ERR_NODEVICE, "hipSetDevice failed");
+    return reserve_unique_one(ctx, unique_plan(n, key_bytes, with_positions != 0), n, nullptr);
+} catch (...) {
+    return RSX_ERR_NOMEM;
+}
+
+int rsx_unique_caps(uint32_t key_bytes, int with_positions, uint32_t* tile, uint32_t* scan_span) {
+    if (!tile || !scan_span || !key_widths_ok(key_bytes, RSX_KEY_UNSIGNED)) return RSX_ERR_ARG;
+    *tile = unique_tile_elems(key_bytes, with_positions != 0);
+    *scan_span = unique_scan_span();
     return RSX_OK;
 }
 

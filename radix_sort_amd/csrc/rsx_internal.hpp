@@ -459,4 +459,24 @@ int launch_pairs_split(rsx_ctx* ctx, const void* elems, void* keys, void* values
 uint32_t pairs_elem_bytes(uint32_t kb, uint32_t vb);    // joined element size, 0: none (proxy route)
 uint32_t pairs_value_offset(uint32_t kb, uint32_t vb);  // of the value in the joined element
 
+// What one rsx_unique_device call asks of the run kernels (rsx_unique.hip, rsx_unique_kernels.hpp) once its joined
+// elements are sorted.
+struct UniqueCall {
+    const void* elems;        // n sorted joined elements: the mapped key alone (pos false) or (mapped key, u32 position)
+    uint32_t* tile_heads;     // per tile of unique_tile_elems: its heads, and ...
+    uint64_t* tile_base;      // ... the heads in front of it
+    size_t n;
+    uint32_t kb, kind, desc;
+    bool pos;
+    uint32_t ib;              // bytes of an index in out_perm / out_inverse
+    void* out_keys;           // every output but out_num may be null
+    uint64_t* out_offsets;
+    void* out_perm;
+    void* out_inverse;
+    uint64_t* out_num;
+};
+int launch_unique(rsx_ctx* ctx, const UniqueCall& call, uint32_t* launched, hipStream_t st);
+uint32_t unique_tile_elems(uint32_t kb, bool pos);  // elements per workgroup of the count and write kernels
+uint32_t unique_scan_span();                        // tiles per sweep of the scan kernel's loop
+
 }  // namespace rsxh

@@ -13,6 +13,7 @@
 //     rsx::radix_sort_device(T* d_data, T* d_tmp, size_t n, hipStream_t)   // device-resident
 //     rsx::radix_sort_pairs(K* d_keys, V* d_values, size_t n, bool descending, hipStream_t)   // separate columns
 //     rsx::radix_argsort(const K* d_keys, I* d_index, size_t n, bool descending, hipStream_t)
+//     rsx::unique(const K* d_keys, size_t n, K* keys, uint64_t* offsets, I* perm, I* inverse, uint64_t* num, bool descending, hipStream_t)
 // Errors: the reference panics (mod.rs:68,106); here std::runtime_error is thrown.
 // Empty and one-element slices return immediately (the reference panics on an empty
 // slice -- chunks(0), mod.rs:66-70,92 -- there is no output to differ from).
@@ -204,6 +205,28 @@ void radix_argsort(const K* d_keys, I* d_index, size_t n, bool descending = fals
     if (L.key_offset != 0 || L.key_bytes != L.elem_bytes) throw std::invalid_argument("radix_argsort: the key type must be its own key");
     ctx.check(rsx_argsort_device(ctx.get(), d_keys, d_index, n, L.key_bytes, L.key_kind, (uint32_t)sizeof(I),
                                  descending ? RSX_ORDER_DESCENDING : RSX_ORDER_ASCENDING, stream), "rsx_argsort_device");
+}
+
+// The groups of equal keys of that permutation (rsx_unique_device): d_out_keys[j], j < m, the distinct keys in order;
+// d_out_offsets[j], j <= m, where group j starts in the sorted order (n + 1 entries; the d_offsets of the segmented
+// calls below); d_out_perm the permutation itself; d_out_inverse[q] the group of input position q; *d_out_num = m.
+// Every output but d_out_num may be nullptr; without perm and inverse the keys are sorted alone.  The keys are only
+// read.  Stream-ordered, never synchronised (rsx_ctx_reserve_unique before a stream capture).
+template <typename K, typename I = uint64_t>
+void unique(const K* d_keys, size_t n, K* d_out_keys, uint64_t* d_out_offsets, I* d_out_perm, I* d_out_inverse, uint64_t* d_out_num,
+            bool descending = false, void* stream = nullptr, Context& ctx = default_context()) {
+    static_assert(std::is_integral<I>::value && (sizeof(I) == 4 || sizeof(I) == 8), "indices are 4- or 8-byte integers");
+    const rsx_layout L = RadixDigits<K>::layout();
+    if (L.key_offset != 0 || L.key_bytes != L.elem_bytes) throw std::invalid_argument("unique: the key type must be its own key");
+    ctx.check(rsx_unique_device(ctx.get(), d_keys, n, L.key_bytes, L.key_kind, descending ? RSX_ORDER_DESCENDING : RSX_ORDER_ASCENDING,
+                                d_out_keys, d_out_offsets, d_out_perm, d_out_inverse, (uint32_t)sizeof(I), d_out_num, stream),
+              "rsx_unique_device");
+}
+// ... keys alone: the distinct keys, the offsets (their differences are the counts) and their number
+template <typename K>
+void unique_keys(const K* d_keys, size_t n, K* d_out_keys, uint64_t* d_out_offsets, uint64_t* d_out_num, bool descending = false,
+                 void* stream = nullptr, Context& ctx = default_context()) {
+    unique<K, uint64_t>(d_keys, n, d_out_keys, d_out_offsets, nullptr, nullptr, d_out_num, descending, stream, ctx);
 }
 
 // The segmented forms of the three calls above (rsx_sort_segments_pairs_device, rsx_argsort_segments_device and their
