@@ -396,9 +396,9 @@ template <int ES, int KPT, int WG>
 __device__ __forceinline__ uint32_t* mend_count(unsigned char* smem) {
     return reinterpret_cast<uint32_t*>(smem + (size_t)cape<ES, KPT, WG>() * sizeof(Elem<ES>));  // [0] heads listed, [1 ..] the list
 }
-// The end of a bucket whose passes started at digit f > 0: the sorted tile is read back in store order together with
-// every element's predecessor (local_check; true if some neighbours agree); if none do -- the rule -- the registers go
-// straight to memory (local_store_regs).
+// The check ahead of the list mend (local_finish after a run of three or more was seen; the fused key / value kernels
+// after every array): the sorted tile is read back in store order together with every element's predecessor (true if
+// some neighbours agree and differ below); if none do, the registers can go straight to memory (local_store_regs).
 template <int ES, int KPT, int WG>
 __device__ __forceinline__ bool local_check(const PassPlan& pp, const uint32_t n, unsigned char* smem, Elem<ES> (&x)[KPT], uint32_t& ties) {
     using E = Elem<ES>;
@@ -514,15 +514,76 @@ __device__ __forceinline__ void local_store_regs(const SmallArgs& a, Elem<ES>* _
     }
 }
 
-// false: the runs could not be mended (nothing stored)
+// What a bucket of uniform keys leaves to mend is a handful of ISOLATED PAIRS (m keys sorted by b bits: m^2 / 2^(b+1)
+// pairs, m^3 / (6 2^2b) runs of three -- 8 and 1/400 per 16384-key bucket of 2^30 u64), and a pair is one compare and one
+// swap of neighbours.  Thread i looks at s[i] and s[i-1]; if they agree it looks at s[i-2] and s[i+1] too: neither tied to
+// the pair -- it is isolated, and put in order by the skipped digits (strictly smaller moves down: equal keys stay in
+// input order); else it belongs to a run of three or more, which is left alone and reported (true) if some adjacent pair
+// of it differs in the skipped digits (a run of equal keys needs nothing).
+// No barrier inside the loop: pairs are disjoint, each swapped by the thread of its upper index alone, and a neighbouring
+// thread that reads a slot while it is being swapped compares key bits from digit `first` up only -- both values that slot
+// can hold agree on those, so would a torn read, and its verdict "not tied" is the same either way; members of a run of
+// three or more are never moved.  (Rolled: inside the unrolled check the pair logic cost 84-92 bytes of scratch per lane.)
 template <int ES, int KPT, int WG>
+__device__ __forceinline__ bool local_mend_pairs(const PassPlan& pp, const uint32_t n, unsigned char* smem) {
+    using E = Elem<ES>;
+    E* s = reinterpret_cast<E*>(smem);
+    uint32_t longer = 0;
+#pragma nounroll
+    for (uint32_t i = threadIdx.x + 1; i < n; i += WG) {
+        const E x = s[i], p = s[i - 1];
+        if (!agree<ES>(pp, x, p)) continue;
+        bool run = false;
+        if (i >= 2) run = agree<ES>(pp, s[i - 2], p);
+        if (i + 1 < n) run = run || agree<ES>(pp, s[i + 1], x);
+        int order = 0;  // by the skipped digits, the highest first: -1 x is smaller, +1 x is larger
+#pragma unroll
+        for (int w = ES / 4 - 1; w >= 0; --w) {
+            const uint32_t u = x.w[w] & pp.low[w], v = p.w[w] & pp.low[w];
+            if (order == 0 && u != v) order = u < v ? -1 : 1;
+        }
+        if (run) {
+            longer |= order != 0 ? 1u : 0u;
+        } else if (order < 0) {
+            s[i - 1] = x;
+            s[i] = p;
+        }
+    }
+    return __syncthreads_or((int)longer) != 0;
+}
+
+// The end of an array whose passes started at digit f > 0.  The rule: its isolated pairs are mended in LDS
+// (local_mend_pairs), the tile is read back in store order and the registers go straight to memory.  A run of three or
+// more that is not one of equal keys: the check, the list and the store from LDS.
+// PAIRS = false (every caller but rsx_bucket16_kernel): every tie goes to the list.  Where one launch sorts a few hundred
+// small arrays, one workgroup each (the middle sizes' 256 buckets, segments), some array of nearly every launch has a run
+// of three, and the launch then lasts as long as the pair loop AND the list: 2^14 and 2^18 u64 / (u64,u64) / u128 keys
+// 31-35 -> 35-37 us.  And rsx_bucket16_medium_kernel, whose scratch every hybrid sort pays for at dispatch, spilled 70
+// registers into 856 bytes per lane with the pair loop (32 without): 4.8 -> 19 us per gated launch.
+// false: the runs could not be mended (nothing stored)
+template <int ES, int KPT, int WG, bool PAIRS = false>
 __device__ __forceinline__ bool local_finish(const SmallArgs& a, Elem<ES>* __restrict__ dst, const uint32_t n, unsigned char* smem, const PassPlan& pp,
                                              uint32_t* s_flag) {
     Elem<ES> x[KPT];
     uint32_t ties;
-    if (!local_check<ES, KPT, WG>(pp, n, smem, x, ties)) {
-        local_store_regs<ES, KPT, WG>(a, dst, n, x);
-        return true;
+    if constexpr (PAIRS) {
+        if (!local_mend_pairs<ES, KPT, WG>(pp, n, smem)) {
+            const Elem<ES>* s_elems = reinterpret_cast<const Elem<ES>*>(smem);
+#pragma unroll
+            for (int j = 0; j < KPT; ++j) {
+                const uint32_t i = (uint32_t)j * WG + threadIdx.x;
+                x[j] = Elem<ES>{};
+                if (i < n) x[j] = s_elems[i];
+            }
+            local_store_regs<ES, KPT, WG>(a, dst, n, x);
+            return true;
+        }
+        (void)local_check<ES, KPT, WG>(pp, n, smem, x, ties);  // (true: the run reported is still there; called for the list's `ties`)
+    } else {
+        if (!local_check<ES, KPT, WG>(pp, n, smem, x, ties)) {
+            local_store_regs<ES, KPT, WG>(a, dst, n, x);
+            return true;
+        }
     }
     if (!local_mend_listed<ES, KPT, WG>(n, smem, pp, s_flag, ties)) return false;
     local_store<ES, KPT, WG>(a, dst, n, smem);
@@ -531,7 +592,7 @@ __device__ __forceinline__ bool local_finish(const SmallArgs& a, Elem<ES>* __res
 
 // One array of at most WG * KPT elements, src -> dst: the passes [pp.first, pp.end), the check, the mending or -- if the
 // runs are too long for that -- every pass [0, pp.end) (and pp.first = 0 for the caller's later arrays).
-template <int ES, int KPT, int WG>
+template <int ES, int KPT, int WG, bool PAIRS = false>
 __device__ __forceinline__ void local_sort_skip(const SmallArgs& a, const Elem<ES>* __restrict__ src, Elem<ES>* __restrict__ dst, const uint32_t n,
                                                 unsigned char* smem, PassPlan& pp, uint32_t* s_flag) {
     using E = Elem<ES>;
@@ -540,7 +601,7 @@ __device__ __forceinline__ void local_sort_skip(const SmallArgs& a, const Elem<E
     local_passes<ES, KPT, WG>(a, e, n, smem, pp.first, pp.end);
     if (pp.first == 0) {
         local_store<ES, KPT, WG>(a, dst, n, smem);
-    } else if (!local_finish<ES, KPT, WG>(a, dst, n, smem, pp, s_flag)) {
+    } else if (!local_finish<ES, KPT, WG, PAIRS>(a, dst, n, smem, pp, s_flag)) {
         pp.first = 0;
         const uint32_t kp = (n + WG - 1) / WG, seg = (threadIdx.x >> 6) * (WAVE * kp) + (threadIdx.x & 63u);
 #pragma unroll
@@ -624,15 +685,17 @@ __global__ __launch_bounds__(WG, RSX_B16_WAVES(WG)) void rsx_bucket16_kernel(con
     uint32_t* s_flag = reinterpret_cast<uint32_t*>(reinterpret_cast<typename WaveCnt<ES>::T*>(smem + (size_t)cape<ES, KPT, WG>() * sizeof(E)) + NWAVE * RADIX) + NWAVE;  // (s_misc is [NWAVE]; 16 words there)
     // A bucket of m elements that agree on their window (and everything above it) is, as a rule, told apart by the next
     // 2 log2(m) bits or so: the passes start at the digit that leaves them 2 log2(m) - 6 variable bits (first_digit_for:
-    // three passes for the 16384-key buckets of 2^30 u64), the neighbours that still agree afterwards are put right one
-    // run at a time (mend_listed), and a workgroup that meets an input where that does not work -- long runs: few distinct
-    // values in those bits -- runs all passes from then on.
+    // three passes for the 16384-key buckets of 2^30 u64), the neighbours that still agree afterwards are put right --
+    // isolated pairs by a swap in LDS (local_mend_pairs: all there is in nearly every bucket of uniform keys), longer runs
+    // one run at a time (mend_listed) --, and a workgroup that meets an input where that does not work -- long runs: few
+    // distinct values in those bits -- runs all passes from then on.
     // Small buckets (2^24 u64 keys: 256 each) cost a workgroup ~8 us apiece whatever they hold.  The host then sets
     // group_shift: 2^group_shift consecutive buckets -- a contiguous range of the final order -- are sorted as ONE array,
     // by the key's digits up to the window's top.  A group that does not fit after all is done bucket by bucket, every pass.
     // (Requesting the next bucket ahead of this one's check and store -- its registers are free after the last scatter --
     // would cover a 4.6 us round trip of 31 per bucket on 2^30 u64, but every form of that loop tried spilled 50-370
-    // registers and ran slower.)
+    // registers and ran slower.  Without registers -- global_load_lds pieces into the tile once it has been read back for
+    // the store, taken from LDS at the next loop top -- nothing more spilled, and the kernel ran 12 % slower: DESIGN.md.)
     const uint32_t gs = a.group_shift != 0 ? plan->group_shift : 0;  // (the host offers groups up to 2^a.group_shift; rsx_scan16_kernel chose)
     const bool medium = (plan->verdict & VERDICT_MEDIUM) != 0;
     PassPlan pp;  // (uniform: scalar loads and registers)
@@ -682,7 +745,7 @@ __global__ __launch_bounds__(WG, RSX_B16_WAVES(WG)) void rsx_bucket16_kernel(con
                         pp.first = 0;
                         pp.end = end_sub;
                     }
-                    local_sort_skip<ES, KPT, WG>(a, bucket, bucket, (uint32_t)count, smem, pp, s_flag);  // (a failed mend leaves pp.first = 0)
+                    local_sort_skip<ES, KPT, WG, true>(a, bucket, bucket, (uint32_t)count, smem, pp, s_flag);  // (a failed mend leaves pp.first = 0)
                     if (!whole) {
                         pp.first = first;
                         pp.end = end;
