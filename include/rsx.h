@@ -159,8 +159,14 @@ enum {
                                   bits an array of that size is, as a rule, told apart by (2 log2 m - 6 of its variable
                                   bits: three passes for a 16-bit bucket of 2^30 u64 keys) and put right the neighbours
                                   that still agree, by the digits skipped; 0: every pass */
-    RSX_OPT_BUCKET_GROUP = 14  /* the hybrid on arrays whose 16-bit buckets are small (8-byte and wider keys): 1 (default)
+    RSX_OPT_BUCKET_GROUP = 14, /* the hybrid on arrays whose 16-bit buckets are small (8-byte and wider keys): 1 (default)
                                   a workgroup sorts a group of consecutive buckets as one array; 0: bucket by bucket */
+    RSX_OPT_BUCKET_DIRECT = 15 /* the hybrid's buckets of key-only elements of 8 and 16 bytes (the key is the whole element:
+                                  u64, i64, f64, u128 -- equal elements are the same bytes): 1 (default) one unstable
+                                  counting pass in LDS and an exact rank among neighbours, buckets of few distinct keys
+                                  left to the stable passes; 0: the stable passes always.  Same bytes either way.
+                                  No effect where groups of small buckets are on offer (RSX_OPT_BUCKET_GROUP: arrays up to
+                                  about 2^26 8-byte / 2^25 16-byte elements): those sorts keep to the stable passes. */
 };
 int rsx_ctx_set_option(rsx_ctx *ctx, int option, uint64_t value);
 enum {
@@ -184,12 +190,15 @@ enum {
                                  bits 28-29 the route of a layout without kernels of its own: 0 direct, 1 packed
                                  re-layout, 2 key-index proxy (bits 0-27 then describe the sort of the re-laid-out
                                  elements / of the proxies) */
-    RSX_INFO_LAST_PAIRS = 6   /* how the context's last rsx_sort_pairs_device / rsx_argsort_device call ran: 0 none yet,
+    RSX_INFO_LAST_PAIRS = 6,  /* how the context's last rsx_sort_pairs_device / rsx_argsort_device call ran: 0 none yet,
                                  1 joined elements, 2 proxies and gather; bits 8-15 the size of the joined element (of
                                  the proxy).  RSX_INFO_LAST_PASSES describes the inner sort of those elements.
                                  The segmented key / value calls report 3, fused per segment (the joined elements exist
                                  in registers and LDS only), or 4, fused per segment on (key, position) proxies followed
                                  by a gather of the values; bits 8-15 as above, RSX_INFO_LAST_PASSES path 6. */
+    RSX_INFO_LAST_DIRECT = 7  /* the context's last sort (waits for it): ~0 if it did not enqueue the direct bucket kernel
+                                 (RSX_OPT_BUCKET_DIRECT) or the device refused the hybrid, else the number of buckets
+                                 that kernel left to the stable passes -- 0 when it sorted every bucket */
 };
 int rsx_ctx_get_info(rsx_ctx *ctx, int what, uint64_t *out);
 /* Per-launch timing with HIP events on the launch stream (measurement only).

@@ -329,7 +329,7 @@ int sort_wide(rsx_ctx* ctx, const EsLaunchers& K, void* d_data, void* d_tmp, siz
     int rc = ensure_ovf16(ctx, st);
     if (rc) return rc;
     if (!ctx->wide_buf) {
-        RSX_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->wide_buf), WIDE_PLAN_OFFSET + sizeof(WidePlan)));
+        RSX_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->wide_buf), WIDE_BUF_BYTES));
         RSX_HIP(hipMemsetAsync(reinterpret_cast<char*>(ctx->wide_buf) + WIDE_PLAN_OFFSET, 0, sizeof(WidePlan), st));  // (plan_or, plan_done)
     }
     uint64_t* tot = reinterpret_cast<uint64_t*>(ctx->wide_buf);
@@ -360,7 +360,7 @@ int sort_wide(rsx_ctx* ctx, const EsLaunchers& K, void* d_data, void* d_tmp, siz
         const uint64_t cap1024 = wide_big_form((int)es, n) ? wide_cap(es) : bucket_cap((int)es), cap512 = bucket_cap((int)es) / 2;
         hipLaunchKernelGGL(rsx_scan16_kernel, dim3(256), dim3(256), 0, st, tot, BT, starts, cap512 / 2, cap512, cap1024, group_shift(ctx, n, L),
                            ctx->wide_mode == 2 ? 1u : 0u, (uint64_t)bucket_cape((int)es, medium_kpt_for((int)es), 1024) * 150u, (uint64_t)n / 64u, plan,
-                           ctx->host_err_dev + HV_WIDE_HINT);
+                           ctx->host_err_dev + HV_WIDE_HINT, reinterpret_cast<uint32_t*>(ctx->wide_buf + WIDE_LEFT_OFFSET));
         RSX_HIP(hipGetLastError());
     }
     SortRun lsd;
@@ -939,6 +939,10 @@ int rsx_ctx_set_option(rsx_ctx* ctx, int option, uint64_t value) try {
             if (value > 1) return fail(ctx, RSX_ERR_ARG, "RSX_OPT_BUCKET_GROUP: 0 or 1");
             ctx->bucket_group = (uint32_t)value;
             return RSX_OK;
+        case RSX_OPT_BUCKET_DIRECT:
+            if (value > 1) return fail(ctx, RSX_ERR_ARG, "RSX_OPT_BUCKET_DIRECT: 0 or 1");
+            ctx->bucket_direct = (uint32_t)value;
+            return RSX_OK;
         case RSX_OPT_MID_SORT:
             if (value > 3) return fail(ctx, RSX_ERR_ARG, "RSX_OPT_MID_SORT: 0 (off), 1 (forecast), 2 (always split) or 3 (always LSD passes)");
             flag(OPT_NO_MID_SORT, value == 0);
@@ -991,6 +995,17 @@ int rsx_ctx_get_info(rsx_ctx* ctx, int what, uint64_t* out) try {
             return RSX_OK;
         }
         case RSX_INFO_LAST_PAIRS: *out = (uint64_t)ctx->last_pairs; return RSX_OK;
+        case RSX_INFO_LAST_DIRECT: {
+            *out = ~(uint64_t)0;
+            if (ctx->last_path != 5 || !ctx->last_direct || !ctx->wide_buf) return RSX_OK;
+            if (ctx->busy) RSX_HIP(hipEventSynchronize(ctx->last_event));
+            uint32_t verdict = 0, left = 0;  // (both sequences were enqueued: a hybrid the device refused ran no direct kernel)
+            RSX_HIP(hipMemcpy(&verdict, ctx->wide_buf + WIDE_PLAN_OFFSET, sizeof verdict, hipMemcpyDeviceToHost));
+            if ((verdict & VERDICT_PATH_MASK) != VERDICT_HYBRID) return RSX_OK;
+            RSX_HIP(hipMemcpy(&left, ctx->wide_buf + WIDE_LEFT_OFFSET, sizeof left, hipMemcpyDeviceToHost));
+            *out = (uint64_t)left;
+            return RSX_OK;
+        }
         default: return fail(ctx, RSX_ERR_ARG, "unknown info id");
     }
 } catch (...) {

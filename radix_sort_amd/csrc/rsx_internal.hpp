@@ -92,6 +92,8 @@ struct rsx_ctx {
     uint64_t wide_tried_sig = 0, wide_refused_sig = 0;  // (layout, n) of the last hybrid try / of the last refusal
     uint32_t bucket_no_skip = 0;  // RSX_OPT_BUCKET_SKIP == 0
     uint32_t bucket_group = 1;    // RSX_OPT_BUCKET_GROUP: small buckets of the hybrid are sorted in groups
+    uint32_t bucket_direct = 1;   // RSX_OPT_BUCKET_DIRECT: key-only elements go through rsx_bucket16_direct_kernel
+    uint32_t last_direct = 0;     // the last hybrid sort enqueued that kernel (RSX_INFO_LAST_DIRECT)
     uint32_t* ovf16 = nullptr;  // u16 / i16 counting path: 65536 overflow counters, all zero between sorts
     unsigned long long* part_J = nullptr;  // rsx_partition_count_device: one count matrix per sub-range (PART_MAX_SUB x J_BYTES)
     // multi-GPU driver (rsx_sort_sharded): per-slice stream and splitter-search scratch, made once
@@ -257,6 +259,11 @@ constexpr size_t bucket_cnt_bytes() { return 4; }
 constexpr uint32_t segment_cap(int es, int cls) { return bucket_cape(es, bucket_kpt_for(es), cls == 0 ? 256 : 1024); }
 // the hybrid's buffer (ctx->wide_buf): bucket totals [65536], block totals [256], starts [65537] (u64), then its WidePlan
 constexpr size_t WIDE_PLAN_OFFSET = (65536 + 256 + 65537 + 1) * sizeof(uint64_t);
+// ... then what rsx_bucket16_direct_kernel hands over to the kernels behind it: `left`, the number of buckets it left
+// unsorted (a line of its own; cleared by rsx_scan16_kernel in every hybrid sort), and done[65536], a byte per bucket
+constexpr size_t WIDE_LEFT_OFFSET = (WIDE_PLAN_OFFSET + sizeof(WidePlan) + 127) / 128 * 128;
+constexpr size_t WIDE_DONE_OFFSET = WIDE_LEFT_OFFSET + 128;
+constexpr size_t WIDE_BUF_BYTES = WIDE_DONE_OFFSET + 65536;
 constexpr uint32_t bucket_cap(int es) { return 1024u * (uint32_t)bucket_kpt_for(es); }
 // Largest array taken by the middle-size path: the average bucket is 4/7 of the capacity, so uniform top digits
 // pass with a wide margin (2^22 4-byte, 2^20 16-byte elements); skewed ones fall back to LSD passes.  8-byte elements

@@ -439,6 +439,17 @@ int launch_bucket16(rsx_ctx* ctx, const SortRun& run, void* data, void* scratch,
         const uint64_t avg = (uint64_t)n / 65536u;
         const uint32_t gs = group_shift(ctx, n, L);
         const Gate base = run.gate;  // (null word: no gates -- never the case for this kernel)
+        // Key-only elements (the key is the whole element: equal elements are the same bytes, no order among them shows):
+        // rsx_bucket16_direct_kernel of the same form runs ahead of every plain form, behind the same gate, and the old
+        // kernel takes what it leaves (done, left: ctx->wide_buf).  Elements with a payload need the stable passes.
+        bool direct = false;
+        // Not where groups of small buckets are on offer (arrays up to about 2^26 u64 keys: uniform keys take the groups, and
+        // every plain form's direct kernel would be one more launch that returns at once, 4-5 us each: 2^23 u64 +2.5 %).
+        if constexpr (ES == 8 || ES == 16)
+            direct = ctx->bucket_direct != 0 && gs == 0 && L->key_offset == 0 && L->key_bytes == (uint32_t)ES && ctx->wide_buf != nullptr;
+        unsigned char* done = direct ? reinterpret_cast<unsigned char*>(ctx->wide_buf + WIDE_DONE_OFFSET) : nullptr;
+        uint32_t* left = direct ? reinterpret_cast<uint32_t*>(ctx->wide_buf + WIDE_LEFT_OFFSET) : nullptr;
+        ctx->last_direct = direct ? 1u : 0u;
         auto go = [&](auto wgc, auto kc, uint32_t form, uint32_t group_shift) {
             constexpr int WGS = decltype(wgc)::value;
             constexpr int K = decltype(kc)::value;
@@ -453,7 +464,16 @@ int launch_bucket16(rsx_ctx* ctx, const SortRun& run, void* data, void* scratch,
             if (per_cu < 1) per_cu = 1;
             if (per_cu > 4 * RSX_B16_WAVES(WGS) * 64 / WGS) per_cu = 4 * RSX_B16_WAVES(WGS) * 64 / WGS;
             const Gate g{base.word, VERDICT_PATH_MASK | VERDICT_FORM_MASK, VERDICT_HYBRID | form};
-            hipLaunchKernelGGL(kern, dim3((uint32_t)(ctx->num_cu * per_cu)), dim3(WGS), lds, st, b, starts, scratch, plan, g);
+            const bool ahead = direct && group_shift == 0;  // (direct: no groups are enqueued)
+            if constexpr (ES == 8 || ES == 16) {
+                if (ahead) {
+                    auto dkern = rsx_bucket16_direct_kernel<ES, K, WGS>;
+                    ensure_lds(ctx, reinterpret_cast<const void*>(dkern), lds);
+                    hipLaunchKernelGGL(dkern, dim3((uint32_t)(ctx->num_cu * per_cu)), dim3(WGS), lds, st, b, starts, plan, done, left, g);
+                }
+            }
+            hipLaunchKernelGGL(kern, dim3((uint32_t)(ctx->num_cu * per_cu)), dim3(WGS), lds, st, b, starts, scratch, plan, g,
+                               ahead ? static_cast<const unsigned char*>(done) : nullptr, ahead ? static_cast<const uint32_t*>(left) : nullptr);
         };
         using std::integral_constant;
         constexpr int KBIG = wide_kpt_for(ES);  // (the longer form only where the average bucket needs it: wide_big_form)

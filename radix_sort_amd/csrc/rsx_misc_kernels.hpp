@@ -225,7 +225,8 @@ __global__ __launch_bounds__(256) void rsx_total16_kernel(const uint32_t* __rest
 __global__ __launch_bounds__(256) void rsx_scan16_kernel(const uint64_t* __restrict__ tot, const uint64_t* __restrict__ BT,
                                                          uint64_t* __restrict__ starts, uint64_t cap256, uint64_t cap512, uint64_t cap1024,
                                                          uint32_t gs_max, uint32_t forced, uint64_t medium_max, uint64_t crowd_max,
-                                                         WidePlan* __restrict__ plan, uint32_t* __restrict__ host_verdict) {
+                                                         WidePlan* __restrict__ plan, uint32_t* __restrict__ host_verdict,
+                                                         uint32_t* __restrict__ direct_left) {
     __shared__ uint64_t ws[4], wb[4], s_big[4], s_crowd[4];
     __shared__ uint32_t s_cnt[4][8];
     __shared__ uint32_t s_last;
@@ -320,6 +321,7 @@ __global__ __launch_bounds__(256) void rsx_scan16_kernel(const uint64_t* __restr
     else if (n512 <= FEW) v = VERDICT_HYBRID | VERDICT_WG512 | (n512 ? VERDICT_MEDIUM : 0u);
     else v = VERDICT_HYBRID | VERDICT_WG1024 | (n1024 ? VERDICT_MEDIUM : 0u);
     plan->verdict = v;
+    *direct_left = 0;  // what rsx_bucket16_direct_kernel leaves to the kernels behind it is counted from zero in every sort
     __hip_atomic_store(host_verdict, (v & VERDICT_HYBRID) ? 1u : 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);  // the host's forecast for later sorts
 }
 

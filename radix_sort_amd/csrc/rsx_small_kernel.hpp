@@ -8,6 +8,8 @@
 //  rsx_bucket16_kernel     the last stage of the wide-key hybrid (rsx_mid_kernels.hpp): two sweeps have partitioned
 //                          the array by a 16-bit window of the key; persistent workgroups sort the 65536 buckets (or
 //                          groups of small ones) by the digits below it.
+//  rsx_bucket16_direct_kernel  runs ahead of it where the key is the whole element: one unstable counting pass and an
+//                          exact rank among neighbours per bucket; what it leaves (few distinct keys) is the old kernel's.
 //  Both bucket kernels start their passes at the digit their arrays' size allows (first_digit_for, PassPlan) and mend the few
 //  neighbours that still agree afterwards by the skipped digits (local_finish, mend_listed).
 //
@@ -677,7 +679,8 @@ __global__ __launch_bounds__(WG) void rsx_bucket_sort_kernel(const SmallArgs a) 
 
 template <int ES, int KPT, int WG>
 __global__ __launch_bounds__(WG, RSX_B16_WAVES(WG)) void rsx_bucket16_kernel(const SmallArgs a, const uint64_t* __restrict__ starts, void* scratch,
-                                                                         const WidePlan* __restrict__ plan, Gate gate) {
+                                                                         const WidePlan* __restrict__ plan, Gate gate,
+                                                                         const unsigned char* __restrict__ done, const uint32_t* __restrict__ left) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     if (!gate_open(gate)) return;
     using E = Elem<ES>;
@@ -712,6 +715,9 @@ __global__ __launch_bounds__(WG, RSX_B16_WAVES(WG)) void rsx_bucket16_kernel(con
         }
         return;
     }
+    // (done, left: rsx_bucket16_direct_kernel ran ahead of this launch -- done[g] != 0: it sorted bucket g; *left: how many
+    // buckets it left to this kernel, none on uniform key-only elements.  nullptr: no such kernel, every bucket is this one's.)
+    if (left != nullptr && __builtin_amdgcn_readfirstlane((int)__hip_atomic_load(left, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0) return;
     // The passes of an array (a bucket, or a group of 2^gs) run over the byte digits that hold its variable bits -- the
     // b_lo bits below the window and the gs low bits of the window -- from the digit first_digit_for() names for the
     // largest array this launch can meet (the largest bucket the scan saw, times the group, at most what LDS holds).
@@ -729,6 +735,7 @@ __global__ __launch_bounds__(WG, RSX_B16_WAVES(WG)) void rsx_bucket16_kernel(con
         const uint64_t gstart = starts[b0];
         const uint64_t gcount = starts[b0 + (1u << gs)] - gstart;  // (the same for every thread: uniform control flow below)
         if (gcount == 0) continue;
+        if (done != nullptr && done[g] != 0) continue;
         const bool whole = gs == 0 || gcount <= (uint64_t)cape<ES, KPT, WG>();
         const uint32_t nsub = whole ? 1u : 1u << gs;
         for (uint32_t sub = 0; sub < nsub; ++sub) {  // (one call site each for the LDS sort and the sort through memory)
@@ -836,6 +843,244 @@ __global__ __launch_bounds__(WG, RSX_B16_WAVES(WG)) void rsx_bucket16_medium_ker
         }
         __syncthreads();  // smem belongs to the next bucket
     }
+}
+
+// ---- key-only elements: one counting pass and a local rank ---------------------------------------------------------
+// Where the key is the whole element (key_offset == 0, key_bytes == ES: u64, i64, f64, u128) equal elements are the same
+// bytes, no order among them can be observed, and any correct sort of a bucket gives the bytes the stable one gives.
+// rsx_bucket16_direct_kernel sorts a bucket by ONE unstable counting pass on the B bits below the window -- ranks from
+// returned LDS atomics on workgroup-wide counters (2^B of them where rsx_bucket16_kernel keeps its wave counters: B = 12,
+// 11, 10 for 1024, 512, 256 threads), in whatever order the lanes arrive -- and an exact rank among neighbours: in ANY
+// array the sorted place of the element at i is i - #{k < i: s[k] > s[i]} + #{k > i: s[k] < s[i]}, and after the counting
+// pass every inversion lies inside one sub-bucket (about n / 2^B keys: four of uniform u64 at 2^30), so the positions
+// i +- 1 .. i +- T with T = (largest sub-bucket the wave's positions lie in) - 1 are all there is to look at: reads at
+// constant offsets from one base address, one compare and one add per neighbour, no tie to special-case.  Every element
+// then goes straight from its thread's registers to its place in memory (a wave's 64 places are a permutation of a
+// nearly contiguous range).  No second and third pass, no mend, no check, no list.
+// A bucket with a sub-bucket above DIRECT_LIMIT (few distinct keys), an empty one and one above cape() are left to the
+// kernels behind this one untouched: done[g] = 0, and *left counts them; a workgroup that met the first kind leaves all
+// its later buckets too (as the old kernel's failed mend is sticky), so such an input costs each workgroup one abandoned
+// load and rank.  done[g] is written for every bucket; *left is zero when the launch starts (rsx_scan16_kernel).
+constexpr uint32_t DIRECT_LIMIT = 24;
+template <int WG>
+__host__ __device__ constexpr uint32_t direct_bits() {
+    return WG >= 1024 ? 12u : WG >= 512 ? 11u : 10u;
+}
+template <int ES>
+__device__ __forceinline__ bool key_less(const Elem<ES>& x, const Elem<ES>& y) {  // the element as ONE number, highest dword first
+    static_assert(ES == 8 || ES == 16, "key-only elements of 8 and 16 bytes");
+    if constexpr (ES == 8) {
+        return (((uint64_t)x.w[1] << 32) | x.w[0]) < (((uint64_t)y.w[1] << 32) | y.w[0]);
+    } else {
+        const uint64_t xh = ((uint64_t)x.w[3] << 32) | x.w[2], yh = ((uint64_t)y.w[3] << 32) | y.w[2];
+        const uint64_t xl = ((uint64_t)x.w[1] << 32) | x.w[0], yl = ((uint64_t)y.w[1] << 32) | y.w[0];
+        return xh < yh || (xh == yh && xl < yl);
+    }
+}
+__device__ __forceinline__ uint32_t wave_max(uint32_t x) {  // (the DPP steps of wave_incl_scan; lanes without a source read 0)
+    auto step = [](uint32_t v, auto ctrl, auto rows) {
+        const uint32_t y = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, decltype(ctrl)::value, decltype(rows)::value, 0xf, false);
+        return y > v ? y : v;
+    };
+    x = step(x, std::integral_constant<int, 0x111>{}, std::integral_constant<int, 0xf>{});
+    x = step(x, std::integral_constant<int, 0x112>{}, std::integral_constant<int, 0xf>{});
+    x = step(x, std::integral_constant<int, 0x114>{}, std::integral_constant<int, 0xf>{});
+    x = step(x, std::integral_constant<int, 0x118>{}, std::integral_constant<int, 0xf>{});
+    x = step(x, std::integral_constant<int, 0x142>{}, std::integral_constant<int, 0xa>{});
+    x = step(x, std::integral_constant<int, 0x143>{}, std::integral_constant<int, 0xc>{});
+    return (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
+}
+// The G = 16 / ES elements of the 16-byte LDS word q of the tile (one ds_read_b128: half the LDS time of two 8-byte reads).
+template <int ES>
+__device__ __forceinline__ void direct_read(const unsigned char* smem, const uint32_t q, Elem<ES> (&y)[16 / ES]) {
+    const uint4 v = reinterpret_cast<const uint4*>(smem)[q];
+    if constexpr (ES == 8) {
+        y[0].w[0] = v.x;
+        y[0].w[1] = v.y;
+        y[1].w[0] = v.z;
+        y[1].w[1] = v.w;
+    } else {
+        y[0].w[0] = v.x;
+        y[0].w[1] = v.y;
+        y[0].w[2] = v.z;
+        y[0].w[3] = v.w;
+    }
+}
+// What the M words on either side of word q take from and add to the places r[] of its elements x[].  EDGE: the words
+// that do not exist, and the elements past n, count for nothing (the wave's first and last words of the tile).
+template <int ES, bool EDGE>
+__device__ __forceinline__ void direct_rank(const unsigned char* smem, const uint32_t q, const uint32_t M, const uint32_t n, const Elem<ES> (&x)[16 / ES],
+                                            uint32_t (&r)[16 / ES]) {
+    constexpr int G = 16 / ES;
+    const uint32_t words = (n + G - 1) / G;
+#pragma unroll 2
+    for (uint32_t m = 1; m <= M; ++m) {
+        Elem<ES> lo[G], hi[G];
+        uint32_t ql = q - m, qh = q + m;
+        bool vl = true, vh = true;
+        if constexpr (EDGE) {
+            vl = q >= m;
+            vh = qh < words;
+            ql = vl ? ql : q;
+            qh = vh ? qh : q;
+        }
+        direct_read<ES>(smem, ql, lo);
+        direct_read<ES>(smem, qh, hi);
+#pragma unroll
+        for (int h = 0; h < G; ++h) {
+            bool okl = true, okh = true;
+            if constexpr (EDGE) {
+                okl = vl;  // (a word below q is whole)
+                okh = vh && qh * G + (uint32_t)h < n;
+            }
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                r[g] -= (okl && key_less<ES>(x[g], lo[h])) ? 1u : 0u;
+                r[g] += (okh && key_less<ES>(hi[h], x[g])) ? 1u : 0u;
+            }
+        }
+    }
+}
+
+template <int ES, int KPT, int WG>
+__global__ __launch_bounds__(WG, RSX_B16_WAVES(WG)) void rsx_bucket16_direct_kernel(const SmallArgs a, const uint64_t* __restrict__ starts,
+                                                                                const WidePlan* __restrict__ plan, unsigned char* __restrict__ done,
+                                                                                uint32_t* __restrict__ left, Gate gate) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    if (!gate_open(gate)) return;
+    using E = Elem<ES>;
+    constexpr int NWAVE = WG / WAVE;
+    constexpr int G = 16 / ES;
+    constexpr uint32_t CAPE = cape<ES, KPT, WG>();
+    constexpr uint32_t B = direct_bits<WG>(), NB = 1u << B;
+    static_assert(NB == (uint32_t)NWAVE * RADIX && NB == 4u * WG && sizeof(typename WaveCnt<ES>::T) == 4, "the counters take the wave counters' place, four to a thread");
+    static_assert((CAPE * ES) % 16 == 0, "the counters are read and written as uint4");
+    E* s = reinterpret_cast<E*>(smem);                                                // [CAPE]
+    uint32_t* s_cnt = reinterpret_cast<uint32_t*>(smem + (size_t)CAPE * sizeof(E));  // [NB] counts, then starts; [NB] = n
+    uint32_t* s_tot = s_cnt + NB + 4;                                                 // [NWAVE] the waves' sums of counts
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    // the digit: the B bits below the window (all b_lo of them if there are fewer), of the mapped key == the element
+    const uint32_t b_lo = plan->window_top - 15u;
+    const uint32_t bd = b_lo < B ? b_lo : B;
+    const uint32_t dshift = b_lo - bd, dmask = (1u << bd) - 1u;
+    const uint32_t dword = dshift >> 5, dsh = dshift & 31u;
+    auto digit_of = [&](const E& x) -> uint32_t {
+        const uint32_t lo = elem_word<ES>(x, dword);
+        const uint32_t hi = elem_word<ES>(x, dword + 1u < (uint32_t)(ES / 4) ? dword + 1u : dword);  // (a digit at the top of the element: shifted out)
+        return (uint32_t)(((((uint64_t)hi << 32) | lo) >> dsh)) & dmask;
+    };
+    // Bucket g and all later ones of this workgroup are left to the old kernel: marked by all threads at once (one after
+    // the other a workgroup's 85-256 buckets took 0.8 us each: 2^28 keys of 2^20 distinct values +75 us, 1.3 %).  Returns
+    // how many of them hold anything.
+    auto leave_from = [&](const uint32_t g) -> uint32_t {
+        uint32_t mine = 0;
+        for (uint32_t b = g + tid * gridDim.x; b < 65536u; b += (uint32_t)WG * gridDim.x) {
+            done[b] = 0;
+            mine += starts[b + 1] != starts[b] ? 1u : 0u;
+        }
+        if (tid == 0) s_tot[0] = 0;  // (the waves' sums are not in use here)
+        __syncthreads();
+        if (mine != 0) atomicAdd(&s_tot[0], mine);
+        __syncthreads();
+        return s_tot[0];
+    };
+    uint32_t left_here = 0;
+    if (plan->pass_end == 0) {  // the window reaches bit 0: the old kernel maps the keys back, nothing to sort
+        if (blockIdx.x < 65536u) left_here = leave_from(blockIdx.x);
+        if (tid == 0 && left_here != 0) atomicAdd(left, left_here);
+        return;
+    }
+    for (uint32_t g = blockIdx.x; g < 65536u; g += gridDim.x) {
+        const uint64_t start = starts[g];
+        const uint64_t count = starts[g + 1] - start;  // (the same for every thread: uniform control flow below)
+        if (count == 0 || count > (uint64_t)CAPE) {
+            if (tid == 0) done[g] = 0;
+            left_here += count != 0 ? 1u : 0u;
+            continue;
+        }
+        const uint32_t n = (uint32_t)count;
+        E* bucket = static_cast<E*>(a.data) + start;
+        reinterpret_cast<uint4*>(s_cnt)[tid] = uint4{0u, 0u, 0u, 0u};
+        E e[KPT];
+#pragma unroll
+        for (int j = 0; j < KPT; ++j) {  // plain store order: nothing rests on which thread holds what
+            const uint32_t i = (uint32_t)j * WG + tid;
+            e[j] = E{};
+            if (i < n) e[j] = bucket[i];
+        }
+        __syncthreads();
+        uint32_t rk[KPT];
+#pragma unroll
+        for (int j = 0; j < KPT; ++j) {
+            rk[j] = 0;
+            if ((uint32_t)j * WG + tid < n) rk[j] = atomicAdd(&s_cnt[digit_of(e[j])], 1u);
+        }
+        __syncthreads();
+        // counts -> starts: every thread four consecutive counters, a wave scan, the waves before mine
+        const uint4 c = reinterpret_cast<const uint4*>(s_cnt)[tid];
+        const uint32_t sum = c.x + c.y + c.z + c.w;
+        const uint32_t m01 = c.x > c.y ? c.x : c.y, m23 = c.z > c.w ? c.z : c.w;
+        const uint32_t incl = wave_incl_scan<true>(sum);
+        if (lane == 63) s_tot[wave] = incl;
+        if (__syncthreads_or((m01 > m23 ? m01 : m23) > DIRECT_LIMIT ? 1 : 0)) {  // few distinct keys: this bucket and my later ones are the old kernel's
+            left_here += leave_from(g);
+            break;
+        }
+        uint32_t run = incl - sum;
+        for (uint32_t w = 0; w < wave; ++w) run += s_tot[w];
+        reinterpret_cast<uint4*>(s_cnt)[tid] = uint4{run, run + c.x, run + c.x + c.y, run + c.x + c.y + c.z};
+        if (tid == 0) s_cnt[NB] = n;
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < KPT; ++j)
+            if ((uint32_t)j * WG + tid < n) s[s_cnt[digit_of(e[j])] + rk[j]] = e[j];
+        __syncthreads();
+        // the exact rank, one 16-byte word of the tile per thread and round
+        const uint32_t words = (n + G - 1) / G;
+        auto rank_word = [&](const uint32_t q0, const bool live, const uint32_t q, E (&x)[G], uint32_t (&r)[G]) {
+            direct_read<ES>(smem, q, x);
+            uint32_t need = 0;
+#pragma unroll
+            for (int h = 0; h < G; ++h) {
+                const uint32_t p = q * G + (uint32_t)h;
+                r[h] = p;
+                if (live && p < n) {  // how far the sub-bucket of x[h] reaches on either side of p
+                    const uint32_t d = digit_of(x[h]);
+                    const uint32_t below = p - s_cnt[d], above = s_cnt[d + 1u] - 1u - p;
+                    need = need > below ? need : below;
+                    need = need > above ? need : above;
+                }
+            }
+            const uint32_t T = wave_max(need);
+            const uint32_t M = (T + G - 1) / G;
+            if constexpr (G == 2) {  // the word's own two elements
+                const bool both = q * 2u + 1u < n;
+                const uint32_t inv = (both && key_less<ES>(x[1], x[0])) ? 1u : 0u;
+                r[0] += inv;
+                r[1] -= inv;
+            }
+            if (q0 >= M && q0 + 63u + M < n / G) direct_rank<ES, false>(smem, q, M, n, x, r);  // (every word looked at exists and is whole)
+            else direct_rank<ES, true>(smem, q, M, n, x, r);
+        };
+#pragma nounroll
+        for (uint32_t q0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid & ~63u)); q0 < words; q0 += WG) {
+            const bool live = q0 + lane < words;
+            const uint32_t q = live ? q0 + lane : words - 1u;
+            E x[G];
+            uint32_t r[G];
+            rank_word(q0, live, q, x, r);
+#pragma unroll
+            for (int h = 0; h < G; ++h)
+                if (live && q * G + (uint32_t)h < n) {
+                    E y = x[h];
+                    if (a.map_store) key_map<ES, true>(y, a.xf);
+                    if (r[h] < n) bucket[r[h]] = y;  // (always: a place outside the bucket is never written, whatever the ranks)
+                }
+        }
+        if (tid == 0) done[g] = 1;
+        __syncthreads();  // smem belongs to the next bucket
+    }
+    if (tid == 0 && left_here != 0) atomicAdd(left, left_here);
 }
 
 }  // namespace rsx
