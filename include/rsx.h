@@ -187,6 +187,7 @@ enum {
                                  of the selection, and bits 8-23 are 0),
                                  8 groups of equal keys (rsx_unique_device: bits 0-7 are then the kernels launched
                                  after the sort of the joined elements, and bits 8-23 are 0),
+                                 9 reduce by key (rsx_reduce_by_key_device: bits 0-7 and 8-23 as for path 8),
                                  bits 28-29 the route of a layout without kernels of its own: 0 direct, 1 packed
                                  re-layout, 2 key-index proxy (bits 0-27 then describe the sort of the re-laid-out
                                  elements / of the proxies) */
@@ -425,6 +426,56 @@ int rsx_ctx_reserve_unique(rsx_ctx *ctx, size_t n, uint32_t key_bytes, int with_
 /* Host-only, needs no device: *tile = the elements one workgroup of the run kernels takes for this key width and
  * route, *scan_span = the tiles one sweep of the scan kernel's loop sums. */
 int rsx_unique_caps(uint32_t key_bytes, int with_positions, uint32_t *tile, uint32_t *scan_span);
+
+/* -- reduce by key ----------------------------------------------------------- */
+/* What most callers do with a group: combine a column of values over it.  Let p, s, the heads h[0] < ... < h[m-1] and
+ * h[m] = n be exactly those of rsx_unique_device for d_keys in `order`, and (+) the operator `op`.  Every output
+ * optional through a NULL pointer but d_out_num, and at least one of d_out_keys and d_out_values given:
+ *     d_out_keys[j]    = s[h[j]], j < m: the distinct keys in order, as raw keys        (n entries of key_bytes)
+ *     d_out_values[j]  = d_values[p[h[j]]] (+) d_values[p[h[j]+1]] (+) ... (+) d_values[p[h[j+1]-1]], j < m: the values of
+ *                        group j, taken in input order                                  (n entries of value_bytes)
+ *     d_out_offsets[j] = h[j], j <= m: CSR offsets of the groups inside p, uint64               (n + 1 entries)
+ *     d_out_num[0]     = m, uint64
+ * Entries of d_out_keys and d_out_values at m and beyond and of d_out_offsets beyond m are not written; nothing outside
+ * these arrays and the context's workspace is written; d_keys and d_values are only read.
+ *
+ * Keys: every width and kind of rsx_argsort_device (1, 2, 4, 8, 16 bytes; unsigned, signed, float).  Values: value_bytes
+ * 4 or 8, value_kind RSX_KEY_UNSIGNED, RSX_KEY_SIGNED or RSX_KEY_FLOAT (u32, i32, f32, u64, i64, f64).  The operators:
+ *     integer RSX_REDUCE_SUM wraps modulo 2^bits; integer MIN and MAX compare by the value's signedness;
+ *     float MIN and MAX compare by the total order on bit patterns of the float keys (-NaN lowest, -0.0 below +0.0, +NaN
+ *       highest): the result is the bit pattern of one of the group's values, exact and independent of association;
+ *     float SUM is IEEE addition in the value's own type.  The association is the kernels': a function of (n, key_bytes,
+ *       value_bytes, the group's start h[j] and length) alone -- the run kernels' tiling -- so the same input gives the
+ *       same bytes on every call and every context; there are no floating-point atomics.  No zero is ever added: a group
+ *       of -0.0 sums to -0.0.  Accuracy is the order-free bound |result - exact| <= g(c-1) * sum|v| for a group of c
+ *       values, g(k) = k*u / (1 - k*u), u the unit roundoff of the value type.
+ * RSX_ERR_ARG: bad widths, kinds, op, order or alignments (keys and d_out_keys: those of rsx_argsort_device; d_values and
+ * d_out_values: value_bytes; offsets and num: 8 bytes), d_out_num NULL, d_keys or d_values NULL with n > 0, d_out_keys and
+ * d_out_values both NULL.  n >= 2^32 is RSX_ERR_UNSUPPORTED.  n == 0 writes d_out_num[0] = 0 and d_out_offsets[0] = 0 with
+ * stream-ordered memsets and launches nothing.  Stream-ordered, no synchronisation, no caller scratch: the host never
+ * reads m.
+ *
+ * d_out_keys may be d_keys and d_out_values may be d_values: the first kernel of the call joins (mapped key, value)
+ * elements of 8, 12, 16 or 32 bytes in the context's workspace -- the join of rsx_sort_pairs_device -- and has consumed
+ * both inputs before the first output is stored; stream order guarantees it.  The elements are sorted in the workspace
+ * and three run kernels follow: heads and the value of the open tail per tile; one workgroup's scan over the tiles (the
+ * heads in front of each tile and the value of the run that is open in front of it; it writes m and d_out_offsets[m]);
+ * and the write, in which the LAST element of a run stores the run's value.  No kernel waits for another workgroup.  The
+ * workspace -- the two element arrays and four per-tile arrays -- is made on first use or by rsx_ctx_reserve_reduce;
+ * under capture without a sufficient reserve the call returns RSX_ERR_WORKSPACE and enqueues nothing.
+ * RSX_INFO_LAST_PASSES reports path 9 and, in bits 0-7, the kernels launched after the sort; RSX_INFO_LAST_PAIRS route 1
+ * and the joined element's size. */
+enum { RSX_REDUCE_SUM = 0, RSX_REDUCE_MIN = 1, RSX_REDUCE_MAX = 2 };
+int rsx_reduce_by_key_device(rsx_ctx *ctx, const void *d_keys, const void *d_values, size_t n, uint32_t key_bytes,
+                             uint32_t key_kind, uint32_t value_bytes, uint32_t value_kind, int op, int order,
+                             void *d_out_keys, void *d_out_values, uint64_t *d_out_offsets, uint64_t *d_out_num,
+                             void *stream);
+/* Workspace (and the context's first-call set-up) for rsx_reduce_by_key_device on up to n keys of these widths, so that
+ * the call allocates nothing (stream capture). */
+int rsx_ctx_reserve_reduce(rsx_ctx *ctx, size_t n, uint32_t key_bytes, uint32_t value_bytes);
+/* Host-only, needs no device: *tile = the elements one workgroup of the run kernels takes for these widths (256 threads,
+ * each a whole number of 16-byte words), *scan_span = the tiles one sweep of the scan kernel's loop takes. */
+int rsx_reduce_caps(uint32_t key_bytes, uint32_t value_bytes, uint32_t *tile, uint32_t *scan_span);
 
 /* -- per-pass building blocks (multi-GPU bucket exchange) ---------------- */
 /* 256-bin count of digit `digit` (0 = least significant) over `n` elements:

@@ -21,6 +21,7 @@ SYMBOLS = [
     "rsx_segment_pairs_caps",
     "rsx_topk_rows_device", "rsx_ctx_reserve_topk", "rsx_topk_caps",
     "rsx_unique_device", "rsx_ctx_reserve_unique", "rsx_unique_caps",
+    "rsx_reduce_by_key_device", "rsx_ctx_reserve_reduce", "rsx_reduce_caps",
 ]
 SEG_CLASSES = 2  # RSX_SEG_CLASSES
 
@@ -34,6 +35,7 @@ GEN_PAYLOAD_ZERO = 0x100
  OPT_BUCKET_DIRECT) = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15
 INFO_RANK_ATOMIC, INFO_L2_LOCAL, INFO_NUM_CU, INFO_DEVICE, INFO_LAST_PASSES, INFO_LAST_PAIRS, INFO_LAST_DIRECT = 1, 2, 3, 4, 5, 6, 7
 ORDER_ASCENDING, ORDER_DESCENDING = 0, 1
+REDUCE_SUM, REDUCE_MIN, REDUCE_MAX = 0, 1, 2
 SHARD_EXCHANGE_FIRST, SHARD_SORT_FIRST = 0, 1
 
 
@@ -129,6 +131,9 @@ def load():
     L.rsx_unique_device.argtypes = [vp, vp, sz, u32, u32, i, vp, vp, vp, vp, u32, vp, vp]
     L.rsx_ctx_reserve_unique.argtypes = [vp, sz, u32, i]
     L.rsx_unique_caps.argtypes = [u32, i, ctypes.POINTER(u32), ctypes.POINTER(u32)]
+    L.rsx_reduce_by_key_device.argtypes = [vp, vp, vp, sz, u32, u32, u32, u32, i, i, vp, vp, vp, vp, vp]
+    L.rsx_ctx_reserve_reduce.argtypes = [vp, sz, u32, u32]
+    L.rsx_reduce_caps.argtypes = [u32, u32, ctypes.POINTER(u32), ctypes.POINTER(u32)]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("rsx_last_error", "rsx_strerror"):

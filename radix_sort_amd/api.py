@@ -309,6 +309,22 @@ class Context:
                                               d_out_offsets or None, d_out_perm or None, d_out_inverse or None, index_bytes,
                                               d_out_num or None, stream))
 
+    def reserve_reduce(self, n: int, key_bytes: int, value_bytes: int):
+        """rsx_ctx_reserve_reduce: the context's first-call set-up and the workspace of reduce_by_key_device on up to n keys
+        of these widths, so that the call allocates nothing and can be captured."""
+        self._check(self._L.rsx_ctx_reserve_reduce(self._h, n, key_bytes, value_bytes))
+
+    def reduce_by_key_device(self, d_keys: int, d_values: int, n: int, key_bytes: int, key_kind: int, value_bytes: int, value_kind: int,
+                             op: int, d_out_keys: int, d_out_values: int, d_out_offsets: int, d_out_num: int, descending: bool = False,
+                             stream: int = 0):
+        """rsx_reduce_by_key_device: the sum (op 0), minimum (1) or maximum (2) of the values of every group of equal keys
+        of the stable sort of n keys -- the distinct keys, one value per group, the CSR offsets of the groups (each output
+        may be 0: not produced, but not both keys and values) and their number m into d_out_num; d_keys and d_values are
+        only read, and may be the outputs."""
+        self._check(self._L.rsx_reduce_by_key_device(self._h, d_keys or None, d_values or None, n, key_bytes, key_kind, value_bytes,
+                                                     value_kind, op, 1 if descending else 0, d_out_keys or None, d_out_values or None,
+                                                     d_out_offsets or None, d_out_num or None, stream))
+
 
 _DEFAULT = {}
 _DEFAULT_LOCK = threading.Lock()
@@ -830,6 +846,82 @@ def radix_group(keys, descending: bool = False, perm: bool = True, inverse: bool
                         out_perm.data_ptr() if perm else 0, out_inverse.data_ptr() if inverse else 0,
                         8 if index_dtype == torch.int64 else 4, num.data_ptr(), descending, stream)
     return Group(num, out_keys, offsets, out_perm, out_inverse)
+
+
+def reduce_caps(key_bytes: int, value_bytes: int):
+    """rsx_reduce_caps -> (tile, scan_span): the elements one workgroup of the run kernels of radix_reduce_by_key takes for
+    these key and value widths, and the tiles one sweep of their scan kernel takes.  Needs no device."""
+    L = _lib.load()
+    tile, span = ctypes.c_uint32(), ctypes.c_uint32()
+    rc = L.rsx_reduce_caps(key_bytes, value_bytes, ctypes.byref(tile), ctypes.byref(span))
+    if rc != 0:
+        raise RsxError(rc, L.rsx_strerror(rc).decode())
+    return int(tile.value), int(span.value)
+
+
+Reduced = namedtuple("Reduced", ["num", "keys", "values", "offsets"])
+_REDUCE_OPS = {"sum": _lib.REDUCE_SUM, "min": _lib.REDUCE_MIN, "max": _lib.REDUCE_MAX}
+
+
+def _reduce_value_types():
+    import torch
+    types = {torch.int32: (4, KEY_SIGNED), torch.int64: (8, KEY_SIGNED), torch.float32: (4, KEY_FLOAT), torch.float64: (8, KEY_FLOAT)}
+    for name, vb in (("uint32", 4), ("uint64", 8)):  # where the torch build has them
+        if hasattr(torch, name):
+            types[getattr(torch, name)] = (vb, KEY_UNSIGNED)
+    return types
+
+
+def radix_reduce_by_key(keys, values, op: str = "sum", descending: bool = False, offsets: bool = False,
+                        ctx: Optional[Context] = None, key_kind: Optional[int] = None):
+    """Reduces `values` over every group of equal `keys` (rsx_reduce_by_key_device) and returns
+    Reduced(num, keys, values, offsets) without synchronising:
+
+    num      a 0-d int64 device tensor: m, the number of distinct keys.
+    keys     the distinct keys in sorted order in its first m entries (a tensor like `keys`; the rest is not written).
+    values   a tensor like `values`: entry j < m is the sum ("sum"), minimum ("min") or maximum ("max") of the values whose
+             key is keys[j], taken in input order (the rest is not written).
+    offsets  int64, len(keys) + 1, as in radix_group: where group j starts in the stable sort.  None unless offsets=True.
+
+    `keys` follows the rules of radix_group and is not modified; `values` is a 1-D contiguous tensor on the same device
+    with len(keys) entries, of dtype int32, int64, float32 or float64 (uint32 / uint64 where torch has them).  Integer
+    sums wrap; float minima and maxima follow radix_argsort's total order on bit patterns (-0.0 below +0.0, +NaN the
+    largest); a float sum is added in an order fixed by the input's size and the group's place alone, so the same input
+    gives the same bits on every call (there are no atomics)."""
+    import torch
+    kb, kind, n = _pairs_keys(keys, key_kind)
+    if not isinstance(values, torch.Tensor):
+        raise TypeError("values must be a torch tensor on a GPU")
+    if op not in _REDUCE_OPS:
+        raise ValueError(f"op must be 'sum', 'min' or 'max', not {op!r}")
+    vt = _reduce_value_types().get(values.dtype)
+    if vt is None:
+        raise ValueError(f"values must be int32, int64, float32, float64, uint32 or uint64, not {values.dtype}")
+    if values.dim() != 1 or values.shape[0] != n:
+        raise ValueError(f"values must be 1-D with one entry per key ({n}), not of shape {tuple(values.shape)}")
+    if not values.is_contiguous():
+        raise ValueError("values must be contiguous")
+    if values.device != keys.device:
+        raise ValueError(f"keys and values must be on the same device ({keys.device}, {values.device})")
+    _pairs_device(keys, None, "")
+    if n >= 1 << 32:
+        raise ValueError("radix_reduce_by_key takes fewer than 2^32 keys")
+    num = torch.empty((), dtype=torch.int64, device=keys.device)
+    out_keys = torch.empty_like(keys)
+    out_values = torch.empty_like(values)
+    out_offsets = torch.empty(n + 1, dtype=torch.int64, device=keys.device) if offsets else None
+    if n == 0:  # (empty tensors have no address to hand to the C call, which wants one of keys and values: its two memsets)
+        num.zero_()
+        if offsets:
+            out_offsets.zero_()
+        return Reduced(num, out_keys, out_values, out_offsets)
+    dev = keys.device.index if keys.device.index is not None else torch.cuda.current_device()
+    c = ctx or default_context(dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        c.reduce_by_key_device(keys.data_ptr(), values.data_ptr(), n, kb, kind, vt[0], vt[1], _REDUCE_OPS[op], out_keys.data_ptr(),
+                               out_values.data_ptr(), out_offsets.data_ptr() if offsets else 0, num.data_ptr(), descending, stream)
+    return Reduced(num, out_keys, out_values, out_offsets)
 
 
 def radix_unique(keys, return_inverse: bool = False, return_counts: bool = False, descending: bool = False,

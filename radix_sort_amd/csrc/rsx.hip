@@ -969,7 +969,7 @@ int rsx_ctx_get_info(rsx_ctx* ctx, int what, uint64_t* out) try {
         case RSX_INFO_NUM_CU: *out = (uint64_t)ctx->num_cu; return RSX_OK;
         case RSX_INFO_DEVICE: *out = (uint64_t)ctx->device; return RSX_OK;
         case RSX_INFO_LAST_PASSES: {
-            if (ctx->last_path == 6 || ctx->last_path == 7 || ctx->last_path == 8) {  // segmented, top-k, groups: bits 0-7 are the kernels launched
+            if (ctx->last_path == 6 || ctx->last_path == 7 || ctx->last_path == 8 || ctx->last_path == 9) {  // segmented, top-k, groups, reduce by key: bits 0-7 are the kernels launched
                 *out = (uint64_t)(ctx->last_sort_passes & 0xFFu) | (uint64_t)ctx->last_path << 24;
                 return RSX_OK;
             }
@@ -1570,6 +1570,138 @@ int rsx_unique_caps(uint32_t key_bytes, int with_positions, uint32_t* tile, uint
     if (!tile || !scan_span || !key_widths_ok(key_bytes, RSX_KEY_UNSIGNED)) return RSX_ERR_ARG;
     *tile = unique_tile_elems(key_bytes, with_positions != 0);
     *scan_span = unique_scan_span();
+    return RSX_OK;
+}
+
+// ---- reduce by key (rsx_reduce_kernels.hpp, include/rsx.h) ----
+namespace {
+// The workspace of one rsx_reduce_by_key_device call: the two arrays of joined (mapped key, value) elements (the shape
+// of pairs_plan) and, behind them, the four per-tile arrays of the run kernels.
+struct ReducePlan {
+    rsx_layout inner;  // what the sort kernels see
+    size_t half;       // bytes of each of the two element arrays
+    size_t tiles;
+    size_t heads_off;  // tile_heads [tiles] u32
+    size_t base_off;   // tile_base [tiles] u64
+    size_t tail_off;   // tile_tail [tiles] u64
+    size_t carry_off;  // tile_carry [tiles] u64
+    size_t bytes;
+};
+ReducePlan reduce_plan(size_t n, uint32_t kb, uint32_t vb) {
+    ReducePlan P{};
+    const uint32_t es = pairs_elem_bytes(kb, vb);
+    const uint32_t tile = reduce_tile_elems(kb, vb);
+    P.inner = rsx_layout{es, 0, kb, RSX_KEY_UNSIGNED};
+    P.half = (n * (size_t)es + 255) & ~(size_t)255;
+    P.tiles = (n + tile - 1) / tile;
+    const size_t words = (P.tiles * sizeof(uint64_t) + 255) & ~(size_t)255;
+    P.heads_off = 2 * P.half;
+    P.base_off = P.heads_off + ((P.tiles * sizeof(uint32_t) + 255) & ~(size_t)255);
+    P.tail_off = P.base_off + words;
+    P.carry_off = P.tail_off + words;
+    P.bytes = P.carry_off + words;
+    return P;
+}
+int reserve_reduce_one(rsx_ctx* ctx, const ReducePlan& P, size_t n, hipStream_t st) {
+    int rc = ensure_workspace(ctx, n, &P.inner, st);
+    if (rc) return rc;
+    return ensure_any(ctx, P.bytes, st);
+}
+bool reduce_value_ok(uint32_t vb, uint32_t vkind) {
+    return (vb == 4 || vb == 8) && (vkind == RSX_KEY_UNSIGNED || vkind == RSX_KEY_SIGNED || vkind == RSX_KEY_FLOAT);
+}
+}  // namespace
+
+int rsx_reduce_by_key_device(rsx_ctx* ctx, const void* d_keys, const void* d_values, size_t n, uint32_t key_bytes, uint32_t key_kind,
+                             uint32_t value_bytes, uint32_t value_kind, int op, int order, void* d_out_keys, void* d_out_values,
+                             uint64_t* d_out_offsets, uint64_t* d_out_num, void* stream) try {
+    if (!ctx) return RSX_ERR_ARG;
+    if (!key_widths_ok(key_bytes, key_kind)) return fail(ctx, RSX_ERR_ARG, "invalid key width or kind");
+    if (!reduce_value_ok(value_bytes, value_kind)) return fail(ctx, RSX_ERR_ARG, "invalid value width or kind");
+    if (op != RSX_REDUCE_SUM && op != RSX_REDUCE_MIN && op != RSX_REDUCE_MAX) return fail(ctx, RSX_ERR_ARG, "invalid operator");
+    if (order != RSX_ORDER_ASCENDING && order != RSX_ORDER_DESCENDING) return fail(ctx, RSX_ERR_ARG, "invalid order");
+    if (!d_out_num) return fail(ctx, RSX_ERR_ARG, "d_out_num is null");
+    if (!d_out_keys && !d_out_values) return fail(ctx, RSX_ERR_ARG, "d_out_keys and d_out_values are both null");
+    if (n > 0 && (!d_keys || !d_values)) return fail(ctx, RSX_ERR_ARG, "null device pointer");
+    if (!aligned(d_keys, key_bytes) || !aligned(d_out_keys, key_bytes) || !aligned(d_values, value_bytes) || !aligned(d_out_values, value_bytes) ||
+        !aligned(d_out_offsets, 8) || !aligned(d_out_num, 8))
+        return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
+    if (!unique_size_ok(n)) return fail(ctx, RSX_ERR_UNSUPPORTED, "2^32 or more keys");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return fail(ctx, RSX_ERR_NODEVICE, "hipSetDevice failed");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (n == 0) {  // no group: two memsets, no kernel
+        RSX_HIP(hipMemsetAsync(d_out_num, 0, sizeof(uint64_t), st));
+        if (d_out_offsets) RSX_HIP(hipMemsetAsync(d_out_offsets, 0, sizeof(uint64_t), st));
+        ctx->last_path = 9;
+        ctx->last_route = 0;
+        ctx->last_sort_passes = 0;
+        return RSX_OK;
+    }
+    const ReducePlan P = reduce_plan(n, key_bytes, value_bytes);
+    if (P.inner.elem_bytes == 0 || !launchers_for(P.inner.elem_bytes)) return fail(ctx, RSX_ERR_INTERNAL, "no joined element for this key and value");
+    int rc = pending_error(ctx);
+    if (rc) return rc;
+    rc = reserve_reduce_one(ctx, P, n, st);
+    if (rc) return rc;
+    Enqueue enq(ctx, st);  // the workspace arrays belong to this call from the first launch on
+    char* w0 = ctx->any_buf;
+    char* w1 = w0 + P.half;
+    const uint32_t desc = order == RSX_ORDER_DESCENDING ? 1u : 0u;
+    // the join of rsx_sort_pairs_device: both inputs are consumed here, before any output is stored
+    rc = launch_pairs_join(ctx, d_keys, d_values, w0, n, key_bytes, value_bytes, false, key_kind, desc, st);
+    if (rc) return rc;
+    if (n > 1) {
+        rc = sort_device_locked(ctx, w0, w1, n, &P.inner, st);
+        if (rc) return rc;
+    }
+    ReduceCall c{};
+    c.elems = w0;
+    c.tile_heads = reinterpret_cast<uint32_t*>(w0 + P.heads_off);
+    c.tile_base = reinterpret_cast<uint64_t*>(w0 + P.base_off);
+    c.tile_tail = reinterpret_cast<uint64_t*>(w0 + P.tail_off);
+    c.tile_carry = reinterpret_cast<uint64_t*>(w0 + P.carry_off);
+    c.n = n;
+    c.kb = key_bytes;
+    c.kind = key_kind;
+    c.desc = desc;
+    c.vb = value_bytes;
+    c.vkind = value_kind;
+    c.op = (uint32_t)op;
+    c.out_keys = d_out_keys;
+    c.out_values = d_out_values;
+    c.out_offsets = d_out_offsets;
+    c.out_num = d_out_num;
+    uint32_t launched = 0;
+    rc = launch_reduce(ctx, c, &launched, st);
+    if (rc) return rc;
+    ctx->last_pairs = 1u | P.inner.elem_bytes << 8;
+    ctx->last_path = 9;
+    ctx->last_route = 0;
+    ctx->last_sort_passes = launched;
+    return RSX_OK;
+} catch (...) {
+    return RSX_ERR_HIP;
+}
+
+int rsx_ctx_reserve_reduce(rsx_ctx* ctx, size_t n, uint32_t key_bytes, uint32_t value_bytes) try {
+    if (!ctx) return RSX_ERR_ARG;
+    if (!key_widths_ok(key_bytes, RSX_KEY_UNSIGNED)) return fail(ctx, RSX_ERR_ARG, "invalid key width");
+    if (!reduce_value_ok(value_bytes, RSX_KEY_UNSIGNED)) return fail(ctx, RSX_ERR_ARG, "invalid value width");
+    if (!unique_size_ok(n)) return fail(ctx, RSX_ERR_UNSUPPORTED, "2^32 or more keys");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return fail(ctx, RSX_ERR_NODEVICE, "hipSetDevice failed");
+    return reserve_reduce_one(ctx, reduce_plan(n, key_bytes, value_bytes), n, nullptr);
+} catch (...) {
+    return RSX_ERR_NOMEM;
+}
+
+int rsx_reduce_caps(uint32_t key_bytes, uint32_t value_bytes, uint32_t* tile, uint32_t* scan_span) {
+    if (!tile || !scan_span || !key_widths_ok(key_bytes, RSX_KEY_UNSIGNED) || !reduce_value_ok(value_bytes, RSX_KEY_UNSIGNED)) return RSX_ERR_ARG;
+    *tile = reduce_tile_elems(key_bytes, value_bytes);
+    *scan_span = reduce_scan_span();
     return RSX_OK;
 }
 

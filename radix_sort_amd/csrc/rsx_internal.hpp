@@ -486,4 +486,24 @@ int launch_unique(rsx_ctx* ctx, const UniqueCall& call, uint32_t* launched, hipS
 uint32_t unique_tile_elems(uint32_t kb, bool pos);  // elements per workgroup of the count and write kernels
 uint32_t unique_scan_span();                        // tiles per sweep of the scan kernel's loop
 
+// What one rsx_reduce_by_key_device call asks of the run kernels (rsx_reduce.hip, rsx_reduce_kernels.hpp) once its
+// joined (mapped key, value) elements are sorted.
+struct ReduceCall {
+    const void* elems;        // n sorted joined elements
+    uint32_t* tile_heads;     // per tile of reduce_tile_elems: its heads, ...
+    uint64_t* tile_base;      // ... the heads in front of it, ...
+    uint64_t* tile_tail;      // ... the value of its elements from its last head on, and ...
+    uint64_t* tile_carry;     // ... the value of the open run in front of it
+    size_t n;
+    uint32_t kb, kind, desc;
+    uint32_t vb, vkind, op;
+    void* out_keys;           // every output but out_num may be null
+    void* out_values;
+    uint64_t* out_offsets;
+    uint64_t* out_num;
+};
+int launch_reduce(rsx_ctx* ctx, const ReduceCall& call, uint32_t* launched, hipStream_t st);
+uint32_t reduce_tile_elems(uint32_t kb, uint32_t vb);  // elements per workgroup of the count and write kernels
+uint32_t reduce_scan_span();                           // tiles per sweep of the scan kernel's loop
+
 }  // namespace rsxh

@@ -14,6 +14,7 @@
 //     rsx::radix_sort_pairs(K* d_keys, V* d_values, size_t n, bool descending, hipStream_t)   // separate columns
 //     rsx::radix_argsort(const K* d_keys, I* d_index, size_t n, bool descending, hipStream_t)
 //     rsx::unique(const K* d_keys, size_t n, K* keys, uint64_t* offsets, I* perm, I* inverse, uint64_t* num, bool descending, hipStream_t)
+//     rsx::reduce_by_key(const K* d_keys, const V* d_values, size_t n, int op, K* keys, V* values, uint64_t* offsets, uint64_t* num, bool descending, hipStream_t)
 // Errors: the reference panics (mod.rs:68,106); here std::runtime_error is thrown.
 // Empty and one-element slices return immediately (the reference panics on an empty
 // slice -- chunks(0), mod.rs:66-70,92 -- there is no output to differ from).
@@ -227,6 +228,27 @@ template <typename K>
 void unique_keys(const K* d_keys, size_t n, K* d_out_keys, uint64_t* d_out_offsets, uint64_t* d_out_num, bool descending = false,
                  void* stream = nullptr, Context& ctx = default_context()) {
     unique<K, uint64_t>(d_keys, n, d_out_keys, d_out_offsets, nullptr, nullptr, d_out_num, descending, stream, ctx);
+}
+
+// One value per group of those keys (rsx_reduce_by_key_device): d_out_values[j], j < m, the sum (RSX_REDUCE_SUM), minimum
+// or maximum of the values whose key is d_out_keys[j], taken in input order; d_out_offsets and d_out_num as in unique.
+// V: uint32_t, int32_t, float, uint64_t, int64_t or double.  Integer sums wrap; float minima and maxima follow the total
+// order on bit patterns; a float sum is added in an order fixed by n and the group's place alone (no atomics: the same
+// input gives the same bits on every call).  d_out_offsets, and one of d_out_keys and d_out_values, may be nullptr;
+// d_out_keys may be d_keys and d_out_values may be d_values.  Stream-ordered, never synchronised (rsx_ctx_reserve_reduce
+// before a stream capture).
+template <typename K, typename V>
+void reduce_by_key(const K* d_keys, const V* d_values, size_t n, int op, K* d_out_keys, V* d_out_values, uint64_t* d_out_offsets,
+                   uint64_t* d_out_num, bool descending = false, void* stream = nullptr, Context& ctx = default_context()) {
+    static_assert(std::is_arithmetic<V>::value && !std::is_same<V, bool>::value && (sizeof(V) == 4 || sizeof(V) == 8),
+                  "values are 4- or 8-byte integers or floats");
+    const rsx_layout L = RadixDigits<K>::layout();
+    if (L.key_offset != 0 || L.key_bytes != L.elem_bytes) throw std::invalid_argument("reduce_by_key: the key type must be its own key");
+    const uint32_t vkind = std::is_floating_point<V>::value ? RSX_KEY_FLOAT : std::is_signed<V>::value ? RSX_KEY_SIGNED : RSX_KEY_UNSIGNED;
+    ctx.check(rsx_reduce_by_key_device(ctx.get(), d_keys, d_values, n, L.key_bytes, L.key_kind, (uint32_t)sizeof(V), vkind, op,
+                                       descending ? RSX_ORDER_DESCENDING : RSX_ORDER_ASCENDING, d_out_keys, d_out_values, d_out_offsets,
+                                       d_out_num, stream),
+              "rsx_reduce_by_key_device");
 }
 
 // The segmented forms of the three calls above (rsx_sort_segments_pairs_device, rsx_argsort_segments_device and their
