@@ -442,6 +442,7 @@ int launch_bucket16(rsx_ctx* ctx, const SortRun& run, void* data, void* scratch,
         // Key-only elements (the key is the whole element: equal elements are the same bytes, no order among them shows):
         // rsx_bucket16_direct_kernel of the same form runs ahead of every plain form, behind the same gate, and the old
         // kernel takes what it leaves (done, left: ctx->wide_buf).  Elements with a payload need the stable passes.
+        // (Its 2^(B+1) 16-bit counters are the halves of the words where the old kernel keeps its wave counters: the same `lds`.)
         bool direct = false;
         // Not where groups of small buckets are on offer (arrays up to about 2^26 u64 keys: uniform keys take the groups, and
         // every plain form's direct kernel would be one more launch that returns at once, 4-5 us each: 2^23 u64 +2.5 %).

@@ -848,11 +848,12 @@ __global__ __launch_bounds__(WG, RSX_B16_WAVES(WG)) void rsx_bucket16_medium_ker
 // ---- key-only elements: one counting pass and a local rank ---------------------------------------------------------
 // Where the key is the whole element (key_offset == 0, key_bytes == ES: u64, i64, f64, u128) equal elements are the same
 // bytes, no order among them can be observed, and any correct sort of a bucket gives the bytes the stable one gives.
-// rsx_bucket16_direct_kernel sorts a bucket by ONE unstable counting pass on the B bits below the window -- ranks from
-// returned LDS atomics on workgroup-wide counters (2^B of them where rsx_bucket16_kernel keeps its wave counters: B = 12,
-// 11, 10 for 1024, 512, 256 threads), in whatever order the lanes arrive -- and an exact rank among neighbours: in ANY
-// array the sorted place of the element at i is i - #{k < i: s[k] > s[i]} + #{k > i: s[k] < s[i]}, and after the counting
-// pass every inversion lies inside one sub-bucket (about n / 2^B keys: four of uniform u64 at 2^30), so the positions
+// rsx_bucket16_direct_kernel sorts a bucket by ONE unstable counting pass on the B + 1 bits below the window -- ranks from
+// returned LDS atomics on workgroup-wide counters (2^B words of them where rsx_bucket16_kernel keeps its wave counters:
+// B = 12, 11, 10 for 1024, 512, 256 threads; two counters to a word, see below), in whatever order the lanes arrive --
+// and an exact rank among neighbours: in ANY array the sorted place of the element at i is
+// i - #{k < i: s[k] > s[i]} + #{k > i: s[k] < s[i]}, and after the counting
+// pass every inversion lies inside one sub-bucket (about n / 2^(B+1) keys: two of uniform u64 at 2^30), so the positions
 // i +- 1 .. i +- T with T = (largest sub-bucket the wave's positions lie in) - 1 are all there is to look at: reads at
 // constant offsets from one base address, one compare and one add per neighbour, no tie to special-case.  Every element
 // then goes straight from its thread's registers to its place in memory (a wave's 64 places are a permutation of a
@@ -861,11 +862,23 @@ __global__ __launch_bounds__(WG, RSX_B16_WAVES(WG)) void rsx_bucket16_medium_ker
 // kernels behind this one untouched: done[g] = 0, and *left counts them; a workgroup that met the first kind leaves all
 // its later buckets too (as the old kernel's failed mend is sticky), so such an input costs each workgroup one abandoned
 // load and rank.  done[g] is written for every bucket; *left is zero when the launch starts (rsx_scan16_kernel).
+// The counting pass takes ONE MORE bit than there are counter words (B + 1 = 13, 12, 11): the 2^(B+1) counters are the
+// 16-bit halves of the same 2^B words, digit d in half d & 1 of word d >> 1 -- as a uint16_t array, index d.  A half
+// never exceeds the bucket's count (<= cape() < 2^16), so no carry crosses a word, before the scan (counts) or after it
+// (starts); start[2^(B+1)] = n is the low half of the word behind the last.  Half the keys per sub-bucket: T falls from
+// about 7 to about 5 on uniform keys, and the rank loop with it.  Two lanes meet on a word as often as they met on a
+// counter.  The hand-over rule stays on the B-bit sub-buckets -- the two halves of a word together (where the keys have
+// no more than B bits below the window the digit is all of them, and a half is such a sub-bucket by itself).
+// (RSX_DIRECT_PACKED=0: one 32-bit counter per B-bit digit, the form before, for A/B builds.)
+#ifndef RSX_DIRECT_PACKED
+#define RSX_DIRECT_PACKED 1
+#endif
 constexpr uint32_t DIRECT_LIMIT = 24;
 template <int WG>
 __host__ __device__ constexpr uint32_t direct_bits() {
     return WG >= 1024 ? 12u : WG >= 512 ? 11u : 10u;
 }
+constexpr uint32_t DIRECT_EXTRA_BITS = RSX_DIRECT_PACKED ? 1u : 0u;  // digit bits of the counting pass beyond direct_bits()
 template <int ES>
 __device__ __forceinline__ bool key_less(const Elem<ES>& x, const Elem<ES>& y) {  // the element as ONE number, highest dword first
     static_assert(ES == 8 || ES == 16, "key-only elements of 8 and 16 bytes");
@@ -959,15 +972,22 @@ __global__ __launch_bounds__(WG, RSX_B16_WAVES(WG)) void rsx_bucket16_direct_ker
     uint32_t* s_cnt = reinterpret_cast<uint32_t*>(smem + (size_t)CAPE * sizeof(E));  // [NB] counts, then starts; [NB] = n
     uint32_t* s_tot = s_cnt + NB + 4;                                                 // [NWAVE] the waves' sums of counts
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    // the digit: the B bits below the window (all b_lo of them if there are fewer), of the mapped key == the element
+    // the digit: the BC bits below the window (all b_lo of them if there are fewer), of the mapped key == the element
+    constexpr bool PACKED = DIRECT_EXTRA_BITS != 0;
+    constexpr uint32_t BC = B + DIRECT_EXTRA_BITS;
+    static_assert(CAPE < (1u << 16), "a count and a start fit a half");
     const uint32_t b_lo = plan->window_top - 15u;
-    const uint32_t bd = b_lo < B ? b_lo : B;
+    const uint32_t bd = b_lo < BC ? b_lo : BC;
     const uint32_t dshift = b_lo - bd, dmask = (1u << bd) - 1u;
     const uint32_t dword = dshift >> 5, dsh = dshift & 31u;
     auto digit_of = [&](const E& x) -> uint32_t {
         const uint32_t lo = elem_word<ES>(x, dword);
         const uint32_t hi = elem_word<ES>(x, dword + 1u < (uint32_t)(ES / 4) ? dword + 1u : dword);  // (a digit at the top of the element: shifted out)
         return (uint32_t)(((((uint64_t)hi << 32) | lo) >> dsh)) & dmask;
+    };
+    auto start_of = [&](const uint32_t d) -> uint32_t {  // (after the scan; d = number of digits: n)
+        if constexpr (PACKED) return reinterpret_cast<const uint16_t*>(s_cnt)[d];
+        else return s_cnt[d];
     };
     // Bucket g and all later ones of this workgroup are left to the old kernel: marked by all threads at once (one after
     // the other a workgroup's 85-256 buckets took 0.8 us each: 2^28 keys of 2^20 distinct values +75 us, 1.3 %).  Returns
@@ -1013,27 +1033,53 @@ __global__ __launch_bounds__(WG, RSX_B16_WAVES(WG)) void rsx_bucket16_direct_ker
 #pragma unroll
         for (int j = 0; j < KPT; ++j) {
             rk[j] = 0;
-            if ((uint32_t)j * WG + tid < n) rk[j] = atomicAdd(&s_cnt[digit_of(e[j])], 1u);
+            if ((uint32_t)j * WG + tid < n) {
+                const uint32_t d = digit_of(e[j]);
+                if constexpr (PACKED) {
+                    const uint32_t sh = (d & 1u) << 4;
+                    rk[j] = (atomicAdd(&s_cnt[d >> 1], 1u << sh) >> sh) & 0xFFFFu;
+                } else {
+                    rk[j] = atomicAdd(&s_cnt[d], 1u);
+                }
+            }
         }
         __syncthreads();
-        // counts -> starts: every thread four consecutive counters, a wave scan, the waves before mine
+        // counts -> starts: every thread four consecutive words of counters, a wave scan, the waves before mine
         const uint4 c = reinterpret_cast<const uint4*>(s_cnt)[tid];
-        const uint32_t sum = c.x + c.y + c.z + c.w;
-        const uint32_t m01 = c.x > c.y ? c.x : c.y, m23 = c.z > c.w ? c.z : c.w;
+        uint32_t p0 = c.x, p1 = c.y, p2 = c.z, p3 = c.w;  // the words' sums, and the largest B-bit sub-bucket among them
+        uint32_t big;
+        if constexpr (PACKED) {
+            auto low = [](uint32_t v) { return v & 0xFFFFu; };
+            auto larger = [](uint32_t u, uint32_t v) { return u > v ? u : v; };
+            p0 = low(c.x) + (c.x >> 16), p1 = low(c.y) + (c.y >> 16), p2 = low(c.z) + (c.z >> 16), p3 = low(c.w) + (c.w >> 16);
+            const uint32_t pairs = larger(larger(p0, p1), larger(p2, p3));
+            const uint32_t halves = larger(larger(larger(low(c.x), c.x >> 16), larger(low(c.y), c.y >> 16)),
+                                           larger(larger(low(c.z), c.z >> 16), larger(low(c.w), c.w >> 16)));
+            big = b_lo > B ? pairs : halves;  // (no more than B bits below the window: a half IS a B-bit sub-bucket)
+        } else {
+            const uint32_t m01 = c.x > c.y ? c.x : c.y, m23 = c.z > c.w ? c.z : c.w;
+            big = m01 > m23 ? m01 : m23;
+        }
+        const uint32_t sum = p0 + p1 + p2 + p3;
         const uint32_t incl = wave_incl_scan<true>(sum);
         if (lane == 63) s_tot[wave] = incl;
-        if (__syncthreads_or((m01 > m23 ? m01 : m23) > DIRECT_LIMIT ? 1 : 0)) {  // few distinct keys: this bucket and my later ones are the old kernel's
+        if (__syncthreads_or(big > DIRECT_LIMIT ? 1 : 0)) {  // few distinct keys: this bucket and my later ones are the old kernel's
             left_here += leave_from(g);
             break;
         }
         uint32_t run = incl - sum;
         for (uint32_t w = 0; w < wave; ++w) run += s_tot[w];
-        reinterpret_cast<uint4*>(s_cnt)[tid] = uint4{run, run + c.x, run + c.x + c.y, run + c.x + c.y + c.z};
+        if constexpr (PACKED) {  // a word: the start of its first digit in both halves, plus the first digit's count in the high one
+            const uint32_t r1 = run + p0, r2 = r1 + p1, r3 = r2 + p2;
+            reinterpret_cast<uint4*>(s_cnt)[tid] = uint4{(c.x << 16) + run * 0x10001u, (c.y << 16) + r1 * 0x10001u, (c.z << 16) + r2 * 0x10001u, (c.w << 16) + r3 * 0x10001u};
+        } else {
+            reinterpret_cast<uint4*>(s_cnt)[tid] = uint4{run, run + c.x, run + c.x + c.y, run + c.x + c.y + c.z};
+        }
         if (tid == 0) s_cnt[NB] = n;
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < KPT; ++j)
-            if ((uint32_t)j * WG + tid < n) s[s_cnt[digit_of(e[j])] + rk[j]] = e[j];
+            if ((uint32_t)j * WG + tid < n) s[start_of(digit_of(e[j])) + rk[j]] = e[j];
         __syncthreads();
         // the exact rank, one 16-byte word of the tile per thread and round
         const uint32_t words = (n + G - 1) / G;
@@ -1046,7 +1092,7 @@ __global__ __launch_bounds__(WG, RSX_B16_WAVES(WG)) void rsx_bucket16_direct_ker
                 r[h] = p;
                 if (live && p < n) {  // how far the sub-bucket of x[h] reaches on either side of p
                     const uint32_t d = digit_of(x[h]);
-                    const uint32_t below = p - s_cnt[d], above = s_cnt[d + 1u] - 1u - p;
+                    const uint32_t below = p - start_of(d), above = start_of(d + 1u) - 1u - p;
                     need = need > below ? need : below;
                     need = need > above ? need : above;
                 }
