@@ -197,9 +197,12 @@ enum {
                                  The segmented key / value calls report 3, fused per segment (the joined elements exist
                                  in registers and LDS only), or 4, fused per segment on (key, position) proxies followed
                                  by a gather of the values; bits 8-15 as above, RSX_INFO_LAST_PASSES path 6. */
-    RSX_INFO_LAST_DIRECT = 7  /* the context's last sort (waits for it): ~0 if it did not enqueue the direct bucket kernel
+    RSX_INFO_LAST_DIRECT = 7, /* the context's last sort (waits for it): ~0 if it did not enqueue the direct bucket kernel
                                  (RSX_OPT_BUCKET_DIRECT) or the device refused the hybrid, else the number of buckets
                                  that kernel left to the stable passes -- 0 when it sorted every bucket */
+    RSX_INFO_LAST_LEX = 8     /* the context's last rsx_lexsort_device / rsx_sort_columns_device call that sorted (n >= 2;
+                                 0 none yet): bits 0-7 the rounds it ran, bits 8-15 the bytes of the joined element of
+                                 its last round.  RSX_INFO_LAST_PASSES describes the inner sort of that round. */
 };
 int rsx_ctx_get_info(rsx_ctx *ctx, int what, uint64_t *out);
 /* Per-launch timing with HIP events on the launch stream (measurement only).
@@ -476,6 +479,62 @@ int rsx_ctx_reserve_reduce(rsx_ctx *ctx, size_t n, uint32_t key_bytes, uint32_t 
 /* Host-only, needs no device: *tile = the elements one workgroup of the run kernels takes for these widths (256 threads,
  * each a whole number of 16-byte words), *scan_span = the tiles one sweep of the scan kernel's loop takes. */
 int rsx_reduce_caps(uint32_t key_bytes, uint32_t value_bytes, uint32_t *tile, uint32_t *scan_span);
+
+/* -- several key columns ----------------------------------------------------- */
+/* Sorting a table by (a, b descending, c): ncols key columns of n keys each, column 0 the MOST significant (the opposite
+ * of numpy.lexsort, whose last key is the primary one).  Every column has its own key_bytes (1, 2, 4, 8, 16), key_kind
+ * (RSX_KEY_*; float at 4 and 8 bytes only) and direction.  With M(j, i) the mapped key of key i of column j -- the mapping
+ * of rsx_argsort_device, complemented when column j is descending -- the result is the ONE permutation p for which the
+ * tuples (M(0, p[t]), ..., M(ncols-1, p[t])) are non-decreasing in t and equal tuples have increasing p: stable whatever
+ * the directions.  Floats order by bit pattern: -NaN first, +NaN last, -0.0 before +0.0.
+ *
+ *   rsx_lexsort_device       writes p into d_index as index_bytes-wide integers (4 or 8); the columns are only read.
+ *                            n == 0 writes nothing, n == 1 writes 0.
+ *   rsx_sort_columns_device  applies p in place to every column and to the n values of value_bytes (0 .. 32768) at
+ *                            d_values (NULL with value_bytes 0: the keys alone).  THE COLUMNS ARE WRITTEN by this call; the
+ *                            const on rsx_key_column::d_keys is there so that one array of columns serves both calls.
+ *                            n <= 1 writes nothing.
+ * Columns are aligned to their key_bytes, d_index to index_bytes, d_values as in rsx_sort_pairs_device.  Columns that
+ * overlap each other, d_index or d_values are undefined behaviour.  RSX_ERR_ARG: ncols 0 or above RSX_LEX_MAX_COLUMNS,
+ * cols NULL, a nonzero `reserved`, index_bytes not 4 or 8, value_bytes above 32768, d_values and value_bytes disagreeing,
+ * a NULL or misaligned pointer with n > 0.  RSX_ERR_UNSUPPORTED: a key_bytes or key_kind without kernels, n >= 2^32.
+ * Stream-ordered, no synchronisation, the host reads nothing from the device.
+ *
+ * The plan (rsx_lex_plan, a function of the column widths alone): the columns are walked from the last to the first and
+ * whole columns are added to the current round while the round's key bytes K stay <= 16; otherwise the next round begins
+ * (a column is never split).  Round 0 holds the least significant columns and runs first; the last round holds column 0.
+ * A round's compound key has W bytes, the smallest of 1, 2, 4, 8, 16 with W >= K: the round's most significant column in
+ * the highest of the K used bytes, little-endian, the W - K bytes above them zero.  One join kernel per round maps and
+ * packs the columns and puts a uint32 position behind the key (the joined element of rsx_argsort_device for key_bytes W:
+ * 8, 16 or 32 bytes); from the second round on it reads the columns through the positions of the previous round's sorted
+ * elements.  The elements are sorted as unsigned W-byte keys by the kernels every call uses, stable, so that each round
+ * keeps the previous one's order among equal keys.  rsx_lexsort_device then writes the positions of the last round's
+ * elements; rsx_sort_columns_device copies every column, and the values, into a staging area and gathers it back through
+ * those positions, so every input is consumed before it is stored.
+ * Workspace: two element arrays of the widest round and, for rsx_sort_columns_device, n * max(widest column,
+ * value_bytes) bytes of staging, made on first use or by rsx_ctx_reserve_lex; under capture without a sufficient
+ * reserve the calls return RSX_ERR_WORKSPACE and enqueue nothing.  RSX_INFO_LAST_LEX reports the rounds. */
+typedef struct rsx_key_column {
+    const void *d_keys;   /* n keys of key_bytes */
+    uint32_t key_bytes;   /* 1, 2, 4, 8, 16 */
+    uint32_t key_kind;    /* RSX_KEY_* */
+    uint32_t descending;  /* 0 ascending, anything else descending */
+    uint32_t reserved;    /* 0 */
+} rsx_key_column;         /* 24 bytes */
+#define RSX_LEX_MAX_COLUMNS 16
+int rsx_lexsort_device(rsx_ctx *ctx, const rsx_key_column *cols, uint32_t ncols, void *d_index, size_t n,
+                       uint32_t index_bytes, void *stream);
+int rsx_sort_columns_device(rsx_ctx *ctx, const rsx_key_column *cols, uint32_t ncols, void *d_values,
+                            uint32_t value_bytes, size_t n, void *stream);
+/* Workspace (and the context's first-call set-up) for either call on up to n keys of these columns (d_keys is not looked
+ * at) and, for rsx_sort_columns_device, values of value_bytes, so that the call allocates nothing (stream capture). */
+int rsx_ctx_reserve_lex(rsx_ctx *ctx, size_t n, const rsx_key_column *cols, uint32_t ncols, uint32_t value_bytes);
+/* Host-only, needs no device; d_keys is not looked at.  *rounds = the number of rounds; for round r (0 runs first),
+ * first_col[r] = the round's first (most significant) column -- it holds the columns first_col[r] .. first_col[r-1] - 1,
+ * round 0 up to ncols - 1 --, key_bytes[r] = K, the sum of their widths, elem_bytes[r] = the bytes of its joined element.
+ * Each array has room for RSX_LEX_MAX_COLUMNS entries. */
+int rsx_lex_plan(const rsx_key_column *cols, uint32_t ncols, uint32_t *rounds, uint32_t *first_col,
+                 uint32_t *key_bytes, uint32_t *elem_bytes);
 
 /* -- per-pass building blocks (multi-GPU bucket exchange) ---------------- */
 /* 256-bin count of digit `digit` (0 = least significant) over `n` elements:

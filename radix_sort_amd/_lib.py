@@ -22,8 +22,10 @@ SYMBOLS = [
     "rsx_topk_rows_device", "rsx_ctx_reserve_topk", "rsx_topk_caps",
     "rsx_unique_device", "rsx_ctx_reserve_unique", "rsx_unique_caps",
     "rsx_reduce_by_key_device", "rsx_ctx_reserve_reduce", "rsx_reduce_caps",
+    "rsx_lexsort_device", "rsx_sort_columns_device", "rsx_ctx_reserve_lex", "rsx_lex_plan",
 ]
 SEG_CLASSES = 2  # RSX_SEG_CLASSES
+LEX_MAX_COLUMNS = 16  # RSX_LEX_MAX_COLUMNS
 
 OK, ERR_ARG, ERR_UNSUPPORTED, ERR_HIP, ERR_NOMEM, ERR_NODEVICE, ERR_WORKSPACE, ERR_INTERNAL = 0, -1, -2, -3, -4, -5, -6, -7
 KEY_UNSIGNED, KEY_SIGNED, KEY_FLOAT = 0, 1, 2
@@ -33,7 +35,7 @@ GEN_PAYLOAD_ZERO = 0x100
 (OPT_TILE_SCHEDULE, OPT_RANKING, OPT_STATUS_SCOPE, OPT_XCD_MAJOR, OPT_BYTE_COUNTING, OPT_MAX_REGIONS, OPT_HOT_LANES,
  OPT_VERBOSE, OPT_RANK_CHECK, OPT_SMALL_SORT, OPT_MID_SORT, OPT_WIDE_SORT, OPT_BUCKET_SKIP, OPT_BUCKET_GROUP,
  OPT_BUCKET_DIRECT) = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15
-INFO_RANK_ATOMIC, INFO_L2_LOCAL, INFO_NUM_CU, INFO_DEVICE, INFO_LAST_PASSES, INFO_LAST_PAIRS, INFO_LAST_DIRECT = 1, 2, 3, 4, 5, 6, 7
+INFO_RANK_ATOMIC, INFO_L2_LOCAL, INFO_NUM_CU, INFO_DEVICE, INFO_LAST_PASSES, INFO_LAST_PAIRS, INFO_LAST_DIRECT, INFO_LAST_LEX = 1, 2, 3, 4, 5, 6, 7, 8
 ORDER_ASCENDING, ORDER_DESCENDING = 0, 1
 REDUCE_SUM, REDUCE_MIN, REDUCE_MAX = 0, 1, 2
 SHARD_EXCHANGE_FIRST, SHARD_SORT_FIRST = 0, 1
@@ -50,6 +52,17 @@ class Layout(ctypes.Structure):
 
     def __repr__(self):
         return f"Layout(elem_bytes={self.elem_bytes}, key_offset={self.key_offset}, key_bytes={self.key_bytes}, key_kind={self.key_kind})"
+
+
+class KeyColumn(ctypes.Structure):
+    """struct rsx_key_column (include/rsx.h): one key column of rsx_lexsort_device / rsx_sort_columns_device."""
+    _fields_ = [
+        ("d_keys", ctypes.c_void_p),
+        ("key_bytes", ctypes.c_uint32),
+        ("key_kind", ctypes.c_uint32),
+        ("descending", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+    ]
 
 
 class RsxError(RuntimeError):
@@ -134,6 +147,11 @@ def load():
     L.rsx_reduce_by_key_device.argtypes = [vp, vp, vp, sz, u32, u32, u32, u32, i, i, vp, vp, vp, vp, vp]
     L.rsx_ctx_reserve_reduce.argtypes = [vp, sz, u32, u32]
     L.rsx_reduce_caps.argtypes = [u32, u32, ctypes.POINTER(u32), ctypes.POINTER(u32)]
+    kc, pu32 = ctypes.POINTER(KeyColumn), ctypes.POINTER(u32)
+    L.rsx_lexsort_device.argtypes = [vp, kc, u32, vp, sz, u32, vp]
+    L.rsx_sort_columns_device.argtypes = [vp, kc, u32, vp, u32, sz, vp]
+    L.rsx_ctx_reserve_lex.argtypes = [vp, sz, kc, u32, u32]
+    L.rsx_lex_plan.argtypes = [kc, u32, pu32, pu32, pu32, pu32]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("rsx_last_error", "rsx_strerror"):

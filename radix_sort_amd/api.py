@@ -326,6 +326,31 @@ class Context:
                                                      d_out_offsets or None, d_out_num or None, stream))
 
 
+    @staticmethod
+    def _key_columns(columns):
+        """(ptr, key_bytes, key_kind, descending) tuples -> a ctypes array of rsx_key_column."""
+        arr = (_lib.KeyColumn * max(1, len(columns)))()
+        for j, (ptr, kb, kind, desc) in enumerate(columns):
+            arr[j] = _lib.KeyColumn(ptr or None, kb, kind, 1 if desc else 0, 0)
+        return arr
+
+    def reserve_lex(self, n: int, columns, value_bytes: int = 0):
+        """rsx_ctx_reserve_lex: the context's first-call set-up and the workspace of lexsort_device / sort_columns_device on
+        up to n keys of these columns ((ptr, key_bytes, key_kind, descending) tuples; ptr is not looked at), so that the
+        call allocates nothing and can be captured."""
+        self._check(self._L.rsx_ctx_reserve_lex(self._h, n, self._key_columns(columns), len(columns), value_bytes))
+
+    def lexsort_device(self, columns, d_index: int, n: int, index_bytes: int, stream: int = 0):
+        """rsx_lexsort_device: the stable permutation that sorts n rows by several key columns, column 0 the most
+        significant; columns: (ptr, key_bytes, key_kind, descending) tuples.  The columns are only read."""
+        self._check(self._L.rsx_lexsort_device(self._h, self._key_columns(columns), len(columns), d_index or None, n, index_bytes, stream))
+
+    def sort_columns_device(self, columns, d_values: int, value_bytes: int, n: int, stream: int = 0):
+        """rsx_sort_columns_device: that permutation applied in place to every column and to the values (d_values 0 and
+        value_bytes 0: the columns alone)."""
+        self._check(self._L.rsx_sort_columns_device(self._h, self._key_columns(columns), len(columns), d_values or None, value_bytes, n, stream))
+
+
 _DEFAULT = {}
 _DEFAULT_LOCK = threading.Lock()
 
@@ -624,6 +649,119 @@ def radix_argsort(keys, descending: bool = False, out=None, ctx: Optional[Contex
         stream = torch.cuda.current_stream(dev).cuda_stream
         c.argsort_device(keys.data_ptr(), out.data_ptr(), n, kb, kind, out.element_size(), descending, stream)
     return out
+
+
+def lex_plan(specs):
+    """rsx_lex_plan: how radix_lexsort / radix_sort_columns would sort columns of these (key_bytes, key_kind) specs, column
+    0 the most significant: a list of rounds in the order they run, each (first_col, key_bytes, elem_bytes) -- the
+    round takes the columns from first_col up to the previous round's first_col (round 0: to the end), key_bytes is the
+    sum of their widths, elem_bytes the size of the joined (compound key, position) element it sorts.  Needs no device."""
+    L = _lib.load()
+    specs = [tuple(s) for s in specs]
+    arr = (_lib.KeyColumn * max(1, len(specs)))()
+    for j, (kb, kind) in enumerate(specs):
+        arr[j] = _lib.KeyColumn(None, kb, kind, 0, 0)
+    rounds = ctypes.c_uint32()
+    first, kbs, ebs = ((ctypes.c_uint32 * _lib.LEX_MAX_COLUMNS)() for _ in range(3))
+    rc = L.rsx_lex_plan(arr, len(specs), ctypes.byref(rounds), first, kbs, ebs)
+    if rc != 0:
+        raise RsxError(rc, L.rsx_strerror(rc).decode())
+    return [(int(first[r]), int(kbs[r]), int(ebs[r])) for r in range(rounds.value)]
+
+
+def _lex_columns(columns, descending):
+    """The checks of radix_lexsort / radix_sort_columns on their columns (none needs a context) ->
+    ([(tensor, key_bytes, key_kind, descending)], n)."""
+    import torch
+    if isinstance(columns, torch.Tensor) or not isinstance(columns, (list, tuple)):
+        raise TypeError("columns must be a list or tuple of key columns")
+    if not 1 <= len(columns) <= _lib.LEX_MAX_COLUMNS:
+        raise ValueError(f"1 .. {_lib.LEX_MAX_COLUMNS} key columns, not {len(columns)}")
+    if isinstance(descending, (bool, np.bool_)):
+        desc = [bool(descending)] * len(columns)
+    else:
+        desc = list(descending)
+        if len(desc) != len(columns) or not all(isinstance(d, (bool, np.bool_)) for d in desc):
+            raise ValueError(f"descending must be a bool or one bool per column ({len(columns)})")
+    out, n = [], None
+    for j, col in enumerate(columns):
+        kind = None
+        if isinstance(col, tuple):
+            if len(col) != 2:
+                raise TypeError("a column is a tensor or a (tensor, key_kind) pair")
+            col, kind = col
+        kb, kind, m = _pairs_keys(col, kind)
+        if n is None:
+            n = m
+        elif m != n:
+            raise ValueError(f"every column must have the length of the first ({n}); column {j} has {m}")
+        out.append((col, kb, kind, bool(desc[j])))
+    return out, n
+
+
+def _lex_device(cols, other, what: str):
+    """Last of the argument checks (none of them needs a context): every tensor on one GPU."""
+    first = cols[0][0]
+    for j, (col, _kb, _kind, _d) in enumerate(cols):
+        if not col.is_cuda:
+            raise ValueError("the columns must live on a GPU")
+        if col.device != first.device:
+            raise ValueError(f"column {j} must live on the device of column 0")
+    if other is not None and other.device != first.device:
+        raise ValueError(f"the columns and {what} must live on the same device")
+
+
+def radix_lexsort(columns, descending=False, out=None, ctx: Optional[Context] = None):
+    """The stable permutation that sorts rows by several key columns (rsx_lexsort_device): returns a new int64 tensor, or
+    fills and returns `out` (a contiguous 1-D int32 or int64 tensor of the columns' length on their device).
+
+    columns[0] is the MOST significant column -- the opposite of numpy.lexsort, whose last key is the primary one:
+    radix_lexsort([a, b, c]) is np.lexsort((c, b, a)).  Each column is a contiguous 1-D GPU tensor of a dtype radix_sort
+    knows, or an (n, 16) uint8 tensor of 128-bit keys, alone (unsigned) or as a (tensor, key_kind) pair; all of one
+    length on one device, at most 16 of them.  descending: a bool, or one bool per column.  Rows that are equal in every
+    column keep their input order whatever the directions.  No column is modified.
+
+    The order within a column is the reference's total order on bit patterns (radix_digits.rs), not torch's: -NaN sorts
+    below -inf, +NaN above +inf, -0.0 below +0.0.  Enqueued on the current stream, not synchronised."""
+    import torch
+    cols, n = _lex_columns(columns, descending)
+    _index_out(out, (n,), "the columns")
+    _lex_device(cols, out, "out")
+    keys = cols[0][0]
+    if out is None:
+        out = torch.empty(n, dtype=torch.int64, device=keys.device)
+    if n == 0:
+        return out
+    dev = keys.device.index if keys.device.index is not None else torch.cuda.current_device()
+    c = ctx or default_context(dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        c.lexsort_device([(t.data_ptr(), kb, kind, d) for t, kb, kind, d in cols], out.data_ptr(), n, out.element_size(), stream)
+    return out
+
+
+def radix_sort_columns(columns, values=None, descending=False, ctx: Optional[Context] = None):
+    """Sorts rows that are kept as several key columns, in place, and returns None (rsx_sort_columns_device): every column
+    and `values` are permuted by radix_lexsort(columns, descending) -- columns[0] the most significant, equal rows in
+    input order.
+
+    columns, descending: as in radix_lexsort; THE COLUMNS ARE WRITTEN.  values: as in radix_sort_pairs, a contiguous GPU
+    tensor on the same device with one row of 1 .. 32768 bytes per key, moved bitwise; None: the columns alone.  Columns
+    that share memory with each other or with values are undefined.  Enqueued on the current stream, not synchronised."""
+    import torch
+    cols, n = _lex_columns(columns, descending)
+    vb = _value_bytes(values, (n,), "the columns")
+    _lex_device(cols, values, "values")
+    keys = cols[0][0]
+    if n <= 1:
+        return None
+    dev = keys.device.index if keys.device.index is not None else torch.cuda.current_device()
+    c = ctx or default_context(dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        c.sort_columns_device([(t.data_ptr(), kb, kind, d) for t, kb, kind, d in cols], values.data_ptr() if values is not None else 0,
+                              vb, n, stream)
+    return None
 
 
 def segment_pairs_caps(key_bytes: int, value_bytes: int):

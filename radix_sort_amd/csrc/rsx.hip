@@ -995,6 +995,7 @@ int rsx_ctx_get_info(rsx_ctx* ctx, int what, uint64_t* out) try {
             return RSX_OK;
         }
         case RSX_INFO_LAST_PAIRS: *out = (uint64_t)ctx->last_pairs; return RSX_OK;
+        case RSX_INFO_LAST_LEX: *out = (uint64_t)ctx->last_lex; return RSX_OK;
         case RSX_INFO_LAST_DIRECT: {
             *out = ~(uint64_t)0;
             if (ctx->last_path != 5 || !ctx->last_direct || !ctx->wide_buf) return RSX_OK;
@@ -1703,6 +1704,224 @@ int rsx_reduce_caps(uint32_t key_bytes, uint32_t value_bytes, uint32_t* tile, ui
     *tile = reduce_tile_elems(key_bytes, value_bytes);
     *scan_span = reduce_scan_span();
     return RSX_OK;
+}
+
+// ---- several key columns (rsx_lex_kernels.hpp, include/rsx.h) ----
+namespace {
+// One round of the plan: the columns [first, last) make a compound key of k used bytes inside w, joined with a u32
+// position into elements of es bytes.
+struct LexRound {
+    uint32_t first, last, k, w, es;
+};
+struct LexPlan {
+    uint32_t rounds;
+    LexRound r[RSX_LEX_MAX_COLUMNS];
+    uint32_t max_es;  // the widest round's element
+    uint32_t max_kb;  // the widest column
+};
+// RSX_OK, or why the columns are refused (the pointers are not looked at)
+int lex_columns_status(const rsx_key_column* cols, uint32_t ncols) {
+    if (!cols || ncols == 0 || ncols > RSX_LEX_MAX_COLUMNS) return RSX_ERR_ARG;
+    for (uint32_t j = 0; j < ncols; ++j)
+        if (cols[j].reserved != 0) return RSX_ERR_ARG;
+    for (uint32_t j = 0; j < ncols; ++j)
+        if (!key_widths_ok(cols[j].key_bytes, cols[j].key_kind)) return RSX_ERR_UNSUPPORTED;
+    return RSX_OK;
+}
+// From the last column to the first: whole columns join the current round while its key bytes stay <= 16.
+LexPlan lex_plan(const rsx_key_column* cols, uint32_t ncols) {
+    LexPlan P{};
+    auto close = [&](uint32_t first, uint32_t last, uint32_t k) {
+        uint32_t w = 1;
+        while (w < k) w *= 2;
+        const uint32_t es = pairs_elem_bytes(w, 4);
+        P.r[P.rounds++] = LexRound{first, last, k, w, es};
+        if (es > P.max_es) P.max_es = es;
+    };
+    uint32_t last = ncols, k = 0;
+    for (uint32_t j = ncols; j-- > 0;) {
+        const uint32_t kb = cols[j].key_bytes;
+        if (kb > P.max_kb) P.max_kb = kb;
+        if (k + kb > 16) {
+            close(j + 1, last, k);
+            last = j + 1;
+            k = 0;
+        }
+        k += kb;
+    }
+    close(0, last, k);
+    return P;
+}
+size_t lex_round256(size_t b) { return (b + 255) & ~(size_t)255; }
+// the two element arrays of the widest round and, behind them, `stage` bytes per key of staging (rsx_sort_columns_device)
+int reserve_lex_one(rsx_ctx* ctx, size_t n, const LexPlan& P, uint32_t stage, hipStream_t st) {
+    for (uint32_t r = 0; r < P.rounds; ++r) {
+        const rsx_layout L{P.r[r].es, 0, P.r[r].w, RSX_KEY_UNSIGNED};
+        int rc = ensure_workspace(ctx, n, &L, st);
+        if (rc) return rc;
+    }
+    return ensure_any(ctx, 2 * lex_round256(n * (size_t)P.max_es) + lex_round256(n * (size_t)stage), st);
+}
+// The rounds of the plan on n >= 2 keys: join, sort, and the next round reads the columns through this one's positions.
+// *sorted receives the last round's sorted elements (in the workspace), *es / *voff their size and position offset.
+// Caller holds ctx->mu, has set the device, checked the arguments and reserved the workspace under its Enqueue.
+int lex_rounds_locked(rsx_ctx* ctx, const rsx_key_column* cols, const LexPlan& P, size_t n, char** sorted, uint32_t* es, uint32_t* voff,
+                      hipStream_t st) {
+    char* w[2] = {ctx->any_buf, ctx->any_buf + lex_round256(n * (size_t)P.max_es)};
+    const char* prev = nullptr;
+    uint32_t prev_es = 0, prev_voff = 0;
+    for (uint32_t r = 0; r < P.rounds; ++r) {
+        const LexRound& R = P.r[r];
+        char* cur = w[r & 1];
+        LexJoinCall c{};
+        uint32_t off = 0;
+        for (uint32_t j = R.last; j-- > R.first;) {  // the round's last column in the lowest bytes
+            c.col[c.ncols++] = LexJoinCol{cols[j].d_keys, cols[j].key_bytes, cols[j].key_kind, cols[j].descending ? 1u : 0u, off};
+            off += cols[j].key_bytes;
+        }
+        c.w = R.w;
+        c.prev = prev;
+        c.prev_es = prev_es;
+        c.prev_voff = prev_voff;
+        c.elems = cur;
+        c.n = n;
+        int rc = launch_lex_join(ctx, c, st);
+        if (rc) return rc;
+        const rsx_layout L{R.es, 0, R.w, RSX_KEY_UNSIGNED};
+        rc = sort_device_locked(ctx, cur, w[(r & 1) ^ 1], n, &L, st);
+        if (rc) return rc;
+        prev = cur;
+        prev_es = R.es;
+        prev_voff = pairs_value_offset(R.w, 4);
+    }
+    *sorted = const_cast<char*>(prev);
+    *es = prev_es;
+    *voff = prev_voff;
+    ctx->last_lex = P.rounds | prev_es << 8;
+    return RSX_OK;
+}
+// the checks both calls share, once the columns themselves passed lex_columns_status
+int lex_check_pointers(rsx_ctx* ctx, const rsx_key_column* cols, uint32_t ncols) {
+    for (uint32_t j = 0; j < ncols; ++j) {
+        if (!cols[j].d_keys) return fail(ctx, RSX_ERR_ARG, "null device pointer");
+        if (!aligned(cols[j].d_keys, cols[j].key_bytes)) return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
+    }
+    return RSX_OK;
+}
+int lex_fail_columns(rsx_ctx* ctx, int rc) {
+    return fail(ctx, rc, rc == RSX_ERR_UNSUPPORTED ? "a column's key width or kind has no kernels" : "invalid key columns");
+}
+}  // namespace
+
+int rsx_lex_plan(const rsx_key_column* cols, uint32_t ncols, uint32_t* rounds, uint32_t* first_col, uint32_t* key_bytes, uint32_t* elem_bytes) {
+    if (!rounds || !first_col || !key_bytes || !elem_bytes) return RSX_ERR_ARG;
+    const int rc = lex_columns_status(cols, ncols);
+    if (rc) return rc;
+    const LexPlan P = lex_plan(cols, ncols);
+    *rounds = P.rounds;
+    for (uint32_t r = 0; r < P.rounds; ++r) {
+        first_col[r] = P.r[r].first;
+        key_bytes[r] = P.r[r].k;
+        elem_bytes[r] = P.r[r].es;
+    }
+    return RSX_OK;
+}
+
+int rsx_ctx_reserve_lex(rsx_ctx* ctx, size_t n, const rsx_key_column* cols, uint32_t ncols, uint32_t value_bytes) try {
+    if (!ctx) return RSX_ERR_ARG;
+    int rc = lex_columns_status(cols, ncols);
+    if (rc) return lex_fail_columns(ctx, rc);
+    if (value_bytes > RSX_MAX_ELEM_BYTES) return fail(ctx, RSX_ERR_ARG, "value wider than RSX_MAX_ELEM_BYTES");
+    if (!unique_size_ok(n)) return fail(ctx, RSX_ERR_UNSUPPORTED, "2^32 or more keys");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return fail(ctx, RSX_ERR_NODEVICE, "hipSetDevice failed");
+    const LexPlan P = lex_plan(cols, ncols);
+    return reserve_lex_one(ctx, n, P, std::max(P.max_kb, value_bytes), nullptr);
+} catch (...) {
+    return RSX_ERR_NOMEM;
+}
+
+int rsx_lexsort_device(rsx_ctx* ctx, const rsx_key_column* cols, uint32_t ncols, void* d_index, size_t n, uint32_t index_bytes,
+                       void* stream) try {
+    if (!ctx) return RSX_ERR_ARG;
+    int rc = lex_columns_status(cols, ncols);
+    if (rc) return lex_fail_columns(ctx, rc);
+    if (index_bytes != 4 && index_bytes != 8) return fail(ctx, RSX_ERR_ARG, "index_bytes must be 4 or 8");
+    if (!unique_size_ok(n)) return fail(ctx, RSX_ERR_UNSUPPORTED, "2^32 or more keys");
+    if (n == 0) return RSX_OK;
+    if (!d_index) return fail(ctx, RSX_ERR_ARG, "null device pointer");
+    if (!aligned(d_index, index_bytes)) return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
+    rc = lex_check_pointers(ctx, cols, ncols);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return fail(ctx, RSX_ERR_NODEVICE, "hipSetDevice failed");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (n == 1) {  // the one position
+        RSX_HIP(hipMemsetAsync(d_index, 0, index_bytes, st));
+        return RSX_OK;
+    }
+    const LexPlan P = lex_plan(cols, ncols);
+    rc = pending_error(ctx);
+    if (rc) return rc;
+    rc = reserve_lex_one(ctx, n, P, 0, st);
+    if (rc) return rc;
+    Enqueue enq(ctx, st);  // the workspace arrays belong to this call from the first launch on
+    char* sorted = nullptr;
+    uint32_t es = 0, voff = 0;
+    rc = lex_rounds_locked(ctx, cols, P, n, &sorted, &es, &voff, st);
+    if (rc) return rc;
+    // the split of rsx_argsort_device: the position alone, widened to the caller's index type
+    return launch_pairs_split(ctx, sorted, nullptr, d_index, n, P.r[P.rounds - 1].w, 4, 2, index_bytes, RSX_KEY_UNSIGNED, 0, st);
+} catch (...) {
+    return RSX_ERR_HIP;
+}
+
+int rsx_sort_columns_device(rsx_ctx* ctx, const rsx_key_column* cols, uint32_t ncols, void* d_values, uint32_t value_bytes, size_t n,
+                            void* stream) try {
+    if (!ctx) return RSX_ERR_ARG;
+    int rc = lex_columns_status(cols, ncols);
+    if (rc) return lex_fail_columns(ctx, rc);
+    if (value_bytes > RSX_MAX_ELEM_BYTES) return fail(ctx, RSX_ERR_ARG, "value wider than RSX_MAX_ELEM_BYTES");
+    if ((d_values == nullptr) != (value_bytes == 0) && (n > 0 || d_values != nullptr)) return fail(ctx, RSX_ERR_ARG, "d_values and value_bytes disagree");
+    if (!unique_size_ok(n)) return fail(ctx, RSX_ERR_UNSUPPORTED, "2^32 or more keys");
+    if (n == 0) return RSX_OK;
+    rc = lex_check_pointers(ctx, cols, ncols);
+    if (rc) return rc;
+    if (value_bytes && !aligned(d_values, value_align(value_bytes))) return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
+    if (n == 1) return RSX_OK;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return fail(ctx, RSX_ERR_NODEVICE, "hipSetDevice failed");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const LexPlan P = lex_plan(cols, ncols);
+    rc = pending_error(ctx);
+    if (rc) return rc;
+    rc = reserve_lex_one(ctx, n, P, std::max(P.max_kb, value_bytes), st);
+    if (rc) return rc;
+    Enqueue enq(ctx, st);  // the workspace arrays belong to this call from the first launch on
+    char* sorted = nullptr;
+    uint32_t es = 0, voff = 0;
+    rc = lex_rounds_locked(ctx, cols, P, n, &sorted, &es, &voff, st);
+    if (rc) return rc;
+    // every column, then the values: a copy into the staging area, gathered back through the sorted positions.  The
+    // rounds above have read every column for the last time; stream order keeps each copy in front of its gather.
+    char* stage = ctx->any_buf + 2 * lex_round256(n * (size_t)P.max_es);
+    for (uint32_t j = 0; j < ncols; ++j) {
+        void* col = const_cast<void*>(cols[j].d_keys);
+        RSX_HIP(hipMemcpyAsync(stage, col, n * (size_t)cols[j].key_bytes, hipMemcpyDeviceToDevice, st));
+        rc = launch_gather(ctx, stage, col, cols[j].key_bytes, sorted, es, voff, n, st);
+        if (rc) return rc;
+    }
+    if (value_bytes) {
+        RSX_HIP(hipMemcpyAsync(stage, d_values, n * (size_t)value_bytes, hipMemcpyDeviceToDevice, st));
+        rc = launch_gather(ctx, stage, d_values, value_bytes, sorted, es, voff, n, st);
+        if (rc) return rc;
+    }
+    return RSX_OK;
+} catch (...) {
+    return RSX_ERR_HIP;
 }
 
 int rsx_segment_caps(const rsx_layout* L, uint32_t* caps) {

@@ -110,6 +110,7 @@ struct rsx_ctx {
     char* any_buf = nullptr;   // routes 1 / 2: the re-laid-out elements or the proxies, and their ping-pong array
     size_t any_bytes = 0;
     uint32_t last_pairs = 0;   // RSX_INFO_LAST_PAIRS: route of the last pairs / argsort call (1 joined, 2 proxies) | joined element size << 8
+    uint32_t last_lex = 0;     // RSX_INFO_LAST_LEX: rounds of the last lexsort / sort-columns call | element size of its last round << 8
     uint64_t cb_used[2][2] = {{0, 0}, {0, 0}};  // per alternating block: bytes of the top-digit matrix / of count matrix 0 its last sort used
     uint32_t cb_alt = 0;       // which of the two alternating blocks the last uncaptured sort used
     uint32_t cb_last = 0;      // control block of the last sort that ran sweeps (RSX_INFO_LAST_PASSES)
@@ -465,6 +466,25 @@ int launch_pairs_split(rsx_ctx* ctx, const void* elems, void* keys, void* values
                        uint32_t kind, uint32_t desc, hipStream_t st);
 uint32_t pairs_elem_bytes(uint32_t kb, uint32_t vb);    // joined element size, 0: none (proxy route)
 uint32_t pairs_value_offset(uint32_t kb, uint32_t vb);  // of the value in the joined element
+
+// The columns of ONE round of rsx_lexsort_device / rsx_sort_columns_device -> joined (compound key, u32 position) elements
+// (rsx_lex.hip, rsx_lex_kernels.hpp).
+struct LexJoinCol {
+    const void* keys;         // n keys of kb bytes, aligned to kb
+    uint32_t kb, kind, desc;
+    uint32_t off;             // byte offset of the mapped key inside the compound key
+};
+struct LexJoinCall {
+    LexJoinCol col[RSX_LEX_MAX_COLUMNS];
+    uint32_t ncols;
+    uint32_t w;               // bytes of the compound key: 1, 2, 4, 8, 16; the element is pairs_elem_bytes(w, 4)
+    const void* prev;         // null: the first round; else the previous round's n sorted elements of prev_es bytes,
+    uint32_t prev_es;         // whose positions (u32 at prev_voff) say which key of every column slot i takes
+    uint32_t prev_voff;
+    void* elems;              // out: n elements, 16-byte aligned
+    size_t n;                 // 1 .. 2^32 - 1
+};
+int launch_lex_join(rsx_ctx* ctx, const LexJoinCall& call, hipStream_t st);
 
 // What one rsx_unique_device call asks of the run kernels (rsx_unique.hip, rsx_unique_kernels.hpp) once its joined
 // elements are sorted.

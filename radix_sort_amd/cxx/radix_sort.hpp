@@ -15,6 +15,8 @@
 //     rsx::radix_argsort(const K* d_keys, I* d_index, size_t n, bool descending, hipStream_t)
 //     rsx::unique(const K* d_keys, size_t n, K* keys, uint64_t* offsets, I* perm, I* inverse, uint64_t* num, bool descending, hipStream_t)
 //     rsx::reduce_by_key(const K* d_keys, const V* d_values, size_t n, int op, K* keys, V* values, uint64_t* offsets, uint64_t* num, bool descending, hipStream_t)
+//     rsx::lexsort({rsx::key_column(d_a), rsx::key_column(d_b, true)}, I* d_index, size_t n, hipStream_t)   // several key columns
+//     rsx::sort_columns({rsx::key_column(d_a), rsx::key_column(d_b, true)}, V* d_values, size_t n, hipStream_t)
 // Errors: the reference panics (mod.rs:68,106); here std::runtime_error is thrown.
 // Empty and one-element slices return immediately (the reference panics on an empty
 // slice -- chunks(0), mod.rs:66-70,92 -- there is no output to differ from).
@@ -249,6 +251,33 @@ void reduce_by_key(const K* d_keys, const V* d_values, size_t n, int op, K* d_ou
                                        descending ? RSX_ORDER_DESCENDING : RSX_ORDER_ASCENDING, d_out_keys, d_out_values, d_out_offsets,
                                        d_out_num, stream),
               "rsx_reduce_by_key_device");
+}
+
+// Several key columns (rsx_lexsort_device, rsx_sort_columns_device): rows sorted by (column 0, column 1, ...), column 0
+// the MOST significant, every column with its own type and direction; rows equal in every column keep their input order.
+// key_column describes one column of n keys on the device; at most RSX_LEX_MAX_COLUMNS of them.
+template <typename K>
+rsx_key_column key_column(const K* d_keys, bool descending = false) {
+    const rsx_layout L = RadixDigits<K>::layout();
+    if (L.key_offset != 0 || L.key_bytes != L.elem_bytes) throw std::invalid_argument("key_column: the key type must be its own key");
+    return rsx_key_column{d_keys, L.key_bytes, L.key_kind, descending ? 1u : 0u, 0u};
+}
+// d_index[t] = the row that stands at place t (I: 4 or 8 bytes); the columns are only read.
+template <typename I>
+void lexsort(const std::vector<rsx_key_column>& columns, I* d_index, size_t n, void* stream = nullptr, Context& ctx = default_context()) {
+    static_assert(std::is_integral<I>::value && (sizeof(I) == 4 || sizeof(I) == 8), "indices are 32- or 64-bit integers");
+    ctx.check(rsx_lexsort_device(ctx.get(), columns.data(), (uint32_t)columns.size(), d_index, n, (uint32_t)sizeof(I), stream), "rsx_lexsort_device");
+}
+// That permutation applied in place to every column -- THE COLUMNS ARE WRITTEN -- and to the n values (nullptr: the
+// columns alone).  Stream-ordered, never synchronised (rsx_ctx_reserve_lex before a stream capture).
+template <typename V>
+void sort_columns(const std::vector<rsx_key_column>& columns, V* d_values, size_t n, void* stream = nullptr, Context& ctx = default_context()) {
+    static_assert(std::is_trivially_copyable<V>::value, "values are moved bitwise");
+    ctx.check(rsx_sort_columns_device(ctx.get(), columns.data(), (uint32_t)columns.size(), d_values, d_values ? (uint32_t)sizeof(V) : 0u, n, stream),
+              "rsx_sort_columns_device");
+}
+inline void sort_columns(const std::vector<rsx_key_column>& columns, size_t n, void* stream = nullptr, Context& ctx = default_context()) {
+    ctx.check(rsx_sort_columns_device(ctx.get(), columns.data(), (uint32_t)columns.size(), nullptr, 0u, n, stream), "rsx_sort_columns_device");
 }
 
 // The segmented forms of the three calls above (rsx_sort_segments_pairs_device, rsx_argsort_segments_device and their

@@ -32,6 +32,17 @@ pub struct RsxCtx {
     _private: [u8; 0],
 }
 
+/// `struct rsx_key_column` (include/rsx.h): one key column of `rsx_lexsort_device` / `rsx_sort_columns_device`.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RsxKeyColumn {
+    pub d_keys: *const c_void,
+    pub key_bytes: u32,
+    pub key_kind: u32,
+    pub descending: u32,
+    pub reserved: u32,
+}
+
 extern "C" {
     pub fn rsx_ctx_create(device: c_int, out: *mut *mut RsxCtx) -> c_int;
     pub fn rsx_ctx_destroy(ctx: *mut RsxCtx) -> c_int;
@@ -49,6 +60,14 @@ extern "C" {
     pub fn rsx_argsort_device(ctx: *mut RsxCtx, d_keys: *const c_void, d_index: *mut c_void, n: usize, key_bytes: u32,
                               key_kind: u32, index_bytes: u32, order: c_int, stream: *mut c_void) -> c_int;
     pub fn rsx_ctx_reserve_pairs(ctx: *mut RsxCtx, n: usize, key_bytes: u32, value_bytes: u32) -> c_int;
+    // several key columns, column 0 the most significant (include/rsx.h, "several key columns")
+    pub fn rsx_lexsort_device(ctx: *mut RsxCtx, cols: *const RsxKeyColumn, ncols: u32, d_index: *mut c_void, n: usize,
+                              index_bytes: u32, stream: *mut c_void) -> c_int;
+    pub fn rsx_sort_columns_device(ctx: *mut RsxCtx, cols: *const RsxKeyColumn, ncols: u32, d_values: *mut c_void,
+                                   value_bytes: u32, n: usize, stream: *mut c_void) -> c_int;
+    pub fn rsx_ctx_reserve_lex(ctx: *mut RsxCtx, n: usize, cols: *const RsxKeyColumn, ncols: u32, value_bytes: u32) -> c_int;
+    pub fn rsx_lex_plan(cols: *const RsxKeyColumn, ncols: u32, rounds: *mut u32, first_col: *mut u32, key_bytes: *mut u32,
+                        elem_bytes: *mut u32) -> c_int;
     pub fn rsx_sort_sharded(ctxs: *const *mut RsxCtx, ndev: u32, d_slices: *const *mut c_void,
                             d_tmps: *const *mut c_void, n_per_dev: *const usize,
                             layout: *const RsxLayout) -> c_int;
