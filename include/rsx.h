@@ -122,7 +122,7 @@ int rsx_ctx_reserve(rsx_ctx *ctx, size_t n, const rsx_layout *layout);
 int rsx_ctx_check(rsx_ctx *ctx, void *stream);
 /* Alternative code paths of the sweep kernel; every one gives the same bytes (they exist as
  * fall-backs that the library selects itself when a device self-test fails, and are exposed so
- * that callers and tests can force them). */
+ * that callers and tests can force them).  RSX_OPT_HOST_CHUNK is the one option of the host path. */
 enum {
     RSX_OPT_TILE_SCHEDULE = 1, /* 0 (default): static tile assignment behind a start-up roll call, tickets if
                                   it fails; 1: ticketed tiles always */
@@ -161,12 +161,18 @@ enum {
                                   that still agree, by the digits skipped; 0: every pass */
     RSX_OPT_BUCKET_GROUP = 14, /* the hybrid on arrays whose 16-bit buckets are small (8-byte and wider keys): 1 (default)
                                   a workgroup sorts a group of consecutive buckets as one array; 0: bucket by bucket */
-    RSX_OPT_BUCKET_DIRECT = 15 /* the hybrid's buckets of key-only elements of 8 and 16 bytes (the key is the whole element:
+    RSX_OPT_BUCKET_DIRECT = 15,/* the hybrid's buckets of key-only elements of 8 and 16 bytes (the key is the whole element:
                                   u64, i64, f64, u128 -- equal elements are the same bytes): 1 (default) one unstable
                                   counting pass in LDS and an exact rank among neighbours, buckets of few distinct keys
                                   left to the stable passes; 0: the stable passes always.  Same bytes either way.
                                   No effect where groups of small buckets are on offer (RSX_OPT_BUCKET_GROUP: arrays up to
                                   about 2^26 8-byte / 2^25 16-byte elements): those sorts keep to the stable passes. */
+    RSX_OPT_HOST_CHUNK = 16    /* rsx_sort_host: the bytes of one piece of its copy pipeline, a multiple of 4096 in
+                                  4096 .. 33554432 (32 MiB, the default; anything else is RSX_ERR_ARG and leaves the value
+                                  as it was).  The four pinned buffers of the ring keep their 32 MiB whatever the value:
+                                  a smaller one only shortens the pieces.  Same bytes at every value; exposed so that
+                                  tests reach the ring's slot reuse, the short last piece and the drain of the copy
+                                  back with arrays of a few KB instead of hundreds of MB. */
 };
 int rsx_ctx_set_option(rsx_ctx *ctx, int option, uint64_t value);
 enum {

@@ -34,7 +34,7 @@ GEN_UNIFORM, GEN_ZIPF, GEN_STEP, GEN_SORTED, GEN_REVERSED, GEN_CONSTANT, GEN_GEO
 GEN_PAYLOAD_ZERO = 0x100
 (OPT_TILE_SCHEDULE, OPT_RANKING, OPT_STATUS_SCOPE, OPT_XCD_MAJOR, OPT_BYTE_COUNTING, OPT_MAX_REGIONS, OPT_HOT_LANES,
  OPT_VERBOSE, OPT_RANK_CHECK, OPT_SMALL_SORT, OPT_MID_SORT, OPT_WIDE_SORT, OPT_BUCKET_SKIP, OPT_BUCKET_GROUP,
- OPT_BUCKET_DIRECT) = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15
+ OPT_BUCKET_DIRECT, OPT_HOST_CHUNK) = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16
 INFO_RANK_ATOMIC, INFO_L2_LOCAL, INFO_NUM_CU, INFO_DEVICE, INFO_LAST_PASSES, INFO_LAST_PAIRS, INFO_LAST_DIRECT, INFO_LAST_LEX = 1, 2, 3, 4, 5, 6, 7, 8
 ORDER_ASCENDING, ORDER_DESCENDING = 0, 1
 REDUCE_SUM, REDUCE_MIN, REDUCE_MAX = 0, 1, 2

@@ -943,6 +943,11 @@ int rsx_ctx_set_option(rsx_ctx* ctx, int option, uint64_t value) try {
             if (value > 1) return fail(ctx, RSX_ERR_ARG, "RSX_OPT_BUCKET_DIRECT: 0 or 1");
             ctx->bucket_direct = (uint32_t)value;
             return RSX_OK;
+        case RSX_OPT_HOST_CHUNK:
+            if (value < 4096 || value > (uint64_t)HOST_CHUNK || value % 4096)
+                return fail(ctx, RSX_ERR_ARG, "RSX_OPT_HOST_CHUNK: a multiple of 4096 in 4096 .. 32 MiB");
+            ctx->host_chunk = (size_t)value;
+            return RSX_OK;
         case RSX_OPT_MID_SORT:
             if (value > 3) return fail(ctx, RSX_ERR_ARG, "RSX_OPT_MID_SORT: 0 (off), 1 (forecast), 2 (always split) or 3 (always LSD passes)");
             flag(OPT_NO_MID_SORT, value == 0);
@@ -1938,16 +1943,15 @@ int rsx_segment_caps(const rsx_layout* L, uint32_t* caps) {
 // H2D and D2H each on its own stream; the count kernel of pass 0 cannot start before the last
 // chunk, so the sort itself is not overlapped (8 ms of ~150).
 namespace {
-constexpr size_t HOST_CHUNK = 32u << 20;
-constexpr int HOST_RING = 4;
-
 void par_memcpy(char* dst, const char* src, size_t bytes, int threads) {
     if (bytes < (4u << 20) || threads <= 1) {
         std::memcpy(dst, src, bytes);
         return;
     }
     std::vector<std::thread> th;
-    const size_t per = ((bytes / threads) + 4095) & ~(size_t)4095;
+    // bytes / threads rounded UP before it is rounded to 4096: rounded down, threads * per falls short of bytes by
+    // bytes % threads whenever the quotient is a multiple of 4096 (4 MiB + 4 bytes over 8 threads lost its last 4)
+    const size_t per = (((bytes + threads - 1) / threads) + 4095) & ~(size_t)4095;
     for (int t = 0; t < threads; ++t) {
         const size_t off = (size_t)t * per;
         if (off >= bytes) break;
@@ -1965,11 +1969,12 @@ int host_pipeline(rsx_ctx* ctx, char* host, char* dev, size_t bytes, bool to_dev
     if (!ctx->copy_stream) RSX_HIP(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
     hipStream_t cs = ctx->copy_stream;
     const int threads = (int)std::min<unsigned>(8u, std::max(1u, std::thread::hardware_concurrency() / 2));
-    const size_t chunks = (bytes + HOST_CHUNK - 1) / HOST_CHUNK;
+    const size_t chunk = ctx->host_chunk;
+    const size_t chunks = (bytes + chunk - 1) / chunk;
     if (to_device) {
         for (size_t c = 0; c < chunks; ++c) {
             const int slot = (int)(c % HOST_RING);
-            const size_t off = c * HOST_CHUNK, len = std::min(HOST_CHUNK, bytes - off);
+            const size_t off = c * chunk, len = std::min(chunk, bytes - off);
             if (c >= (size_t)HOST_RING) RSX_HIP(hipEventSynchronize(ctx->copy_event[slot]));  // slot's DMA done
             par_memcpy(static_cast<char*>(ctx->pinned[slot]), host + off, len, threads);
             RSX_HIP(hipMemcpyAsync(dev + off, ctx->pinned[slot], len, hipMemcpyHostToDevice, cs));
@@ -1982,13 +1987,13 @@ int host_pipeline(rsx_ctx* ctx, char* host, char* dev, size_t bytes, bool to_dev
             if (c >= (size_t)HOST_RING) {  // drain chunk c - HOST_RING
                 const size_t k = c - HOST_RING;
                 const int slot = (int)(k % HOST_RING);
-                const size_t off = k * HOST_CHUNK, len = std::min(HOST_CHUNK, bytes - off);
+                const size_t off = k * chunk, len = std::min(chunk, bytes - off);
                 RSX_HIP(hipEventSynchronize(ctx->copy_event[slot]));
                 par_memcpy(host + off, static_cast<const char*>(ctx->pinned[slot]), len, threads);
             }
             if (c < chunks) {
                 const int slot = (int)(c % HOST_RING);
-                const size_t off = c * HOST_CHUNK, len = std::min(HOST_CHUNK, bytes - off);
+                const size_t off = c * chunk, len = std::min(chunk, bytes - off);
                 RSX_HIP(hipMemcpyAsync(ctx->pinned[slot], dev + off, len, hipMemcpyDeviceToHost, cs));
                 RSX_HIP(hipEventRecord(ctx->copy_event[slot], cs));
             }

@@ -53,6 +53,9 @@ constexpr size_t AUX_BYTES = OFF_DBG + 1024;
 // words of the host-visible block (rsx_ctx::host_err, 64 bytes): a kernel that gives up a bounded wait sets the first; the
 // second word group holds what the last middle-size sort and the last wide-key try reported, for the host's forecasts
 constexpr uint32_t HV_ERROR = 0, HV_MID_HINT = 8, HV_WIDE_HINT = 9;
+// rsx_sort_host: bytes of one pinned staging buffer -- the largest chunk RSX_OPT_HOST_CHUNK takes, and its default
+constexpr size_t HOST_CHUNK = 32u << 20;
+constexpr int HOST_RING = 4;
 
 // option bits (rsx_ctx_set_option): alternative kernel paths, all bit-exact
 enum : uint32_t {
@@ -84,6 +87,7 @@ struct rsx_ctx {
     size_t host_bytes = 0;
     hipStream_t copy_stream = nullptr;
     void* pinned[4] = {nullptr, nullptr, nullptr, nullptr};  // ring of pinned bounce chunks
+    size_t host_chunk = rsxh::HOST_CHUNK;  // RSX_OPT_HOST_CHUNK: bytes of one piece of the copy pipeline (the buffers keep their size)
     hipEvent_t copy_event[4] = {nullptr, nullptr, nullptr, nullptr};
     uint32_t wide_skip = 0;     // sorts to go without trying the wide-key hybrid (the last try was refused on the device)
     char* wide_buf = nullptr;   // wide-key hybrid: bin totals [65536] u64, bin-block sums [256] u64, bucket starts [65537] u64, verdict u32
