@@ -85,7 +85,8 @@ enum {
  * bounds* and splitter* read the key where it lies, so they take elements of any
  * size (no alignment asked) whose key is 1, 2, 4, 8 or 16 bytes wide, and refuse
  * other key widths with RSX_ERR_ARG; rsx_generate_device and rsx_verify_device
- * take any layout. */
+ * take any layout of up to RSX_MAX_ELEM_BYTES (RSX_ERR_UNSUPPORTED above, as for
+ * the sorts). */
 #define RSX_MAX_ELEM_BYTES 32768u
 typedef struct rsx_layout {
     uint32_t elem_bytes;

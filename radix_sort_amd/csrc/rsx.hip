@@ -2626,6 +2626,7 @@ int rsx_generate_device(rsx_ctx* ctx, void* d_data, size_t n, const rsx_layout* 
                         double param, uint64_t index_base, void* stream) try {
     if (!ctx) return RSX_ERR_ARG;
     if (!layout_ok(L, true)) return fail(ctx, RSX_ERR_ARG, "invalid rsx_layout");
+    if (L->elem_bytes > RSX_MAX_ELEM_BYTES) return fail(ctx, RSX_ERR_UNSUPPORTED, "element larger than RSX_MAX_ELEM_BYTES");
     if (n == 0) return RSX_OK;
     if (!d_data) return fail(ctx, RSX_ERR_ARG, "null pointer");
     const uint32_t payload_zero = (gen & RSX_GEN_PAYLOAD_ZERO) ? 1u : 0u;
@@ -2664,6 +2665,7 @@ int rsx_verify_device(rsx_ctx* ctx, const void* d_data, size_t n, const rsx_layo
                       void* stream) try {
     if (!ctx) return RSX_ERR_ARG;
     if (!layout_ok(L, true)) return fail(ctx, RSX_ERR_ARG, "invalid rsx_layout");
+    if (L->elem_bytes > RSX_MAX_ELEM_BYTES) return fail(ctx, RSX_ERR_UNSUPPORTED, "element larger than RSX_MAX_ELEM_BYTES");
     if (!d_out) return fail(ctx, RSX_ERR_ARG, "null pointer");
     std::lock_guard<std::mutex> lk(ctx->mu);
     DeviceGuard g(ctx->device);

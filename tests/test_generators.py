@@ -42,24 +42,28 @@ def test_restated_generators_have_the_reference_shapes(orc):
     assert (orc.generate(100, u32, orc.GEN_CONSTANT, 0, 77.0).view("<u4") == 77).all()
 
 
+# elements at and near RSX_MAX_ELEM_BYTES: the key in the last 8 bytes, and a 16-byte key at an odd offset
+WIDE_LAYOUTS = [(32768, 32760, 8, util.UNSIGNED), (4097, 1, 16, util.SIGNED)]
+
 GENS = [("GEN_UNIFORM", 0.0), ("GEN_ZIPF", 1.0), ("GEN_STEP", 16.0), ("GEN_SORTED", 0.0), ("GEN_REVERSED", 0.0),
         ("GEN_CONSTANT", 123456.0), ("GEN_GEOMETRIC", 0.001), ("GEN_GEOMETRIC", 0.37)]
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("t", ["u32", "u64", "(u64,u64)", "(u32,u32)", "u128", "u16", "(pay32+u32)"] + util.ANY_LAYOUTS,
+@pytest.mark.parametrize("t", ["u32", "u64", "(u64,u64)", "(u32,u32)", "u128", "u16", "(pay32+u32)"] + util.ANY_LAYOUTS + WIDE_LAYOUTS,
                          ids=lambda t: t if isinstance(t, str) else "any%d-%d-%d" % t[:3])
 @pytest.mark.parametrize("gen,param", GENS)
 def test_device_generators_match_the_restatement(orc, t, gen, param):
-    """Seven layouts with sort kernels of their own and four without (6-, 7-, 40- and 100-byte elements, keys of 2, 6, 8
-    and 16 bytes at offsets 0, 1, 0 and 36): rsx_generate_device takes any layout."""
+    """Seven layouts with sort kernels of their own and six without (6-, 7-, 40-, 100-, 4097- and 32768-byte elements,
+    keys of 2, 6, 8, 16, 16 and 8 bytes at offsets 0, 1, 0, 36, 1 and 32760): rsx_generate_device takes any layout.  The
+    two wide ones at 1031 elements (32 MiB of 32768-byte elements; more than the 256 threads of one workgroup)."""
     import torch
     import radix_sort_amd as rs
     ctx = rs.default_context(torch.cuda.current_device())
     tup = util.TYPES[t] if isinstance(t, str) else t
     d = rs.RadixDigits(*tup)
     lay = orc.Layout(*tup)
-    n, base = 300007, 5_000_000_000  # index_base beyond 2^32: 64-bit indices
+    n, base = (300007 if tup[0] <= 100 else 1031), 5_000_000_000  # index_base beyond 2^32: 64-bit indices
     for pz in (False, True):
         x = torch.empty(n * d.elem_bytes, dtype=torch.uint8, device="cuda")
         g = getattr(rs, gen) | (rs.GEN_PAYLOAD_ZERO if pz else 0)

@@ -173,6 +173,17 @@ def test_large_n_on_the_device(rs, torch, ctx, lay):
         _device_check(rs, torch, ctx, lay, 1 << 24, gen, param, need_stable=lay[0] - lay[2] >= 3)
 
 
+def test_route_1_past_2pow32_bytes(rs, torch):
+    """The packed re-layout and its restore with byte offsets beyond 32 bits: 7-byte elements, 2^32 + 86415 bytes."""
+    c = rs.Context(torch.cuda.current_device())
+    lay, n = (7, 1, 6, S), 2 ** 32 // 7 + 12345
+    assert n * 7 > 2 ** 32
+    _device_check(rs, torch, c, lay, n, rs.GEN_UNIFORM, need_stable=False)  # (one payload byte: the index wraps)
+    assert route_of(c, rs) == 1
+    c.close()
+    torch.cuda.empty_cache()
+
+
 @pytest.mark.parametrize("lay", [(40, 0, 8, U), (20, 0, 4, U), (6, 0, 2, U), (7, 0, 6, U), (7, 1, 6, S), (100, 36, 16, U),
                                  (48, 4, 4, F), (5, 0, 3, S)])
 def test_stability(rs, torch, ctx, orc, lay):
@@ -280,8 +291,10 @@ def test_direct_parity_of_the_inner_layouts(rs, torch, ctx, orc, inner):
 
 def test_still_rejected(rs, torch, ctx):
     lib = ctx._L
-    x = torch.zeros(4096, dtype=torch.uint8, device="cuda")
-    t = torch.zeros(4096, dtype=torch.uint8, device="cuda")
+    # descending bytes in the array and another fill in the scratch: a sort or a copy that did get enqueued shows
+    x = (255 - torch.arange(4096, device="cuda") % 256).to(torch.uint8)
+    t = torch.full((4096,), 0x3C, dtype=torch.uint8, device="cuda")
+    x0, t0 = x.clone(), t.clone()
     p, q = x.data_ptr(), t.data_ptr()
 
     def sort(es, ko, kb, kind, n=100):
@@ -294,8 +307,13 @@ def test_still_rejected(rs, torch, ctx):
     assert sort(6, 3, 4, U) == rs._lib.ERR_ARG
     assert sort(0, 0, 1, U) == rs._lib.ERR_ARG
     assert sort(40000, 0, 8, U, n=0) == rs._lib.ERR_UNSUPPORTED
+    assert sort(32769, 0, 8, U, n=0) == rs._lib.ERR_UNSUPPORTED  # RSX_MAX_ELEM_BYTES + 1, with and without elements
+    assert sort(32769, 32761, 8, S, n=1) == rs._lib.ERR_UNSUPPORTED
+    assert b"RSX_MAX_ELEM_BYTES" in lib.rsx_last_error(ctx._h)
     lay = rs._lib.Layout(6, 0, 2, U)
     assert lib.rsx_ctx_reserve(ctx._h, 10, ctypes.byref(rs._lib.Layout(6, 0, 17, U))) == rs._lib.ERR_ARG
+    assert lib.rsx_ctx_reserve(ctx._h, 10, ctypes.byref(rs._lib.Layout(32769, 0, 8, U))) == rs._lib.ERR_UNSUPPORTED
+    assert lib.rsx_ctx_reserve(ctx._h, 2, ctypes.byref(rs._lib.Layout(32768, 0, 8, U))) == 0
     h = torch.zeros(256 * 8, dtype=torch.uint8, device="cuda")
     assert lib.rsx_histogram_device(ctx._h, p, 100, ctypes.byref(lay), 0, h.data_ptr(), None) == rs._lib.ERR_UNSUPPORTED
     assert lib.rsx_partition_device(ctx._h, p, q, 100, ctypes.byref(lay), 0, None, None) == rs._lib.ERR_UNSUPPORTED
@@ -303,6 +321,8 @@ def test_still_rejected(rs, torch, ctx):
     assert lib.rsx_partition_device(ctx._h, p, q, 100, ctypes.byref(lay6), 0, None, None) == rs._lib.ERR_ARG
     with pytest.raises(rs.RsxError):
         rs.radix_sort_sharded([x[:600]], rs.RadixDigits(6, 0, 2, U), ctxs=[ctx])
+    torch.cuda.synchronize()
+    assert torch.equal(x, x0) and torch.equal(t, t0)  # no refusal enqueued anything
 
 
 def test_flat_byte_buffer_needs_the_element_shape(rs, torch, ctx, orc):

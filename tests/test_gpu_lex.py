@@ -370,6 +370,7 @@ def test_refusals_with_a_context(rs, torch, ctx):
     assert L.rsx_sort_columns_device(h, col, 2, None, 0, 2 ** 32, st) == rs._lib.ERR_UNSUPPORTED
     assert L.rsx_sort_columns_device(h, col, 2, None, 4, 64, st) == rs._lib.ERR_ARG
     assert L.rsx_sort_columns_device(h, col, 2, out.data_ptr(), 32769, 64, st) == rs._lib.ERR_ARG
+    assert L.rsx_ctx_reserve_lex(h, 64, col, 2, 32769) == rs._lib.ERR_ARG
     bad = (rs._lib.KeyColumn * 2)(rs._lib.KeyColumn(t.data_ptr(), 4, 1, 0, 0), rs._lib.KeyColumn(t.data_ptr(), 4, 1, 0, 5))
     assert L.rsx_lexsort_device(h, bad, 2, out.data_ptr(), 64, 8, st) == rs._lib.ERR_ARG  # reserved
     bad[1] = rs._lib.KeyColumn(t.data_ptr(), 3, 0, 0, 0)

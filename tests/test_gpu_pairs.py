@@ -220,6 +220,8 @@ def test_bad_arguments_on_the_device(rs, torch, ctx):
     assert L.rsx_argsort_device(h, k.data_ptr(), None, 64, 4, 0, 8, 0, None) == E
     assert L.rsx_argsort_device(h, k.data_ptr(), v.data_ptr() + 4, 32, 4, 0, 8, 0, None) == E
     assert L.rsx_ctx_reserve_pairs(h, 64, 5, 4) == E
+    assert L.rsx_ctx_reserve_pairs(h, 64, 4, 32769) == E  # value width
+    assert L.rsx_ctx_reserve_pairs(h, 2, 4, 32768) == 0
     assert L.rsx_sort_pairs_device(h, None, None, 0, 4, 0, 0, 0, None) == 0  # nothing to sort
     torch.cuda.synchronize()
     assert not k.any() and not v.any()

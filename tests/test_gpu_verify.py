@@ -92,6 +92,26 @@ def test_small_sizes(rs, torch, ctx, orc, name, lay):
             _check(torch, ctx, rs, orc, _input(name, lay, n, dist, seed=300 + n), lay, (name, n, dist))
 
 
+def test_elements_of_32768_bytes(rs, torch, ctx, orc):
+    """RSX_MAX_ELEM_BYTES: 600 elements of 32768 random bytes (the checksum chain runs over every one of them), the key in
+    the first 8 and the index behind it, unsorted and sorted, at offset 0 and three bytes in."""
+    lay = (32768, 0, 8, U)
+    n = 600
+    rng = np.random.default_rng(32768)
+    raw = rng.integers(0, 256, size=(n, 32768), dtype=np.uint8)
+    raw[:, 0:8] = util._key_ints("step16", n, 8, rng)
+    raw[:, 8:16] = np.arange(n, dtype="<u8").view(np.uint8).reshape(n, 8)
+    raw = raw.reshape(-1)
+    srt = orc.sort_parallel(raw, orc.Layout(*lay), 4)
+    w = _check(torch, ctx, rs, orc, raw, lay, "32768 unsorted")
+    s = _check(torch, ctx, rs, orc, srt, lay, "32768 sorted", offset=3)
+    assert w[0] > n // 4 and s[0] == 0 and s[2] == 0 and s[1] == w[1]
+    bad = srt.copy()
+    bad[-1] ^= 0x80  # the last byte of the last element: only that element's hash moves
+    moved = (s[1] - util.element_hash_int(srt[-32768:]) + util.element_hash_int(bad[-32768:])) & ((1 << 64) - 1)
+    assert moved != s[1] and _device_words(torch, ctx, rs, bad, lay) == (0, moved, 0)
+
+
 @pytest.mark.parametrize("name", ["u32", "f64", "(u64,u64)", "(u128,u128)", "any7-1-6"])
 def test_sizes_above_the_grid_cap(rs, torch, ctx, orc, stride, name):
     """More elements than the largest grid has threads: the grid-stride loop takes a second and a third turn; one
