@@ -195,6 +195,8 @@ enum {
                                  8 groups of equal keys (rsx_unique_device: bits 0-7 are then the kernels launched
                                  after the sort of the joined elements, and bits 8-23 are 0),
                                  9 reduce by key (rsx_reduce_by_key_device: bits 0-7 and 8-23 as for path 8),
+                                 10 search (rsx_search_sorted_device: bits 0-7 are then the kernels launched after
+                                 any sort of the needles, bit 8 is set when they were sorted first, bits 9-23 are 0),
                                  bits 28-29 the route of a layout without kernels of its own: 0 direct, 1 packed
                                  re-layout, 2 key-index proxy (bits 0-27 then describe the sort of the re-laid-out
                                  elements / of the proxies) */
@@ -486,6 +488,50 @@ int rsx_ctx_reserve_reduce(rsx_ctx *ctx, size_t n, uint32_t key_bytes, uint32_t 
 /* Host-only, needs no device: *tile = the elements one workgroup of the run kernels takes for these widths (256 threads,
  * each a whole number of 16-byte words), *scan_span = the tiles one sweep of the scan kernel's loop takes. */
 int rsx_reduce_caps(uint32_t key_bytes, uint32_t value_bytes, uint32_t *tile, uint32_t *scan_span);
+
+/* -- bounds of many needles in a sorted key array ---------------------------- */
+/* The other thing callers do with a sorted array: look keys up in it (searchsorted / bucketize, membership, the probe side
+ * of a sort-merge join against the keys rsx_unique_device leaves on the device).  Let M be the key mapping of
+ * rsx_argsort_device for (key_bytes, key_kind), complemented when `order` is descending (floats by the total order on bit
+ * patterns), and N = n, or min(n, *d_sorted_num) when that pointer is given: it is read on the device, so the d_out_num of
+ * rsx_unique_device can be passed without a host read.  PRECONDITION: M(d_sorted[j]) is non-decreasing for j < N -- what
+ * rsx_sort_device, rsx_sort_pairs_device and rsx_unique_device produce in that `order`.  For every needle i < m:
+ *     d_out_lower[i] = #{ j < N : M(d_sorted[j]) <  M(d_needles[i]) }
+ *     d_out_upper[i] = #{ j < N : M(d_sorted[j]) <= M(d_needles[i]) }
+ * so d_sorted[lower[i] .. upper[i]) are exactly the keys equal to needle i in every bit.  Either output may be NULL, not
+ * both.  Indices are index_bytes (4 or 8) wide; with 4, n >= 2^32 is RSX_ERR_ARG.  Key widths, kinds and alignments are
+ * those of rsx_argsort_device (1, 2, 4, 8, 16 bytes); the outputs are aligned to index_bytes, d_sorted_num to 8.  The inputs
+ * are only read; nothing outside the m-entry outputs and the context's workspace is written.  If the precondition does not
+ * hold, every output is still in [0, N] and no byte outside the arrays is read; nothing else is promised.  m == 0 launches
+ * nothing and looks at no pointer.  N == 0 gives zeros (n == 0: stream-ordered memsets, no kernel).  Stream-ordered, no
+ * synchronisation; the host reads nothing.  RSX_ERR_ARG: bad widths, kinds, order, index_bytes or alignments, NULL inputs
+ * with n or m > 0, both outputs NULL, unknown flag bits.
+ *
+ * One kernel, one workgroup per tile of `tile` consecutive needles (rsx_search_caps): it reduces the smallest and largest
+ * mapped key of the tile, finds lo = lower(smallest) and hi = upper(largest) in the whole haystack by a cooperative 64-ary
+ * search (one wave each, a probe per lane and round), and, when hi - lo <= `window`, stages the mapped keys of
+ * d_sorted[lo .. hi) in LDS, where every needle does its two binary searches; otherwise every needle searches [lo, hi) in
+ * global memory.  Every answer of the tile lies in [lo, hi] whatever the order of the needles: their order decides how
+ * narrow the window is, never the result.  No workgroup waits for another one, there are no atomics.  Weak spot: a run of
+ * equal keys in d_sorted longer than `window` sends its tiles to the global searches even when the needles are ordered.
+ *
+ * The route is the caller's choice.  flags == 0, the needles as given: the streaming merge when the needles are ordered
+ * or clustered, a binary search per needle when they are scattered; no workspace, so the call can be captured once the
+ * context has made its first call.  RSX_SEARCH_PRESORT: the needles are joined with their positions (the join of
+ * rsx_argsort_device) and sorted in the context's pairs workspace, the same kernel reads the sorted elements and stores
+ * at out[position]; m >= 2^32 is RSX_ERR_UNSUPPORTED; the workspace is made on first use or by rsx_ctx_reserve_search, and
+ * under capture without a sufficient reserve the call returns RSX_ERR_WORKSPACE and enqueues nothing.
+ * RSX_INFO_LAST_PASSES reports path 10. */
+enum { RSX_SEARCH_PRESORT = 1 };
+int rsx_search_sorted_device(rsx_ctx *ctx, const void *d_sorted, size_t n, const uint64_t *d_sorted_num,
+                             const void *d_needles, size_t m, uint32_t key_bytes, uint32_t key_kind, int order,
+                             void *d_out_lower, void *d_out_upper, uint32_t index_bytes, uint32_t flags, void *stream);
+/* Workspace (and the context's first-call set-up) of the RSX_SEARCH_PRESORT route for up to m needles of this width, so
+ * that the call allocates nothing (stream capture). */
+int rsx_ctx_reserve_search(rsx_ctx *ctx, size_t m, uint32_t key_bytes);
+/* Host-only, needs no device: *tile = the needles one workgroup takes, *window = the most haystack keys it stages in LDS
+ * (window >= 2 * tile; window * key_bytes leaves more than two workgroups per CU).  Both routes run the same shape. */
+int rsx_search_caps(uint32_t key_bytes, int with_positions, uint32_t *tile, uint32_t *window);
 
 /* -- several key columns ----------------------------------------------------- */
 /* Sorting a table by (a, b descending, c): ncols key columns of n keys each, column 0 the MOST significant (the opposite

@@ -23,6 +23,7 @@ SYMBOLS = [
     "rsx_unique_device", "rsx_ctx_reserve_unique", "rsx_unique_caps",
     "rsx_reduce_by_key_device", "rsx_ctx_reserve_reduce", "rsx_reduce_caps",
     "rsx_lexsort_device", "rsx_sort_columns_device", "rsx_ctx_reserve_lex", "rsx_lex_plan",
+    "rsx_search_sorted_device", "rsx_ctx_reserve_search", "rsx_search_caps",
 ]
 SEG_CLASSES = 2  # RSX_SEG_CLASSES
 LEX_MAX_COLUMNS = 16  # RSX_LEX_MAX_COLUMNS
@@ -38,6 +39,7 @@ GEN_PAYLOAD_ZERO = 0x100
 INFO_RANK_ATOMIC, INFO_L2_LOCAL, INFO_NUM_CU, INFO_DEVICE, INFO_LAST_PASSES, INFO_LAST_PAIRS, INFO_LAST_DIRECT, INFO_LAST_LEX = 1, 2, 3, 4, 5, 6, 7, 8
 ORDER_ASCENDING, ORDER_DESCENDING = 0, 1
 REDUCE_SUM, REDUCE_MIN, REDUCE_MAX = 0, 1, 2
+SEARCH_PRESORT = 1
 SHARD_EXCHANGE_FIRST, SHARD_SORT_FIRST = 0, 1
 
 
@@ -152,6 +154,9 @@ def load():
     L.rsx_sort_columns_device.argtypes = [vp, kc, u32, vp, u32, sz, vp]
     L.rsx_ctx_reserve_lex.argtypes = [vp, sz, kc, u32, u32]
     L.rsx_lex_plan.argtypes = [kc, u32, pu32, pu32, pu32, pu32]
+    L.rsx_search_sorted_device.argtypes = [vp, vp, sz, vp, vp, sz, u32, u32, i, vp, vp, u32, u32, vp]
+    L.rsx_ctx_reserve_search.argtypes = [vp, sz, u32]
+    L.rsx_search_caps.argtypes = [u32, i, pu32, pu32]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("rsx_last_error", "rsx_strerror"):

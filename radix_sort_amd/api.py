@@ -309,6 +309,20 @@ class Context:
                                               d_out_offsets or None, d_out_perm or None, d_out_inverse or None, index_bytes,
                                               d_out_num or None, stream))
 
+    def reserve_search(self, m: int, key_bytes: int):
+        """rsx_ctx_reserve_search: the context's first-call set-up and the workspace of search_sorted_device with
+        SEARCH_PRESORT on up to m needles of this width, so that the call allocates nothing and can be captured."""
+        self._check(self._L.rsx_ctx_reserve_search(self._h, m, key_bytes))
+
+    def search_sorted_device(self, d_sorted: int, n: int, d_needles: int, m: int, key_bytes: int, key_kind: int, d_out_lower: int,
+                             d_out_upper: int, index_bytes: int, descending: bool = False, d_sorted_num: int = 0, flags: int = 0,
+                             stream: int = 0):
+        """rsx_search_sorted_device: for each of m needles the number of the first n (or min(n, *d_sorted_num)) sorted keys
+        that order before it (d_out_lower) and that do not order behind it (d_out_upper); either output may be 0."""
+        self._check(self._L.rsx_search_sorted_device(self._h, d_sorted or None, n, d_sorted_num or None, d_needles or None, m, key_bytes,
+                                                     key_kind, 1 if descending else 0, d_out_lower or None, d_out_upper or None,
+                                                     index_bytes, flags, stream))
+
     def reserve_reduce(self, n: int, key_bytes: int, value_bytes: int):
         """rsx_ctx_reserve_reduce: the context's first-call set-up and the workspace of reduce_by_key_device on up to n keys
         of these widths, so that the call allocates nothing and can be captured."""
@@ -1078,6 +1092,111 @@ def radix_unique(keys, return_inverse: bool = False, return_counts: bool = False
     if return_counts:
         out += (g.offsets[1:m + 1] - g.offsets[:m],)
     return out if len(out) > 1 else out[0]
+
+
+def search_caps(key_bytes: int, with_positions: bool = False):
+    """rsx_search_caps -> (tile, window): the needles one workgroup of the search kernel takes and the most sorted keys it
+    stages in LDS for this key width.  Needs no device."""
+    L = _lib.load()
+    tile, window = ctypes.c_uint32(), ctypes.c_uint32()
+    rc = L.rsx_search_caps(key_bytes, 1 if with_positions else 0, ctypes.byref(tile), ctypes.byref(window))
+    if rc != 0:
+        raise RsxError(rc, L.rsx_strerror(rc).decode())
+    return int(tile.value), int(window.value)
+
+
+def _search_presort(n: int, m: int, key_bytes: int) -> bool:
+    """presort=None of radix_searchsorted: sort the needles first?  The rule of DESIGN.md section 5 ("Search"), which cannot
+    see whether the needles are ordered: from 2^19 needles on, in a haystack of 512 MiB or more -- where scattered needles
+    measured 1.3 (2^19) to 6 times (m = n) faster sorted first, and ordered ones up to 3.6 times slower.  Callers who know
+    their needles are ordered (both sides of a join out of this library) pass presort=False."""
+    return m >= 1 << 19 and n * key_bytes >= 1 << 29
+
+
+def radix_searchsorted(sorted_keys, needles, side: str = "left", descending: bool = False, out=None, index_dtype=None,
+                       sorted_num=None, presort: Optional[bool] = None, ctx: Optional[Context] = None, key_kind: Optional[int] = None):
+    """Where every needle falls in `sorted_keys` (rsx_search_sorted_device), like `torch.searchsorted(sorted_keys, needles,
+    right=...)`: side="left" gives, per needle, the number of sorted keys that order before it, side="right" the number
+    that do not order behind it, side="both" the tuple (left, right), so that sorted_keys[left:right] are the keys equal
+    to the needle.  The result has the needles' shape and index_dtype (torch.int64, the default, or torch.int32), or is
+    `out` (for "both": a pair), contiguous int32 or int64 tensors of that shape on the same device.
+
+    sorted_keys: a contiguous 1-D GPU tensor of a dtype radix_sort knows, or (n, 16) uint8 128-bit keys (key_kind=), in the
+       order radix_sort / radix_sort_pairs(descending=descending) / radix_group leave: the total order on bit patterns
+       (-NaN below -inf, -0.0 below +0.0, +NaN above +inf), not torch's.  Only its first min(n, sorted_num) keys count
+       when sorted_num is given: a one-element int64 device tensor such as radix_group(...).num, read on the device.
+    needles: a contiguous tensor of any shape, the same dtype and device (128-bit keys: shape (..., 16)).
+    presort: sort the needles first (True), take them as given (False), or decide from the sizes (None: sorted first
+       from 2^19 needles on in a haystack of 512 MiB or more).  The result is the same; needles that are ordered or
+       clustered run at streaming speed as given, so pass presort=False for those.
+
+    Enqueued on the current stream, not synchronised."""
+    import torch
+    kb, kind, n = _pairs_keys(sorted_keys, key_kind)
+    if not isinstance(needles, torch.Tensor):
+        raise TypeError("needles must be a torch tensor on a GPU")
+    if needles.dtype != sorted_keys.dtype:
+        raise TypeError(f"needles must have the dtype of sorted_keys ({sorted_keys.dtype}), not {needles.dtype}")
+    if needles.device != sorted_keys.device:
+        raise ValueError("sorted_keys and needles must live on the same device")
+    if not needles.is_contiguous():
+        raise ValueError("needles must be contiguous")
+    if kb == 16:
+        if needles.dim() < 1 or needles.shape[-1] != 16:
+            raise ValueError("needles of 128-bit keys must have shape (..., 16)")
+        shape = tuple(needles.shape[:-1])
+    else:
+        shape = tuple(needles.shape)
+    if side not in ("left", "right", "both"):
+        raise ValueError(f'side must be "left", "right" or "both", not {side!r}')
+    outs = out if side == "both" and out is not None else (out,)
+    if side == "both" and out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
+        raise TypeError('out must be a pair of tensors for side="both"')
+    for o in outs:
+        _index_out(o, shape, "the needles")
+        if o is not None and o.device != sorted_keys.device:
+            raise ValueError("sorted_keys and out must live on the same device")
+    if out is not None:
+        if len({o.dtype for o in outs}) != 1:
+            raise TypeError("both tensors of out must have one dtype")
+        index_dtype = outs[0].dtype
+    elif index_dtype is None:
+        index_dtype = torch.int64
+    if index_dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"index_dtype must be torch.int32 or torch.int64, not {index_dtype}")
+    if sorted_num is not None:
+        if not isinstance(sorted_num, torch.Tensor) or sorted_num.dtype != torch.int64 or sorted_num.numel() != 1:
+            raise TypeError("sorted_num must be a one-element int64 tensor")
+        if sorted_num.device != sorted_keys.device:
+            raise ValueError("sorted_keys and sorted_num must live on the same device")
+    _pairs_device(sorted_keys, None, "")
+    if index_dtype == torch.int32 and n >= 1 << 32:
+        raise ValueError("2^32 or more sorted keys need int64 indices")
+    m = 1
+    for d in shape:
+        m *= d
+    want_lower, want_upper = side in ("left", "both"), side in ("right", "both")
+    if out is None:
+        lower = torch.empty(shape, dtype=index_dtype, device=needles.device) if want_lower else None
+        upper = torch.empty(shape, dtype=index_dtype, device=needles.device) if want_upper else None
+    else:
+        lower = outs[0] if want_lower else None
+        upper = outs[-1] if want_upper else None
+    if m > 0:
+        if presort is None:
+            presort = _search_presort(n, m, kb)
+        dev = sorted_keys.device.index if sorted_keys.device.index is not None else torch.cuda.current_device()
+        c = ctx or default_context(dev)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            c.search_sorted_device(sorted_keys.data_ptr() if n else 0, n, needles.data_ptr(), m, kb, kind,
+                                   lower.data_ptr() if want_lower else 0, upper.data_ptr() if want_upper else 0,
+                                   8 if index_dtype == torch.int64 else 4, descending,
+                                   sorted_num.data_ptr() if sorted_num is not None else 0,
+                                   _lib.SEARCH_PRESORT if presort and m < 1 << 32 else 0, stream)
+    if side == "both":
+        return lower, upper
+    return lower if want_lower else upper
 
 
 def _segments_common(keys, offsets, max_seg_len):

@@ -978,6 +978,10 @@ int rsx_ctx_get_info(rsx_ctx* ctx, int what, uint64_t* out) try {
                 *out = (uint64_t)(ctx->last_sort_passes & 0xFFu) | (uint64_t)ctx->last_path << 24;
                 return RSX_OK;
             }
+            if (ctx->last_path == 10) {  // search: bits 0-7 the kernels launched after any sort, bit 8 the needles were sorted first
+                *out = (uint64_t)(ctx->last_sort_passes & 0x1FFu) | (uint64_t)ctx->last_path << 24;
+                return RSX_OK;
+            }
             *out = (uint64_t)ctx->last_path << 24 | (uint64_t)ctx->last_route << 28;
             if (!ctx->aux || ctx->last_sort_passes == 0) return RSX_OK;
             if (ctx->busy) RSX_HIP(hipEventSynchronize(ctx->last_event));
@@ -1576,6 +1580,120 @@ int rsx_unique_caps(uint32_t key_bytes, int with_positions, uint32_t* tile, uint
     if (!tile || !scan_span || !key_widths_ok(key_bytes, RSX_KEY_UNSIGNED)) return RSX_ERR_ARG;
     *tile = unique_tile_elems(key_bytes, with_positions != 0);
     *scan_span = unique_scan_span();
+    return RSX_OK;
+}
+
+// ---- bounds of many needles in a sorted key array (rsx_search_kernels.hpp, include/rsx.h) ----
+namespace {
+// the presort route's workspace: the two arrays of joined (mapped key, u32 position) elements of the m needles
+int reserve_search_one(rsx_ctx* ctx, size_t m, uint32_t kb, hipStream_t st) { return reserve_pairs_one(ctx, m, kb, 4, st); }
+}  // namespace
+
+int rsx_search_sorted_device(rsx_ctx* ctx, const void* d_sorted, size_t n, const uint64_t* d_sorted_num, const void* d_needles, size_t m,
+                             uint32_t key_bytes, uint32_t key_kind, int order, void* d_out_lower, void* d_out_upper, uint32_t index_bytes,
+                             uint32_t flags, void* stream) try {
+    if (!ctx) return RSX_ERR_ARG;
+    if (!key_widths_ok(key_bytes, key_kind)) return fail(ctx, RSX_ERR_ARG, "invalid key width or kind");
+    if (order != RSX_ORDER_ASCENDING && order != RSX_ORDER_DESCENDING) return fail(ctx, RSX_ERR_ARG, "invalid order");
+    if (index_bytes != 4 && index_bytes != 8) return fail(ctx, RSX_ERR_ARG, "index_bytes must be 4 or 8");
+    if (flags & ~(uint32_t)RSX_SEARCH_PRESORT) return fail(ctx, RSX_ERR_ARG, "unknown flag bits");
+    if (index_bytes == 4 && (uint64_t)n >= (1ull << 32)) return fail(ctx, RSX_ERR_ARG, "2^32 or more sorted keys need 8-byte indices");
+    const bool presort = (flags & RSX_SEARCH_PRESORT) != 0;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (m == 0) {  // nothing asked: no pointer is looked at
+        ctx->last_path = 10;
+        ctx->last_route = 0;
+        ctx->last_sort_passes = 0;
+        return RSX_OK;
+    }
+    if (!d_out_lower && !d_out_upper) return fail(ctx, RSX_ERR_ARG, "d_out_lower and d_out_upper are both null");
+    if (!d_needles || (n > 0 && !d_sorted)) return fail(ctx, RSX_ERR_ARG, "null device pointer");
+    if (!aligned(d_sorted, key_bytes) || !aligned(d_needles, key_bytes) || !aligned(d_sorted_num, 8) || !aligned(d_out_lower, index_bytes) ||
+        !aligned(d_out_upper, index_bytes))
+        return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
+    if (presort && (uint64_t)m >= (1ull << 32)) return fail(ctx, RSX_ERR_UNSUPPORTED, "2^32 or more needles to sort first");
+    if (((uint64_t)m + search_tile_elems(key_bytes) - 1) / search_tile_elems(key_bytes) >= (1ull << 31)) return fail(ctx, RSX_ERR_UNSUPPORTED, "too many needles for one launch");
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return fail(ctx, RSX_ERR_NODEVICE, "hipSetDevice failed");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (n == 0) {  // an empty haystack: every count is zero
+        if (d_out_lower) RSX_HIP(hipMemsetAsync(d_out_lower, 0, m * (size_t)index_bytes, st));
+        if (d_out_upper) RSX_HIP(hipMemsetAsync(d_out_upper, 0, m * (size_t)index_bytes, st));
+        ctx->last_path = 10;
+        ctx->last_route = 0;
+        ctx->last_sort_passes = 0;
+        return RSX_OK;
+    }
+    int rc = pending_error(ctx);
+    if (rc) return rc;
+    const uint32_t desc = order == RSX_ORDER_DESCENDING ? 1u : 0u;
+    SearchCall c{};
+    c.sorted = d_sorted;
+    c.n = n;
+    c.sorted_num = d_sorted_num;
+    c.needles = d_needles;
+    c.m = m;
+    c.kb = key_bytes;
+    c.kind = key_kind;
+    c.desc = desc;
+    c.pos = presort;
+    c.ib = index_bytes;
+    c.out_lower = d_out_lower;
+    c.out_upper = d_out_upper;
+    uint32_t launched = 0;
+    if (!presort) {  // the needles as given: one launch, no workspace
+        rc = ensure_aux(ctx, st);
+        if (rc) return rc;
+        Enqueue enq(ctx, st);
+        rc = launch_search(ctx, c, &launched, st);
+        if (rc) return rc;
+        ctx->last_path = 10;
+        ctx->last_route = 0;
+        ctx->last_sort_passes = launched;
+        return RSX_OK;
+    }
+    const PairsPlan P = pairs_plan(m, key_bytes, 4);
+    if (P.route != 1 || !launchers_for(P.inner.elem_bytes)) return fail(ctx, RSX_ERR_INTERNAL, "no joined element for this key width");
+    rc = reserve_search_one(ctx, m, key_bytes, st);
+    if (rc) return rc;
+    Enqueue enq(ctx, st);  // the workspace arrays belong to this call from the first launch on
+    char* w0 = ctx->any_buf;
+    char* w1 = w0 + P.half;
+    rc = launch_pairs_join(ctx, d_needles, nullptr, w0, m, key_bytes, 4, true, key_kind, desc, st);
+    if (rc) return rc;
+    if (m > 1) {
+        rc = sort_device_locked(ctx, w0, w1, m, &P.inner, st);
+        if (rc) return rc;
+    }
+    c.needles = w0;
+    rc = launch_search(ctx, c, &launched, st);
+    if (rc) return rc;
+    ctx->last_pairs = 1u | P.inner.elem_bytes << 8;
+    ctx->last_path = 10;
+    ctx->last_route = 0;
+    ctx->last_sort_passes = launched | 0x100u;
+    return RSX_OK;
+} catch (...) {
+    return RSX_ERR_HIP;
+}
+
+int rsx_ctx_reserve_search(rsx_ctx* ctx, size_t m, uint32_t key_bytes) try {
+    if (!ctx) return RSX_ERR_ARG;
+    if (!key_widths_ok(key_bytes, RSX_KEY_UNSIGNED)) return fail(ctx, RSX_ERR_ARG, "invalid key width");
+    if ((uint64_t)m >= (1ull << 32)) return fail(ctx, RSX_ERR_UNSUPPORTED, "2^32 or more needles to sort first");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return fail(ctx, RSX_ERR_NODEVICE, "hipSetDevice failed");
+    return reserve_search_one(ctx, m, key_bytes, nullptr);
+} catch (...) {
+    return RSX_ERR_NOMEM;
+}
+
+int rsx_search_caps(uint32_t key_bytes, int with_positions, uint32_t* tile, uint32_t* window) {
+    (void)with_positions;  // both routes run one tile shape
+    if (!tile || !window || !key_widths_ok(key_bytes, RSX_KEY_UNSIGNED)) return RSX_ERR_ARG;
+    *tile = search_tile_elems(key_bytes);
+    *window = search_window_elems(key_bytes);
     return RSX_OK;
 }
 

@@ -530,4 +530,21 @@ int launch_reduce(rsx_ctx* ctx, const ReduceCall& call, uint32_t* launched, hipS
 uint32_t reduce_tile_elems(uint32_t kb, uint32_t vb);  // elements per workgroup of the count and write kernels
 uint32_t reduce_scan_span();                           // tiles per sweep of the scan kernel's loop
 
+// What one rsx_search_sorted_device call asks of the search kernel (rsx_search.hip, rsx_search_kernels.hpp).
+struct SearchCall {
+    const void* sorted;          // n keys of kb bytes, sorted by mapped key in the call's order
+    size_t n;
+    const uint64_t* sorted_num;  // null, or one device word: only the first min(n, *sorted_num) keys count
+    const void* needles;         // m keys as given (pos false) or m sorted joined (mapped key, u32 position) elements
+    size_t m;
+    uint32_t kb, kind, desc;
+    bool pos;
+    uint32_t ib;                 // bytes of an index in out_lower / out_upper
+    void* out_lower;             // either may be null
+    void* out_upper;
+};
+int launch_search(rsx_ctx* ctx, const SearchCall& call, uint32_t* launched, hipStream_t st);
+uint32_t search_tile_elems(uint32_t kb);     // needles per workgroup
+uint32_t search_window_elems(uint32_t kb);  // haystack keys a workgroup stages in LDS at most
+
 }  // namespace rsxh

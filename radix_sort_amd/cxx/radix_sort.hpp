@@ -15,6 +15,7 @@
 //     rsx::radix_argsort(const K* d_keys, I* d_index, size_t n, bool descending, hipStream_t)
 //     rsx::unique(const K* d_keys, size_t n, K* keys, uint64_t* offsets, I* perm, I* inverse, uint64_t* num, bool descending, hipStream_t)
 //     rsx::reduce_by_key(const K* d_keys, const V* d_values, size_t n, int op, K* keys, V* values, uint64_t* offsets, uint64_t* num, bool descending, hipStream_t)
+//     rsx::search_sorted(const K* d_sorted, size_t n, const K* d_needles, size_t m, I* lower, I* upper, bool descending, const uint64_t* d_sorted_num, bool presort, hipStream_t)
 //     rsx::lexsort({rsx::key_column(d_a), rsx::key_column(d_b, true)}, I* d_index, size_t n, hipStream_t)   // several key columns
 //     rsx::sort_columns({rsx::key_column(d_a), rsx::key_column(d_b, true)}, V* d_values, size_t n, hipStream_t)
 // Errors: the reference panics (mod.rs:68,106); here std::runtime_error is thrown.
@@ -251,6 +252,24 @@ void reduce_by_key(const K* d_keys, const V* d_values, size_t n, int op, K* d_ou
                                        descending ? RSX_ORDER_DESCENDING : RSX_ORDER_ASCENDING, d_out_keys, d_out_values, d_out_offsets,
                                        d_out_num, stream),
               "rsx_reduce_by_key_device");
+}
+
+// Where m needles fall in n keys sorted in that order (rsx_search_sorted_device): d_out_lower[i] the number of the sorted
+// keys that order before needle i, d_out_upper[i] the number that do not order behind it, so that
+// d_sorted[lower[i] .. upper[i]) are the keys equal to it in every bit.  Either output may be nullptr.  d_sorted_num, when
+// given, is one device word (the d_out_num of unique): only the first min(n, *d_sorted_num) keys count.  presort: sort the
+// needles first (RSX_SEARCH_PRESORT; rsx_ctx_reserve_search before a stream capture) instead of taking them as given,
+// which is the streaming merge for ordered needles.  Both arrays are only read.  Stream-ordered, never synchronised.
+template <typename K, typename I = uint64_t>
+void search_sorted(const K* d_sorted, size_t n, const K* d_needles, size_t m, I* d_out_lower, I* d_out_upper, bool descending = false,
+                   const uint64_t* d_sorted_num = nullptr, bool presort = false, void* stream = nullptr, Context& ctx = default_context()) {
+    static_assert(std::is_integral<I>::value && (sizeof(I) == 4 || sizeof(I) == 8), "indices are 4- or 8-byte integers");
+    const rsx_layout L = RadixDigits<K>::layout();
+    if (L.key_offset != 0 || L.key_bytes != L.elem_bytes) throw std::invalid_argument("search_sorted: the key type must be its own key");
+    ctx.check(rsx_search_sorted_device(ctx.get(), d_sorted, n, d_sorted_num, d_needles, m, L.key_bytes, L.key_kind,
+                                       descending ? RSX_ORDER_DESCENDING : RSX_ORDER_ASCENDING, d_out_lower, d_out_upper, (uint32_t)sizeof(I),
+                                       presort ? (uint32_t)RSX_SEARCH_PRESORT : 0u, stream),
+              "rsx_search_sorted_device");
 }
 
 // Several key columns (rsx_lexsort_device, rsx_sort_columns_device): rows sorted by (column 0, column 1, ...), column 0

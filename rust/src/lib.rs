@@ -68,6 +68,14 @@ extern "C" {
     pub fn rsx_ctx_reserve_lex(ctx: *mut RsxCtx, n: usize, cols: *const RsxKeyColumn, ncols: u32, value_bytes: u32) -> c_int;
     pub fn rsx_lex_plan(cols: *const RsxKeyColumn, ncols: u32, rounds: *mut u32, first_col: *mut u32, key_bytes: *mut u32,
                         elem_bytes: *mut u32) -> c_int;
+    // lower and upper bounds of m needles in n sorted keys (include/rsx.h, "bounds of many needles in a sorted key
+    // array"); flags: 0 the needles as given, 1 sort them first (RSX_SEARCH_PRESORT); either output may be null
+    pub fn rsx_search_sorted_device(ctx: *mut RsxCtx, d_sorted: *const c_void, n: usize, d_sorted_num: *const u64,
+                                    d_needles: *const c_void, m: usize, key_bytes: u32, key_kind: u32, order: c_int,
+                                    d_out_lower: *mut c_void, d_out_upper: *mut c_void, index_bytes: u32, flags: u32,
+                                    stream: *mut c_void) -> c_int;
+    pub fn rsx_ctx_reserve_search(ctx: *mut RsxCtx, m: usize, key_bytes: u32) -> c_int;
+    pub fn rsx_search_caps(key_bytes: u32, with_positions: c_int, tile: *mut u32, window: *mut u32) -> c_int;
     pub fn rsx_sort_sharded(ctxs: *const *mut RsxCtx, ndev: u32, d_slices: *const *mut c_void,
                             d_tmps: *const *mut c_void, n_per_dev: *const usize,
                             layout: *const RsxLayout) -> c_int;
