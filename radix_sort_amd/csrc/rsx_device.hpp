@@ -343,6 +343,22 @@ struct WidePlan {
 #ifndef RSX_HIST_UNROLL
 #define RSX_HIST_UNROLL 1  // more loads in flight per thread measured slower (0.217 -> 0.228 ms per 2^28 u32 at 4)
 #endif
+// rsx_count16top_kernel starts behind a sort as well (8- and 16-byte elements): its chunk in 16-byte words
+// (RSX_COUNT16_VEC; 0 = one element per load), with the streaming hint (RSX_COUNT16_NT), RSX_COUNT16_UNROLL of them in
+// flight per thread.  2^30 u64: 1.59 ms with 8-byte plain loads, 1.42 with 16-byte plain ones, 1.37 streaming
+// (4 in flight: the same bytes per CU as before; 8: the same time, 2: 1.44).
+#ifndef RSX_COUNT16_VEC
+#define RSX_COUNT16_VEC 1
+#endif
+#ifndef RSX_COUNT16_NT
+#define RSX_COUNT16_NT 1
+#endif
+#ifndef RSX_COUNT16_NT_BYTES
+#define RSX_COUNT16_NT_BYTES (256ull << 20)  // the memory-side cache
+#endif
+#ifndef RSX_COUNT16_UNROLL
+#define RSX_COUNT16_UNROLL 4
+#endif
 // What a sort's first count kernel does on its way (one launch instead of four):
 __device__ __forceinline__ void count_side_jobs(const RegionGeom& g, unsigned long long* __restrict__ jclear, uint4* __restrict__ zero16,
                                                 uint64_t zero16_n, const CleanList& clean) {

@@ -287,6 +287,7 @@ __global__ __launch_bounds__(1024) void rsx_wideplan_kernel(const Elem<ES>* __re
 // shares): a workgroup then stays inside ONE region of the sweeps' geometry, and the count matrix of the first sweep
 // (the window's low digit, per region) is a marginal of these counters -- rsx_marginal16_kernel reads
 // them back (32 MiB) instead of a count kernel reading the array again (1.37 ms of 21 on 2^30 u64).
+// 8- and 16-byte elements are read in 16-byte words, streaming from 256 MiB on (RSX_COUNT16_* in rsx_device.hpp).
 template <int ES, bool MAP>
 __global__ __launch_bounds__(1024) void rsx_count16top_kernel(const Elem<ES>* __restrict__ src, uint64_t n, WidePlan* __restrict__ plan, KeyXform xf,
                                                               uint32_t* __restrict__ P, uint32_t* __restrict__ ovf, uint32_t region_shift,
@@ -332,6 +333,60 @@ __global__ __launch_bounds__(1024) void rsx_count16top_kernel(const Elem<ES>* __
     };
     constexpr int UNR = ES <= 8 ? 8 : ES <= 16 ? 4 : 2;  // loads in flight per thread (one workgroup per CU: 16 waves)
     uint64_t i = p0 + tid;
+    if constexpr (RSX_COUNT16_VEC != 0 && (ES == 8 || ES == 16)) {
+        // Order inside a chunk does not matter for a count, its membership does: the chunk [p0, p1) is read in 16-byte
+        // words with the streaming hint (as rsx_hist_kernel reads its region), two 8-byte elements or one 16-byte
+        // element each.  The C-ABI promises element alignment only, the multi-GPU drivers pass interior pointers and p0
+        // may be odd: an 8-byte element ahead of the chunk's first 16-byte boundary and an odd one at its end are
+        // counted one by one, and a chunk whose elements do not lie on multiples of their size takes the loop below.
+        typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+        constexpr uint32_t VEC = 16 / ES;
+        constexpr int VU = RSX_COUNT16_UNROLL;  // 16-byte loads in flight per thread
+        static_assert(VU >= 1 && VU <= 16, "RSX_COUNT16_UNROLL");
+        const uintptr_t addr = reinterpret_cast<uintptr_t>(src) + p0 * ES;  // (the same in every lane)
+        if (p0 < p1 && (addr & (uintptr_t)(ES - 1)) == 0) {
+            const uint64_t head = (addr & 15u) != 0 ? 1u : 0u;  // (8-byte elements only: the other size has none here)
+            const uint64_t nvec = (p1 - p0 - head) / VEC;
+            const v4u* vsrc = reinterpret_cast<const v4u*>(src + p0 + head);
+            // (the streaming hint from RSX_COUNT16_NT_BYTES on: a smaller array is still in the memory-side cache when the
+            // first sweep reads it again, and stays there only under plain loads; the same for every thread of the launch)
+            const bool stream = RSX_COUNT16_NT != 0 && n * (uint64_t)ES >= (uint64_t)RSX_COUNT16_NT_BYTES;
+            auto count_word = [&](const v4u& v) {
+                if constexpr (ES == 8) {
+                    Elem<ES> a, b;
+                    a.w[0] = v.x, a.w[1] = v.y, b.w[0] = v.z, b.w[1] = v.w;
+                    count(a);
+                    count(b);
+                } else {
+                    Elem<ES> a;
+                    a.w[0] = v.x, a.w[1] = v.y, a.w[2] = v.z, a.w[3] = v.w;
+                    count(a);
+                }
+            };
+            auto words = [&](auto nt) {  // (one copy of the loops per kind of load: no test between the loads of a round)
+                auto load = [&](uint64_t j) -> v4u {
+                    if constexpr (decltype(nt)::value) return __builtin_nontemporal_load(vsrc + j);
+                    else return vsrc[j];
+                };
+                uint64_t j = tid;
+                for (; j + (uint64_t)(VU - 1) * 1024u < nvec; j += (uint64_t)VU * 1024u) {
+                    v4u v[VU];
+#pragma unroll
+                    for (int u = 0; u < VU; ++u) v[u] = load(j + (uint64_t)u * 1024u);
+#pragma unroll
+                    for (int u = 0; u < VU; ++u) count_word(v[u]);
+                }
+                for (; j < nvec; j += 1024u) count_word(load(j));
+            };
+            if (stream) words(std::true_type{});
+            else words(std::false_type{});
+            if constexpr (ES == 8) {  // the element ahead of the first word and the one behind the last: wave 0 / wave 1
+                if (tid == 0 && head != 0) count(src[p0]);
+                if (tid == 64 && p0 + head + nvec * VEC < p1) count(src[p1 - 1]);
+            }
+            i = p1;
+        }
+    }
     for (; i + (uint64_t)(UNR - 1) * 1024u < p1; i += (uint64_t)UNR * 1024u) {
         Elem<ES> e[UNR];
 #pragma unroll

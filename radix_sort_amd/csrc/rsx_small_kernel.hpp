@@ -873,6 +873,10 @@ __global__ __launch_bounds__(WG, RSX_B16_WAVES(WG)) void rsx_bucket16_medium_ker
 #ifndef RSX_DIRECT_PACKED
 #define RSX_DIRECT_PACKED 1
 #endif
+// (RSX_DIRECT_LOAD16=0: one 8-byte element per global load of the bucket, the form before, for A/B builds.)
+#ifndef RSX_DIRECT_LOAD16
+#define RSX_DIRECT_LOAD16 1
+#endif
 constexpr uint32_t DIRECT_LIMIT = 24;
 template <int WG>
 __host__ __device__ constexpr uint32_t direct_bits() {
@@ -1022,8 +1026,32 @@ __global__ __launch_bounds__(WG, RSX_B16_WAVES(WG)) void rsx_bucket16_direct_ker
         E* bucket = static_cast<E*>(a.data) + start;
         reinterpret_cast<uint4*>(s_cnt)[tid] = uint4{0u, 0u, 0u, 0u};
         E e[KPT];
+        // 8-byte elements, 512 and 1024 threads: a thread takes KPT / 2 16-byte words of two neighbours each (and an odd
+        // KPT's last element by itself).  A bucket starts on an 8-byte boundary only; gfx950 takes 16-byte loads at that
+        // alignment.  (The 256-thread form, three workgroups per CU, measured slower with them: 2^27 u64 1.79 -> 1.81 ms.)
+        constexpr bool LOAD16 = RSX_DIRECT_LOAD16 != 0 && ES == 8 && WG >= 512;
+        constexpr int NPAIR = LOAD16 ? KPT / 2 : 0;
+        auto pos_of = [&](const int j) -> uint32_t {  // which element of the bucket e[j] is
+            if (j < 2 * NPAIR) return 2u * ((uint32_t)(j >> 1) * WG + tid) + (uint32_t)(j & 1);
+            return (uint32_t)j * WG + tid;
+        };
+        if constexpr (LOAD16) {
+            typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+            typedef v4u v4u_a8 __attribute__((aligned(8)));
 #pragma unroll
-        for (int j = 0; j < KPT; ++j) {  // plain store order: nothing rests on which thread holds what
+            for (int jj = 0; jj < NPAIR; ++jj) {  // (two ifs, no else: the loads of all rounds stay in flight together)
+                const uint32_t i = pos_of(2 * jj);
+                e[2 * jj] = E{};
+                e[2 * jj + 1] = E{};
+                if (i + 1u < n) {
+                    const v4u v = *reinterpret_cast<const v4u_a8*>(bucket + i);
+                    e[2 * jj].w[0] = v.x, e[2 * jj].w[1] = v.y, e[2 * jj + 1].w[0] = v.z, e[2 * jj + 1].w[1] = v.w;
+                }
+                if (i + 1u == n) e[2 * jj] = bucket[i];  // the bucket's last element, alone in its word
+            }
+        }
+#pragma unroll
+        for (int j = 2 * NPAIR; j < KPT; ++j) {  // plain store order: nothing rests on which thread holds what
             const uint32_t i = (uint32_t)j * WG + tid;
             e[j] = E{};
             if (i < n) e[j] = bucket[i];
@@ -1033,7 +1061,7 @@ __global__ __launch_bounds__(WG, RSX_B16_WAVES(WG)) void rsx_bucket16_direct_ker
 #pragma unroll
         for (int j = 0; j < KPT; ++j) {
             rk[j] = 0;
-            if ((uint32_t)j * WG + tid < n) {
+            if (pos_of(j) < n) {
                 const uint32_t d = digit_of(e[j]);
                 if constexpr (PACKED) {
                     const uint32_t sh = (d & 1u) << 4;
@@ -1079,7 +1107,7 @@ __global__ __launch_bounds__(WG, RSX_B16_WAVES(WG)) void rsx_bucket16_direct_ker
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < KPT; ++j)
-            if ((uint32_t)j * WG + tid < n) s[start_of(digit_of(e[j])) + rk[j]] = e[j];
+            if (pos_of(j) < n) s[start_of(digit_of(e[j])) + rk[j]] = e[j];
         __syncthreads();
         // the exact rank, one 16-byte word of the tile per thread and round
         const uint32_t words = (n + G - 1) / G;
