@@ -111,8 +111,7 @@ class Context:
         self._L = _lib.load()
         h = ctypes.c_void_p()
         rc = self._L.rsx_ctx_create(device, ctypes.byref(h))
-        if rc != 0:
-            raise RsxError(rc, self._L.rsx_strerror(rc).decode())
+        _check_rc(self._L, rc)
         self._h = h
 
     def _check(self, rc: int):
@@ -408,6 +407,47 @@ def _check_element_stated(shape, itemsize: int, d: RadixDigits):
                    f"array whose dtype or last dimension is the {d.elem_bytes}-byte element")
 
 
+class _on_device:
+    """`with _on_device(t, ctx) as (c, stream):` -- a call on the GPU tensor `t`: its device selected, c = ctx or that
+    device's default context, stream = the handle of the device's current stream.  (A class, not a generator under
+    contextlib.contextmanager: that costs 1.5 us a call, which a sort of 2^16 keys shows.)"""
+    __slots__ = ("_c", "_dev", "_guard", "_torch")
+
+    def __init__(self, t, ctx: Optional[Context]):
+        import torch
+        self._dev = t.device.index if t.device.index is not None else torch.cuda.current_device()
+        self._c = ctx or default_context(self._dev)
+        self._guard = torch.cuda.device(self._dev)
+        self._torch = torch
+
+    def __enter__(self):
+        self._guard.__enter__()
+        try:
+            return self._c, self._torch.cuda.current_stream(self._dev).cuda_stream
+        except BaseException:
+            self._guard.__exit__(None, None, None)
+            raise
+
+    def __exit__(self, *exc):
+        return self._guard.__exit__(*exc)
+
+
+def _check_rc(L, rc: int):
+    """Raises what a call that takes no context returned, unless it is 0."""
+    if rc != 0:
+        raise RsxError(rc, L.rsx_strerror(rc).decode())
+
+
+def _index_dtype(index_dtype):
+    """The index_dtype argument of a call that makes its index tensors: torch.int64 unless torch.int32 is asked for."""
+    import torch
+    if index_dtype is None:
+        index_dtype = torch.int64
+    if index_dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"index_dtype must be torch.int32 or torch.int64, not {index_dtype}")
+    return index_dtype
+
+
 def radix_sort(x, digits: Optional[RadixDigits] = None, tmp=None, ctx: Optional[Context] = None):
     """`<[T]>::radix_sort(&mut self)` (mod.rs:62): sorts `x` in place and returns None.
 
@@ -448,16 +488,13 @@ def radix_sort(x, digits: Optional[RadixDigits] = None, tmp=None, ctx: Optional[
         c = ctx or default_context(-1)
         c.sort_host(x.data_ptr(), n, d)
         return None
-    dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
-    c = ctx or default_context(dev)
-    if n <= 1:
-        return None
-    if tmp is None:
-        tmp = torch.empty_like(x)
-    elif tmp.device != x.device or tmp.numel() * tmp.element_size() < nbytes or not tmp.is_contiguous():
-        raise ValueError("tmp must be a contiguous buffer on the same device, at least as large as x")
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
+    with _on_device(x, ctx) as (c, stream):
+        if n <= 1:
+            return None
+        if tmp is None:
+            tmp = torch.empty_like(x)
+        elif tmp.device != x.device or tmp.numel() * tmp.element_size() < nbytes or not tmp.is_contiguous():
+            raise ValueError("tmp must be a contiguous buffer on the same device, at least as large as x")
         c.sort_device(x.data_ptr(), tmp.data_ptr(), n, d, stream)
     return None
 
@@ -469,8 +506,7 @@ def segment_caps(digits: RadixDigits):
     caps = (ctypes.c_uint32 * _lib.SEG_CLASSES)()
     lay = digits.layout()
     rc = L.rsx_segment_caps(ctypes.byref(lay), caps)
-    if rc != 0:
-        raise RsxError(rc, L.rsx_strerror(rc).decode())
+    _check_rc(L, rc)
     return [int(c) for c in caps]
 
 
@@ -532,12 +568,9 @@ def radix_sort_segments(x, offsets, digits: Optional[RadixDigits] = None, tmp=No
     nseg = offsets.numel() - 1
     if nseg <= 0 or n == 0:
         return None
-    dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
-    c = ctx or default_context(dev)
-    if tmp is None:
-        tmp = torch.empty_like(x)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
+    with _on_device(x, ctx) as (c, stream):
+        if tmp is None:
+            tmp = torch.empty_like(x)
         c.sort_segments_device(x.data_ptr(), tmp.data_ptr(), n, d, offsets.data_ptr(), nseg, max_seg_len, stream)
     return None
 
@@ -560,12 +593,9 @@ def radix_sort_rows(x, digits: Optional[RadixDigits] = None, tmp=None, ctx: Opti
     if row_len <= 1 or n == 0:
         return None
     rows = n // row_len
-    dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
-    c = ctx or default_context(dev)
-    if tmp is None:
-        tmp = torch.empty_like(x)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
+    with _on_device(x, ctx) as (c, stream):
+        if tmp is None:
+            tmp = torch.empty_like(x)
         c.sort_rows_device(x.data_ptr(), tmp.data_ptr(), rows, row_len, d, stream)
     return None
 
@@ -628,10 +658,7 @@ def radix_sort_pairs(keys, values, descending: bool = False, ctx: Optional[Conte
     _pairs_device(keys, values, "values")
     if n <= 1:
         return None
-    dev = keys.device.index if keys.device.index is not None else torch.cuda.current_device()
-    c = ctx or default_context(dev)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
+    with _on_device(keys, ctx) as (c, stream):
         c.sort_pairs_device(keys.data_ptr(), values.data_ptr() if values is not None else 0, n, kb, kind, vb, descending, stream)
     return None
 
@@ -657,10 +684,7 @@ def radix_argsort(keys, descending: bool = False, out=None, ctx: Optional[Contex
         out = torch.empty(n, dtype=torch.int64, device=keys.device)
     if n == 0:
         return out
-    dev = keys.device.index if keys.device.index is not None else torch.cuda.current_device()
-    c = ctx or default_context(dev)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
+    with _on_device(keys, ctx) as (c, stream):
         c.argsort_device(keys.data_ptr(), out.data_ptr(), n, kb, kind, out.element_size(), descending, stream)
     return out
 
@@ -678,8 +702,7 @@ def lex_plan(specs):
     rounds = ctypes.c_uint32()
     first, kbs, ebs = ((ctypes.c_uint32 * _lib.LEX_MAX_COLUMNS)() for _ in range(3))
     rc = L.rsx_lex_plan(arr, len(specs), ctypes.byref(rounds), first, kbs, ebs)
-    if rc != 0:
-        raise RsxError(rc, L.rsx_strerror(rc).decode())
+    _check_rc(L, rc)
     return [(int(first[r]), int(kbs[r]), int(ebs[r])) for r in range(rounds.value)]
 
 
@@ -746,10 +769,7 @@ def radix_lexsort(columns, descending=False, out=None, ctx: Optional[Context] = 
         out = torch.empty(n, dtype=torch.int64, device=keys.device)
     if n == 0:
         return out
-    dev = keys.device.index if keys.device.index is not None else torch.cuda.current_device()
-    c = ctx or default_context(dev)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
+    with _on_device(keys, ctx) as (c, stream):
         c.lexsort_device([(t.data_ptr(), kb, kind, d) for t, kb, kind, d in cols], out.data_ptr(), n, out.element_size(), stream)
     return out
 
@@ -762,17 +782,13 @@ def radix_sort_columns(columns, values=None, descending=False, ctx: Optional[Con
     columns, descending: as in radix_lexsort; THE COLUMNS ARE WRITTEN.  values: as in radix_sort_pairs, a contiguous GPU
     tensor on the same device with one row of 1 .. 32768 bytes per key, moved bitwise; None: the columns alone.  Columns
     that share memory with each other or with values are undefined.  Enqueued on the current stream, not synchronised."""
-    import torch
     cols, n = _lex_columns(columns, descending)
     vb = _value_bytes(values, (n,), "the columns")
     _lex_device(cols, values, "values")
     keys = cols[0][0]
     if n <= 1:
         return None
-    dev = keys.device.index if keys.device.index is not None else torch.cuda.current_device()
-    c = ctx or default_context(dev)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
+    with _on_device(keys, ctx) as (c, stream):
         c.sort_columns_device([(t.data_ptr(), kb, kind, d) for t, kb, kind, d in cols], values.data_ptr() if values is not None else 0,
                               vb, n, stream)
     return None
@@ -784,8 +800,7 @@ def segment_pairs_caps(key_bytes: int, value_bytes: int):
     L = _lib.load()
     caps = (ctypes.c_uint32 * _lib.SEG_CLASSES)()
     rc = L.rsx_segment_pairs_caps(key_bytes, value_bytes, caps)
-    if rc != 0:
-        raise RsxError(rc, L.rsx_strerror(rc).decode())
+    _check_rc(L, rc)
     return [int(c) for c in caps]
 
 
@@ -846,16 +861,12 @@ def radix_sort_rows_pairs(keys, values, descending: bool = False, ctx: Optional[
     The order is radix_sort_pairs' (a total order on bit patterns, stable in both directions).  Values of 1, 2, 4, 8 or 16
     bytes stay in registers and LDS with their keys; wider ones are gathered through a copy in the context's workspace.
     Rows above segment_pairs_caps(key_bytes, value_bytes)[-1] are sorted through memory or row by row: slow."""
-    import torch
     kb, kind, rows, row_len = _rows_keys(keys)
     vb = _value_bytes(values, keys.shape, "keys")
     _pairs_device(keys, values, "values")
     if rows == 0 or row_len <= 1:
         return None
-    dev = keys.device.index if keys.device.index is not None else torch.cuda.current_device()
-    c = ctx or default_context(dev)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
+    with _on_device(keys, ctx) as (c, stream):
         c.sort_rows_pairs_device(keys.data_ptr(), values.data_ptr() if values is not None else 0, rows, row_len, kb, kind, vb,
                                  descending, stream)
     return None
@@ -873,10 +884,7 @@ def radix_argsort_rows(keys, descending: bool = False, out=None, ctx: Optional[C
         out = torch.empty(keys.shape, dtype=torch.int64, device=keys.device)
     if rows == 0 or row_len == 0:
         return out
-    dev = keys.device.index if keys.device.index is not None else torch.cuda.current_device()
-    c = ctx or default_context(dev)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
+    with _on_device(keys, ctx) as (c, stream):
         c.argsort_rows_device(keys.data_ptr(), out.data_ptr(), rows, row_len, kb, kind, out.element_size(), descending, stream)
     return out
 
@@ -888,8 +896,7 @@ def topk_caps(key_bytes: int):
     caps = (ctypes.c_uint32 * _lib.SEG_CLASSES)()
     max_k = ctypes.c_uint32()
     rc = L.rsx_topk_caps(key_bytes, caps, ctypes.byref(max_k))
-    if rc != 0:
-        raise RsxError(rc, L.rsx_strerror(rc).decode())
+    _check_rc(L, rc)
     return [int(c) for c in caps], int(max_k.value)
 
 
@@ -917,29 +924,23 @@ def radix_topk(keys, k: int, largest: bool = True, index_dtype=None, ctx: Option
     k = operator.index(k)
     if k < 0 or k > row_len:
         raise ValueError(f"k must be in 0 .. {row_len} (the last dimension), not {k}")
-    if index_dtype is None:
-        index_dtype = torch.int64
-    if index_dtype not in (torch.int32, torch.int64):
-        raise ValueError(f"index_dtype must be torch.int32 or torch.int64, not {index_dtype}")
+    index_dtype = _index_dtype(index_dtype)
     _pairs_device(keys, None, "")
     shape = tuple(keys.shape[:-1]) + (k,)
     values = torch.empty(shape, dtype=keys.dtype, device=keys.device)
     indices = torch.empty(shape, dtype=index_dtype, device=keys.device)
     if rows == 0 or k == 0:
         return values, indices
-    dev = keys.device.index if keys.device.index is not None else torch.cuda.current_device()
-    c = ctx or default_context(dev)
-    caps, max_k = topk_caps(kb)
-    if (row_len > caps[-1] and k > max_k) or _topk_by_sort(rows, row_len, k, kb):
-        full = radix_argsort_rows(keys, descending=largest, ctx=c)
-        first = full[..., :k]
-        indices.copy_(first)
-        # (a gather of the raw bits: dtypes torch cannot index, uint32 / uint64, go as their signed twins)
-        bits = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[kb]
-        values.view(bits).copy_(torch.gather(keys.view(bits), -1, first))
-        return values, indices
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
+    with _on_device(keys, ctx) as (c, stream):
+        caps, max_k = topk_caps(kb)
+        if (row_len > caps[-1] and k > max_k) or _topk_by_sort(rows, row_len, k, kb):
+            full = radix_argsort_rows(keys, descending=largest, ctx=c)
+            first = full[..., :k]
+            indices.copy_(first)
+            # (a gather of the raw bits: dtypes torch cannot index, uint32 / uint64, go as their signed twins)
+            bits = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[kb]
+            values.view(bits).copy_(torch.gather(keys.view(bits), -1, first))
+            return values, indices
         c.topk_rows_device(keys.data_ptr(), values.data_ptr(), indices.data_ptr(), rows, row_len, k, kb, kind,
                            indices.element_size(), largest, stream)
     return values, indices
@@ -951,8 +952,7 @@ def unique_caps(key_bytes: int, with_positions: bool = True):
     L = _lib.load()
     tile, span = ctypes.c_uint32(), ctypes.c_uint32()
     rc = L.rsx_unique_caps(key_bytes, 1 if with_positions else 0, ctypes.byref(tile), ctypes.byref(span))
-    if rc != 0:
-        raise RsxError(rc, L.rsx_strerror(rc).decode())
+    _check_rc(L, rc)
     return int(tile.value), int(span.value)
 
 
@@ -978,10 +978,7 @@ def radix_group(keys, descending: bool = False, perm: bool = True, inverse: bool
     of different payloads too.  With perm=False and inverse=False the keys are sorted alone, without positions."""
     import torch
     kb, kind, n = _pairs_keys(keys, key_kind)
-    if index_dtype is None:
-        index_dtype = torch.int64
-    if index_dtype not in (torch.int32, torch.int64):
-        raise ValueError(f"index_dtype must be torch.int32 or torch.int64, not {index_dtype}")
+    index_dtype = _index_dtype(index_dtype)
     _pairs_device(keys, None, "")
     if n >= 1 << 32:
         raise ValueError("radix_group takes fewer than 2^32 keys")
@@ -990,10 +987,7 @@ def radix_group(keys, descending: bool = False, perm: bool = True, inverse: bool
     offsets = torch.empty(n + 1, dtype=torch.int64, device=keys.device)
     out_perm = torch.empty(n, dtype=index_dtype, device=keys.device) if perm else None
     out_inverse = torch.empty(n, dtype=index_dtype, device=keys.device) if inverse else None
-    dev = keys.device.index if keys.device.index is not None else torch.cuda.current_device()
-    c = ctx or default_context(dev)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
+    with _on_device(keys, ctx) as (c, stream):
         c.unique_device(keys.data_ptr(), n, kb, kind, out_keys.data_ptr(), offsets.data_ptr(),
                         out_perm.data_ptr() if perm else 0, out_inverse.data_ptr() if inverse else 0,
                         8 if index_dtype == torch.int64 else 4, num.data_ptr(), descending, stream)
@@ -1006,8 +1000,7 @@ def reduce_caps(key_bytes: int, value_bytes: int):
     L = _lib.load()
     tile, span = ctypes.c_uint32(), ctypes.c_uint32()
     rc = L.rsx_reduce_caps(key_bytes, value_bytes, ctypes.byref(tile), ctypes.byref(span))
-    if rc != 0:
-        raise RsxError(rc, L.rsx_strerror(rc).decode())
+    _check_rc(L, rc)
     return int(tile.value), int(span.value)
 
 
@@ -1067,10 +1060,7 @@ def radix_reduce_by_key(keys, values, op: str = "sum", descending: bool = False,
         if offsets:
             out_offsets.zero_()
         return Reduced(num, out_keys, out_values, out_offsets)
-    dev = keys.device.index if keys.device.index is not None else torch.cuda.current_device()
-    c = ctx or default_context(dev)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
+    with _on_device(keys, ctx) as (c, stream):
         c.reduce_by_key_device(keys.data_ptr(), values.data_ptr(), n, kb, kind, vt[0], vt[1], _REDUCE_OPS[op], out_keys.data_ptr(),
                                out_values.data_ptr(), out_offsets.data_ptr() if offsets else 0, num.data_ptr(), descending, stream)
     return Reduced(num, out_keys, out_values, out_offsets)
@@ -1100,8 +1090,7 @@ def search_caps(key_bytes: int, with_positions: bool = False):
     L = _lib.load()
     tile, window = ctypes.c_uint32(), ctypes.c_uint32()
     rc = L.rsx_search_caps(key_bytes, 1 if with_positions else 0, ctypes.byref(tile), ctypes.byref(window))
-    if rc != 0:
-        raise RsxError(rc, L.rsx_strerror(rc).decode())
+    _check_rc(L, rc)
     return int(tile.value), int(window.value)
 
 
@@ -1160,10 +1149,7 @@ def radix_searchsorted(sorted_keys, needles, side: str = "left", descending: boo
         if len({o.dtype for o in outs}) != 1:
             raise TypeError("both tensors of out must have one dtype")
         index_dtype = outs[0].dtype
-    elif index_dtype is None:
-        index_dtype = torch.int64
-    if index_dtype not in (torch.int32, torch.int64):
-        raise ValueError(f"index_dtype must be torch.int32 or torch.int64, not {index_dtype}")
+    index_dtype = _index_dtype(index_dtype)
     if sorted_num is not None:
         if not isinstance(sorted_num, torch.Tensor) or sorted_num.dtype != torch.int64 or sorted_num.numel() != 1:
             raise TypeError("sorted_num must be a one-element int64 tensor")
@@ -1185,10 +1171,7 @@ def radix_searchsorted(sorted_keys, needles, side: str = "left", descending: boo
     if m > 0:
         if presort is None:
             presort = _search_presort(n, m, kb)
-        dev = sorted_keys.device.index if sorted_keys.device.index is not None else torch.cuda.current_device()
-        c = ctx or default_context(dev)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
+        with _on_device(sorted_keys, ctx) as (c, stream):
             c.search_sorted_device(sorted_keys.data_ptr() if n else 0, n, needles.data_ptr(), m, kb, kind,
                                    lower.data_ptr() if want_lower else 0, upper.data_ptr() if want_upper else 0,
                                    8 if index_dtype == torch.int64 else 4, descending,
@@ -1218,7 +1201,6 @@ def radix_sort_segments_pairs(keys, values, offsets, descending: bool = False, m
     keys: as in radix_sort_pairs (1-D, or (n, 16) uint8 for unsigned 128-bit keys).  values: one row per key, or None.
     offsets, max_seg_len: as in radix_sort_segments; keys and values outside [offsets[0], offsets[-1]) are not touched,
     a bad segment is left as it is and the context's next check() raises."""
-    import torch
     kb, kind, n = _segments_common(keys, offsets, max_seg_len)
     vb = _value_bytes(values, (n,), "one row per key,")
     _pairs_device(keys, values, "values")
@@ -1227,10 +1209,7 @@ def radix_sort_segments_pairs(keys, values, offsets, descending: bool = False, m
     nseg = offsets.numel() - 1
     if nseg <= 0 or n == 0:
         return None
-    dev = keys.device.index if keys.device.index is not None else torch.cuda.current_device()
-    c = ctx or default_context(dev)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
+    with _on_device(keys, ctx) as (c, stream):
         c.sort_segments_pairs_device(keys.data_ptr(), values.data_ptr() if values is not None else 0, n, kb, kind, vb,
                                      offsets.data_ptr(), nseg, descending, max_seg_len, stream)
     return None
@@ -1253,10 +1232,7 @@ def radix_argsort_segments(keys, offsets, descending: bool = False, out=None, ma
     nseg = offsets.numel() - 1
     if nseg <= 0 or n == 0:
         return out
-    dev = keys.device.index if keys.device.index is not None else torch.cuda.current_device()
-    c = ctx or default_context(dev)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
+    with _on_device(keys, ctx) as (c, stream):
         c.argsort_segments_device(keys.data_ptr(), out.data_ptr(), n, kb, kind, out.element_size(), offsets.data_ptr(), nseg,
                                   descending, max_seg_len, stream)
     return out

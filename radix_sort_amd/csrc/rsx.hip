@@ -208,6 +208,36 @@ struct DeviceGuard {
     }
 };
 
+// What an entry point holds from its argument checks to its return: the context's mutex, the context's device as the
+// current one, and the caller's stream.  !ok: the device could not be set (the entries that sort refuse to go on, see
+// no_device; the older ones never looked and still do not).
+struct Entry {
+    std::lock_guard<std::mutex> lk;
+    DeviceGuard dev;
+    const bool ok;
+    const hipStream_t st;
+    explicit Entry(rsx_ctx* ctx, void* stream = nullptr) : lk(ctx->mu), dev(ctx->device), ok(dev.ok), st(static_cast<hipStream_t>(stream)) {}
+};
+int no_device(rsx_ctx* ctx) { return fail(ctx, RSX_ERR_NODEVICE, "hipSetDevice failed"); }
+
+// the checks of an `order` and an `index_bytes` argument
+int order_desc(rsx_ctx* ctx, int order, uint32_t* desc) {
+    if (order != RSX_ORDER_ASCENDING && order != RSX_ORDER_DESCENDING) return fail(ctx, RSX_ERR_ARG, "invalid order");
+    *desc = order == RSX_ORDER_DESCENDING ? 1u : 0u;
+    return RSX_OK;
+}
+int check_index_bytes(rsx_ctx* ctx, uint32_t ib) {
+    if (ib != 4 && ib != 8) return fail(ctx, RSX_ERR_ARG, "index_bytes must be 4 or 8");
+    return RSX_OK;
+}
+
+// what the call being enqueued ran, for RSX_INFO_LAST_PASSES
+void note_path(rsx_ctx* ctx, uint32_t path, uint32_t passes, uint32_t route = 0) {
+    ctx->last_path = path;
+    ctx->last_sort_passes = passes;
+    ctx->last_route = route;
+}
+
 // A kernel of this context gave up a bounded wait (the word is host-visible: no sync needed to see it).
 int pending_error(rsx_ctx* ctx) {
     if (ctx->host_err && host_word(ctx, HV_ERROR))
@@ -279,7 +309,7 @@ int sort_counting16(rsx_ctx* ctx, void* d_data, void* d_tmp, size_t n, const rsx
     hipLaunchKernelGGL(rsx_expand16_kernel, dim3((uint32_t)ctx->num_cu * 8), dim3(256), 0, st, static_cast<uint16_t*>(d_data), (uint64_t)n, tot,
                        BT, xor_mask);
     RSX_HIP(hipGetLastError());
-    ctx->last_path = 4;
+    ctx->last_path = PATH_COUNT16;
     return RSX_OK;
 }
 
@@ -390,7 +420,7 @@ int sort_wide(rsx_ctx* ctx, const EsLaunchers& K, void* d_data, void* d_tmp, siz
     rc = lsd_passes(ctx, K, lsd, d_data, d_tmp, n, L, geom, false, 0, st);
     if (rc) return rc;
     ctx->last_sort_passes = D;
-    ctx->last_path = 5;
+    ctx->last_path = PATH_WIDE;
     end_control(ctx);
     return RSX_OK;
 }
@@ -424,7 +454,7 @@ int sort_mid_split(rsx_ctx* ctx, const EsLaunchers& K, void* d_data, void* d_tmp
     if (rc) return rc;
     rc = K.bucket_sort(ctx, d_tmp, d_data, L, bucket_small, st);  // ... sorted, they land in d_data
     if (rc) return rc;
-    ctx->last_path = 2;
+    ctx->last_path = PATH_MID_SPLIT;
     return RSX_OK;
 }
 
@@ -459,7 +489,7 @@ int sort_counting8(rsx_ctx* ctx, const EsLaunchers& K, void* d_data, size_t n, c
                        L->key_kind == RSX_KEY_SIGNED ? 0x80u : 0u);
     RSX_HIP(hipGetLastError());
     end_control(ctx);
-    ctx->last_path = 3;
+    ctx->last_path = PATH_COUNT8;
     return RSX_OK;
 }
 
@@ -475,12 +505,10 @@ int sort_device_locked(rsx_ctx* ctx, void* d_data, void* d_tmp, size_t n, const 
     const uint32_t D = L->key_bytes;  // T::NUMBER_OF_DIGITS
     const bool general_bytes = (ctx->options & OPT_GENERAL_BYTES) != 0;
     const bool counting8 = L->elem_bytes == 1 && !general_bytes;  // no sweep follows
-    ctx->last_sort_passes = 0;
-    ctx->last_path = 0;
-    ctx->last_route = 0;
+    note_path(ctx, PATH_LSD, 0);
     // at most one tile: all D passes in one launch of one workgroup (rsx_small_kernel.hpp)
     if (!counting8 && n <= (size_t)512 * kpt_for((int)L->elem_bytes) && !(ctx->options & OPT_NO_SMALL_SORT)) {  // one 512-thread tile
-        ctx->last_path = 1;
+        ctx->last_path = PATH_SMALL;
         return K->small_sort(ctx, d_data, n, L, st);
     }
     if (L->elem_bytes == 2 && D == 2 && n >= ((size_t)1 << 23) && !general_bytes && (ctx->ovf16 != nullptr || !capturing(st)))
@@ -557,7 +585,17 @@ AnyMap map_restore(const rsx_layout* L, const AnyPlan& P) {
         m.m[b] = b >= L->elem_bytes ? ANY_ZERO : (b >= ko && b < ko + kb) ? (int16_t)(b - ko) : (int16_t)(P.kw + (b < ko ? b : b - kb));
     return m;
 }
-size_t any_half(size_t n, const AnyPlan& P) { return (n * (size_t)P.inner.elem_bytes + 255) & ~(size_t)255; }
+// Lays the arrays of the second workspace out one behind the other: take() gives the next array's offset, and `bytes`
+// is then what ensure_any is asked for.  A call's plan is made of these, and both its reserve entry and its launches
+// read that one plan.
+struct Carve {
+    size_t bytes;  // (no initialiser: the plans stay plain structs; make it with {})
+    size_t take(size_t b) {
+        const size_t off = bytes;
+        bytes += round256(b);
+        return off;
+    }
+};
 
 int ensure_any(rsx_ctx* ctx, size_t bytes, hipStream_t st) {
     if (bytes <= ctx->any_bytes) return RSX_OK;
@@ -576,7 +614,7 @@ int reserve_any(rsx_ctx* ctx, size_t n, const rsx_layout* L, hipStream_t st) {
     const AnyPlan P = any_plan(L);
     int rc = ensure_workspace(ctx, n, &P.inner, st);
     if (rc) return rc;
-    return ensure_any(ctx, 2 * any_half(n, P), st);
+    return ensure_any(ctx, 2 * round256(n * (size_t)P.inner.elem_bytes), st);
 }
 
 int launch_move(rsx_ctx* ctx, const void* src, uint32_t s_in, void* dst, uint32_t s_out, void* dst2, size_t n, const AnyMap& map,
@@ -637,7 +675,7 @@ int sort_any_locked(rsx_ctx* ctx, void* d_data, void* d_tmp, size_t n, const rsx
     if (rc) return rc;
     Enqueue enq(ctx, st);  // the workspace arrays belong to this sort from the first launch on
     char* w0 = ctx->any_buf;
-    char* w1 = ctx->any_buf + any_half(n, P);
+    char* w1 = ctx->any_buf + round256(n * (size_t)P.inner.elem_bytes);
     const uint32_t s = L->elem_bytes, sp = P.inner.elem_bytes;
     if (P.route == 1) {
         rc = launch_move(ctx, d_data, s, w0, sp, nullptr, n, map_forward(L, P), st);
@@ -665,29 +703,59 @@ int sort_any_locked(rsx_ctx* ctx, void* d_data, void* d_tmp, size_t n, const rsx
 //     element size with sort kernels (rsx_pairs_kernels.hpp, pairs_elem); join, sort, split;
 //   route 2, proxies and gather: (mapped key, u32 position) proxies for wider values; the keys are written from the
 //     sorted proxies and the values gathered through a copy kept behind the two proxy arrays.
-struct PairsPlan {
-    uint32_t route;
-    uint32_t vb;       // bytes of the value inside the element (route 2: the 4-byte position)
-    rsx_layout inner;  // what the sort kernels see
-    size_t half;       // bytes of each of the two element arrays
-    size_t copy;       // route 2: bytes of the copy of the values
+// The two arrays of n joined elements every such call sorts in, at the front of the second workspace; what a call keeps
+// behind them it takes from `ws`.
+struct JoinedPlan {
+    size_t n;
+    uint32_t vb;       // bytes of the value inside the element
+    rsx_layout inner;  // what the sort kernels see (elem_bytes 0: no joined element for these widths)
+    size_t half;       // bytes of each of the two element arrays: the second one's offset
+    Carve ws;          // ws.bytes: the whole workspace of the call
 };
-PairsPlan pairs_plan(size_t n, uint32_t kb, uint32_t vb) {
-    PairsPlan P{};
-    uint32_t es = pairs_elem_bytes(kb, vb);
-    P.route = es ? 1u : 2u;
-    P.vb = es ? vb : 4u;
-    if (!es) es = pairs_elem_bytes(kb, 4);
+JoinedPlan joined_plan(size_t n, uint32_t kb, uint32_t vb) {
+    JoinedPlan P{};
+    const uint32_t es = pairs_elem_bytes(kb, vb);
+    P.n = n;
+    P.vb = vb;
     P.inner = rsx_layout{es, 0, kb, RSX_KEY_UNSIGNED};
-    P.half = (n * (size_t)es + 255) & ~(size_t)255;
-    P.copy = P.route == 2 ? (n * (size_t)vb + 255) & ~(size_t)255 : 0;
+    P.ws.take(n * (size_t)es);
+    P.half = P.ws.take(n * (size_t)es);
     return P;
 }
-int reserve_pairs_one(rsx_ctx* ctx, size_t n, uint32_t kb, uint32_t vb, hipStream_t st) {
-    const PairsPlan P = pairs_plan(n, kb, vb);
-    int rc = ensure_workspace(ctx, n, &P.inner, st);
+int reserve_joined(rsx_ctx* ctx, const JoinedPlan& P, hipStream_t st) {
+    int rc = ensure_workspace(ctx, P.n, &P.inner, st);
     if (rc) return rc;
-    return ensure_any(ctx, 2 * P.half + P.copy, st);
+    return ensure_any(ctx, P.ws.bytes, st);
+}
+// Joins keys and values (gen: every key's position) into the first array and sorts them there; *w0 receives the sorted
+// elements.  The caller has reserved P (reserve_joined) and opened its Enqueue, in that order.
+int joined_sort(rsx_ctx* ctx, const JoinedPlan& P, const void* d_keys, const void* d_values, bool gen, uint32_t kind, uint32_t desc, hipStream_t st,
+                char** w0) {
+    char* w = ctx->any_buf;
+    int rc = launch_pairs_join(ctx, d_keys, d_values, w, P.n, P.inner.key_bytes, P.vb, gen, kind, desc, st);
+    if (rc) return rc;
+    if (P.n > 1) {
+        rc = sort_device_locked(ctx, w, w + P.half, P.n, &P.inner, st);
+        if (rc) return rc;
+    }
+    ctx->last_pairs = 1u | P.inner.elem_bytes << 8;
+    *w0 = w;
+    return RSX_OK;
+}
+struct PairsPlan {
+    uint32_t route;
+    JoinedPlan j;     // route 2: (mapped key, u32 position) proxies
+    size_t copy_off;  // route 2: the copy of the values, behind the two proxy arrays
+};
+// route 2 for n values of vb bytes (the segmented calls take it for every width without a fused kernel)
+PairsPlan proxy_plan(size_t n, uint32_t kb, uint32_t vb) {
+    PairsPlan P{2u, joined_plan(n, kb, 4), 0};
+    P.copy_off = P.j.ws.take(n * (size_t)vb);
+    return P;
+}
+PairsPlan pairs_plan(size_t n, uint32_t kb, uint32_t vb) {
+    if (!pairs_elem_bytes(kb, vb)) return proxy_plan(n, kb, vb);
+    return PairsPlan{1u, joined_plan(n, kb, vb), 0};
 }
 bool key_widths_ok(uint32_t kb, uint32_t kind) {  // the key array as a layout of its own
     const rsx_layout L{kb, 0, kb, kind};
@@ -698,11 +766,6 @@ bool typed_value_width(uint32_t vb) { return vb == 0 || vb == 1 || vb == 2 || vb
 // the joined element the fused kernels sort: the value itself, or a four-byte position (argsort; values too wide to join)
 uint32_t segment_pairs_elem(uint32_t kb, uint32_t vb, bool argsort) {
     return pairs_elem_bytes(kb, (!argsort && typed_value_width(vb)) ? vb : 4u);
-}
-// route B's workspace: two arrays of proxies and the copy of the values
-size_t segment_pairs_wide_bytes(size_t n, uint32_t kb, uint32_t vb) {
-    const size_t half = (n * (size_t)pairs_elem_bytes(kb, 4) + 255) & ~(size_t)255;
-    return 2 * half + ((n * (size_t)vb + 255) & ~(size_t)255);
 }
 uint32_t value_align(uint32_t vb) {
     uint32_t a = 1;
@@ -721,12 +784,11 @@ int pairs_locked(rsx_ctx* ctx, void* d_keys, void* d_values, void* d_index, size
     if (P.route == 2 && (uint64_t)n >= (1ull << 32)) return fail(ctx, RSX_ERR_UNSUPPORTED, "2^32 or more pairs with values too wide to join");
     int rc = pending_error(ctx);
     if (rc) return rc;
-    rc = reserve_pairs_one(ctx, n, kb, argsort ? pw : vb, st);
+    rc = reserve_joined(ctx, P.j, st);
     if (rc) return rc;
     Enqueue enq(ctx, st);  // the workspace arrays belong to this call from the first launch on
     char* w0 = ctx->any_buf;
-    char* w1 = w0 + P.half;
-    const uint32_t es = P.inner.elem_bytes;
+    const uint32_t es = P.j.inner.elem_bytes;
     if (!argsort && vb == 0 && !desc) {  // ascending keys alone: the sort of one array, the workspace as its ping-pong
         const rsx_layout L{kb, 0, kb, kind};
         rc = sort_device_locked(ctx, d_keys, w0, n, &L, st);
@@ -735,18 +797,16 @@ int pairs_locked(rsx_ctx* ctx, void* d_keys, void* d_values, void* d_index, size
         return RSX_OK;
     }
     if (P.route == 1) {
-        rc = launch_pairs_join(ctx, d_keys, d_values, w0, n, kb, P.vb, argsort, kind, desc, st);
+        rc = joined_sort(ctx, P.j, d_keys, d_values, argsort, kind, desc, st, &w0);
         if (rc) return rc;
-        rc = sort_device_locked(ctx, w0, w1, n, &P.inner, st);
-        if (rc) return rc;
-        if (argsort) rc = launch_pairs_split(ctx, w0, nullptr, d_index, n, kb, P.vb, 2, ib, kind, desc, st);
-        else rc = launch_pairs_split(ctx, w0, d_keys, d_values, n, kb, P.vb, 0, 0, kind, desc, st);
-    } else {
-        char* cp = w1 + P.half;
+        if (argsort) rc = launch_pairs_split(ctx, w0, nullptr, d_index, n, kb, P.j.vb, 2, ib, kind, desc, st);
+        else rc = launch_pairs_split(ctx, w0, d_keys, d_values, n, kb, P.j.vb, 0, 0, kind, desc, st);
+    } else {  // (the copy of the values stands between the join and the sort: not joined_sort)
+        char* cp = w0 + P.copy_off;
         rc = launch_pairs_join(ctx, d_keys, nullptr, w0, n, kb, 4, true, kind, desc, st);
         if (rc) return rc;
         RSX_HIP(hipMemcpyAsync(cp, d_values, n * (size_t)vb, hipMemcpyDeviceToDevice, st));
-        rc = sort_device_locked(ctx, w0, w1, n, &P.inner, st);
+        rc = sort_device_locked(ctx, w0, w0 + P.j.half, n, &P.j.inner, st);
         if (rc) return rc;
         rc = launch_pairs_split(ctx, w0, d_keys, nullptr, n, kb, 4, 1, 0, kind, desc, st);
         if (rc) return rc;
@@ -857,8 +917,7 @@ int rsx_ctx_destroy(rsx_ctx* ctx) try {
 int rsx_ctx_reserve(rsx_ctx* ctx, size_t n, const rsx_layout* layout) try {
     int rc = check_any(ctx, layout);
     if (rc) return rc;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
+    Entry held(ctx);
     if (!direct_layout(layout)) return reserve_any(ctx, n, layout, nullptr);
     return ensure_workspace(ctx, n, layout, nullptr);
 } catch (...) {
@@ -867,8 +926,7 @@ int rsx_ctx_reserve(rsx_ctx* ctx, size_t n, const rsx_layout* layout) try {
 
 int rsx_ctx_check(rsx_ctx* ctx, void* stream) try {
     if (!ctx) return RSX_ERR_ARG;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
+    Entry held(ctx);
     RSX_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
     if (!ctx->host_err) return RSX_OK;
     if (host_word(ctx, HV_ERROR)) {
@@ -962,8 +1020,7 @@ int rsx_ctx_set_option(rsx_ctx* ctx, int option, uint64_t value) try {
 
 int rsx_ctx_get_info(rsx_ctx* ctx, int what, uint64_t* out) try {
     if (!ctx || !out) return RSX_ERR_ARG;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
+    Entry held(ctx);
     if (what == RSX_INFO_RANK_ATOMIC || what == RSX_INFO_L2_LOCAL) {
         int rc = ensure_aux(ctx, nullptr);  // runs the self-tests on first use
         if (rc) return rc;
@@ -974,24 +1031,25 @@ int rsx_ctx_get_info(rsx_ctx* ctx, int what, uint64_t* out) try {
         case RSX_INFO_NUM_CU: *out = (uint64_t)ctx->num_cu; return RSX_OK;
         case RSX_INFO_DEVICE: *out = (uint64_t)ctx->device; return RSX_OK;
         case RSX_INFO_LAST_PASSES: {
-            if (ctx->last_path == 6 || ctx->last_path == 7 || ctx->last_path == 8 || ctx->last_path == 9) {  // segmented, top-k, groups, reduce by key: bits 0-7 are the kernels launched
-                *out = (uint64_t)(ctx->last_sort_passes & 0xFFu) | (uint64_t)ctx->last_path << 24;
-                return RSX_OK;
-            }
-            if (ctx->last_path == 10) {  // search: bits 0-7 the kernels launched after any sort, bit 8 the needles were sorted first
-                *out = (uint64_t)(ctx->last_sort_passes & 0x1FFu) | (uint64_t)ctx->last_path << 24;
-                return RSX_OK;
+            switch (ctx->last_path) {
+                case PATH_SEGMENTS: case PATH_TOPK: case PATH_UNIQUE: case PATH_REDUCE:  // bits 0-7 are the kernels launched
+                    *out = (uint64_t)(ctx->last_sort_passes & 0xFFu) | (uint64_t)ctx->last_path << 24;
+                    return RSX_OK;
+                case PATH_SEARCH:  // bits 0-7 the kernels launched after any sort, bit 8 the needles were sorted first
+                    *out = (uint64_t)(ctx->last_sort_passes & 0x1FFu) | (uint64_t)ctx->last_path << 24;
+                    return RSX_OK;
+                default: break;
             }
             *out = (uint64_t)ctx->last_path << 24 | (uint64_t)ctx->last_route << 28;
             if (!ctx->aux || ctx->last_sort_passes == 0) return RSX_OK;
             if (ctx->busy) RSX_HIP(hipEventSynchronize(ctx->last_event));
             uint64_t stat = 0, placed = 0;
             uint32_t path = ctx->last_path, passes = ctx->last_sort_passes;
-            if (path == 5 && ctx->wide_buf) {  // both sequences were enqueued: the device's verdict says which one ran
+            if (path == PATH_WIDE && ctx->wide_buf) {  // both sequences were enqueued: the device's verdict says which one ran
                 uint32_t verdict = 0;
                 RSX_HIP(hipMemcpy(&verdict, reinterpret_cast<char*>(ctx->wide_buf) + WIDE_PLAN_OFFSET, sizeof verdict, hipMemcpyDeviceToHost));
                 if ((verdict & VERDICT_PATH_MASK) == VERDICT_HYBRID) passes = 2;
-                else path = 0;
+                else path = PATH_LSD;
             }
             for (uint32_t p = 0; p < passes && p < (uint32_t)MAX_PASSES; ++p) {
                 uint32_t mode = 0;  // the roll call's verdict word: 1 static, 3 static + placement verified, 2 / 0 tickets
@@ -1007,7 +1065,7 @@ int rsx_ctx_get_info(rsx_ctx* ctx, int what, uint64_t* out) try {
         case RSX_INFO_LAST_LEX: *out = (uint64_t)ctx->last_lex; return RSX_OK;
         case RSX_INFO_LAST_DIRECT: {
             *out = ~(uint64_t)0;
-            if (ctx->last_path != 5 || !ctx->last_direct || !ctx->wide_buf) return RSX_OK;
+            if (ctx->last_path != PATH_WIDE || !ctx->last_direct || !ctx->wide_buf) return RSX_OK;
             if (ctx->busy) RSX_HIP(hipEventSynchronize(ctx->last_event));
             uint32_t verdict = 0, left = 0;  // (both sequences were enqueued: a hybrid the device refused ran no direct kernel)
             RSX_HIP(hipMemcpy(&verdict, ctx->wide_buf + WIDE_PLAN_OFFSET, sizeof verdict, hipMemcpyDeviceToHost));
@@ -1025,8 +1083,7 @@ int rsx_ctx_get_info(rsx_ctx* ctx, int what, uint64_t* out) try {
 // Diagnostic counters of the sweep kernel (RSX_TUNING builds, RSX_DEBUG & 0x100); not part of include/rsx.h.
 int rsx_debug_counters(rsx_ctx* ctx, unsigned long long* out128, int reset) try {
     if (!ctx || !out128 || !ctx->aux) return RSX_ERR_ARG;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
+    Entry held(ctx);
     RSX_HIP(hipDeviceSynchronize());
     RSX_HIP(hipMemcpy(out128, ctx->aux + OFF_DBG, 1024, hipMemcpyDeviceToHost));  // caller passes 128 u64
     if (reset) RSX_HIP(hipMemset(ctx->aux + OFF_DBG, 0, 1024));
@@ -1070,8 +1127,7 @@ int rsx_debug_sweep_times(rsx_ctx* ctx, float* out, int max) try {
 
 int rsx_ctx_profile_read(rsx_ctx* ctx, double* ms, uint64_t* launches) try {
     if (!ctx || !ms || !launches) return RSX_ERR_ARG;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
+    Entry held(ctx);
     for (int k = 0; k < RSX_PROF_KINDS; ++k) {
         for (auto& e : ctx->prof_pending[k]) {
             RSX_HIP(hipEventSynchronize(e.second));
@@ -1100,10 +1156,9 @@ int rsx_sort_device(rsx_ctx* ctx, void* d_data, void* d_tmp, size_t n, const rsx
         const uint32_t al = elem_align(L->elem_bytes);
         if (!aligned(d_data, al) || !aligned(d_tmp, al)) return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
     }
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return fail(ctx, RSX_ERR_NODEVICE, "hipSetDevice failed");
-    return sort_any_locked(ctx, d_data, d_tmp, n, L, static_cast<hipStream_t>(stream));
+    Entry held(ctx, stream);
+    if (!held.ok) return no_device(ctx);
+    return sort_any_locked(ctx, d_data, d_tmp, n, L, held.st);
 } catch (...) {
     return RSX_ERR_HIP;
 }
@@ -1111,14 +1166,13 @@ int rsx_sort_device(rsx_ctx* ctx, void* d_data, void* d_tmp, size_t n, const rsx
 int rsx_ctx_reserve_pairs(rsx_ctx* ctx, size_t n, uint32_t key_bytes, uint32_t value_bytes) try {
     if (!ctx) return RSX_ERR_ARG;
     if (!key_widths_ok(key_bytes, RSX_KEY_UNSIGNED) || value_bytes > RSX_MAX_ELEM_BYTES) return fail(ctx, RSX_ERR_ARG, "invalid key or value width");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return fail(ctx, RSX_ERR_NODEVICE, "hipSetDevice failed");
-    int rc = reserve_pairs_one(ctx, n, key_bytes, value_bytes, nullptr);
+    Entry held(ctx);
+    if (!held.ok) return no_device(ctx);
+    int rc = reserve_joined(ctx, pairs_plan(n, key_bytes, value_bytes).j, nullptr);
     // an argsort with 8-byte indices joins 4-byte positions while n < 2^32: another element size
-    if (!rc && value_bytes == 8 && (uint64_t)n < (1ull << 32)) rc = reserve_pairs_one(ctx, n, key_bytes, 4, nullptr);
+    if (!rc && value_bytes == 8 && (uint64_t)n < (1ull << 32)) rc = reserve_joined(ctx, pairs_plan(n, key_bytes, 4).j, nullptr);
     // the segmented calls keep values without a fused kernel behind four-byte positions, whatever their width
-    if (!rc && !typed_value_width(value_bytes)) rc = ensure_any(ctx, segment_pairs_wide_bytes(n, key_bytes, value_bytes), nullptr);
+    if (!rc && !typed_value_width(value_bytes)) rc = ensure_any(ctx, proxy_plan(n, key_bytes, value_bytes).j.ws.bytes, nullptr);
     return rc;
 } catch (...) {
     return RSX_ERR_NOMEM;
@@ -1129,17 +1183,16 @@ int rsx_sort_pairs_device(rsx_ctx* ctx, void* d_keys, void* d_values, size_t n, 
     if (!ctx) return RSX_ERR_ARG;
     if (!key_widths_ok(key_bytes, key_kind)) return fail(ctx, RSX_ERR_ARG, "invalid key width or kind");
     if (value_bytes > RSX_MAX_ELEM_BYTES) return fail(ctx, RSX_ERR_ARG, "value wider than RSX_MAX_ELEM_BYTES");
-    if (order != RSX_ORDER_ASCENDING && order != RSX_ORDER_DESCENDING) return fail(ctx, RSX_ERR_ARG, "invalid order");
+    uint32_t desc = 0;
+    if (int rc = order_desc(ctx, order, &desc)) return rc;
     if ((d_values == nullptr) != (value_bytes == 0) && (n > 0 || d_values != nullptr)) return fail(ctx, RSX_ERR_ARG, "d_values and value_bytes disagree");
     if (n == 0) return RSX_OK;
     if (!d_keys) return fail(ctx, RSX_ERR_ARG, "null device pointer");
     if (!aligned(d_keys, key_bytes) || (value_bytes && !aligned(d_values, value_align(value_bytes)))) return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
     if (n == 1) return RSX_OK;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return fail(ctx, RSX_ERR_NODEVICE, "hipSetDevice failed");
-    return pairs_locked(ctx, d_keys, d_values, nullptr, n, key_bytes, key_kind, value_bytes, 0, order == RSX_ORDER_DESCENDING ? 1u : 0u,
-                        static_cast<hipStream_t>(stream));
+    Entry held(ctx, stream);
+    if (!held.ok) return no_device(ctx);
+    return pairs_locked(ctx, d_keys, d_values, nullptr, n, key_bytes, key_kind, value_bytes, 0, desc, held.st);
 } catch (...) {
     return RSX_ERR_HIP;
 }
@@ -1148,27 +1201,33 @@ int rsx_argsort_device(rsx_ctx* ctx, const void* d_keys, void* d_index, size_t n
                        int order, void* stream) try {
     if (!ctx) return RSX_ERR_ARG;
     if (!key_widths_ok(key_bytes, key_kind)) return fail(ctx, RSX_ERR_ARG, "invalid key width or kind");
-    if (index_bytes != 4 && index_bytes != 8) return fail(ctx, RSX_ERR_ARG, "index_bytes must be 4 or 8");
-    if (order != RSX_ORDER_ASCENDING && order != RSX_ORDER_DESCENDING) return fail(ctx, RSX_ERR_ARG, "invalid order");
+    if (int rc = check_index_bytes(ctx, index_bytes)) return rc;
+    uint32_t desc = 0;
+    if (int rc = order_desc(ctx, order, &desc)) return rc;
     if (n == 0) return RSX_OK;
     if (!d_keys || !d_index) return fail(ctx, RSX_ERR_ARG, "null device pointer");
     if (!aligned(d_keys, key_bytes) || !aligned(d_index, index_bytes)) return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return fail(ctx, RSX_ERR_NODEVICE, "hipSetDevice failed");
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    Entry held(ctx, stream);
+    if (!held.ok) return no_device(ctx);
+    const hipStream_t st = held.st;
     if (n == 1) {  // the one position
         RSX_HIP(hipMemsetAsync(d_index, 0, index_bytes, st));
         return RSX_OK;
     }
-    return pairs_locked(ctx, const_cast<void*>(d_keys), nullptr, d_index, n, key_bytes, key_kind, 0, index_bytes,
-                        order == RSX_ORDER_DESCENDING ? 1u : 0u, st);
+    return pairs_locked(ctx, const_cast<void*>(d_keys), nullptr, d_index, n, key_bytes, key_kind, 0, index_bytes, desc, st);
 } catch (...) {
     return RSX_ERR_HIP;
 }
 
 // Shared body of rsx_sort_segments_device (d_offsets) and rsx_sort_rows_device (d_offsets == nullptr, nseg rows of row_len).
 namespace {
+// Rows above what a workgroup holds in LDS (cap, the largest class): the whole-array call, row by row (the context's
+// workspace as for any sort).  Only where every CU has a row of its own and the rows are short enough for one workgroup's
+// passes through memory to beat a launch sequence per row does the through-memory class take them (measured, DESIGN
+// section 5: 4681 rows of 28673 u32 12 ms against 121 ms; the two meet at some 10 x cap elements per row).
+bool rows_one_by_one(const rsx_ctx* ctx, size_t nseg, uint64_t row_len, uint64_t cap) {
+    return row_len > cap && !(nseg >= (size_t)ctx->num_cu && row_len <= 4 * cap);
+}
 int sort_segments_common(rsx_ctx* ctx, void* d_data, void* d_tmp, size_t n, const rsx_layout* L, const uint64_t* d_offsets, size_t nseg,
                          uint64_t row_len, uint64_t max_len, void* stream) {
     int rc = check_common(ctx, L);
@@ -1177,16 +1236,11 @@ int sort_segments_common(rsx_ctx* ctx, void* d_data, void* d_tmp, size_t n, cons
     if (!d_data || !d_tmp) return fail(ctx, RSX_ERR_ARG, "null device pointer");
     const uint32_t al = elem_align(L->elem_bytes);
     if (!aligned(d_data, al) || !aligned(d_tmp, al) || !aligned(d_offsets, 8)) return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return fail(ctx, RSX_ERR_NODEVICE, "hipSetDevice failed");
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    Entry held(ctx, stream);
+    if (!held.ok) return no_device(ctx);
+    const hipStream_t st = held.st;
     const uint64_t cap = segment_cap((int)L->elem_bytes, RSX_SEG_CLASSES - 1);
-    // Rows above what a workgroup holds in LDS: the sort of one array, row by row (the context's workspace as for any sort).
-    // Only where every CU has a row of its own and the rows are short enough for one workgroup's passes through memory
-    // to beat a launch sequence per row does the through-memory class take them (measured, DESIGN section 5: 4681 rows of
-    // 28673 u32 12 ms against 121 ms; the two meet at some 10 x cap elements per row).
-    if (!d_offsets && row_len > cap && !(nseg >= (size_t)ctx->num_cu && row_len <= 4 * cap)) {
+    if (!d_offsets && rows_one_by_one(ctx, nseg, row_len, cap)) {
         for (size_t i = 0; i < nseg; ++i) {
             const size_t off = i * (size_t)row_len * L->elem_bytes;
             rc = sort_device_locked(ctx, static_cast<char*>(d_data) + off, static_cast<char*>(d_tmp) + off, (size_t)row_len, L, st);
@@ -1201,9 +1255,7 @@ int sort_segments_common(rsx_ctx* ctx, void* d_data, void* d_tmp, size_t n, cons
     Enqueue enq(ctx, st);
     uint32_t launched = 0;
     rc = launchers_for(L->elem_bytes)->segment_sort(ctx, d_data, d_tmp, n, L, d_offsets, nseg, row_len, max_len, &launched, st);
-    ctx->last_path = 6;
-    ctx->last_route = 0;
-    ctx->last_sort_passes = launched;
+    note_path(ctx, PATH_SEGMENTS, launched);
     return rc;
 }
 }  // namespace
@@ -1233,9 +1285,12 @@ int segments_pairs_common(rsx_ctx* ctx, void* d_keys, void* d_values, void* d_in
                           uint32_t ib, int order, const uint64_t* d_offsets, bool rows, size_t nseg, uint64_t row_len, uint64_t max_len, void* stream) {
     if (!ctx) return RSX_ERR_ARG;
     if (!key_widths_ok(kb, kind)) return fail(ctx, RSX_ERR_ARG, "invalid key width or kind");
-    if (argsort && ib != 4 && ib != 8) return fail(ctx, RSX_ERR_ARG, "index_bytes must be 4 or 8");
+    int rc = argsort ? check_index_bytes(ctx, ib) : RSX_OK;
+    if (rc) return rc;
     if (!argsort && vb > RSX_MAX_ELEM_BYTES) return fail(ctx, RSX_ERR_ARG, "value wider than RSX_MAX_ELEM_BYTES");
-    if (order != RSX_ORDER_ASCENDING && order != RSX_ORDER_DESCENDING) return fail(ctx, RSX_ERR_ARG, "invalid order");
+    uint32_t desc = 0;
+    rc = order_desc(ctx, order, &desc);
+    if (rc) return rc;
     if (!argsort && (d_values == nullptr) != (vb == 0)) return fail(ctx, RSX_ERR_ARG, "d_values and value_bytes disagree");
     if (nseg == 0 || n == 0 || (rows && row_len == 0)) return RSX_OK;
     if (rows && row_len == 1 && !argsort) return RSX_OK;
@@ -1243,11 +1298,9 @@ int segments_pairs_common(rsx_ctx* ctx, void* d_keys, void* d_values, void* d_in
     if (!d_keys || (argsort && !d_index)) return fail(ctx, RSX_ERR_ARG, "null device pointer");
     if (!aligned(d_keys, kb) || (argsort && !aligned(d_index, ib)) || (vb && !aligned(d_values, value_align(vb))) || !aligned(d_offsets, 8))
         return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return fail(ctx, RSX_ERR_NODEVICE, "hipSetDevice failed");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const uint32_t desc = order == RSX_ORDER_DESCENDING ? 1u : 0u;
+    Entry held(ctx, stream);
+    if (!held.ok) return no_device(ctx);
+    const hipStream_t st = held.st;
     if (rows && row_len == 1) {  // argsort: every row's one position
         RSX_HIP(hipMemsetAsync(d_index, 0, n * (size_t)ib, st));
         return RSX_OK;
@@ -1256,11 +1309,7 @@ int segments_pairs_common(rsx_ctx* ctx, void* d_keys, void* d_values, void* d_in
     const uint32_t es = segment_pairs_elem(kb, vb, argsort);
     if (es == 0 || !launchers_for(es)) return fail(ctx, RSX_ERR_INTERNAL, "no joined element for these widths");
     if (wide && (uint64_t)n >= (1ull << 32)) return fail(ctx, RSX_ERR_UNSUPPORTED, "2^32 or more pairs with values too wide to join");
-    const uint64_t cap = segment_cap((int)es, RSX_SEG_CLASSES - 1);
-    int rc;
-    // Rows above what a workgroup holds in LDS: the rule of rsx_sort_rows_device -- the whole-array call row by row, unless
-    // every CU has a row of its own and the rows are short enough for one workgroup's passes through memory.
-    if (rows && row_len > cap && !(nseg >= (size_t)ctx->num_cu && row_len <= 4 * cap)) {
+    if (rows && rows_one_by_one(ctx, nseg, row_len, segment_cap((int)es, RSX_SEG_CLASSES - 1))) {
         for (size_t i = 0; i < nseg; ++i) {
             const size_t off = i * (size_t)row_len;
             char* k = static_cast<char*>(d_keys) + off * kb;
@@ -1273,19 +1322,20 @@ int segments_pairs_common(rsx_ctx* ctx, void* d_keys, void* d_values, void* d_in
     rc = pending_error(ctx);
     if (rc) return rc;
     const bool mem = segment_pairs_mem(es, d_offsets, row_len, max_len);
+    // either way two arrays of n elements of es bytes; route B keeps the copy of the values behind them
+    const PairsPlan P = wide ? proxy_plan(n, kb, vb) : pairs_plan(n, kb, argsort ? 4u : vb);
     if (wide) {
         rc = ensure_aux(ctx, st);
-        if (!rc) rc = ensure_any(ctx, segment_pairs_wide_bytes(n, kb, vb), st);
+        if (!rc) rc = ensure_any(ctx, P.j.ws.bytes, st);
     } else if (mem) {
-        rc = reserve_pairs_one(ctx, n, kb, argsort ? 4u : vb, st);  // (two arrays of n joined elements)
+        rc = reserve_joined(ctx, P.j, st);
     } else {
         rc = ensure_aux(ctx, st);  // (the error word and the ranking self-test: a context's first call, never a captured one)
     }
     if (rc) return rc;
     Enqueue enq(ctx, st);
-    const size_t half = (n * (size_t)es + 255) & ~(size_t)255;
     char* w0 = (wide || mem) ? ctx->any_buf : nullptr;
-    char* w1 = w0 ? w0 + half : nullptr;
+    char* w1 = w0 ? w0 + P.j.half : nullptr;
     SegPairsCall c{};
     c.keys = d_keys;
     c.values = argsort ? d_index : wide ? static_cast<void*>(w0) : d_values;
@@ -1304,7 +1354,7 @@ int segments_pairs_common(rsx_ctx* ctx, void* d_keys, void* d_values, void* d_in
     c.max_len = max_len;
     char* cp = nullptr;
     if (wide) {  // every element's own position first: what no segment covers, and what a bad one holds, stays where it is
-        cp = w1 + half;
+        cp = w0 + P.copy_off;
         rc = launch_pairs_join(ctx, d_keys, nullptr, w0, n, kb, 4, true, kind, desc, st);
         if (rc) return rc;
         RSX_HIP(hipMemcpyAsync(cp, d_values, n * (size_t)vb, hipMemcpyDeviceToDevice, st));
@@ -1316,9 +1366,7 @@ int segments_pairs_common(rsx_ctx* ctx, void* d_keys, void* d_values, void* d_in
         rc = launch_gather(ctx, cp, d_values, vb, w0, es, pairs_value_offset(kb, 4), n, st);
         if (rc) return rc;
     }
-    ctx->last_path = 6;
-    ctx->last_route = 0;
-    ctx->last_sort_passes = launched;
+    note_path(ctx, PATH_SEGMENTS, launched);
     ctx->last_pairs = (wide ? 4u : 3u) | es << 8;
     return RSX_OK;
 }
@@ -1391,20 +1439,22 @@ int rsx_topk_rows_device(rsx_ctx* ctx, const void* d_keys, void* d_out_keys, voi
                          uint32_t key_bytes, uint32_t key_kind, uint32_t index_bytes, int order, void* stream) try {
     if (!ctx) return RSX_ERR_ARG;
     if (!key_widths_ok(key_bytes, key_kind)) return fail(ctx, RSX_ERR_ARG, "invalid key width or kind");
-    if (index_bytes != 4 && index_bytes != 8) return fail(ctx, RSX_ERR_ARG, "index_bytes must be 4 or 8");
-    if (order != RSX_ORDER_ASCENDING && order != RSX_ORDER_DESCENDING) return fail(ctx, RSX_ERR_ARG, "invalid order");
+    int rc = check_index_bytes(ctx, index_bytes);
+    if (rc) return rc;
+    uint32_t desc = 0;
+    rc = order_desc(ctx, order, &desc);
+    if (rc) return rc;
     uint32_t es = 0;
-    int rc = topk_shape(ctx, rows, row_len, k, key_bytes, &es);
+    rc = topk_shape(ctx, rows, row_len, k, key_bytes, &es);
     if (rc) return rc;
     if (rows == 0 || k == 0) return RSX_OK;  // (empty outputs: no pointer is looked at)
     if (!d_out_keys && !d_out_index) return fail(ctx, RSX_ERR_ARG, "both output pointers are null");
     if (!d_keys) return fail(ctx, RSX_ERR_ARG, "null device pointer");
     if (!aligned(d_keys, key_bytes) || !aligned(d_out_keys, key_bytes) || !aligned(d_out_index, index_bytes))
         return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return fail(ctx, RSX_ERR_NODEVICE, "hipSetDevice failed");
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    Entry held(ctx, stream);
+    if (!held.ok) return no_device(ctx);
+    const hipStream_t st = held.st;
     rc = pending_error(ctx);
     if (rc) return rc;
     rc = ensure_aux(ctx, st);  // (the error word and the ranking self-test: a context's first call, never a captured one)
@@ -1423,14 +1473,12 @@ int rsx_topk_rows_device(rsx_ctx* ctx, const void* d_keys, void* d_out_keys, voi
     c.k = k;
     c.kb = key_bytes;
     c.kind = key_kind;
-    c.desc = order == RSX_ORDER_DESCENDING ? 1u : 0u;
+    c.desc = desc;
     c.ib = index_bytes;
     uint32_t launched = 0;
     rc = launchers_for(es)->topk(ctx, c, &launched, st);
     if (rc) return rc;
-    ctx->last_path = 7;
-    ctx->last_route = 0;
-    ctx->last_sort_passes = launched;
+    note_path(ctx, PATH_TOPK, launched);
     return RSX_OK;
 } catch (...) {
     return RSX_ERR_HIP;
@@ -1442,9 +1490,8 @@ int rsx_ctx_reserve_topk(rsx_ctx* ctx, size_t rows, size_t row_len, size_t k, ui
     uint32_t es = 0;
     int rc = topk_shape(ctx, rows, row_len, k, key_bytes, &es);
     if (rc) return rc;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return fail(ctx, RSX_ERR_NODEVICE, "hipSetDevice failed");
+    Entry held(ctx);
+    if (!held.ok) return no_device(ctx);
     rc = ensure_aux(ctx, nullptr);
     const size_t half = (rows == 0 || k == 0) ? 0 : topk_workspace_half(es, rows, row_len, k);
     if (!rc && half) rc = ensure_any(ctx, 2 * half, nullptr);
@@ -1464,34 +1511,35 @@ int rsx_topk_caps(uint32_t key_bytes, uint32_t* caps, uint32_t* max_k) {
 
 // ---- groups of equal keys (rsx_unique_kernels.hpp, include/rsx.h) ----
 namespace {
-// The workspace of one rsx_unique_device call: the two arrays of joined elements (the shape of pairs_plan) and, behind
-// them, the per-tile arrays of the run kernels.
+// The workspace of one rsx_unique_device call: the two arrays of joined elements and, behind them, the per-tile arrays
+// of the run kernels.
 struct UniquePlan {
-    rsx_layout inner;  // what the sort kernels see
-    size_t half;       // bytes of each of the two element arrays
-    size_t tiles;
+    JoinedPlan j;
     size_t heads_off;  // tile_heads [tiles] u32
     size_t base_off;   // tile_base [tiles] u64
-    size_t bytes;
 };
 UniquePlan unique_plan(size_t n, uint32_t kb, bool pos) {
-    UniquePlan P{};
-    const uint32_t es = pairs_elem_bytes(kb, pos ? 4u : 0u);
+    UniquePlan P{joined_plan(n, kb, pos ? 4u : 0u), 0, 0};
     const uint32_t tile = unique_tile_elems(kb, pos);
-    P.inner = rsx_layout{es, 0, kb, RSX_KEY_UNSIGNED};
-    P.half = (n * (size_t)es + 255) & ~(size_t)255;
-    P.tiles = (n + tile - 1) / tile;
-    P.heads_off = 2 * P.half;
-    P.base_off = P.heads_off + ((P.tiles * sizeof(uint32_t) + 255) & ~(size_t)255);
-    P.bytes = P.base_off + ((P.tiles * sizeof(uint64_t) + 255) & ~(size_t)255);
+    const size_t tiles = (n + tile - 1) / tile;
+    P.heads_off = P.j.ws.take(tiles * sizeof(uint32_t));
+    P.base_off = P.j.ws.take(tiles * sizeof(uint64_t));
     return P;
 }
-int reserve_unique_one(rsx_ctx* ctx, const UniquePlan& P, size_t n, hipStream_t st) {
-    int rc = ensure_workspace(ctx, n, &P.inner, st);
-    if (rc) return rc;
-    return ensure_any(ctx, P.bytes, st);
-}
 bool unique_size_ok(size_t n) { return (uint64_t)n < (1ull << 32); }
+// a reserve entry's body once its arguments are checked
+int reserve_joined_entry(rsx_ctx* ctx, const JoinedPlan& P) {
+    Entry held(ctx);
+    if (!held.ok) return no_device(ctx);
+    return reserve_joined(ctx, P, nullptr);
+}
+// rsx_unique_device and rsx_reduce_by_key_device on no keys: no group, so two memsets and no kernel
+int no_group(rsx_ctx* ctx, uint32_t path, uint64_t* d_out_num, uint64_t* d_out_offsets, hipStream_t st) {
+    RSX_HIP(hipMemsetAsync(d_out_num, 0, sizeof(uint64_t), st));
+    if (d_out_offsets) RSX_HIP(hipMemsetAsync(d_out_offsets, 0, sizeof(uint64_t), st));
+    note_path(ctx, path, 0);
+    return RSX_OK;
+}
 }  // namespace
 
 int rsx_unique_device(rsx_ctx* ctx, const void* d_keys, size_t n, uint32_t key_bytes, uint32_t key_kind, int order, void* d_out_keys,
@@ -1499,44 +1547,32 @@ int rsx_unique_device(rsx_ctx* ctx, const void* d_keys, size_t n, uint32_t key_b
                       void* stream) try {
     if (!ctx) return RSX_ERR_ARG;
     if (!key_widths_ok(key_bytes, key_kind)) return fail(ctx, RSX_ERR_ARG, "invalid key width or kind");
-    if (order != RSX_ORDER_ASCENDING && order != RSX_ORDER_DESCENDING) return fail(ctx, RSX_ERR_ARG, "invalid order");
+    uint32_t desc = 0;
+    if (int rc = order_desc(ctx, order, &desc)) return rc;
     if (!d_out_num) return fail(ctx, RSX_ERR_ARG, "d_out_num is null");
     const bool pos = d_out_perm != nullptr || d_out_inverse != nullptr;
-    if (pos && index_bytes != 4 && index_bytes != 8) return fail(ctx, RSX_ERR_ARG, "index_bytes must be 4 or 8");
+    int rc = pos ? check_index_bytes(ctx, index_bytes) : RSX_OK;
+    if (rc) return rc;
     if (n > 0 && !d_keys) return fail(ctx, RSX_ERR_ARG, "null device pointer");
     if (!aligned(d_keys, key_bytes) || !aligned(d_out_keys, key_bytes) || !aligned(d_out_offsets, 8) || !aligned(d_out_num, 8) ||
         (pos && (!aligned(d_out_perm, index_bytes) || !aligned(d_out_inverse, index_bytes))))
         return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
     if (!unique_size_ok(n)) return fail(ctx, RSX_ERR_UNSUPPORTED, "2^32 or more keys");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return fail(ctx, RSX_ERR_NODEVICE, "hipSetDevice failed");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (n == 0) {  // no group: two memsets, no kernel
-        RSX_HIP(hipMemsetAsync(d_out_num, 0, sizeof(uint64_t), st));
-        if (d_out_offsets) RSX_HIP(hipMemsetAsync(d_out_offsets, 0, sizeof(uint64_t), st));
-        ctx->last_path = 8;
-        ctx->last_route = 0;
-        ctx->last_sort_passes = 0;
-        return RSX_OK;
-    }
+    Entry held(ctx, stream);
+    if (!held.ok) return no_device(ctx);
+    const hipStream_t st = held.st;
+    if (n == 0) return no_group(ctx, PATH_UNIQUE, d_out_num, d_out_offsets, st);
     const UniquePlan P = unique_plan(n, key_bytes, pos);
-    if (P.inner.elem_bytes == 0 || !launchers_for(P.inner.elem_bytes)) return fail(ctx, RSX_ERR_INTERNAL, "no joined element for this key width");
-    int rc = pending_error(ctx);
+    if (P.j.inner.elem_bytes == 0 || !launchers_for(P.j.inner.elem_bytes)) return fail(ctx, RSX_ERR_INTERNAL, "no joined element for this key width");
+    rc = pending_error(ctx);
     if (rc) return rc;
-    rc = reserve_unique_one(ctx, P, n, st);
+    rc = reserve_joined(ctx, P.j, st);
     if (rc) return rc;
     Enqueue enq(ctx, st);  // the workspace arrays belong to this call from the first launch on
-    char* w0 = ctx->any_buf;
-    char* w1 = w0 + P.half;
-    const uint32_t desc = order == RSX_ORDER_DESCENDING ? 1u : 0u;
+    char* w0 = nullptr;
     // the join of rsx_argsort_device (mapped key, u32 position), or of keys alone in descending order (the mapped key)
-    rc = launch_pairs_join(ctx, d_keys, nullptr, w0, n, key_bytes, pos ? 4u : 0u, pos, key_kind, desc, st);
+    rc = joined_sort(ctx, P.j, d_keys, nullptr, pos, key_kind, desc, st, &w0);
     if (rc) return rc;
-    if (n > 1) {
-        rc = sort_device_locked(ctx, w0, w1, n, &P.inner, st);
-        if (rc) return rc;
-    }
     UniqueCall c{};
     c.elems = w0;
     c.tile_heads = reinterpret_cast<uint32_t*>(w0 + P.heads_off);
@@ -1555,10 +1591,7 @@ int rsx_unique_device(rsx_ctx* ctx, const void* d_keys, size_t n, uint32_t key_b
     uint32_t launched = 0;
     rc = launch_unique(ctx, c, &launched, st);
     if (rc) return rc;
-    ctx->last_pairs = 1u | P.inner.elem_bytes << 8;
-    ctx->last_path = 8;
-    ctx->last_route = 0;
-    ctx->last_sort_passes = launched;
+    note_path(ctx, PATH_UNIQUE, launched);
     return RSX_OK;
 } catch (...) {
     return RSX_ERR_HIP;
@@ -1568,10 +1601,7 @@ int rsx_ctx_reserve_unique(rsx_ctx* ctx, size_t n, uint32_t key_bytes, int with_
     if (!ctx) return RSX_ERR_ARG;
     if (!key_widths_ok(key_bytes, RSX_KEY_UNSIGNED)) return fail(ctx, RSX_ERR_ARG, "invalid key width");
     if (!unique_size_ok(n)) return fail(ctx, RSX_ERR_UNSUPPORTED, "2^32 or more keys");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return fail(ctx, RSX_ERR_NODEVICE, "hipSetDevice failed");
-    return reserve_unique_one(ctx, unique_plan(n, key_bytes, with_positions != 0), n, nullptr);
+    return reserve_joined_entry(ctx, unique_plan(n, key_bytes, with_positions != 0).j);
 } catch (...) {
     return RSX_ERR_NOMEM;
 }
@@ -1584,26 +1614,21 @@ int rsx_unique_caps(uint32_t key_bytes, int with_positions, uint32_t* tile, uint
 }
 
 // ---- bounds of many needles in a sorted key array (rsx_search_kernels.hpp, include/rsx.h) ----
-namespace {
-// the presort route's workspace: the two arrays of joined (mapped key, u32 position) elements of the m needles
-int reserve_search_one(rsx_ctx* ctx, size_t m, uint32_t kb, hipStream_t st) { return reserve_pairs_one(ctx, m, kb, 4, st); }
-}  // namespace
-
 int rsx_search_sorted_device(rsx_ctx* ctx, const void* d_sorted, size_t n, const uint64_t* d_sorted_num, const void* d_needles, size_t m,
                              uint32_t key_bytes, uint32_t key_kind, int order, void* d_out_lower, void* d_out_upper, uint32_t index_bytes,
                              uint32_t flags, void* stream) try {
     if (!ctx) return RSX_ERR_ARG;
     if (!key_widths_ok(key_bytes, key_kind)) return fail(ctx, RSX_ERR_ARG, "invalid key width or kind");
-    if (order != RSX_ORDER_ASCENDING && order != RSX_ORDER_DESCENDING) return fail(ctx, RSX_ERR_ARG, "invalid order");
-    if (index_bytes != 4 && index_bytes != 8) return fail(ctx, RSX_ERR_ARG, "index_bytes must be 4 or 8");
+    uint32_t desc = 0;
+    int rc = order_desc(ctx, order, &desc);
+    if (!rc) rc = check_index_bytes(ctx, index_bytes);
+    if (rc) return rc;
     if (flags & ~(uint32_t)RSX_SEARCH_PRESORT) return fail(ctx, RSX_ERR_ARG, "unknown flag bits");
     if (index_bytes == 4 && (uint64_t)n >= (1ull << 32)) return fail(ctx, RSX_ERR_ARG, "2^32 or more sorted keys need 8-byte indices");
     const bool presort = (flags & RSX_SEARCH_PRESORT) != 0;
     std::lock_guard<std::mutex> lk(ctx->mu);
     if (m == 0) {  // nothing asked: no pointer is looked at
-        ctx->last_path = 10;
-        ctx->last_route = 0;
-        ctx->last_sort_passes = 0;
+        note_path(ctx, PATH_SEARCH, 0);
         return RSX_OK;
     }
     if (!d_out_lower && !d_out_upper) return fail(ctx, RSX_ERR_ARG, "d_out_lower and d_out_upper are both null");
@@ -1619,14 +1644,11 @@ int rsx_search_sorted_device(rsx_ctx* ctx, const void* d_sorted, size_t n, const
     if (n == 0) {  // an empty haystack: every count is zero
         if (d_out_lower) RSX_HIP(hipMemsetAsync(d_out_lower, 0, m * (size_t)index_bytes, st));
         if (d_out_upper) RSX_HIP(hipMemsetAsync(d_out_upper, 0, m * (size_t)index_bytes, st));
-        ctx->last_path = 10;
-        ctx->last_route = 0;
-        ctx->last_sort_passes = 0;
+        note_path(ctx, PATH_SEARCH, 0);
         return RSX_OK;
     }
-    int rc = pending_error(ctx);
+    rc = pending_error(ctx);
     if (rc) return rc;
-    const uint32_t desc = order == RSX_ORDER_DESCENDING ? 1u : 0u;
     SearchCall c{};
     c.sorted = d_sorted;
     c.n = n;
@@ -1647,31 +1669,22 @@ int rsx_search_sorted_device(rsx_ctx* ctx, const void* d_sorted, size_t n, const
         Enqueue enq(ctx, st);
         rc = launch_search(ctx, c, &launched, st);
         if (rc) return rc;
-        ctx->last_path = 10;
-        ctx->last_route = 0;
-        ctx->last_sort_passes = launched;
+        note_path(ctx, PATH_SEARCH, launched);
         return RSX_OK;
     }
-    const PairsPlan P = pairs_plan(m, key_bytes, 4);
-    if (P.route != 1 || !launchers_for(P.inner.elem_bytes)) return fail(ctx, RSX_ERR_INTERNAL, "no joined element for this key width");
-    rc = reserve_search_one(ctx, m, key_bytes, st);
+    // the presort route: the m needles as joined (mapped key, u32 position) elements, sorted
+    const JoinedPlan P = joined_plan(m, key_bytes, 4);
+    if (P.inner.elem_bytes == 0 || !launchers_for(P.inner.elem_bytes)) return fail(ctx, RSX_ERR_INTERNAL, "no joined element for this key width");
+    rc = reserve_joined(ctx, P, st);
     if (rc) return rc;
     Enqueue enq(ctx, st);  // the workspace arrays belong to this call from the first launch on
-    char* w0 = ctx->any_buf;
-    char* w1 = w0 + P.half;
-    rc = launch_pairs_join(ctx, d_needles, nullptr, w0, m, key_bytes, 4, true, key_kind, desc, st);
+    char* w0 = nullptr;
+    rc = joined_sort(ctx, P, d_needles, nullptr, true, key_kind, desc, st, &w0);
     if (rc) return rc;
-    if (m > 1) {
-        rc = sort_device_locked(ctx, w0, w1, m, &P.inner, st);
-        if (rc) return rc;
-    }
     c.needles = w0;
     rc = launch_search(ctx, c, &launched, st);
     if (rc) return rc;
-    ctx->last_pairs = 1u | P.inner.elem_bytes << 8;
-    ctx->last_path = 10;
-    ctx->last_route = 0;
-    ctx->last_sort_passes = launched | 0x100u;
+    note_path(ctx, PATH_SEARCH, launched | 0x100u);
     return RSX_OK;
 } catch (...) {
     return RSX_ERR_HIP;
@@ -1681,10 +1694,7 @@ int rsx_ctx_reserve_search(rsx_ctx* ctx, size_t m, uint32_t key_bytes) try {
     if (!ctx) return RSX_ERR_ARG;
     if (!key_widths_ok(key_bytes, RSX_KEY_UNSIGNED)) return fail(ctx, RSX_ERR_ARG, "invalid key width");
     if ((uint64_t)m >= (1ull << 32)) return fail(ctx, RSX_ERR_UNSUPPORTED, "2^32 or more needles to sort first");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return fail(ctx, RSX_ERR_NODEVICE, "hipSetDevice failed");
-    return reserve_search_one(ctx, m, key_bytes, nullptr);
+    return reserve_joined_entry(ctx, joined_plan(m, key_bytes, 4));
 } catch (...) {
     return RSX_ERR_NOMEM;
 }
@@ -1699,37 +1709,24 @@ int rsx_search_caps(uint32_t key_bytes, int with_positions, uint32_t* tile, uint
 
 // ---- reduce by key (rsx_reduce_kernels.hpp, include/rsx.h) ----
 namespace {
-// The workspace of one rsx_reduce_by_key_device call: the two arrays of joined (mapped key, value) elements (the shape
-// of pairs_plan) and, behind them, the four per-tile arrays of the run kernels.
+// The workspace of one rsx_reduce_by_key_device call: the two arrays of joined (mapped key, value) elements and, behind
+// them, the four per-tile arrays of the run kernels.
 struct ReducePlan {
-    rsx_layout inner;  // what the sort kernels see
-    size_t half;       // bytes of each of the two element arrays
-    size_t tiles;
+    JoinedPlan j;
     size_t heads_off;  // tile_heads [tiles] u32
     size_t base_off;   // tile_base [tiles] u64
     size_t tail_off;   // tile_tail [tiles] u64
     size_t carry_off;  // tile_carry [tiles] u64
-    size_t bytes;
 };
 ReducePlan reduce_plan(size_t n, uint32_t kb, uint32_t vb) {
-    ReducePlan P{};
-    const uint32_t es = pairs_elem_bytes(kb, vb);
+    ReducePlan P{joined_plan(n, kb, vb), 0, 0, 0, 0};
     const uint32_t tile = reduce_tile_elems(kb, vb);
-    P.inner = rsx_layout{es, 0, kb, RSX_KEY_UNSIGNED};
-    P.half = (n * (size_t)es + 255) & ~(size_t)255;
-    P.tiles = (n + tile - 1) / tile;
-    const size_t words = (P.tiles * sizeof(uint64_t) + 255) & ~(size_t)255;
-    P.heads_off = 2 * P.half;
-    P.base_off = P.heads_off + ((P.tiles * sizeof(uint32_t) + 255) & ~(size_t)255);
-    P.tail_off = P.base_off + words;
-    P.carry_off = P.tail_off + words;
-    P.bytes = P.carry_off + words;
+    const size_t tiles = (n + tile - 1) / tile;
+    P.heads_off = P.j.ws.take(tiles * sizeof(uint32_t));
+    P.base_off = P.j.ws.take(tiles * sizeof(uint64_t));
+    P.tail_off = P.j.ws.take(tiles * sizeof(uint64_t));
+    P.carry_off = P.j.ws.take(tiles * sizeof(uint64_t));
     return P;
-}
-int reserve_reduce_one(rsx_ctx* ctx, const ReducePlan& P, size_t n, hipStream_t st) {
-    int rc = ensure_workspace(ctx, n, &P.inner, st);
-    if (rc) return rc;
-    return ensure_any(ctx, P.bytes, st);
 }
 bool reduce_value_ok(uint32_t vb, uint32_t vkind) {
     return (vb == 4 || vb == 8) && (vkind == RSX_KEY_UNSIGNED || vkind == RSX_KEY_SIGNED || vkind == RSX_KEY_FLOAT);
@@ -1743,7 +1740,8 @@ int rsx_reduce_by_key_device(rsx_ctx* ctx, const void* d_keys, const void* d_val
     if (!key_widths_ok(key_bytes, key_kind)) return fail(ctx, RSX_ERR_ARG, "invalid key width or kind");
     if (!reduce_value_ok(value_bytes, value_kind)) return fail(ctx, RSX_ERR_ARG, "invalid value width or kind");
     if (op != RSX_REDUCE_SUM && op != RSX_REDUCE_MIN && op != RSX_REDUCE_MAX) return fail(ctx, RSX_ERR_ARG, "invalid operator");
-    if (order != RSX_ORDER_ASCENDING && order != RSX_ORDER_DESCENDING) return fail(ctx, RSX_ERR_ARG, "invalid order");
+    uint32_t desc = 0;
+    if (int rc = order_desc(ctx, order, &desc)) return rc;
     if (!d_out_num) return fail(ctx, RSX_ERR_ARG, "d_out_num is null");
     if (!d_out_keys && !d_out_values) return fail(ctx, RSX_ERR_ARG, "d_out_keys and d_out_values are both null");
     if (n > 0 && (!d_keys || !d_values)) return fail(ctx, RSX_ERR_ARG, "null device pointer");
@@ -1751,35 +1749,21 @@ int rsx_reduce_by_key_device(rsx_ctx* ctx, const void* d_keys, const void* d_val
         !aligned(d_out_offsets, 8) || !aligned(d_out_num, 8))
         return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
     if (!unique_size_ok(n)) return fail(ctx, RSX_ERR_UNSUPPORTED, "2^32 or more keys");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return fail(ctx, RSX_ERR_NODEVICE, "hipSetDevice failed");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (n == 0) {  // no group: two memsets, no kernel
-        RSX_HIP(hipMemsetAsync(d_out_num, 0, sizeof(uint64_t), st));
-        if (d_out_offsets) RSX_HIP(hipMemsetAsync(d_out_offsets, 0, sizeof(uint64_t), st));
-        ctx->last_path = 9;
-        ctx->last_route = 0;
-        ctx->last_sort_passes = 0;
-        return RSX_OK;
-    }
+    Entry held(ctx, stream);
+    if (!held.ok) return no_device(ctx);
+    const hipStream_t st = held.st;
+    if (n == 0) return no_group(ctx, PATH_REDUCE, d_out_num, d_out_offsets, st);
     const ReducePlan P = reduce_plan(n, key_bytes, value_bytes);
-    if (P.inner.elem_bytes == 0 || !launchers_for(P.inner.elem_bytes)) return fail(ctx, RSX_ERR_INTERNAL, "no joined element for this key and value");
+    if (P.j.inner.elem_bytes == 0 || !launchers_for(P.j.inner.elem_bytes)) return fail(ctx, RSX_ERR_INTERNAL, "no joined element for this key and value");
     int rc = pending_error(ctx);
     if (rc) return rc;
-    rc = reserve_reduce_one(ctx, P, n, st);
+    rc = reserve_joined(ctx, P.j, st);
     if (rc) return rc;
     Enqueue enq(ctx, st);  // the workspace arrays belong to this call from the first launch on
-    char* w0 = ctx->any_buf;
-    char* w1 = w0 + P.half;
-    const uint32_t desc = order == RSX_ORDER_DESCENDING ? 1u : 0u;
+    char* w0 = nullptr;
     // the join of rsx_sort_pairs_device: both inputs are consumed here, before any output is stored
-    rc = launch_pairs_join(ctx, d_keys, d_values, w0, n, key_bytes, value_bytes, false, key_kind, desc, st);
+    rc = joined_sort(ctx, P.j, d_keys, d_values, false, key_kind, desc, st, &w0);
     if (rc) return rc;
-    if (n > 1) {
-        rc = sort_device_locked(ctx, w0, w1, n, &P.inner, st);
-        if (rc) return rc;
-    }
     ReduceCall c{};
     c.elems = w0;
     c.tile_heads = reinterpret_cast<uint32_t*>(w0 + P.heads_off);
@@ -1800,10 +1784,7 @@ int rsx_reduce_by_key_device(rsx_ctx* ctx, const void* d_keys, const void* d_val
     uint32_t launched = 0;
     rc = launch_reduce(ctx, c, &launched, st);
     if (rc) return rc;
-    ctx->last_pairs = 1u | P.inner.elem_bytes << 8;
-    ctx->last_path = 9;
-    ctx->last_route = 0;
-    ctx->last_sort_passes = launched;
+    note_path(ctx, PATH_REDUCE, launched);
     return RSX_OK;
 } catch (...) {
     return RSX_ERR_HIP;
@@ -1814,10 +1795,7 @@ int rsx_ctx_reserve_reduce(rsx_ctx* ctx, size_t n, uint32_t key_bytes, uint32_t 
     if (!key_widths_ok(key_bytes, RSX_KEY_UNSIGNED)) return fail(ctx, RSX_ERR_ARG, "invalid key width");
     if (!reduce_value_ok(value_bytes, RSX_KEY_UNSIGNED)) return fail(ctx, RSX_ERR_ARG, "invalid value width");
     if (!unique_size_ok(n)) return fail(ctx, RSX_ERR_UNSUPPORTED, "2^32 or more keys");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return fail(ctx, RSX_ERR_NODEVICE, "hipSetDevice failed");
-    return reserve_reduce_one(ctx, reduce_plan(n, key_bytes, value_bytes), n, nullptr);
+    return reserve_joined_entry(ctx, reduce_plan(n, key_bytes, value_bytes).j);
 } catch (...) {
     return RSX_ERR_NOMEM;
 }
@@ -1875,22 +1853,35 @@ LexPlan lex_plan(const rsx_key_column* cols, uint32_t ncols) {
     close(0, last, k);
     return P;
 }
-size_t lex_round256(size_t b) { return (b + 255) & ~(size_t)255; }
 // the two element arrays of the widest round and, behind them, `stage` bytes per key of staging (rsx_sort_columns_device)
-int reserve_lex_one(rsx_ctx* ctx, size_t n, const LexPlan& P, uint32_t stage, hipStream_t st) {
+struct LexSpace {
+    size_t half;       // the second array's offset
+    size_t stage_off;
+    size_t bytes;
+};
+LexSpace lex_space(size_t n, const LexPlan& P, uint32_t stage) {
+    Carve ws{};
+    ws.take(n * (size_t)P.max_es);
+    LexSpace S{};
+    S.half = ws.take(n * (size_t)P.max_es);
+    S.stage_off = ws.take(n * (size_t)stage);
+    S.bytes = ws.bytes;
+    return S;
+}
+int reserve_lex_one(rsx_ctx* ctx, size_t n, const LexPlan& P, const LexSpace& S, hipStream_t st) {
     for (uint32_t r = 0; r < P.rounds; ++r) {
         const rsx_layout L{P.r[r].es, 0, P.r[r].w, RSX_KEY_UNSIGNED};
         int rc = ensure_workspace(ctx, n, &L, st);
         if (rc) return rc;
     }
-    return ensure_any(ctx, 2 * lex_round256(n * (size_t)P.max_es) + lex_round256(n * (size_t)stage), st);
+    return ensure_any(ctx, S.bytes, st);
 }
 // The rounds of the plan on n >= 2 keys: join, sort, and the next round reads the columns through this one's positions.
 // *sorted receives the last round's sorted elements (in the workspace), *es / *voff their size and position offset.
 // Caller holds ctx->mu, has set the device, checked the arguments and reserved the workspace under its Enqueue.
-int lex_rounds_locked(rsx_ctx* ctx, const rsx_key_column* cols, const LexPlan& P, size_t n, char** sorted, uint32_t* es, uint32_t* voff,
-                      hipStream_t st) {
-    char* w[2] = {ctx->any_buf, ctx->any_buf + lex_round256(n * (size_t)P.max_es)};
+int lex_rounds_locked(rsx_ctx* ctx, const rsx_key_column* cols, const LexPlan& P, const LexSpace& S, size_t n, char** sorted, uint32_t* es,
+                      uint32_t* voff, hipStream_t st) {
+    char* w[2] = {ctx->any_buf, ctx->any_buf + S.half};
     const char* prev = nullptr;
     uint32_t prev_es = 0, prev_voff = 0;
     for (uint32_t r = 0; r < P.rounds; ++r) {
@@ -1956,11 +1947,10 @@ int rsx_ctx_reserve_lex(rsx_ctx* ctx, size_t n, const rsx_key_column* cols, uint
     if (rc) return lex_fail_columns(ctx, rc);
     if (value_bytes > RSX_MAX_ELEM_BYTES) return fail(ctx, RSX_ERR_ARG, "value wider than RSX_MAX_ELEM_BYTES");
     if (!unique_size_ok(n)) return fail(ctx, RSX_ERR_UNSUPPORTED, "2^32 or more keys");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return fail(ctx, RSX_ERR_NODEVICE, "hipSetDevice failed");
+    Entry held(ctx);
+    if (!held.ok) return no_device(ctx);
     const LexPlan P = lex_plan(cols, ncols);
-    return reserve_lex_one(ctx, n, P, std::max(P.max_kb, value_bytes), nullptr);
+    return reserve_lex_one(ctx, n, P, lex_space(n, P, std::max(P.max_kb, value_bytes)), nullptr);
 } catch (...) {
     return RSX_ERR_NOMEM;
 }
@@ -1970,30 +1960,31 @@ int rsx_lexsort_device(rsx_ctx* ctx, const rsx_key_column* cols, uint32_t ncols,
     if (!ctx) return RSX_ERR_ARG;
     int rc = lex_columns_status(cols, ncols);
     if (rc) return lex_fail_columns(ctx, rc);
-    if (index_bytes != 4 && index_bytes != 8) return fail(ctx, RSX_ERR_ARG, "index_bytes must be 4 or 8");
+    rc = check_index_bytes(ctx, index_bytes);
+    if (rc) return rc;
     if (!unique_size_ok(n)) return fail(ctx, RSX_ERR_UNSUPPORTED, "2^32 or more keys");
     if (n == 0) return RSX_OK;
     if (!d_index) return fail(ctx, RSX_ERR_ARG, "null device pointer");
     if (!aligned(d_index, index_bytes)) return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
     rc = lex_check_pointers(ctx, cols, ncols);
     if (rc) return rc;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return fail(ctx, RSX_ERR_NODEVICE, "hipSetDevice failed");
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    Entry held(ctx, stream);
+    if (!held.ok) return no_device(ctx);
+    const hipStream_t st = held.st;
     if (n == 1) {  // the one position
         RSX_HIP(hipMemsetAsync(d_index, 0, index_bytes, st));
         return RSX_OK;
     }
     const LexPlan P = lex_plan(cols, ncols);
+    const LexSpace S = lex_space(n, P, 0);
     rc = pending_error(ctx);
     if (rc) return rc;
-    rc = reserve_lex_one(ctx, n, P, 0, st);
+    rc = reserve_lex_one(ctx, n, P, S, st);
     if (rc) return rc;
     Enqueue enq(ctx, st);  // the workspace arrays belong to this call from the first launch on
     char* sorted = nullptr;
     uint32_t es = 0, voff = 0;
-    rc = lex_rounds_locked(ctx, cols, P, n, &sorted, &es, &voff, st);
+    rc = lex_rounds_locked(ctx, cols, P, S, n, &sorted, &es, &voff, st);
     if (rc) return rc;
     // the split of rsx_argsort_device: the position alone, widened to the caller's index type
     return launch_pairs_split(ctx, sorted, nullptr, d_index, n, P.r[P.rounds - 1].w, 4, 2, index_bytes, RSX_KEY_UNSIGNED, 0, st);
@@ -2014,23 +2005,23 @@ int rsx_sort_columns_device(rsx_ctx* ctx, const rsx_key_column* cols, uint32_t n
     if (rc) return rc;
     if (value_bytes && !aligned(d_values, value_align(value_bytes))) return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
     if (n == 1) return RSX_OK;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return fail(ctx, RSX_ERR_NODEVICE, "hipSetDevice failed");
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    Entry held(ctx, stream);
+    if (!held.ok) return no_device(ctx);
+    const hipStream_t st = held.st;
     const LexPlan P = lex_plan(cols, ncols);
+    const LexSpace S = lex_space(n, P, std::max(P.max_kb, value_bytes));
     rc = pending_error(ctx);
     if (rc) return rc;
-    rc = reserve_lex_one(ctx, n, P, std::max(P.max_kb, value_bytes), st);
+    rc = reserve_lex_one(ctx, n, P, S, st);
     if (rc) return rc;
     Enqueue enq(ctx, st);  // the workspace arrays belong to this call from the first launch on
     char* sorted = nullptr;
     uint32_t es = 0, voff = 0;
-    rc = lex_rounds_locked(ctx, cols, P, n, &sorted, &es, &voff, st);
+    rc = lex_rounds_locked(ctx, cols, P, S, n, &sorted, &es, &voff, st);
     if (rc) return rc;
     // every column, then the values: a copy into the staging area, gathered back through the sorted positions.  The
     // rounds above have read every column for the last time; stream order keeps each copy in front of its gather.
-    char* stage = ctx->any_buf + 2 * lex_round256(n * (size_t)P.max_es);
+    char* stage = ctx->any_buf + S.stage_off;
     for (uint32_t j = 0; j < ncols; ++j) {
         void* col = const_cast<void*>(cols[j].d_keys);
         RSX_HIP(hipMemcpyAsync(stage, col, n * (size_t)cols[j].key_bytes, hipMemcpyDeviceToDevice, st));
@@ -2127,9 +2118,8 @@ int rsx_sort_host(rsx_ctx* ctx, void* data, size_t n, const rsx_layout* L) try {
     if (n <= 1) return RSX_OK;
     if (!data) return fail(ctx, RSX_ERR_ARG, "null host pointer");
     const size_t bytes = n * (size_t)L->elem_bytes;
-    std::lock_guard<std::mutex> lk(ctx->mu);  // one lock across copy-in, sort and copy-out: the staging buffers are the context's
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return fail(ctx, RSX_ERR_NODEVICE, "hipSetDevice failed");
+    Entry held(ctx);  // one lock across copy-in, sort and copy-out: the staging buffers are the context's
+    if (!held.ok) return no_device(ctx);
     if (bytes > ctx->host_bytes) {
         if (ctx->busy) RSX_HIP(hipEventSynchronize(ctx->last_event));
         for (void*& p : ctx->host_buf) {
@@ -2165,9 +2155,8 @@ int rsx_histogram_device(rsx_ctx* ctx, const void* d_src, size_t n, const rsx_la
     int rc = check_common(ctx, L);
     if (rc) return rc;
     if (digit >= L->key_bytes || !d_hist) return fail(ctx, RSX_ERR_ARG, "bad digit / null histogram");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    Entry held(ctx, stream);
+    const hipStream_t st = held.st;
     if (n == 0) {
         RSX_HIP(hipMemsetAsync(d_hist, 0, RADIX * sizeof(uint64_t), st));
         return RSX_OK;
@@ -2219,9 +2208,8 @@ int rsx_partition_device(rsx_ctx* ctx, const void* d_src, void* d_dst, size_t n,
     int rc = check_common(ctx, L);
     if (rc) return rc;
     if (digit >= L->key_bytes) return fail(ctx, RSX_ERR_ARG, "bad digit");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    Entry held(ctx, stream);
+    const hipStream_t st = held.st;
     if (n == 0) {
         if (d_hist) RSX_HIP(hipMemsetAsync(d_hist, 0, RADIX * sizeof(uint64_t), st));
         return RSX_OK;
@@ -2244,9 +2232,8 @@ int rsx_partition_count_device(rsx_ctx* ctx, const void* d_src, size_t n, const 
     if (rc) return rc;
     if (digit >= L->key_bytes) return fail(ctx, RSX_ERR_ARG, "bad digit");
     if (nsub == 0 || nsub > PART_MAX_SUB || !d_hist) return fail(ctx, RSX_ERR_ARG, "1..16 sub-ranges, non-null histogram");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    Entry held(ctx, stream);
+    const hipStream_t st = held.st;
     if (n && (!d_src || !aligned(d_src, elem_align(L->elem_bytes)))) return fail(ctx, RSX_ERR_ARG, "bad source pointer");
     rc = ensure_aux(ctx, st);
     if (rc) return rc;
@@ -2282,9 +2269,8 @@ int rsx_partition_scatter_device(rsx_ctx* ctx, const void* d_src, void* d_dst, s
     if (rc) return rc;
     if (digit >= L->key_bytes) return fail(ctx, RSX_ERR_ARG, "bad digit");
     if (nsub == 0 || nsub > PART_MAX_SUB || k >= nsub) return fail(ctx, RSX_ERR_ARG, "bad sub-range");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    Entry held(ctx, stream);
+    const hipStream_t st = held.st;
     const uint64_t beg = sub_start(n, nsub, k), nk = sub_start(n, nsub, k + 1) - beg;
     if (nk == 0) return RSX_OK;
     const uint32_t al = elem_align(L->elem_bytes);
@@ -2314,8 +2300,7 @@ int rsx_splitter_count_device(rsx_ctx* ctx, const void* d_data, size_t n, const 
     if (!layout_ok(L)) return fail(ctx, RSX_ERR_ARG, "invalid rsx_layout");
     if (nb == 0) return RSX_OK;
     if (digit >= L->key_bytes || !d_ranges || !d_prefix || !d_less || (n && !d_data)) return fail(ctx, RSX_ERR_ARG, "bad digit / null pointer");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
+    Entry held(ctx);
     hipLaunchKernelGGL(rsx_splitter_count_kernel, dim3(nb), dim3(RADIX), 0, static_cast<hipStream_t>(stream),
                        static_cast<const uint8_t*>(d_data), (uint64_t)n, L->elem_bytes, L->key_offset, L->key_bytes, L->key_kind,
                        d_ranges, d_prefix, digit, d_less);
@@ -2330,8 +2315,7 @@ int rsx_splitter_pick_device(rsx_ctx* ctx, const uint64_t* d_total, const uint64
     if (!ctx) return RSX_ERR_ARG;
     if (nb == 0) return RSX_OK;
     if (digit >= 16 || !d_total || !d_rank || !d_prefix) return fail(ctx, RSX_ERR_ARG, "bad digit / null pointer");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
+    Entry held(ctx);
     hipLaunchKernelGGL(rsx_splitter_pick_kernel, dim3(nb), dim3(RADIX), 0, static_cast<hipStream_t>(stream), d_total, d_rank,
                        d_prefix, digit);
     RSX_HIP(hipGetLastError());
@@ -2347,9 +2331,8 @@ int rsx_segmented_copy_device(rsx_ctx* ctx, const void* d_src, void* d_dst, uint
     if (nseg == 0) return RSX_OK;
     if (!d_src || !d_dst || !d_src_off || !d_dst_off || !d_len) return fail(ctx, RSX_ERR_ARG, "null pointer");
     if (!size_supported(elem_bytes)) return fail(ctx, RSX_ERR_UNSUPPORTED, "element size has no device kernel");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    Entry held(ctx, stream);
+    const hipStream_t st = held.st;
     return launchers_for(elem_bytes)->segcopy(ctx, d_src, d_dst, d_src_off, d_dst_off, d_len, nseg, st);
 } catch (...) {
     return RSX_ERR_HIP;
@@ -2366,9 +2349,8 @@ int rsx_bounds_ranges_device(rsx_ctx* ctx, const void* d_sorted, size_t n, const
     if (!layout_ok(L)) return fail(ctx, RSX_ERR_ARG, "invalid rsx_layout");
     if (nq == 0) return RSX_OK;
     if (!d_queries || !d_out || (n && !d_sorted)) return fail(ctx, RSX_ERR_ARG, "null pointer");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    Entry held(ctx, stream);
+    const hipStream_t st = held.st;
     hipLaunchKernelGGL(rsx_bounds_kernel, dim3((nq + 255) / 256), dim3(256), 0, st, static_cast<const uint8_t*>(d_sorted),
                        (uint64_t)n, L->elem_bytes, L->key_offset, L->key_bytes, L->key_kind, d_queries, nq, d_out,
                        d_ranges);
@@ -2764,9 +2746,8 @@ int rsx_generate_device(rsx_ctx* ctx, void* d_data, size_t n, const rsx_layout* 
     } else if (gen == RSX_GEN_ZIPF) {
         if (!(param > 0.0)) return fail(ctx, RSX_ERR_ARG, "Zipf generator needs param > 0");
     }
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    Entry held(ctx, stream);
+    const hipStream_t st = held.st;
     uint64_t blocks = (n + 255) / 256;
     const uint64_t cap = (uint64_t)ctx->num_cu * 16;
     if (blocks > cap) blocks = cap;
@@ -2785,9 +2766,8 @@ int rsx_verify_device(rsx_ctx* ctx, const void* d_data, size_t n, const rsx_layo
     if (!layout_ok(L, true)) return fail(ctx, RSX_ERR_ARG, "invalid rsx_layout");
     if (L->elem_bytes > RSX_MAX_ELEM_BYTES) return fail(ctx, RSX_ERR_UNSUPPORTED, "element larger than RSX_MAX_ELEM_BYTES");
     if (!d_out) return fail(ctx, RSX_ERR_ARG, "null pointer");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    Entry held(ctx, stream);
+    const hipStream_t st = held.st;
     RSX_HIP(hipMemsetAsync(d_out, 0, 3 * sizeof(uint64_t), st));
     if (n == 0) return RSX_OK;
     if (!d_data) return fail(ctx, RSX_ERR_ARG, "null pointer");

@@ -1,7 +1,12 @@
-// rsx_internal.hpp -- host-side state and helpers shared by the translation units of librsx.so:
-//   rsx.hip     the C-ABI of include/rsx.h (context, pass loop, multi-GPU driver, harness)
-//   rsx_es.hip  the kernel launchers of ONE element size (compiled once per size with -DRSX_ES=n,
-//               so the eight sizes build in parallel), reached through that size's EsLaunchers table
+// rsx_internal.hpp -- host-side state and helpers shared by the fourteen translation units of librsx.so:
+//   rsx.hip         the C-ABI of include/rsx.h (context, pass loop, multi-GPU driver, harness)
+//   rsx_es.hip      the kernel launchers of ONE element size (compiled once per size with -DRSX_ES=n,
+//                   so the eight sizes build in parallel), reached through that size's EsLaunchers table
+//   rsx_pairs.hip   the join and split kernels of the key / value calls
+//   rsx_unique.hip  the run kernels of rsx_unique_device
+//   rsx_reduce.hip  those of rsx_reduce_by_key_device
+//   rsx_search.hip  the kernel of rsx_search_sorted_device
+//   rsx_lex.hip     the join of several key columns (rsx_lexsort_device, rsx_sort_columns_device)
 #pragma once
 #include "rsx_device.hpp"
 
@@ -56,6 +61,23 @@ constexpr uint32_t HV_ERROR = 0, HV_MID_HINT = 8, HV_WIDE_HINT = 9;
 // rsx_sort_host: bytes of one pinned staging buffer -- the largest chunk RSX_OPT_HOST_CHUNK takes, and its default
 constexpr size_t HOST_CHUNK = 32u << 20;
 constexpr int HOST_RING = 4;
+// every array carved out of a workspace starts on a 256-byte boundary
+constexpr size_t round256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+
+// rsx_ctx::last_path, what the last call ran.  The values are frozen: RSX_INFO_LAST_PASSES reports them in bits 24..27.
+enum : uint32_t {
+    PATH_LSD = 0,        // general passes
+    PATH_SMALL = 1,      // one-launch sort
+    PATH_MID_SPLIT = 2,  // middle-size bucket split
+    PATH_COUNT8 = 3,     // one-byte counting
+    PATH_COUNT16 = 4,    // two-byte counting
+    PATH_WIDE = 5,       // wide-key hybrid (the device's verdict says whether it ran)
+    PATH_SEGMENTS = 6,   // segmented and row sorts
+    PATH_TOPK = 7,
+    PATH_UNIQUE = 8,
+    PATH_REDUCE = 9,
+    PATH_SEARCH = 10,
+};
 
 // option bits (rsx_ctx_set_option): alternative kernel paths, all bit-exact
 enum : uint32_t {
@@ -108,7 +130,7 @@ struct rsx_ctx {
     uint64_t* shard_host = nullptr;  // pinned: answers, then the 256 counts
     std::vector<uint64_t> shard_stage;
     int num_cu = 256;
-    uint32_t last_path = 0;    // 0 general passes, 1 one-launch sort, 2 middle-size bucket split, 3 / 4 one- / two-byte counting
+    uint32_t last_path = 0;    // rsxh::PATH_*
     uint32_t last_sort_passes = 0;  // sweep passes of the last sort (RSX_INFO_LAST_PASSES)
     uint32_t last_route = 0;   // how the last sort reached the kernels: 0 direct, 1 packed re-layout, 2 key-index proxy
     char* any_buf = nullptr;   // routes 1 / 2: the re-laid-out elements or the proxies, and their ping-pong array
@@ -411,7 +433,7 @@ inline size_t topk_workspace_half(uint32_t es, uint64_t rows, uint64_t row_len, 
     if (row_len <= L) return 0;
     const uint64_t cpr = (row_len + L - 1) / L, last = row_len - (cpr - 1) * L;
     const uint64_t m1 = (cpr - 1) * k + (k < last ? k : last);
-    return ((size_t)(rows * m1) * es + 255) & ~(size_t)255;
+    return round256((size_t)(rows * m1) * es);
 }
 
 // ---- per-element-size launchers: defined in rsx_launch_impl.hpp; rsx_es.hip fills ONE size's table with them (which

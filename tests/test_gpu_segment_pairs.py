@@ -327,3 +327,36 @@ def test_graph_capture(rs, torch):
     c.check()
     assert torch.equal(bout.to(torch.int64), torch.sort(big, dim=-1, stable=True).indices)
     c.close()
+
+
+@pytest.mark.parametrize("vb", [12, 3])
+def test_reserve_pairs_then_captured_wide_values(rs, torch, vb):
+    """reserve_pairs alone readies a fresh context for a CAPTURED call on values without a fused kernel (route 4: proxies,
+    the copy of the values behind them, a gather): 12-byte values, and 3-byte ones, for which that route's workspace is
+    the largest of the three sizes the reserve entry asks for.  Three segments of 4099 keys, a head and a tail outside."""
+    from segment_pairs_gpu import guarded, key_tensor, same
+    from segment_pairs_ref import with_guards
+    n, offs = 4099, [3, 1400, 2801, 4090]
+    rng = np.random.default_rng(vb)
+    keys_raw = util.make_input("u32", n, "two", seed=5)
+    v = rng.integers(0, 256, size=(n, vb), dtype=np.uint8)
+    v[:, 0] = np.arange(n) & 0xFF  # (neighbours differ: a tie out of order shows)
+    values_raw = v.reshape(-1)
+    wk, wv, _local = segments_reference(keys_raw, values_raw, 4, U, vb, True, offs)
+    c = rs.Context(torch.cuda.current_device())
+    c.reserve_pairs(n, 4, vb)
+    kbuf, kmid = guarded(torch, keys_raw)
+    vbuf, vmid = guarded(torch, values_raw)
+    o = torch.from_numpy(np.asarray(offs, dtype=np.int64)).cuda()
+    s = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=s):
+        rs.radix_sort_segments_pairs(key_tensor(torch, kmid, "u32"), vmid.view(n, vb), o, descending=True, ctx=c)
+    graph.replay()
+    torch.cuda.synchronize()
+    c.check()
+    assert c.get_info(rs.INFO_LAST_PAIRS) == expected_info(4, vb)
+    assert same(kbuf.cpu().numpy(), with_guards(wk, 0), ("keys", vb))
+    assert same(vbuf.cpu().numpy(), with_guards(wv, 0), ("values", vb))
+    c.close()
