@@ -3,12 +3,9 @@
 `hipcc --offload-arch=gfx950` cross-compiles without a GPU; the resulting
 radix_sort_amd/lib/librsx.so is git-ignored but travels to the GPU box.
 
-The library is fourteen translation units: rsx.hip (the C-ABI and the size-independent kernels), rsx_pairs.hip
-(the join and split kernels of the key / value calls), rsx_unique.hip (the run kernels of rsx_unique_device),
-rsx_reduce.hip (those of rsx_reduce_by_key_device), rsx_search.hip (the kernel of rsx_search_sorted_device), rsx_lex.hip (the join of several key columns behind
-rsx_lexsort_device and rsx_sort_columns_device) and rsx_es.hip once per element size
-(-DRSX_ES=1,2,4,8,12,16,24,32), compiled in parallel and linked into one shared object.  `python -m radix_sort_amd._build --variant NAME --es 4 -DX=1 ...` relinks a
-tuning variant (lib/v/NAME.so) that recompiles only the named size with the extra flags.
+The library is the translation units of UNITS below (one line each, with what it holds; rsx_es.hip once per element
+size), compiled in parallel and linked into one shared object.  `python -m radix_sort_amd._build --variant NAME --es 4
+-DX=1 ...` relinks a tuning variant (lib/v/NAME.so) that recompiles only the named size with the extra flags.
 """
 from __future__ import annotations
 
@@ -24,9 +21,18 @@ LIBDIR = os.path.join(_HERE, "lib")
 OBJDIR = os.path.join(LIBDIR, "obj")
 LIB = os.path.join(LIBDIR, "librsx.so")
 ELEM_SIZES = (1, 2, 4, 8, 12, 16, 24, 32)
-DEPS = ["rsx.hip", "rsx_es.hip", "rsx_device.hpp", "rsx_internal.hpp", "rsx_launch_impl.hpp", "rsx_misc_kernels.hpp", "rsx_small_kernel.hpp", "rsx_mid_kernels.hpp", "rsx_any_kernels.hpp", "rsx_segment_kernels.hpp", "rsx_segment_pairs_kernels.hpp", "rsx_topk_kernels.hpp",
-        "rsx_pairs.hip", "rsx_pairs_kernels.hpp", "rsx_unique.hip", "rsx_unique_kernels.hpp", "rsx_reduce.hip", "rsx_reduce_kernels.hpp", "rsx_lex.hip", "rsx_lex_kernels.hpp", "rsx_search.hip", "rsx_search_kernels.hpp",
-        os.path.join("..", "..", "include", "rsx.h")]
+# (source, object name, extra flags): every translation unit of the library, in link order
+UNITS = (
+    ("rsx.hip", "rsx.o", ()),                # the C-ABI and the size-independent kernels
+    ("rsx_pairs.hip", "rsx_pairs.o", ()),    # the join and split kernels of the key / value calls
+    ("rsx_unique.hip", "rsx_unique.o", ()),  # the run kernels of rsx_unique_device
+    ("rsx_reduce.hip", "rsx_reduce.o", ()),  # those of rsx_reduce_by_key_device
+    ("rsx_lex.hip", "rsx_lex.o", ()),        # the join of several key columns: rsx_lexsort_device, rsx_sort_columns_device
+    ("rsx_search.hip", "rsx_search.o", ()),  # the kernel of rsx_search_sorted_device
+) + tuple(("rsx_es.hip", f"rsx_es{es}.o", (f"-DRSX_ES={es}",)) for es in ELEM_SIZES)  # the sort kernels, once per element size
+# what the library is stale against: every unit, every header beside them, and the public header
+DEPS = sorted({src for src, _obj, _flags in UNITS}) + sorted(f for f in os.listdir(CSRC) if f.endswith(".hpp")) + \
+    [os.path.join("..", "..", "include", "rsx.h")]
 CXXFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 
 
@@ -58,29 +64,12 @@ def _objects(extra, only_es, objdir, verbose, reuse_from=None):
     other sizes' objects are taken from `reuse_from` (the main build) instead of being recompiled."""
     os.makedirs(objdir, exist_ok=True)
     jobs, objs = [], []
-    host = os.path.join(objdir, "rsx.o")
-    pairs = os.path.join(objdir, "rsx_pairs.o")
-    unique = os.path.join(objdir, "rsx_unique.o")
-    reduce_ = os.path.join(objdir, "rsx_reduce.o")
-    lex = os.path.join(objdir, "rsx_lex.o")
-    search = os.path.join(objdir, "rsx_search.o")
-    if only_es is None:
-        jobs.append(("rsx.hip", host, list(extra), verbose))
-        jobs.append(("rsx_pairs.hip", pairs, list(extra), verbose))
-        jobs.append(("rsx_unique.hip", unique, list(extra), verbose))
-        jobs.append(("rsx_reduce.hip", reduce_, list(extra), verbose))
-        jobs.append(("rsx_lex.hip", lex, list(extra), verbose))
-        jobs.append(("rsx_search.hip", search, list(extra), verbose))
-        objs += [host, pairs, unique, reduce_, lex, search]
-    else:
-        objs += [os.path.join(reuse_from, "rsx.o"), os.path.join(reuse_from, "rsx_pairs.o"), os.path.join(reuse_from, "rsx_unique.o"),
-                 os.path.join(reuse_from, "rsx_reduce.o"), os.path.join(reuse_from, "rsx_lex.o"), os.path.join(reuse_from, "rsx_search.o")]
-    for es in ELEM_SIZES:
-        if only_es is None or es in only_es:
-            obj = os.path.join(objdir, f"rsx_es{es}.o")
-            jobs.append(("rsx_es.hip", obj, [f"-DRSX_ES={es}"] + list(extra), verbose))
+    for src, name, flags in UNITS:
+        if only_es is None or any(f"-DRSX_ES={es}" in flags for es in only_es):
+            obj = os.path.join(objdir, name)
+            jobs.append((src, obj, list(flags) + list(extra), verbose))
         else:
-            obj = os.path.join(reuse_from, f"rsx_es{es}.o")
+            obj = os.path.join(reuse_from, name)
         objs.append(obj)
     workers = min(len(jobs), max(1, (os.cpu_count() or 2)))
     with concurrent.futures.ThreadPoolExecutor(max_workers=workers) as pool:

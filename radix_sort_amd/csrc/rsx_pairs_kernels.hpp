@@ -77,6 +77,8 @@ __device__ __forceinline__ void pairs_store(uint8_t* __restrict__ p, const unsig
 struct PairsU128 {
     uint64_t lo, hi;
 };
+__device__ __forceinline__ bool operator!=(const PairsU128& a, const PairsU128& b) { return a.lo != b.lo || a.hi != b.hi; }
+__device__ __forceinline__ bool operator<(const PairsU128& a, const PairsU128& b) { return a.hi < b.hi || (a.hi == b.hi && a.lo < b.lo); }
 template <int KB> struct PairsKey;
 template <> struct PairsKey<1> { using type = uint8_t; };
 template <> struct PairsKey<2> { using type = uint16_t; };
@@ -117,6 +119,29 @@ __device__ __forceinline__ PairsU128 pairs_unmap<PairsU128>(PairsU128 k, uint32_
     }
     if (kind == PAIRS_SIGNED) k.hi ^= 1ull << 63;
     return k;
+}
+
+// A wave shuffle of a key or value of any width up to 16 bytes (an integer or PairsU128): 32-bit words, each on its own
+template <typename T, typename F>
+__device__ __forceinline__ T pairs_shfl(T x, F&& word) {
+    if constexpr (sizeof(T) <= 4) {
+        return (T)word((uint32_t)x);
+    } else {
+        uint32_t w[sizeof(T) / 4];
+        __builtin_memcpy(w, &x, sizeof(T));
+#pragma unroll
+        for (int i = 0; i < (int)(sizeof(T) / 4); ++i) w[i] = word(w[i]);
+        __builtin_memcpy(&x, w, sizeof(T));
+        return x;
+    }
+}
+template <typename T>
+__device__ __forceinline__ T pairs_shfl_up(T x, int o) {
+    return pairs_shfl(x, [o](uint32_t w) { return (uint32_t)__shfl_up(w, o); });
+}
+template <typename T>
+__device__ __forceinline__ T pairs_shfl_xor(T x, int o) {
+    return pairs_shfl(x, [o](uint32_t w) { return (uint32_t)__shfl_xor(w, o); });
 }
 
 // V consecutive elements from e0 on

@@ -1,9 +1,8 @@
 // rsx_reduce_kernels.hpp -- the run kernels behind rsx_reduce_by_key_device (rsx.hip; launched by rsx_reduce.hip): what
 // follows the sort of the joined (mapped key, value) elements (rsx_pairs_kernels.hpp) when the caller wants ONE value per
 // group of equal keys: the sum, minimum or maximum of the group's values.  Heads are those of rsx_unique_kernels.hpp
-// (element i is a HEAD when i == 0 or its mapped key differs from that of element i - 1), and reduce_differ, reduce_flags
-// and reduce_share below are that header's unique_differ, unique_flags and unique_share: the header itself defines a
-// kernel that is no template, so only one translation unit of the library can include it.  Three launches, tiled alike
+// (element i is a HEAD when i == 0 or its mapped key differs from that of element i - 1), found and written out by the
+// helpers the two sets of run kernels share (rsx_runs.hpp).  Three launches, tiled alike
 // (reduce_tile elements per workgroup of 256 threads, every thread reduce_ipt CONSECUTIVE elements: one run of 64
 // bytes, or 48 for the 12- and 24-byte elements, loaded in 16-byte words):
 //   rsx_reduce_count_kernel  tile t -> tile_heads[t], the heads among its elements, and tile_tail[t], the (+) of its
@@ -26,8 +25,7 @@
 // out_num [1].
 #pragma once
 
-#include "rsx_device.hpp"
-#include "rsx_pairs_kernels.hpp"
+#include "rsx_runs.hpp"
 
 namespace rsx {
 
@@ -40,57 +38,6 @@ constexpr uint32_t reduce_elem(uint32_t kb, uint32_t vb) { return pairs_elem(kb,
 // elements per thread: whole 16-byte words -- 64 bytes of elements, 48 where the element is 12 or 24 bytes
 constexpr uint32_t reduce_ipt(uint32_t e) { return e == 12 ? 4u : e == 24 ? 2u : e <= 4 ? 16u : 64u / e; }
 constexpr uint32_t reduce_tile(uint32_t e) { return REDUCE_WG * reduce_ipt(e); }
-
-template <typename K>
-__device__ __forceinline__ bool reduce_differ(const K& a, const K& b) {
-    return a != b;
-}
-template <>
-__device__ __forceinline__ bool reduce_differ<PairsU128>(const PairsU128& a, const PairsU128& b) {
-    return a.lo != b.lo || a.hi != b.hi;
-}
-
-// One thread's elements [e0, e0 + cnt) into `er` (cnt <= IPT; the whole run in 16-byte words when cnt == IPT, zeros behind
-// cnt) and its head flags: bit j set when element e0 + j is a head.  The key in front of e0 comes from global memory (a
-// line the neighbouring thread loads anyway); element 0 has none.
-template <int KB, int E, int IPT>
-__device__ __forceinline__ uint32_t reduce_flags(const uint8_t* __restrict__ elems, uint64_t e0, uint32_t cnt, unsigned char* er) {
-    using K = typename PairsKey<KB>::type;
-    if (cnt == (uint32_t)IPT) {
-        pairs_load<E * IPT>(er, elems + e0 * E);
-    } else {
-#pragma unroll
-        for (int j = 0; j < IPT; ++j) {
-            if ((uint32_t)j < cnt) pairs_load<E>(er + j * E, elems + (e0 + (uint64_t)j) * E);
-            else __builtin_memset(er + j * E, 0, E);
-        }
-    }
-    K prev{};
-    if (cnt != 0 && e0 != 0) {
-        unsigned char pr[KB];
-        pairs_load<KB>(pr, elems + (e0 - 1) * E);
-        __builtin_memcpy(&prev, pr, KB);
-    }
-    uint32_t flags = 0;
-#pragma unroll
-    for (int j = 0; j < IPT; ++j) {
-        K k;
-        __builtin_memcpy(&k, er + j * E, KB);
-        const bool head = (j == 0 && e0 == 0) || reduce_differ<K>(k, prev);
-        if ((uint32_t)j < cnt && head) flags |= 1u << j;
-        prev = k;
-    }
-    return flags;
-}
-
-// this thread's first element and how many of the tile's it holds (0: none, behind the end of the array)
-template <int IPT>
-__device__ __forceinline__ uint32_t reduce_share(uint64_t n, uint64_t* e0) {
-    *e0 = ((uint64_t)blockIdx.x * REDUCE_WG + threadIdx.x) * IPT;
-    if (*e0 >= n) return 0;
-    const uint64_t left = n - *e0;
-    return left < (uint64_t)IPT ? (uint32_t)left : (uint32_t)IPT;
-}
 
 // A value type: VB bytes of kind VK (0 unsigned, PAIRS_SIGNED, PAIRS_FLOAT), held as its bit pattern.
 template <int VB, int VK>
@@ -142,15 +89,6 @@ __device__ __forceinline__ ReduceItem<U> reduce_join(const ReduceItem<U>& l, con
     o.f = l.f | r.f;
     return o;
 }
-template <typename U>
-__device__ __forceinline__ U reduce_shfl_up(U x, int o) {
-    if constexpr (sizeof(U) == 4) {
-        return (U)__shfl_up((unsigned)x, o);
-    } else {
-        const uint32_t lo = __shfl_up((unsigned)x, o), hi = __shfl_up((unsigned)(x >> 32), o);
-        return (U)lo | (U)hi << 32;
-    }
-}
 // inclusive segmented scan over the 64 lanes of a wave
 template <typename RV, typename U>
 __device__ __forceinline__ ReduceItem<U> reduce_wave_scan(ReduceItem<U> x, uint32_t op) {
@@ -158,7 +96,7 @@ __device__ __forceinline__ ReduceItem<U> reduce_wave_scan(ReduceItem<U> x, uint3
 #pragma unroll
     for (int o = 1; o < (int)WAVE; o <<= 1) {
         ReduceItem<U> y;
-        y.v = reduce_shfl_up<U>(x.v, o);
+        y.v = pairs_shfl_up<U>(x.v, o);
         y.f = __shfl_up(x.f, o);
         if (lane >= (uint32_t)o) x = reduce_join<RV, U>(y, x, op);
     }
@@ -195,9 +133,9 @@ __global__ __launch_bounds__(REDUCE_WG) void rsx_reduce_count_kernel(const uint8
     __shared__ U s_v[NW];
     __shared__ uint32_t s_f[NW];
     uint64_t e0;
-    const uint32_t cnt = reduce_share<IPT>(n, &e0);
+    const uint32_t cnt = runs_share<REDUCE_WG, IPT>(n, &e0);
     unsigned char er[E * IPT];
-    const uint32_t flags = reduce_flags<KB, E, IPT>(elems, e0, cnt, er);
+    const uint32_t flags = runs_flags<KB, E, IPT>(elems, e0, cnt, er);
     U s[IPT];
     const ReduceItem<U> mine = reduce_thread_scan<RV, E, IPT, VOFF, U>(er, flags, cnt, op, s);
     const uint32_t incl = wave_incl_scan<false>((uint32_t)__popc(flags));
@@ -265,7 +203,7 @@ __global__ __launch_bounds__(REDUCE_SCAN_WG) void rsx_reduce_scan_kernel(const u
         }
         // the lanes in front of this one: the wave's inclusive scan of the lane before
         ReduceItem<U> lanes;
-        lanes.v = reduce_shfl_up<U>(wi.v, 1);
+        lanes.v = pairs_shfl_up<U>(wi.v, 1);
         lanes.f = __shfl_up(wi.f, 1);
         if ((threadIdx.x & (WAVE - 1)) == 0) lanes.f = 0;
         front = reduce_join<RV, U>(front, lanes, op);
@@ -298,9 +236,9 @@ __global__ __launch_bounds__(REDUCE_WG) void rsx_reduce_write_kernel(const uint8
     __shared__ U s_v[NW];
     __shared__ uint32_t s_f[NW];
     uint64_t e0;
-    const uint32_t cnt = reduce_share<IPT>(n, &e0);
+    const uint32_t cnt = runs_share<REDUCE_WG, IPT>(n, &e0);
     unsigned char er[E * IPT];
-    const uint32_t flags = reduce_flags<KB, E, IPT>(elems, e0, cnt, er);
+    const uint32_t flags = runs_flags<KB, E, IPT>(elems, e0, cnt, er);
     // bit j: element e0 + j is the last of its run.  Inside the thread that is the next flag; behind the thread's last
     // element it is the successor's key in global memory (a line the neighbouring thread loads anyway), or the array's end.
     uint32_t lasts = flags >> 1;
@@ -312,7 +250,7 @@ __global__ __launch_bounds__(REDUCE_WG) void rsx_reduce_write_kernel(const uint8
             K nk, lk;
             __builtin_memcpy(&nk, nr, KB);
             __builtin_memcpy(&lk, er + (IPT - 1) * E, KB);
-            end = reduce_differ<K>(nk, lk);
+            end = nk != lk;
         }
         if (end) lasts |= 1u << (cnt - 1);
     }
@@ -341,28 +279,13 @@ __global__ __launch_bounds__(REDUCE_WG) void rsx_reduce_write_kernel(const uint8
         if ((uint32_t)w < wave) front = reduce_join<RV, U>(front, ReduceItem<U>{s_v[w], s_f[w]}, op);
     }
     ReduceItem<U> lanes;
-    lanes.v = reduce_shfl_up<U>(wi.v, 1);
+    lanes.v = pairs_shfl_up<U>(wi.v, 1);
     lanes.f = __shfl_up(wi.f, 1);
     if ((threadIdx.x & (WAVE - 1)) == 0) lanes.f = 0;
     front = reduce_join<RV, U>(front, lanes, op);
     if (cnt == 0) return;
     const uint64_t first = tile_base[blockIdx.x] + below + (incl - heads);  // heads in front of element e0
-    if (out_keys || out_offsets) {
-#pragma unroll
-        for (int j = 0; j < IPT; ++j) {
-            if (!(flags >> j & 1u)) continue;
-            const uint64_t r = first + (uint32_t)__popc(flags & ((1u << j) - 1u));
-            if (out_keys) {
-                K k;
-                __builtin_memcpy(&k, er + j * E, KB);
-                k = pairs_unmap<K>(k, kind, desc);
-                unsigned char kr[KB];
-                __builtin_memcpy(kr, &k, KB);
-                pairs_store<KB>(out_keys + r * KB, kr);
-            }
-            if (out_offsets) out_offsets[r] = e0 + (uint64_t)j;
-        }
-    }
+    runs_write_heads<KB, E, IPT>(er, flags, first, e0, out_keys, out_offsets, kind, desc);
     if (out_values) {
 #pragma unroll
         for (int j = 0; j < IPT; ++j) {

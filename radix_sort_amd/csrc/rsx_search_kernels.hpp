@@ -42,31 +42,10 @@ constexpr uint32_t search_tile(uint32_t kb) { return SEARCH_WG * search_ipt(kb);
 // the needle element: the key alone, or the joined (mapped key, u32 position)
 constexpr uint32_t search_elem(uint32_t kb, bool pos) { return pos ? pairs_elem(kb, 4u) : kb; }
 
-template <typename K>
-__device__ __forceinline__ bool search_less(const K& a, const K& b) {
-    return a < b;
-}
-template <>
-__device__ __forceinline__ bool search_less<PairsU128>(const PairsU128& a, const PairsU128& b) {
-    return a.hi < b.hi || (a.hi == b.hi && a.lo < b.lo);
-}
 // UP false: a < key (lower bound); UP true: a <= key (upper bound)
 template <typename K, bool UP>
 __device__ __forceinline__ bool search_before(const K& a, const K& key) {
-    return UP ? !search_less<K>(key, a) : search_less<K>(a, key);
-}
-
-template <typename K>
-__device__ __forceinline__ K search_shfl_xor(K k, int o) {
-    return (K)__shfl_xor((uint32_t)k, o);
-}
-template <>
-__device__ __forceinline__ uint64_t search_shfl_xor<uint64_t>(uint64_t k, int o) {
-    return __shfl_xor(k, o);
-}
-template <>
-__device__ __forceinline__ PairsU128 search_shfl_xor<PairsU128>(PairsU128 k, int o) {
-    return PairsU128{__shfl_xor(k.lo, o), __shfl_xor(k.hi, o)};
+    return UP ? !(key < a) : a < key;
 }
 
 template <typename K>
@@ -238,16 +217,16 @@ __global__ __launch_bounds__(SEARCH_WG) void rsx_search_kernel(const uint8_t* __
             } else {
                 key[j] = pairs_map<K>(key[j], kind, desc);
             }
-            if (search_less<K>(key[j], kmin)) kmin = key[j];
-            if (search_less<K>(kmax, key[j])) kmax = key[j];
+            if (key[j] < kmin) kmin = key[j];
+            if (kmax < key[j]) kmax = key[j];
         }
     }
     // (a lane without a valid needle holds kmin = all ones, kmax = 0: it changes neither; every tile has a valid needle)
 #pragma unroll
     for (int w = WAVE / 2; w > 0; w >>= 1) {
-        const K a = search_shfl_xor<K>(kmin, w), b = search_shfl_xor<K>(kmax, w);
-        if (search_less<K>(a, kmin)) kmin = a;
-        if (search_less<K>(kmax, b)) kmax = b;
+        const K a = pairs_shfl_xor<K>(kmin, w), b = pairs_shfl_xor<K>(kmax, w);
+        if (a < kmin) kmin = a;
+        if (kmax < b) kmax = b;
     }
     const uint32_t wave = threadIdx.x / WAVE;
     if ((threadIdx.x & (WAVE - 1)) == 0) {
@@ -261,9 +240,9 @@ __global__ __launch_bounds__(SEARCH_WG) void rsx_search_kernel(const uint8_t* __
 #pragma unroll
         for (int w = 1; w < NW; ++w) {
             if (wave == 0) {
-                if (search_less<K>(s_min[w], k)) k = s_min[w];
+                if (s_min[w] < k) k = s_min[w];
             } else {
-                if (search_less<K>(k, s_max[w])) k = s_max[w];
+                if (k < s_max[w]) k = s_max[w];
             }
         }
         const uint64_t r = wave == 0 ? search_wave_bound<KB, false>(sorted, N, k, kind, desc) : search_wave_bound<KB, true>(sorted, N, k, kind, desc);

@@ -12,13 +12,13 @@
 //                            a head of rank r at i writes out_keys[r] (mapping undone) and out_offsets[r] = i; every
 //                            element writes out_perm[i] = its position and out_inverse[position] = the rank of its run.
 // No workgroup waits for another one: the three launches are the only ordering ("Groups of equal
-// keys", has the trade against a chained single-pass scan).  The partial last tile goes element by element.  No kernel
-// reads outside the n elements or writes outside tile_heads / tile_base [tiles], out_keys [m], out_offsets [m + 1],
-// out_perm [n], out_inverse [n] and out_num [1].
+// keys", has the trade against a chained single-pass scan).  A thread's share of the tile, its head flags and the
+// write-out of its heads are rsx_runs.hpp's, shared with rsx_reduce_kernels.hpp.  The partial last tile goes element by
+// element.  No kernel reads outside the n elements or writes outside tile_heads / tile_base [tiles], out_keys [m],
+// out_offsets [m + 1], out_perm [n], out_inverse [n] and out_num [1].
 #pragma once
 
-#include "rsx_device.hpp"
-#include "rsx_pairs_kernels.hpp"
+#include "rsx_runs.hpp"
 
 namespace rsx {
 
@@ -31,66 +31,15 @@ constexpr uint32_t unique_elem(uint32_t kb, bool pos) { return pairs_elem(kb, po
 constexpr uint32_t unique_ipt(uint32_t e) { return e <= 4 ? 16u : 64u / e; }
 constexpr uint32_t unique_tile(uint32_t e) { return UNIQUE_WG * unique_ipt(e); }
 
-template <typename K>
-__device__ __forceinline__ bool unique_differ(const K& a, const K& b) {
-    return a != b;
-}
-template <>
-__device__ __forceinline__ bool unique_differ<PairsU128>(const PairsU128& a, const PairsU128& b) {
-    return a.lo != b.lo || a.hi != b.hi;
-}
-
-// One thread's elements [e0, e0 + cnt) into `er` (cnt <= IPT; the whole run in 16-byte words when cnt == IPT) and its
-// head flags: bit j set when element e0 + j is a head.  The key in front of e0 comes from global memory (a line the
-// neighbouring thread loads anyway); element 0 has none.
-template <int KB, int E, int IPT>
-__device__ __forceinline__ uint32_t unique_flags(const uint8_t* __restrict__ elems, uint64_t e0, uint32_t cnt, unsigned char* er) {
-    using K = typename PairsKey<KB>::type;
-    if (cnt == (uint32_t)IPT) {
-        pairs_load<E * IPT>(er, elems + e0 * E);
-    } else {
-#pragma unroll
-        for (int j = 0; j < IPT; ++j) {
-            if ((uint32_t)j < cnt) pairs_load<E>(er + j * E, elems + (e0 + (uint64_t)j) * E);
-            else __builtin_memset(er + j * E, 0, E);
-        }
-    }
-    K prev{};
-    if (cnt != 0 && e0 != 0) {
-        unsigned char pr[KB];
-        pairs_load<KB>(pr, elems + (e0 - 1) * E);
-        __builtin_memcpy(&prev, pr, KB);
-    }
-    uint32_t flags = 0;
-#pragma unroll
-    for (int j = 0; j < IPT; ++j) {
-        K k;
-        __builtin_memcpy(&k, er + j * E, KB);
-        const bool head = (j == 0 && e0 == 0) || unique_differ<K>(k, prev);
-        if ((uint32_t)j < cnt && head) flags |= 1u << j;
-        prev = k;
-    }
-    return flags;
-}
-
-// this thread's first element and how many of the tile's it holds (0: none, behind the end of the array)
-template <int IPT>
-__device__ __forceinline__ uint32_t unique_share(uint64_t n, uint64_t* e0) {
-    *e0 = ((uint64_t)blockIdx.x * UNIQUE_WG + threadIdx.x) * IPT;
-    if (*e0 >= n) return 0;
-    const uint64_t left = n - *e0;
-    return left < (uint64_t)IPT ? (uint32_t)left : (uint32_t)IPT;
-}
-
 template <int KB, bool POS>
 __global__ __launch_bounds__(UNIQUE_WG) void rsx_unique_count_kernel(const uint8_t* __restrict__ elems, uint64_t n,
                                                                      uint32_t* __restrict__ tile_heads) {
     constexpr int E = (int)unique_elem(KB, POS), IPT = (int)unique_ipt(E);
     __shared__ uint32_t s_wave[UNIQUE_WG / WAVE];
     uint64_t e0;
-    const uint32_t cnt = unique_share<IPT>(n, &e0);
+    const uint32_t cnt = runs_share<UNIQUE_WG, IPT>(n, &e0);
     unsigned char er[E * IPT];
-    const uint32_t heads = (uint32_t)__popc(unique_flags<KB, E, IPT>(elems, e0, cnt, er));
+    const uint32_t heads = (uint32_t)__popc(runs_flags<KB, E, IPT>(elems, e0, cnt, er));
     const uint32_t incl = wave_incl_scan<false>(heads);
     if ((threadIdx.x & (WAVE - 1)) == WAVE - 1) s_wave[threadIdx.x / WAVE] = incl;
     __syncthreads();
@@ -144,14 +93,13 @@ __global__ __launch_bounds__(UNIQUE_WG) void rsx_unique_write_kernel(const uint8
                                                                      uint8_t* __restrict__ out_inverse, uint32_t perm_words, uint32_t kind,
                                                                      uint32_t desc) {
     constexpr int E = (int)unique_elem(KB, POS), IPT = (int)unique_ipt(E), VOFF = (int)pairs_voff(KB, 4);
-    using K = typename PairsKey<KB>::type;
     using I = typename std::conditional<IB == 4, uint32_t, uint64_t>::type;
     constexpr int NW = (int)(UNIQUE_WG / WAVE);
     __shared__ uint32_t s_wave[NW];
     uint64_t e0;
-    const uint32_t cnt = unique_share<IPT>(n, &e0);
+    const uint32_t cnt = runs_share<UNIQUE_WG, IPT>(n, &e0);
     unsigned char er[E * IPT];
-    const uint32_t flags = unique_flags<KB, E, IPT>(elems, e0, cnt, er);
+    const uint32_t flags = runs_flags<KB, E, IPT>(elems, e0, cnt, er);
     const uint32_t heads = (uint32_t)__popc(flags);
     const uint32_t incl = wave_incl_scan<false>(heads);
     const uint32_t wave = threadIdx.x / WAVE;
@@ -162,22 +110,7 @@ __global__ __launch_bounds__(UNIQUE_WG) void rsx_unique_write_kernel(const uint8
     for (int w = 0; w < NW; ++w) below += (uint32_t)w < wave ? s_wave[w] : 0u;
     if (cnt == 0) return;
     const uint64_t first = tile_base[blockIdx.x] + below + (incl - heads);  // heads in front of element e0
-    if (out_keys || out_offsets) {
-#pragma unroll
-        for (int j = 0; j < IPT; ++j) {
-            if (!(flags >> j & 1u)) continue;
-            const uint64_t r = first + (uint32_t)__popc(flags & ((1u << j) - 1u));
-            if (out_keys) {
-                K k;
-                __builtin_memcpy(&k, er + j * E, KB);
-                k = pairs_unmap<K>(k, kind, desc);
-                unsigned char kr[KB];
-                __builtin_memcpy(kr, &k, KB);
-                pairs_store<KB>(out_keys + r * KB, kr);
-            }
-            if (out_offsets) out_offsets[r] = e0 + (uint64_t)j;
-        }
-    }
+    runs_write_heads<KB, E, IPT>(er, flags, first, e0, out_keys, out_offsets, kind, desc);
     if constexpr (POS) {
         if (out_perm) {
             if (perm_words && cnt == (uint32_t)IPT) {

@@ -4,32 +4,17 @@ The LDS bucket kernels keep KPT elements, their ranks and a read-back copy in re
 1024 threads per CU).  Twice in round 3 a harmless-looking change of their loop (a second call site, a loop-carried
 element array) made the compiler spill hundreds of registers and the sort 5-10x slower -- bit-exact, so no parity test
 saw it.  This test compiles the 8-byte unit with -Rpass-analysis=kernel-resource-usage and bounds the spills."""
-import functools, os, re, subprocess, tempfile
+import os
 
 import pytest
 
-from radix_sort_amd import _build
+from resources import kernel_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@functools.lru_cache(maxsize=None)
 def _resources(es):
-    with tempfile.TemporaryDirectory() as d:
-        cmd = [_build.hipcc()] + _build.CXXFLAGS + [f"-DRSX_ES={es}", "-Rpass-analysis=kernel-resource-usage", "-c",
-                                                    os.path.join(_build.CSRC, "rsx_es.hip"), "-o", os.path.join(d, "o.o")]
-        p = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-        assert p.returncode == 0, p.stderr[-2000:]
-    out, name = {}, None
-    for line in p.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            out[name] = {}
-        m = re.search(r"remark:\s+(VGPRs Spill|VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
-        if m and name:
-            out[name][m.group(1)] = int(m.group(2))
-    return out
+    return kernel_resources("rsx_es.hip", (f"-DRSX_ES={es}",))
 
 
 @pytest.mark.parametrize("es", [8, 16])

@@ -6,34 +6,13 @@ together by shifts, the columns read from the kernel arguments by a wave-uniform
 leave the registers -- in particular the byte offset of a column inside the compound key, a run-time value, must not
 turn the key into an array in scratch memory -- so any spill and any scratch, in any instantiation, is a defect: the
 bounds are 0."""
-import functools
 import os
 import re
-import subprocess
-import tempfile
 
 from radix_sort_amd import _build
+from resources import kernel_resources
 
 WIDTHS = (1, 2, 4, 8, 16)
-
-
-@functools.lru_cache(maxsize=None)
-def _resources():
-    with tempfile.TemporaryDirectory() as d:
-        cmd = [_build.hipcc()] + _build.CXXFLAGS + ["-Rpass-analysis=kernel-resource-usage", "-c",
-                                                    os.path.join(_build.CSRC, "rsx_lex.hip"), "-o", os.path.join(d, "o.o")]
-        p = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-        assert p.returncode == 0, p.stderr[-2000:]  # (the static_asserts on the argument struct are part of this compile)
-    out, name = {}, None
-    for line in p.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            out[name] = {}
-        m = re.search(r"remark:\s+(VGPRs Spill|SGPRs Spill|VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
-        if m and name:
-            out[name][m.group(1)] = int(m.group(2))
-    return out
 
 
 def test_the_unit_is_part_of_the_library():
@@ -43,7 +22,7 @@ def test_the_unit_is_part_of_the_library():
 
 
 def test_join_kernels_use_no_scratch():
-    res = _resources()
+    res = kernel_resources("rsx_lex.hip")
     kernels = {n: r for n, r in res.items() if "rsx_lex_join_kernel" in n}
     seen = []
     for name, r in kernels.items():

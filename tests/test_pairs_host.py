@@ -2,17 +2,13 @@
 the numpy reference of tests/pairs_ref.py held against the C oracle, the argument checks that need no device, and the
 join / split kernels' presence and register budget in the gfx950 code object."""
 import ctypes
-import functools
-import os
-import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 import util
 from pairs_ref import mapped_columns, pairs_reference
+from resources import kernel_resources
 
 U, S, F = util.UNSIGNED, util.SIGNED, util.FLOAT
 
@@ -147,29 +143,8 @@ def test_code_object_holds_the_join_and_split_kernels():
         assert name in blob, name
 
 
-@functools.lru_cache(maxsize=None)
-def _pairs_resources():
-    """The method of tests/test_kernel_resources.py on the unit that holds the join and split kernels."""
-    from radix_sort_amd import _build
-    with tempfile.TemporaryDirectory() as d:
-        cmd = [_build.hipcc()] + _build.CXXFLAGS + ["-Rpass-analysis=kernel-resource-usage", "-c",
-                                                    os.path.join(_build.CSRC, "rsx_pairs.hip"), "-o", os.path.join(d, "o.o")]
-        p = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-        assert p.returncode == 0, p.stderr[-2000:]
-    out, name = {}, None
-    for line in p.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            out[name] = {}
-        m = re.search(r"remark:\s+(VGPRs Spill|VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
-        if m and name:
-            out[name][m.group(1)] = int(m.group(2))
-    return out
-
-
 def test_join_and_split_kernels_use_no_scratch():
-    res = _pairs_resources()
+    res = kernel_resources("rsx_pairs.hip")
     names = [n for n in res if "rsx_pairs_" in n]
     typed_join = [n for n in names if "rsx_pairs_join_kernel" in n]
     typed_split = [n for n in names if "rsx_pairs_split_kernel" in n]

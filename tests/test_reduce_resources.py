@@ -5,35 +5,13 @@ rsx_reduce_count_kernel, rsx_reduce_scan_kernel and rsx_reduce_write_kernel are 
 elements per thread, one word of flags, as many partial values as elements, a few ranks.  Nothing in them has a reason to
 leave the registers, so any spill and any scratch, in any instantiation, is a defect and not a tuning matter: the bounds
 are 0."""
-import functools
-import os
 import re
-import subprocess
-import tempfile
 
 from radix_sort_amd import _build
+from resources import kernel_resources
 
 KEY_WIDTHS = (1, 2, 4, 8, 16)
 VALUE_TYPES = {(vb, vk) for vb in (4, 8) for vk in (0, 1, 2)}  # u32 i32 f32 u64 i64 f64
-
-
-@functools.lru_cache(maxsize=None)
-def _resources():
-    with tempfile.TemporaryDirectory() as d:
-        cmd = [_build.hipcc()] + _build.CXXFLAGS + ["-Rpass-analysis=kernel-resource-usage", "-c",
-                                                    os.path.join(_build.CSRC, "rsx_reduce.hip"), "-o", os.path.join(d, "o.o")]
-        p = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-        assert p.returncode == 0, p.stderr[-2000:]
-    out, name = {}, None
-    for line in p.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            out[name] = {}
-        m = re.search(r"remark:\s+(VGPRs Spill|SGPRs Spill|VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
-        if m and name:
-            out[name][m.group(1)] = int(m.group(2))
-    return out
 
 
 def _template_ints(name):
@@ -48,7 +26,7 @@ def test_the_unit_is_part_of_the_library():
 
 
 def test_run_kernels_use_no_scratch():
-    res = _resources()
+    res = kernel_resources("rsx_reduce.hip")
     kernels = {n: r for n, r in res.items() if "rsx_reduce_" in n and "_kernel" in n}
     seen = {"count": [], "write": [], "scan": []}
     for name, r in kernels.items():

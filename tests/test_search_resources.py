@@ -5,33 +5,11 @@ rsx_search_kernel keeps four needles, their bounds and a few cursors per thread;
 registers, so any spill and any scratch, in any instantiation, is a defect: the bounds are 0.  Its static LDS is the
 window of mapped keys plus the tile's own words: one smallest and one largest key per wave and the two ends of the
 window."""
-import functools
-import os
 import re
-import subprocess
-import tempfile
 
 import radix_sort_amd as rs
 from radix_sort_amd import _build
-
-
-@functools.lru_cache(maxsize=None)
-def _resources():
-    with tempfile.TemporaryDirectory() as d:
-        cmd = [_build.hipcc()] + _build.CXXFLAGS + ["-Rpass-analysis=kernel-resource-usage", "-c",
-                                                    os.path.join(_build.CSRC, "rsx_search.hip"), "-o", os.path.join(d, "o.o")]
-        p = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-        assert p.returncode == 0, p.stderr[-2000:]
-    out, name = {}, None
-    for line in p.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            out[name] = {}
-        m = re.search(r"remark:\s+(VGPRs Spill|SGPRs Spill|VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
-        if m and name:
-            out[name][m.group(1)] = int(m.group(2))
-    return out
+from resources import kernel_resources
 
 
 def _template_ints(name):
@@ -47,7 +25,7 @@ def test_the_search_unit_is_part_of_the_library():
 
 
 def test_search_kernels_use_no_scratch_and_the_lds_of_their_window():
-    res = _resources()
+    res = kernel_resources("rsx_search.hip")
     kernels = {n: r for n, r in res.items() if "rsx_search_kernel" in n}
     seen = set()
     for name, r in kernels.items():

@@ -4,32 +4,9 @@ of tests/test_kernel_resources.py).
 rsx_unique_count_kernel, rsx_unique_scan_kernel and rsx_unique_write_kernel are streaming kernels: 64 bytes of elements
 per thread, one word of flags, a few ranks.  Nothing in them has a reason to leave the registers, so any spill and any
 scratch, in any instantiation, is a defect and not a tuning matter: the bounds are 0."""
-import functools
-import os
 import re
-import subprocess
-import tempfile
 
-from radix_sort_amd import _build
-
-
-@functools.lru_cache(maxsize=None)
-def _resources():
-    with tempfile.TemporaryDirectory() as d:
-        cmd = [_build.hipcc()] + _build.CXXFLAGS + ["-Rpass-analysis=kernel-resource-usage", "-c",
-                                                    os.path.join(_build.CSRC, "rsx_unique.hip"), "-o", os.path.join(d, "o.o")]
-        p = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-        assert p.returncode == 0, p.stderr[-2000:]
-    out, name = {}, None
-    for line in p.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            out[name] = {}
-        m = re.search(r"remark:\s+(VGPRs Spill|SGPRs Spill|VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
-        if m and name:
-            out[name][m.group(1)] = int(m.group(2))
-    return out
+from resources import kernel_resources
 
 
 def _template_ints(name):
@@ -44,7 +21,7 @@ def _joined(kb, pos):
 
 
 def test_run_kernels_use_no_scratch():
-    res = _resources()
+    res = kernel_resources("rsx_unique.hip")
     kernels = {n: r for n, r in res.items() if "rsx_unique_" in n and "_kernel" in n}
     seen = {"count": set(), "write": set(), "scan": 0}
     for name, r in kernels.items():
