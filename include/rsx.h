@@ -197,6 +197,8 @@ enum {
                                  9 reduce by key (rsx_reduce_by_key_device: bits 0-7 and 8-23 as for path 8),
                                  10 search (rsx_search_sorted_device: bits 0-7 are then the kernels launched after
                                  any sort of the needles, bit 8 is set when they were sorted first, bits 9-23 are 0),
+                                 11 merge (rsx_merge_device: bits 0-7 are then the kernels launched, bit 8 is set on the
+                                 wide-value route, bits 9-23 are 0),
                                  bits 28-29 the route of a layout without kernels of its own: 0 direct, 1 packed
                                  re-layout, 2 key-index proxy (bits 0-27 then describe the sort of the re-laid-out
                                  elements / of the proxies) */
@@ -532,6 +534,51 @@ int rsx_ctx_reserve_search(rsx_ctx *ctx, size_t m, uint32_t key_bytes);
 /* Host-only, needs no device: *tile = the needles one workgroup takes, *window = the most haystack keys it stages in LDS
  * (window >= 2 * tile; window * key_bytes leaves more than two workgroups per CU).  Both routes run the same shape. */
 int rsx_search_caps(uint32_t key_bytes, int with_positions, uint32_t *tile, uint32_t *window);
+
+/* -- stable merge of two sorted key arrays ------------------------------------ */
+/* Combining two arrays the sorting calls left on the device (append a sorted batch to a sorted index, fold the keys of two
+ * rsx_unique_device results together) in one read and one write of every byte, where concatenating and sorting again
+ * moves every byte several times.  Let M be the key mapping of rsx_argsort_device for (key_bytes, key_kind), complemented
+ * when `order` is descending (floats by the total order on bit patterns: -NaN first, -0.0 before +0.0, +NaN last), and
+ * n = na + nb.  PRECONDITION: M(d_a_keys[i]) is non-decreasing and M(d_b_keys[j]) is non-decreasing -- what every sorting
+ * call of the library leaves in that `order`.  Let c = a ++ b and p the stable permutation that sorts c by M, exactly
+ * rsx_argsort_device of the concatenation: equal keys of a come before equal keys of b, and equal keys inside one array
+ * keep their order.  Then, for t < n:
+ *     d_out_keys[t]   = c[p[t]]                          as raw key bytes
+ *     d_out_values[t] = (a_values ++ b_values)[p[t]]     moved bitwise
+ *     d_out_index[t]  = p[t]                             index_bytes wide: below na a position in a, else p[t] - na in b
+ * Each output is optional through a NULL pointer; at least one must be given.  The inputs are only read; nothing outside
+ * the n-entry outputs and the context's workspace is written.  Key widths, kinds and alignments are those of
+ * rsx_argsort_device (1, 2, 4, 8, 16 bytes); value_bytes is 0 .. RSX_MAX_ELEM_BYTES with the value alignment of
+ * rsx_sort_pairs_device, and value_bytes == 0 goes with all three value pointers NULL; index_bytes is 4 or 8 and is looked
+ * at only when d_out_index is given.  RSX_ERR_ARG: bad widths, kinds, order, index_bytes or alignments; a NULL input with
+ * a nonzero count; values given on one side only; all outputs NULL; index_bytes == 4 with n > 2^32; an output range that
+ * overlaps an input range or another output (the merge is not in place; checked on the host from the pointers and byte
+ * lengths).  RSX_ERR_UNSUPPORTED: n of 2^31 tiles or more.  n == 0 launches nothing and looks at no pointer; na == 0 or
+ * nb == 0 is a copy through the same kernel.  Stream-ordered, no synchronisation; the host reads nothing.
+ * If the precondition does not hold, every read stays inside the two inputs, every write inside the outputs and every
+ * d_out_index[t] is below n; nothing else is promised, and the output need not be a permutation.
+ *
+ * One kernel, one workgroup per tile of `tile` consecutive OUTPUT positions (rsx_merge_caps): two of its waves find the
+ * tile's two cuts on the merge path by the cooperative 64-ary search of rsx_search_sorted_device, the mapped keys of the
+ * two input ranges between the cuts go to LDS, every thread merges its share there, and keys, values and positions are
+ * stored as contiguous ranges.  No workgroup waits for another one, there are no atomics.  Values of 1, 2, 4, 8 and 16
+ * bytes move in that kernel, which needs no workspace: the call can be captured once the context has made its first call.
+ * Values of any other width: the kernel writes 8-byte source positions into the context's workspace and a row gather
+ * moves the values; the workspace is made on first use or by rsx_ctx_reserve_merge, and under capture without a sufficient
+ * reserve the call returns RSX_ERR_WORKSPACE and enqueues nothing.  RSX_INFO_LAST_PASSES reports path 11. */
+int rsx_merge_device(rsx_ctx *ctx,
+                     const void *d_a_keys, const void *d_a_values, size_t na,
+                     const void *d_b_keys, const void *d_b_values, size_t nb,
+                     uint32_t key_bytes, uint32_t key_kind, uint32_t value_bytes, int order,
+                     void *d_out_keys, void *d_out_values, void *d_out_index, uint32_t index_bytes,
+                     void *stream);
+/* Workspace (and the context's first-call set-up) of a merge into up to n_total outputs of these widths, so that the call
+ * allocates nothing (stream capture). */
+int rsx_ctx_reserve_merge(rsx_ctx *ctx, size_t n_total, uint32_t key_bytes, uint32_t value_bytes);
+/* Host-only, needs no device: *tile = the output positions one workgroup takes (256 threads; tile * (key_bytes + 2) + 16
+ * bytes of LDS at most, which leaves more than two workgroups per CU). */
+int rsx_merge_caps(uint32_t key_bytes, uint32_t value_bytes, uint32_t *tile);
 
 /* -- several key columns ----------------------------------------------------- */
 /* Sorting a table by (a, b descending, c): ncols key columns of n keys each, column 0 the MOST significant (the opposite

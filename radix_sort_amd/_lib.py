@@ -24,6 +24,7 @@ SYMBOLS = [
     "rsx_reduce_by_key_device", "rsx_ctx_reserve_reduce", "rsx_reduce_caps",
     "rsx_lexsort_device", "rsx_sort_columns_device", "rsx_ctx_reserve_lex", "rsx_lex_plan",
     "rsx_search_sorted_device", "rsx_ctx_reserve_search", "rsx_search_caps",
+    "rsx_merge_device", "rsx_ctx_reserve_merge", "rsx_merge_caps",
 ]
 SEG_CLASSES = 2  # RSX_SEG_CLASSES
 LEX_MAX_COLUMNS = 16  # RSX_LEX_MAX_COLUMNS
@@ -157,6 +158,9 @@ def load():
     L.rsx_search_sorted_device.argtypes = [vp, vp, sz, vp, vp, sz, u32, u32, i, vp, vp, u32, u32, vp]
     L.rsx_ctx_reserve_search.argtypes = [vp, sz, u32]
     L.rsx_search_caps.argtypes = [u32, i, pu32, pu32]
+    L.rsx_merge_device.argtypes = [vp, vp, vp, sz, vp, vp, sz, u32, u32, u32, i, vp, vp, vp, u32, vp]
+    L.rsx_ctx_reserve_merge.argtypes = [vp, sz, u32, u32]
+    L.rsx_merge_caps.argtypes = [u32, u32, pu32]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("rsx_last_error", "rsx_strerror"):

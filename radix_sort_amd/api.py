@@ -322,6 +322,22 @@ class Context:
                                                      key_kind, 1 if descending else 0, d_out_lower or None, d_out_upper or None,
                                                      index_bytes, flags, stream))
 
+    def reserve_merge(self, n_total: int, key_bytes: int, value_bytes: int = 0):
+        """rsx_ctx_reserve_merge: the context's first-call set-up and the workspace of merge_device into up to n_total
+        outputs of these widths (values of 1, 2, 4, 8, 16 bytes need none), so that the call allocates nothing and can be
+        captured."""
+        self._check(self._L.rsx_ctx_reserve_merge(self._h, n_total, key_bytes, value_bytes))
+
+    def merge_device(self, d_a_keys: int, d_a_values: int, na: int, d_b_keys: int, d_b_values: int, nb: int, key_bytes: int,
+                     key_kind: int, value_bytes: int, d_out_keys: int, d_out_values: int, d_out_index: int, index_bytes: int = 8,
+                     descending: bool = False, stream: int = 0):
+        """rsx_merge_device: the stable merge of two sorted key arrays (equal keys of a first) -- the merged keys, the
+        values moved with them and the position of every output in a ++ b (each output may be 0: not produced); the inputs
+        are only read and no output may overlap them."""
+        self._check(self._L.rsx_merge_device(self._h, d_a_keys or None, d_a_values or None, na, d_b_keys or None, d_b_values or None, nb,
+                                             key_bytes, key_kind, value_bytes, 1 if descending else 0, d_out_keys or None,
+                                             d_out_values or None, d_out_index or None, index_bytes, stream))
+
     def reserve_reduce(self, n: int, key_bytes: int, value_bytes: int):
         """rsx_ctx_reserve_reduce: the context's first-call set-up and the workspace of reduce_by_key_device on up to n keys
         of these widths, so that the call allocates nothing and can be captured."""
@@ -1180,6 +1196,136 @@ def radix_searchsorted(sorted_keys, needles, side: str = "left", descending: boo
     if side == "both":
         return lower, upper
     return lower if want_lower else upper
+
+
+def merge_caps(key_bytes: int, value_bytes: int = 0):
+    """rsx_merge_caps -> tile: the output positions one workgroup of the merge kernel takes for these widths.  Needs no
+    device."""
+    L = _lib.load()
+    tile = ctypes.c_uint32()
+    _check_rc(L, L.rsx_merge_caps(key_bytes, value_bytes, ctypes.byref(tile)))
+    return int(tile.value)
+
+
+def _merge_keys(a, b, key_kind):
+    """(key_bytes, key_kind, na, nb) of the two key columns of radix_merge / radix_merge_pairs."""
+    import torch
+    kb, kind, na = _pairs_keys(a, key_kind)
+    if not isinstance(b, torch.Tensor):
+        raise TypeError("keys must be a torch tensor on a GPU")
+    if b.dtype != a.dtype:
+        raise TypeError(f"both key tensors must have one dtype, not {a.dtype} and {b.dtype}")
+    if b.device != a.device:
+        raise ValueError("both key tensors must live on the same device")
+    kb2, _kind, nb = _pairs_keys(b, key_kind)
+    if kb2 != kb:
+        raise ValueError("both key tensors must be 1-D, or both (n, 16) uint8 tensors of 128-bit keys")
+    return kb, kind, na, nb
+
+
+def _merge_out(out, like, n: int, what: str):
+    """An output tensor of radix_merge / radix_merge_pairs: n rows shaped and typed like `like` (the first input)."""
+    import torch
+    if not isinstance(out, torch.Tensor):
+        raise TypeError(f"out ({what}) must be a torch tensor")
+    if out.dtype != like.dtype:
+        raise TypeError(f"out ({what}) must have dtype {like.dtype}, not {out.dtype}")
+    shape = (n,) + tuple(like.shape[1:])
+    if tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError(f"out ({what}) must be a contiguous tensor of shape {shape}")
+    if out.device != like.device:
+        raise ValueError(f"the keys and out ({what}) must live on the same device")
+
+
+def radix_merge(a, b, descending: bool = False, return_index: bool = False, index_dtype=None, out=None,
+                ctx: Optional[Context] = None, key_kind: Optional[int] = None):
+    """The stable merge of two sorted key tensors (rsx_merge_device): what `torch.sort(torch.cat((a, b)), stable=True,
+    descending=descending)` gives for inputs that are each sorted already, in one read and one write of every key.  Equal
+    keys of `a` come before equal keys of `b`.  Returns the merged 1-D keys, or with return_index=True the pair (keys,
+    index): index[t] is the position of output t in the concatenation, below len(a) a position in `a`, otherwise
+    index[t] - len(a) a position in `b` -- radix_argsort(torch.cat((a, b))).
+
+    a, b: contiguous 1-D GPU tensors of one dtype radix_sort knows, or (n, 16) uint8 128-bit keys (key_kind=), each in the
+       order radix_sort / radix_sort_pairs(descending=descending) / radix_group leave: the total order on bit patterns
+       (-NaN below -inf, -0.0 below +0.0, +NaN above +inf), not torch's.  Neither is modified.
+    out: the keys tensor to fill (with return_index: a pair (keys, index), index int32 or int64), contiguous, on the same
+       device, len(a) + len(b) long; it must not overlap an input.  index_dtype: torch.int64 (default) or torch.int32.
+
+    If an input is not sorted the result is unspecified but nothing outside the outputs is written.  Enqueued on the
+    current stream, not synchronised."""
+    import torch
+    kb, kind, na, nb = _merge_keys(a, b, key_kind)
+    n = na + nb
+    out_keys, out_index = out, None
+    if return_index and out is not None:
+        if not isinstance(out, (tuple, list)) or len(out) != 2:
+            raise TypeError("out must be a pair (keys, index) with return_index=True")
+        out_keys, out_index = out
+    if out_keys is not None:
+        _merge_out(out_keys, a, n, "keys")
+    if out_index is not None:
+        _index_out(out_index, (n,), "the merged keys")
+        if out_index.device != a.device:
+            raise ValueError("the keys and out (index) must live on the same device")
+        index_dtype = out_index.dtype
+    index_dtype = _index_dtype(index_dtype)
+    _pairs_device(a, None, "")
+    if return_index and index_dtype == torch.int32 and n > 1 << 32:
+        raise ValueError("more than 2^32 keys need int64 indices")
+    if out_keys is None:
+        out_keys = torch.empty((n,) + tuple(a.shape[1:]), dtype=a.dtype, device=a.device)
+    if return_index and out_index is None:
+        out_index = torch.empty(n, dtype=index_dtype, device=a.device)
+    if n > 0:
+        with _on_device(a, ctx) as (c, stream):
+            c.merge_device(a.data_ptr() if na else 0, 0, na, b.data_ptr() if nb else 0, 0, nb, kb, kind, 0, out_keys.data_ptr(), 0,
+                           out_index.data_ptr() if return_index else 0, out_index.element_size() if return_index else 8, descending, stream)
+    return (out_keys, out_index) if return_index else out_keys
+
+
+def radix_merge_pairs(a_keys, a_values, b_keys, b_values, descending: bool = False, out=None, ctx: Optional[Context] = None,
+                      key_kind: Optional[int] = None):
+    """The stable merge of two sorted key tensors with their values (rsx_merge_device): returns (keys, values), what
+    radix_sort_pairs leaves of torch.cat((a_keys, b_keys)) and torch.cat((a_values, b_values)) when each input is sorted
+    already.  Equal keys of `a` come before equal keys of `b`.
+
+    a_keys, b_keys: as in radix_merge.  a_values, b_values: contiguous GPU tensors of one dtype on the same device with one
+       row per key and the same trailing dimensions; a row (trailing dimensions included) is one value of up to 32768
+       bytes, moved bitwise.  Values of 1, 2, 4, 8 and 16 bytes move in the merge kernel; any other width goes through
+       8-byte source positions in the context's workspace and a row gather.
+    out: a pair (keys, values) to fill, shaped like the concatenations; it must not overlap an input.
+
+    Enqueued on the current stream, not synchronised."""
+    import torch
+    kb, kind, na, nb = _merge_keys(a_keys, b_keys, key_kind)
+    n = na + nb
+    va = _value_bytes(a_values, (na,), "a_keys")
+    vb = _value_bytes(b_values, (nb,), "b_keys")
+    if a_values is None or b_values is None:
+        raise TypeError("a_values and b_values must be torch tensors (keys alone: radix_merge)")
+    if a_values.dtype != b_values.dtype:
+        raise TypeError(f"both value tensors must have one dtype, not {a_values.dtype} and {b_values.dtype}")
+    if tuple(a_values.shape[1:]) != tuple(b_values.shape[1:]) or va != vb:
+        raise ValueError(f"both value tensors must have the same trailing shape, not {tuple(a_values.shape)} and {tuple(b_values.shape)}")
+    out_keys = out_values = None
+    if out is not None:
+        if not isinstance(out, (tuple, list)) or len(out) != 2:
+            raise TypeError("out must be a pair (keys, values)")
+        out_keys, out_values = out
+        _merge_out(out_keys, a_keys, n, "keys")
+        _merge_out(out_values, a_values, n, "values")
+    for v, what in ((a_values, "a_values"), (b_values, "b_values")):
+        if v.device != a_keys.device:
+            raise ValueError(f"keys and {what} must live on the same device")
+    _pairs_device(a_keys, None, "")
+    if out_keys is None:
+        out_keys = torch.empty((n,) + tuple(a_keys.shape[1:]), dtype=a_keys.dtype, device=a_keys.device)
+        out_values = torch.empty((n,) + tuple(a_values.shape[1:]), dtype=a_values.dtype, device=a_keys.device)
+    if n > 0:
+        with _on_device(a_keys, ctx) as (c, stream):
+            c.merge_device(a_keys.data_ptr() if na else 0, a_values.data_ptr() if na else 0, na, b_keys.data_ptr() if nb else 0,
+                           b_values.data_ptr() if nb else 0, nb, kb, kind, va, out_keys.data_ptr(), out_values.data_ptr(), 0, 8, descending, stream)
+    return out_keys, out_values
 
 
 def _segments_common(keys, offsets, max_seg_len):

@@ -1036,6 +1036,7 @@ int rsx_ctx_get_info(rsx_ctx* ctx, int what, uint64_t* out) try {
                     *out = (uint64_t)(ctx->last_sort_passes & 0xFFu) | (uint64_t)ctx->last_path << 24;
                     return RSX_OK;
                 case PATH_SEARCH:  // bits 0-7 the kernels launched after any sort, bit 8 the needles were sorted first
+                case PATH_MERGE:   // bits 0-7 the kernels launched, bit 8 the wide-value route
                     *out = (uint64_t)(ctx->last_sort_passes & 0x1FFu) | (uint64_t)ctx->last_path << 24;
                     return RSX_OK;
                 default: break;
@@ -1704,6 +1705,141 @@ int rsx_search_caps(uint32_t key_bytes, int with_positions, uint32_t* tile, uint
     if (!tile || !window || !key_widths_ok(key_bytes, RSX_KEY_UNSIGNED)) return RSX_ERR_ARG;
     *tile = search_tile_elems(key_bytes);
     *window = search_window_elems(key_bytes);
+    return RSX_OK;
+}
+
+// ---- stable merge of two sorted key arrays (rsx_merge_kernels.hpp, include/rsx.h) ----
+namespace {
+// The workspace of one rsx_merge_device call: nothing on the fused route; n u64 source positions for values the kernel
+// does not move itself.
+struct MergePlan {
+    bool wide;
+    Carve ws;
+    size_t pos_off;
+};
+MergePlan merge_plan(size_t n, uint32_t vb) {
+    MergePlan P{};
+    P.wide = !merge_value_fused(vb);
+    if (P.wide) P.pos_off = P.ws.take(n * sizeof(uint64_t));
+    return P;
+}
+bool merge_size_ok(uint64_t n, uint32_t kb, uint32_t vb) {
+    const uint32_t tile = merge_tile_elems(kb, vb);
+    return (n + tile - 1) / tile < (1ull << 31);
+}
+// [p, p + bytes) and [q, q + qbytes) share a byte (an absent or empty range shares none)
+bool ranges_overlap(const void* p, uint64_t bytes, const void* q, uint64_t qbytes) {
+    if (!p || !q || bytes == 0 || qbytes == 0) return false;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+    return a < b + qbytes && b < a + bytes;
+}
+}  // namespace
+
+int rsx_merge_device(rsx_ctx* ctx, const void* d_a_keys, const void* d_a_values, size_t na, const void* d_b_keys, const void* d_b_values, size_t nb,
+                     uint32_t key_bytes, uint32_t key_kind, uint32_t value_bytes, int order, void* d_out_keys, void* d_out_values, void* d_out_index,
+                     uint32_t index_bytes, void* stream) try {
+    if (!ctx) return RSX_ERR_ARG;
+    if (!key_widths_ok(key_bytes, key_kind)) return fail(ctx, RSX_ERR_ARG, "invalid key width or kind");
+    if (value_bytes > RSX_MAX_ELEM_BYTES) return fail(ctx, RSX_ERR_ARG, "value wider than RSX_MAX_ELEM_BYTES");
+    uint32_t desc = 0;
+    if (int rc = order_desc(ctx, order, &desc)) return rc;
+    const uint64_t n = (uint64_t)na + (uint64_t)nb;
+    if (n < (uint64_t)na) return fail(ctx, RSX_ERR_UNSUPPORTED, "too many keys for one launch");
+    Entry held(ctx, stream);
+    if (!held.ok) return no_device(ctx);
+    const hipStream_t st = held.st;
+    if (n == 0) {  // nothing asked: no pointer is looked at
+        note_path(ctx, PATH_MERGE, 0);
+        return RSX_OK;
+    }
+    if (d_out_index) {
+        if (int rc = check_index_bytes(ctx, index_bytes)) return rc;
+        if (index_bytes == 4 && n > (1ull << 32)) return fail(ctx, RSX_ERR_ARG, "more than 2^32 keys need 8-byte indices");
+    }
+    if (!d_out_keys && !d_out_values && !d_out_index) return fail(ctx, RSX_ERR_ARG, "d_out_keys, d_out_values and d_out_index are all null");
+    if (value_bytes == 0 && (d_a_values || d_b_values || d_out_values)) return fail(ctx, RSX_ERR_ARG, "value pointers and value_bytes disagree");
+    if ((na > 0 && !d_a_keys) || (nb > 0 && !d_b_keys)) return fail(ctx, RSX_ERR_ARG, "null device pointer");
+    if (value_bytes != 0 && ((na > 0 && !d_a_values) || (nb > 0 && !d_b_values))) return fail(ctx, RSX_ERR_ARG, "values are given on one side only");
+    const uint32_t va = value_bytes ? value_align(value_bytes) : 1u, ia = d_out_index ? index_bytes : 1u;
+    if (!aligned(d_a_keys, key_bytes) || !aligned(d_b_keys, key_bytes) || !aligned(d_out_keys, key_bytes) || !aligned(d_a_values, va) ||
+        !aligned(d_b_values, va) || !aligned(d_out_values, va) || !aligned(d_out_index, ia))
+        return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
+    if (!merge_size_ok(n, key_bytes, value_bytes)) return fail(ctx, RSX_ERR_UNSUPPORTED, "too many keys for one launch");
+    {  // the merge is not in place: no output may share a byte with an input or with another output
+        const void* in_p[4] = {d_a_keys, d_b_keys, d_a_values, d_b_values};
+        const uint64_t in_b[4] = {(uint64_t)na * key_bytes, (uint64_t)nb * key_bytes, (uint64_t)na * value_bytes, (uint64_t)nb * value_bytes};
+        const void* out_p[3] = {d_out_keys, d_out_values, d_out_index};
+        const uint64_t out_b[3] = {n * key_bytes, n * value_bytes, n * (d_out_index ? index_bytes : 0u)};
+        for (int o = 0; o < 3; ++o) {
+            for (int i = 0; i < 4; ++i)
+                if (ranges_overlap(out_p[o], out_b[o], in_p[i], in_b[i])) return fail(ctx, RSX_ERR_ARG, "an output overlaps an input");
+            for (int p = o + 1; p < 3; ++p)
+                if (ranges_overlap(out_p[o], out_b[o], out_p[p], out_b[p])) return fail(ctx, RSX_ERR_ARG, "two outputs overlap");
+        }
+    }
+    int rc = pending_error(ctx);
+    if (rc) return rc;
+    MergeCall c{};
+    c.a_keys = d_a_keys;
+    c.a_values = d_a_values;
+    c.na = na;
+    c.b_keys = d_b_keys;
+    c.b_values = d_b_values;
+    c.nb = nb;
+    c.kb = key_bytes;
+    c.kind = key_kind;
+    c.desc = desc;
+    c.vb = value_bytes;
+    c.ib = index_bytes;
+    c.out_keys = d_out_keys;
+    c.out_values = d_out_values;
+    c.out_index = d_out_index;
+    uint32_t launched = 0;
+    const MergePlan P = merge_plan((size_t)n, d_out_values ? value_bytes : 0u);
+    rc = ensure_aux(ctx, st);
+    if (rc) return rc;
+    if (!P.wide) {  // one launch, no workspace
+        Enqueue enq(ctx, st);
+        rc = launch_merge(ctx, c, &launched, st);
+        if (rc) return rc;
+        note_path(ctx, PATH_MERGE, launched);
+        return RSX_OK;
+    }
+    // the wide-value route: keys and u64 source positions from the same kernel, then the two-source row gather
+    rc = ensure_any(ctx, P.ws.bytes, st);
+    if (rc) return rc;
+    Enqueue enq(ctx, st);  // the workspace array belongs to this call from the first launch on
+    uint64_t* pos = reinterpret_cast<uint64_t*>(ctx->any_buf + P.pos_off);
+    MergeCall k = c;
+    k.out_values = nullptr;
+    k.out_index = pos;
+    k.ib = 8;
+    rc = launch_merge(ctx, k, &launched, st);
+    if (rc) return rc;
+    rc = launch_merge_gather(ctx, c, pos, d_out_values, d_out_index, st);
+    if (rc) return rc;
+    note_path(ctx, PATH_MERGE, (launched + 1u) | 0x100u);
+    return RSX_OK;
+} catch (...) {
+    return RSX_ERR_HIP;
+}
+
+int rsx_ctx_reserve_merge(rsx_ctx* ctx, size_t n_total, uint32_t key_bytes, uint32_t value_bytes) try {
+    if (!ctx) return RSX_ERR_ARG;
+    if (!key_widths_ok(key_bytes, RSX_KEY_UNSIGNED) || value_bytes > RSX_MAX_ELEM_BYTES) return fail(ctx, RSX_ERR_ARG, "invalid key or value width");
+    if (!merge_size_ok(n_total, key_bytes, value_bytes)) return fail(ctx, RSX_ERR_UNSUPPORTED, "too many keys for one launch");
+    Entry held(ctx);
+    if (!held.ok) return no_device(ctx);
+    int rc = ensure_aux(ctx, nullptr);
+    if (rc) return rc;
+    return ensure_any(ctx, merge_plan(n_total, value_bytes).ws.bytes, nullptr);
+} catch (...) {
+    return RSX_ERR_NOMEM;
+}
+
+int rsx_merge_caps(uint32_t key_bytes, uint32_t value_bytes, uint32_t* tile) {
+    if (!tile || !key_widths_ok(key_bytes, RSX_KEY_UNSIGNED) || value_bytes > RSX_MAX_ELEM_BYTES) return RSX_ERR_ARG;
+    *tile = merge_tile_elems(key_bytes, value_bytes);
     return RSX_OK;
 }
 

@@ -1,4 +1,4 @@
-// rsx_internal.hpp -- host-side state and helpers shared by the fourteen translation units of librsx.so:
+// rsx_internal.hpp -- host-side state and helpers shared by the fifteen translation units of librsx.so:
 //   rsx.hip         the C-ABI of include/rsx.h (context, pass loop, multi-GPU driver, harness)
 //   rsx_es.hip      the kernel launchers of ONE element size (compiled once per size with -DRSX_ES=n,
 //                   so the eight sizes build in parallel), reached through that size's EsLaunchers table
@@ -6,6 +6,7 @@
 //   rsx_unique.hip  the run kernels of rsx_unique_device
 //   rsx_reduce.hip  those of rsx_reduce_by_key_device
 //   rsx_search.hip  the kernel of rsx_search_sorted_device
+//   rsx_merge.hip   the kernels of rsx_merge_device
 //   rsx_lex.hip     the join of several key columns (rsx_lexsort_device, rsx_sort_columns_device)
 #pragma once
 #include "rsx_device.hpp"
@@ -77,6 +78,7 @@ enum : uint32_t {
     PATH_UNIQUE = 8,
     PATH_REDUCE = 9,
     PATH_SEARCH = 10,
+    PATH_MERGE = 11,
 };
 
 // option bits (rsx_ctx_set_option): alternative kernel paths, all bit-exact
@@ -568,5 +570,26 @@ struct SearchCall {
 int launch_search(rsx_ctx* ctx, const SearchCall& call, uint32_t* launched, hipStream_t st);
 uint32_t search_tile_elems(uint32_t kb);     // needles per workgroup
 uint32_t search_window_elems(uint32_t kb);  // haystack keys a workgroup stages in LDS at most
+
+// What one rsx_merge_device call asks of the merge kernel (rsx_merge.hip, rsx_merge_kernels.hpp).
+struct MergeCall {
+    const void* a_keys;          // na keys of kb bytes, sorted by mapped key in the call's order; b likewise
+    const void* a_values;        // na values of vb bytes (read only when out_values is given)
+    size_t na;
+    const void* b_keys;
+    const void* b_values;
+    size_t nb;
+    uint32_t kb, kind, desc;
+    uint32_t vb;                 // launch_merge: a fused width (merge_value_fused) when out_values is given
+    uint32_t ib;                 // bytes of a position in out_index
+    void* out_keys;              // each may be null
+    void* out_values;
+    void* out_index;
+};
+int launch_merge(rsx_ctx* ctx, const MergeCall& call, uint32_t* launched, hipStream_t st);
+// the values of any other width: out_values row r = row pos[r] of a_values ++ b_values; out_index (or null) receives pos
+int launch_merge_gather(rsx_ctx* ctx, const MergeCall& call, const uint64_t* pos, void* out_values, void* out_index, hipStream_t st);
+uint32_t merge_tile_elems(uint32_t kb, uint32_t vb);  // outputs per workgroup
+bool merge_value_fused(uint32_t vb);                  // the kernel moves values of this width itself
 
 }  // namespace rsxh

@@ -68,13 +68,11 @@ __device__ __forceinline__ typename PairsKey<KB>::type search_hay(const uint8_t*
     return pairs_map<K>(k, kind, desc);
 }
 
-// One wave, all 64 lanes: the number of j in [0, N) with sorted[j] before `key`, for a sorted haystack; for any haystack
-// a value in [0, N] from reads below N.  [a, b] always holds the answer; a round counts the probes that are before the
-// key (a ballot) and keeps the gap behind the last of them.
-template <int KB, bool UP>
-__device__ __forceinline__ uint64_t search_wave_bound(const uint8_t* __restrict__ sorted, uint64_t N, const typename PairsKey<KB>::type& key,
-                                                       uint32_t kind, uint32_t desc) {
-    using K = typename PairsKey<KB>::type;
+// One wave, all 64 lanes: the number of j in [0, N) for which before(j) holds, when before is true on a prefix of [0, N) and
+// false behind it; for any predicate a value in [0, N] from calls below N.  [a, b] always holds the answer; a round counts
+// the probes that are before (a ballot) and keeps the gap behind the last of them.
+template <typename F>
+__device__ __forceinline__ uint64_t search_wave_count(uint64_t N, F&& before_at) {
     const uint32_t lane = threadIdx.x & (WAVE - 1);
     uint64_t a = 0, b = N;
     while (a < b) {
@@ -82,7 +80,7 @@ __device__ __forceinline__ uint64_t search_wave_bound(const uint8_t* __restrict_
         const uint64_t step = (s + WAVE - 1) / WAVE;   // s <= 64: every element is probed and the round is the last
         const uint64_t p = a + (uint64_t)(lane + 1) * step - 1;  // (no overflow: p < a + s + 64 * 1)
         bool before = false;
-        if (p < b) before = search_before<K, UP>(search_hay<KB>(sorted, p, kind, desc), key);
+        if (p < b) before = before_at(p);
         const uint64_t c = (uint64_t)__popcll(__ballot(before));
         const uint64_t na = a + c * step;             // c probes lie below b: na <= b
         const uint64_t nb = na + step - 1;            // the probe behind them is not before the key (or lies at b or beyond)
@@ -90,6 +88,14 @@ __device__ __forceinline__ uint64_t search_wave_bound(const uint8_t* __restrict_
         b = nb < b ? nb : b;
     }
     return a;
+}
+// ... the number of j in [0, N) with sorted[j] before `key`, for a sorted haystack; for any haystack a value in [0, N]
+// from reads below N.
+template <int KB, bool UP>
+__device__ __forceinline__ uint64_t search_wave_bound(const uint8_t* __restrict__ sorted, uint64_t N, const typename PairsKey<KB>::type& key,
+                                                       uint32_t kind, uint32_t desc) {
+    using K = typename PairsKey<KB>::type;
+    return search_wave_count(N, [&](uint64_t p) { return search_before<K, UP>(search_hay<KB>(sorted, p, kind, desc), key); });
 }
 
 // G searches in step, one thread, in positions [0, cnt), cnt >= 1: needle g looks in [base[g], base[g] + len[g]) for the

@@ -16,6 +16,8 @@
 //     rsx::unique(const K* d_keys, size_t n, K* keys, uint64_t* offsets, I* perm, I* inverse, uint64_t* num, bool descending, hipStream_t)
 //     rsx::reduce_by_key(const K* d_keys, const V* d_values, size_t n, int op, K* keys, V* values, uint64_t* offsets, uint64_t* num, bool descending, hipStream_t)
 //     rsx::search_sorted(const K* d_sorted, size_t n, const K* d_needles, size_t m, I* lower, I* upper, bool descending, const uint64_t* d_sorted_num, bool presort, hipStream_t)
+//     rsx::merge(const K* d_a_keys, size_t na, const K* d_b_keys, size_t nb, K* d_out_keys, bool descending, hipStream_t)   // two sorted arrays
+//     rsx::merge_pairs(const K* d_a_keys, const V* d_a_values, size_t na, const K* d_b_keys, const V* d_b_values, size_t nb, K* keys, V* values[, I* index], bool descending, hipStream_t)
 //     rsx::lexsort({rsx::key_column(d_a), rsx::key_column(d_b, true)}, I* d_index, size_t n, hipStream_t)   // several key columns
 //     rsx::sort_columns({rsx::key_column(d_a), rsx::key_column(d_b, true)}, V* d_values, size_t n, hipStream_t)
 // Errors: the reference panics (mod.rs:68,106); here std::runtime_error is thrown.
@@ -270,6 +272,39 @@ void search_sorted(const K* d_sorted, size_t n, const K* d_needles, size_t m, I*
                                        descending ? RSX_ORDER_DESCENDING : RSX_ORDER_ASCENDING, d_out_lower, d_out_upper, (uint32_t)sizeof(I),
                                        presort ? (uint32_t)RSX_SEARCH_PRESORT : 0u, stream),
               "rsx_search_sorted_device");
+}
+
+// The stable merge of two key arrays that are each sorted in that order (rsx_merge_device): d_out_keys receives the
+// na + nb keys of the stable sort of a ++ b, equal keys of a in front of equal keys of b.  merge_pairs moves the values
+// with their keys (V: any trivially copyable type; 1, 2, 4, 8 and 16 bytes move in the merge kernel, any other width through
+// the context's workspace: rsx_ctx_reserve_merge before a stream capture); its overload with d_out_index also stores the
+// position of every output in a ++ b (below na a position in a, else that minus na a position in b).  Any output may be
+// nullptr, not all; the inputs are only read and no output may overlap them.  Stream-ordered, never synchronised.
+template <typename K, typename V, typename I>
+void merge_pairs(const K* d_a_keys, const V* d_a_values, size_t na, const K* d_b_keys, const V* d_b_values, size_t nb, K* d_out_keys,
+                 V* d_out_values, I* d_out_index, bool descending = false, void* stream = nullptr, Context& ctx = default_context()) {
+    static_assert(std::is_trivially_copyable<V>::value, "values are moved bitwise");
+    static_assert(std::is_integral<I>::value && (sizeof(I) == 4 || sizeof(I) == 8), "indices are 4- or 8-byte integers");
+    const rsx_layout L = RadixDigits<K>::layout();
+    if (L.key_offset != 0 || L.key_bytes != L.elem_bytes) throw std::invalid_argument("merge: the key type must be its own key");
+    ctx.check(rsx_merge_device(ctx.get(), d_a_keys, d_a_values, na, d_b_keys, d_b_values, nb, L.key_bytes, L.key_kind, (uint32_t)sizeof(V),
+                               descending ? RSX_ORDER_DESCENDING : RSX_ORDER_ASCENDING, d_out_keys, d_out_values, d_out_index, (uint32_t)sizeof(I),
+                               stream),
+              "rsx_merge_device");
+}
+template <typename K, typename V>
+void merge_pairs(const K* d_a_keys, const V* d_a_values, size_t na, const K* d_b_keys, const V* d_b_values, size_t nb, K* d_out_keys,
+                 V* d_out_values, bool descending = false, void* stream = nullptr, Context& ctx = default_context()) {
+    merge_pairs(d_a_keys, d_a_values, na, d_b_keys, d_b_values, nb, d_out_keys, d_out_values, static_cast<uint64_t*>(nullptr), descending, stream, ctx);
+}
+template <typename K>
+void merge(const K* d_a_keys, size_t na, const K* d_b_keys, size_t nb, K* d_out_keys, bool descending = false, void* stream = nullptr,
+           Context& ctx = default_context()) {
+    const rsx_layout L = RadixDigits<K>::layout();
+    if (L.key_offset != 0 || L.key_bytes != L.elem_bytes) throw std::invalid_argument("merge: the key type must be its own key");
+    ctx.check(rsx_merge_device(ctx.get(), d_a_keys, nullptr, na, d_b_keys, nullptr, nb, L.key_bytes, L.key_kind, 0u,
+                               descending ? RSX_ORDER_DESCENDING : RSX_ORDER_ASCENDING, d_out_keys, nullptr, nullptr, 8u, stream),
+              "rsx_merge_device");
 }
 
 // Several key columns (rsx_lexsort_device, rsx_sort_columns_device): rows sorted by (column 0, column 1, ...), column 0

@@ -76,6 +76,14 @@ extern "C" {
                                     stream: *mut c_void) -> c_int;
     pub fn rsx_ctx_reserve_search(ctx: *mut RsxCtx, m: usize, key_bytes: u32) -> c_int;
     pub fn rsx_search_caps(key_bytes: u32, with_positions: c_int, tile: *mut u32, window: *mut u32) -> c_int;
+    // stable merge of two sorted key arrays (include/rsx.h, "stable merge of two sorted key arrays"): keys, values and
+    // the position of every output in a ++ b; each output may be null, not all; no output may overlap an input
+    pub fn rsx_merge_device(ctx: *mut RsxCtx, d_a_keys: *const c_void, d_a_values: *const c_void, na: usize,
+                            d_b_keys: *const c_void, d_b_values: *const c_void, nb: usize, key_bytes: u32, key_kind: u32,
+                            value_bytes: u32, order: c_int, d_out_keys: *mut c_void, d_out_values: *mut c_void,
+                            d_out_index: *mut c_void, index_bytes: u32, stream: *mut c_void) -> c_int;
+    pub fn rsx_ctx_reserve_merge(ctx: *mut RsxCtx, n_total: usize, key_bytes: u32, value_bytes: u32) -> c_int;
+    pub fn rsx_merge_caps(key_bytes: u32, value_bytes: u32, tile: *mut u32) -> c_int;
     pub fn rsx_sort_sharded(ctxs: *const *mut RsxCtx, ndev: u32, d_slices: *const *mut c_void,
                             d_tmps: *const *mut c_void, n_per_dev: *const usize,
                             layout: *const RsxLayout) -> c_int;
