@@ -277,13 +277,19 @@ constexpr int wide_kpt_for(int es) { return es <= 4 ? 28 : es == 8 ? 17 : es == 
 constexpr int medium_kpt_for(int es) { return es == 8 ? RSX_KMED8 : wide_kpt_for(es); }
 // whether an array's 1024-thread form is the longer one: when the average bucket is above 7/8 of what the shorter holds
 constexpr bool wide_big_form(int es, uint64_t n) { return n / 65536u > (uint64_t)1024 * (uint64_t)bucket_kpt_for(es) * 7u / 8u; }
-// elements a workgroup of `wg` threads x `kpt` registers holds in LDS (rsx_small_kernel.hpp cape<ES, KPT, WG>, same formula)
+// The dynamic LDS of a workgroup that sorts in LDS (rsx_small_kernel.hpp, LdsTile, which carves it): the elements, the
+// wave counters [wg / 64][256], 64 bytes of the waves' totals and the 3 KiB of the sort through memory.
+constexpr uint32_t LDS_PER_CU = 163840u;  // gfx950: 160 KiB
+constexpr size_t bucket_cnt_bytes() { return 4; }
+constexpr uint32_t lds_tile_fixed(int wg) { return (uint32_t)(wg / 64) * 256u * (uint32_t)bucket_cnt_bytes() + 64u + 3u * 256u * 4u; }
+// elements a workgroup of `wg` threads x `kpt` registers holds there: wg * kpt, or what 160 KiB leave beside the rest and
+// 1 KiB for the kernels' static LDS (1024 threads of 16-byte elements: 9020 of 9216 slots)
 constexpr uint32_t bucket_cape(int es, int kpt, int wg) {
     const uint32_t slots = (uint32_t)wg * (uint32_t)kpt;
-    const uint32_t room = ((163840u - 1024u - (uint32_t)(wg / 64) * 256u * 4u - 64u - 3u * 256u * 4u) / (uint32_t)es) & ~3u;
+    const uint32_t room = ((LDS_PER_CU - 1024u - lds_tile_fixed(wg)) / (uint32_t)es) & ~3u;
     return slots < room ? slots : room;
 }
-constexpr size_t bucket_cnt_bytes() { return 4; }
+constexpr size_t lds_tile_bytes(int es, int kpt, int wg) { return (size_t)bucket_cape(es, kpt, wg) * (size_t)es + lds_tile_fixed(wg); }
 // the LDS size classes of a segmented sort (rsx_segment_kernels.hpp): 256 and 1024 threads x bucket_kpt_for(es) elements
 constexpr uint32_t segment_cap(int es, int cls) { return bucket_cape(es, bucket_kpt_for(es), cls == 0 ? 256 : 1024); }
 // the hybrid's buffer (ctx->wide_buf): bucket totals [65536], block totals [256], starts [65537] (u64), then its WidePlan

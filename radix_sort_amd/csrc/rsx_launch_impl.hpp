@@ -346,10 +346,10 @@ int launch_bucket_sort(rsx_ctx* ctx, const void* src, void* dst, const rsx_layou
         a.hint = ctx->host_err_dev + HV_MID_HINT;
         LaunchTimer lt(ctx, RSX_PROF_OTHER, st);
         if (small) {  // small buckets, all known to fit: 256 threads each
-            const size_t lds = (size_t)cape<ES, KPT, 256>() * ES + 4 * RADIX * bucket_cnt_bytes() + 64 + 3 * RADIX * sizeof(uint32_t);
+            constexpr size_t lds = LdsTile<ES, KPT, 256>::bytes();
             hipLaunchKernelGGL((rsx_bucket_sort_kernel<ES, KPT, 256>), dim3(RADIX), dim3(256), lds, st, a);
         } else {
-            const size_t lds = (size_t)cape<ES, KPT, 1024>() * ES + 16 * RADIX * bucket_cnt_bytes() + 64 + 3 * RADIX * sizeof(uint32_t);
+            constexpr size_t lds = LdsTile<ES, KPT, 1024>::bytes();
             auto kern = rsx_bucket_sort_kernel<ES, KPT, 1024>;
             ensure_lds(ctx, reinterpret_cast<const void*>(kern), lds);
             hipLaunchKernelGGL(kern, dim3(RADIX), dim3(1024), lds, st, a);
@@ -457,11 +457,10 @@ int launch_bucket16(rsx_ctx* ctx, const SortRun& run, void* data, void* scratch,
             SmallArgs b = a;
             b.group_shift = group_shift;
             if (group_shift) b.passes = L->key_bytes;
-            static_assert(cape<ES, K, WGS>() == bucket_cape(ES, K, WGS), "host and device agree on what a workgroup holds");
-            const size_t lds = (size_t)cape<ES, K, WGS>() * ES + (WGS / 64) * RADIX * bucket_cnt_bytes() + 64 + 3 * RADIX * sizeof(uint32_t);
+            constexpr size_t lds = LdsTile<ES, K, WGS>::bytes();
             auto kern = rsx_bucket16_kernel<ES, K, WGS>;
             ensure_lds(ctx, reinterpret_cast<const void*>(kern), lds);
-            int per_cu = (int)((size_t)163840 / lds);
+            int per_cu = (int)(LDS_PER_CU / lds);
             if (per_cu < 1) per_cu = 1;
             if (per_cu > 4 * RSX_B16_WAVES(WGS) * 64 / WGS) per_cu = 4 * RSX_B16_WAVES(WGS) * 64 / WGS;
             const Gate g{base.word, VERDICT_PATH_MASK | VERDICT_FORM_MASK, VERDICT_HYBRID | form};
@@ -486,7 +485,7 @@ int launch_bucket16(rsx_ctx* ctx, const SortRun& run, void* data, void* scratch,
         else go(integral_constant<int, 1024>{}, integral_constant<int, KPT>{}, VERDICT_WG1024, 0);
         {   // the buckets above the chosen form's workgroup (VERDICT_MEDIUM): one workgroup of the largest kind each
             constexpr int KMED = medium_kpt_for(ES);
-            const size_t lds = (size_t)cape<ES, KMED, 1024>() * ES + 16 * RADIX * bucket_cnt_bytes() + 64 + 3 * RADIX * sizeof(uint32_t);
+            constexpr size_t lds = LdsTile<ES, KMED, 1024>::bytes();
             auto kern = rsx_bucket16_medium_kernel<ES, KMED, 1024>;
             ensure_lds(ctx, reinterpret_cast<const void*>(kern), lds);
             const Gate g{base.word, VERDICT_PATH_MASK | VERDICT_MEDIUM, VERDICT_HYBRID | VERDICT_MEDIUM};
@@ -508,6 +507,57 @@ int launch_segcopy(rsx_ctx* ctx, const void* src, void* dst, const uint64_t* so,
     return RSX_OK;
 }
 
+// ---- the classes of the LDS sort: what the segmented sorts and top-k launch ------------------------------------------
+// One class is a workgroup size x bucket_kpt_for(ES) elements; its persistent grid fills the device.
+struct LdsGeometry {
+    size_t lds;     // dynamic LDS of a workgroup
+    uint64_t full;  // workgroups that fill the device
+};
+template <int ES, int KPT, int WG, typename Kern>
+LdsGeometry lds_class_geometry(rsx_ctx* ctx, Kern kern) {
+    constexpr size_t lds = LdsTile<ES, KPT, WG>::bytes();
+    ensure_lds(ctx, reinterpret_cast<const void*>(kern), lds);
+    uint32_t per_cu = (uint32_t)(LDS_PER_CU / (lds + 1024));
+    if (per_cu > 1024u / WG) per_cu = 1024u / WG;  // (128 registers a lane: 16 waves a CU)
+    if (per_cu < 1) per_cu = 1;
+    return {lds, (uint64_t)ctx->num_cu * per_cu};
+}
+// the grid of a segmented class, and the workgroups of a team (rsx_segment_kernels.hpp, Dispatch)
+inline uint64_t segment_grid(uint64_t full, const uint64_t* offsets, uint64_t nseg, uint32_t* team) {
+    *team = 1;
+    if (!offsets) return full > nseg ? nseg : full;
+    const uint64_t nblocks = (nseg + SEG_BLOCK - 1) / SEG_BLOCK;  // few blocks: the workgroups of a team share a block's members
+    while (*team < SEG_BLOCK && (uint64_t)*team < nseg && nblocks * *team < full) *team *= 2;
+    uint64_t teams = full / *team;
+    if (teams < 1) teams = 1;
+    if (teams > nblocks) teams = nblocks;
+    return teams * *team;
+}
+// The three classes of a segmented launch, segments of lo < length <= hi each: 256 threads in LDS from `lo0`, 1024 threads
+// in LDS, 1024 threads through memory.  go(workgroup size, through memory, walk with lo and hi set) launches one; a class
+// that `max_len` (0: unknown), or the one row length, leaves no segment is passed over.
+template <int ES, typename Go>
+int for_segment_classes(const SegWalk& w, uint64_t max_len, uint64_t lo0, Go&& go) {
+    constexpr uint32_t CAP0 = segment_cap(ES, 0), CAP1 = segment_cap(ES, 1);
+    const uint64_t longest = w.offsets ? (max_len ? max_len : ~0ull) : w.row_len;
+    auto one = [&](auto wgc, auto memc, uint64_t lo, uint64_t hi) -> int {
+        if (longest <= lo || (!w.offsets && w.row_len > hi)) return RSX_OK;  // no segment of this class can occur
+        SegWalk c = w;
+        c.lo = lo;
+        c.hi = hi;
+        return go(wgc, memc, c);
+    };
+    using std::integral_constant;
+    int rc = one(integral_constant<int, 256>{}, integral_constant<bool, false>{}, lo0, CAP0);
+    if (rc) return rc;
+    rc = one(integral_constant<int, 1024>{}, integral_constant<bool, false>{}, CAP0, CAP1);
+    if (rc) return rc;
+    return one(integral_constant<int, 1024>{}, integral_constant<bool, true>{}, CAP1, 0xFFFFFFFFull);
+}
+inline SegWalk seg_walk(rsx_ctx* ctx, uint64_t n, const uint64_t* offsets, uint64_t nseg, uint64_t row_len) {
+    return SegWalk{n, offsets, nseg, row_len, 0, 0, 1, ctx->host_err_dev};  // (lo, hi and team: set per class)
+}
+
 // ---- many segments of one array (rsx_segment_kernels.hpp) ------------------------------------------
 // One launch per size class that `max_len` (0: unknown) leaves possible; rows (offsets == nullptr): the one class of
 // row_len.  *launched receives the number of kernels enqueued.
@@ -515,62 +565,25 @@ template <int ES>
 int launch_segment_sort(rsx_ctx* ctx, void* data, void* tmp, size_t n, const rsx_layout* L, const uint64_t* offsets, uint64_t nseg,
                         uint64_t row_len, uint64_t max_len, uint32_t* launched, hipStream_t st) {
     constexpr int KPT = bucket_kpt_for(ES);
-    constexpr uint32_t CAP0 = cape<ES, KPT, 256>(), CAP1 = cape<ES, KPT, 1024>();
-    static_assert(CAP0 == segment_cap(ES, 0) && CAP1 == segment_cap(ES, 1), "host and device agree on what a workgroup holds");
     if (L->key_bytes > 16) return fail(ctx, RSX_ERR_INTERNAL, "launch_segment_sort: key width out of range");
     SmallArgs a = small_args(ctx, L, L->key_bytes, L->key_bytes, true);  // the LDS forms
     if (L->key_bytes < 6) a.no_skip = 1u;
     SmallArgs am = a;  // through memory: the keys stay raw, every pass reads its digit through the key map
     am.map_load = am.map_store = 0;
     for (uint32_t d = 0; d < L->key_bytes; ++d) am.spec[d] = make_spec(L, d);
-    SegArgs s;
-    std::memset(&s, 0, sizeof s);
-    s.data = data;
-    s.tmp = tmp;
-    s.n = n;
-    s.offsets = offsets;
-    s.nseg = nseg;
-    s.row_len = row_len;
-    s.error = ctx->host_err_dev;
-    const uint64_t longest = offsets ? (max_len ? max_len : ~0ull) : row_len;
-    auto go = [&](auto wgc, auto memc, uint64_t lo, uint64_t hi) -> int {
+    return for_segment_classes<ES>(seg_walk(ctx, n, offsets, nseg, row_len), max_len, 1, [&](auto wgc, auto memc, const SegWalk& w) -> int {
         constexpr int WGS = decltype(wgc)::value;
         constexpr bool MEM = decltype(memc)::value;
-        if (longest <= lo || (!offsets && row_len > hi)) return RSX_OK;  // no segment of this class can occur
-        const size_t lds = (size_t)cape<ES, KPT, WGS>() * ES + (WGS / 64) * RADIX * bucket_cnt_bytes() + 64 + 3 * RADIX * sizeof(uint32_t);
         auto kern = rsx_segment_sort_kernel<ES, KPT, WGS, MEM>;
-        ensure_lds(ctx, reinterpret_cast<const void*>(kern), lds);
-        uint32_t per_cu = (uint32_t)((size_t)163840 / (lds + 1024));
-        if (per_cu > 1024u / WGS) per_cu = 1024u / WGS;  // (128 registers a lane: 16 waves a CU)
-        if (per_cu < 1) per_cu = 1;
-        const uint64_t full = (uint64_t)ctx->num_cu * per_cu;
-        SegArgs b = s;
-        b.lo = lo;
-        b.hi = hi;
-        b.team = 1;
-        uint64_t grid = full;
-        if (!offsets) {
-            if (grid > nseg) grid = nseg;
-        } else {  // few blocks: the workgroups of a team share a block's members
-            const uint64_t nblocks = (nseg + SEG_BLOCK - 1) / SEG_BLOCK;
-            while (b.team < SEG_BLOCK && (uint64_t)b.team < nseg && nblocks * b.team < full) b.team *= 2;
-            uint64_t teams = full / b.team;
-            if (teams < 1) teams = 1;
-            if (teams > nblocks) teams = nblocks;
-            grid = teams * b.team;
-        }
+        const LdsGeometry g = lds_class_geometry<ES, KPT, WGS>(ctx, kern);
+        SegArgs b{data, tmp, w};
+        const uint64_t grid = segment_grid(g.full, offsets, nseg, &b.w.team);
         LaunchTimer lt(ctx, RSX_PROF_OTHER, st);
-        hipLaunchKernelGGL(kern, dim3((uint32_t)grid), dim3(WGS), lds, st, MEM ? am : a, b);
+        hipLaunchKernelGGL(kern, dim3((uint32_t)grid), dim3(WGS), g.lds, st, MEM ? am : a, b);
         RSX_HIP(hipGetLastError());
         ++*launched;
         return RSX_OK;
-    };
-    using std::integral_constant;
-    int rc = go(integral_constant<int, 256>{}, integral_constant<bool, false>{}, 1, CAP0);
-    if (rc) return rc;
-    rc = go(integral_constant<int, 1024>{}, integral_constant<bool, false>{}, CAP0, CAP1);
-    if (rc) return rc;
-    return go(integral_constant<int, 1024>{}, integral_constant<bool, true>{}, CAP1, 0xFFFFFFFFull);
+    });
 }
 
 // ---- many segments of separate key and value columns (rsx_segment_pairs_kernels.hpp) ----------------------
@@ -579,67 +592,25 @@ int launch_segment_sort(rsx_ctx* ctx, void* data, void* tmp, size_t n, const rsx
 template <int ES, int KB, int VB>
 int launch_segment_pairs_kv(rsx_ctx* ctx, const SegPairsCall& c, uint32_t* launched, hipStream_t st) {
     constexpr int KPT = bucket_kpt_for(ES);
-    constexpr uint32_t CAP0 = cape<ES, KPT, 256>(), CAP1 = cape<ES, KPT, 1024>();
-    static_assert(CAP0 == segment_cap(ES, 0) && CAP1 == segment_cap(ES, 1), "host and device agree on what a workgroup holds");
     const rsx_layout L{(uint32_t)ES, 0, (uint32_t)KB, RSX_KEY_UNSIGNED};  // what the passes see: the mapped key in front
     SmallArgs a = small_args(ctx, &L, KB, KB, false);
     if (KB < 6) a.no_skip = 1u;
-    SegPairsArgs s;
-    std::memset(&s, 0, sizeof s);
-    s.keys = static_cast<uint8_t*>(c.keys);
-    s.values = static_cast<uint8_t*>(c.values);
-    s.w0 = c.w0;
-    s.w1 = c.w1;
-    s.n = c.n;
-    s.offsets = c.offsets;
-    s.nseg = c.nseg;
-    s.row_len = c.row_len;
-    s.error = ctx->host_err_dev;
-    s.kind = c.kind;
-    s.desc = c.desc;
-    s.mode = c.mode;
-    s.ib = c.ib;
-    const uint64_t longest = c.offsets ? (c.max_len ? c.max_len : ~0ull) : c.row_len;
-    auto go = [&](auto wgc, auto memc, uint64_t lo, uint64_t hi) -> int {
+    // (argsort: a segment of one element gets its one 0, so the first class starts at length 1)
+    return for_segment_classes<ES>(seg_walk(ctx, c.n, c.offsets, c.nseg, c.row_len), c.max_len, c.mode == SEGP_LOCAL ? 0 : 1,
+                                   [&](auto wgc, auto memc, const SegWalk& w) -> int {
         constexpr int WGS = decltype(wgc)::value;
         constexpr bool MEM = decltype(memc)::value;
-        if (longest <= lo || (!c.offsets && c.row_len > hi)) return RSX_OK;  // no segment of this class can occur
         if (MEM && (!c.w0 || !c.w1)) return fail(ctx, RSX_ERR_INTERNAL, "launch_segment_pairs: no workspace for the through-memory class");
-        const size_t lds = (size_t)cape<ES, KPT, WGS>() * ES + (WGS / 64) * RADIX * bucket_cnt_bytes() + 64 + 3 * RADIX * sizeof(uint32_t);
         auto kern = rsx_segment_pairs_kernel<ES, KB, VB, KPT, WGS, MEM>;
-        ensure_lds(ctx, reinterpret_cast<const void*>(kern), lds);
-        uint32_t per_cu = (uint32_t)((size_t)163840 / (lds + 1024));
-        if (per_cu > 1024u / WGS) per_cu = 1024u / WGS;  // (128 registers a lane: 16 waves a CU)
-        if (per_cu < 1) per_cu = 1;
-        const uint64_t full = (uint64_t)ctx->num_cu * per_cu;
-        SegPairsArgs b = s;
-        b.lo = lo;
-        b.hi = hi;
-        b.team = 1;
-        uint64_t grid = full;
-        if (!c.offsets) {
-            if (grid > c.nseg) grid = c.nseg;
-        } else {  // few blocks: the workgroups of a team share a block's members
-            const uint64_t nblocks = (c.nseg + SEG_BLOCK - 1) / SEG_BLOCK;
-            while (b.team < SEG_BLOCK && (uint64_t)b.team < c.nseg && nblocks * b.team < full) b.team *= 2;
-            uint64_t teams = full / b.team;
-            if (teams < 1) teams = 1;
-            if (teams > nblocks) teams = nblocks;
-            grid = teams * b.team;
-        }
+        const LdsGeometry g = lds_class_geometry<ES, KPT, WGS>(ctx, kern);
+        SegPairsArgs b{static_cast<uint8_t*>(c.keys), static_cast<uint8_t*>(c.values), c.w0, c.w1, w, c.kind, c.desc, c.mode, c.ib};
+        const uint64_t grid = segment_grid(g.full, c.offsets, c.nseg, &b.w.team);
         LaunchTimer lt(ctx, RSX_PROF_OTHER, st);
-        hipLaunchKernelGGL(kern, dim3((uint32_t)grid), dim3(WGS), lds, st, a, b);
+        hipLaunchKernelGGL(kern, dim3((uint32_t)grid), dim3(WGS), g.lds, st, a, b);
         RSX_HIP(hipGetLastError());
         ++*launched;
         return RSX_OK;
-    };
-    using std::integral_constant;
-    // (argsort: a segment of one element gets its one 0, so the first class starts at length 1)
-    int rc = go(integral_constant<int, 256>{}, integral_constant<bool, false>{}, c.mode == SEGP_LOCAL ? 0 : 1, CAP0);
-    if (rc) return rc;
-    rc = go(integral_constant<int, 1024>{}, integral_constant<bool, false>{}, CAP0, CAP1);
-    if (rc) return rc;
-    return go(integral_constant<int, 1024>{}, integral_constant<bool, true>{}, CAP1, 0xFFFFFFFFull);
+    });
 }
 
 template <int ES, int KB, int VB>
@@ -677,8 +648,7 @@ int launch_segment_pairs(rsx_ctx* ctx, const SegPairsCall& c, uint32_t* launched
 template <int ES, int KB>
 int launch_topk_kb(rsx_ctx* ctx, const TopkCall& c, uint32_t* launched, hipStream_t st) {
     constexpr int KPT = bucket_kpt_for(ES);
-    constexpr uint32_t CAP0 = cape<ES, KPT, 256>(), CAP1 = cape<ES, KPT, 1024>();
-    static_assert(CAP0 == segment_cap(ES, 0) && CAP1 == segment_cap(ES, 1), "host and device agree on what a workgroup holds");
+    constexpr uint32_t CAP0 = segment_cap(ES, 0), CAP1 = segment_cap(ES, 1);
     const rsx_layout L{(uint32_t)ES, 0, (uint32_t)KB, RSX_KEY_UNSIGNED};  // what the passes see: the mapped key in front
     SmallArgs a = small_args(ctx, &L, KB, KB, false);
     if (KB < 6) a.no_skip = 1u;
@@ -694,17 +664,11 @@ int launch_topk_kb(rsx_ctx* ctx, const TopkCall& c, uint32_t* launched, hipStrea
     t.ib = c.ib;
     auto go = [&](auto wgc) -> int {
         constexpr int WGS = decltype(wgc)::value;
-        const size_t lds = (size_t)cape<ES, KPT, WGS>() * ES + (WGS / 64) * RADIX * bucket_cnt_bytes() + 64 + 3 * RADIX * sizeof(uint32_t);
         auto kern = rsx_topk_kernel<ES, KB, KPT, WGS>;
-        ensure_lds(ctx, reinterpret_cast<const void*>(kern), lds);
-        uint32_t per_cu = (uint32_t)((size_t)163840 / (lds + 1024));
-        if (per_cu > 1024u / WGS) per_cu = 1024u / WGS;  // (128 registers a lane: 16 waves a CU)
-        if (per_cu < 1) per_cu = 1;
-        uint64_t grid = (uint64_t)ctx->num_cu * per_cu;
+        const LdsGeometry g = lds_class_geometry<ES, KPT, WGS>(ctx, kern);
         const uint64_t total = t.rows * t.cpr;
-        if (grid > total) grid = total;
         LaunchTimer lt(ctx, RSX_PROF_OTHER, st);
-        hipLaunchKernelGGL(kern, dim3((uint32_t)grid), dim3(WGS), lds, st, a, t);
+        hipLaunchKernelGGL(kern, dim3((uint32_t)(g.full > total ? total : g.full)), dim3(WGS), g.lds, st, a, t);
         RSX_HIP(hipGetLastError());
         ++*launched;
         return RSX_OK;

@@ -22,16 +22,20 @@
 
 namespace rsx {
 
-struct SegArgs {
-    void* data;               // n elements
-    void* tmp;                // n elements: the ping-pong array of the sort through memory
-    uint64_t n;
+// What the walk over the segments reads; the kernels' argument blocks hold one behind their arrays.
+struct SegWalk {
+    uint64_t n;               // elements in the arrays
     const uint64_t* offsets;  // nseg + 1 element offsets, or nullptr: segment i = [i * row_len, (i + 1) * row_len)
     uint64_t nseg;
     uint64_t row_len;
     uint64_t lo, hi;          // this launch sorts the segments of lo < length <= hi
     uint32_t team;            // workgroups that share a block of SEG_BLOCK segments (a power of two, <= SEG_BLOCK)
     uint32_t* error;          // host-visible error word of the context
+};
+struct SegArgs {
+    void* data;  // n elements
+    void* tmp;   // n elements: the ping-pong array of the sort through memory
+    SegWalk w;
 };
 
 // One segment [0, len) at `seg`, in place (scratch at `scr`).  MEM == false: len <= cape<ES, KPT, WG>().
@@ -60,12 +64,13 @@ __device__ __forceinline__ void segment_sort_one(const SmallArgs& a, Elem<ES>* s
         // As rsx_bucket_sort_kernel: the passes start at the digit a uniform array of this length is told apart by, the
         // neighbours that still agree are mended by the digits skipped.  A workgroup that meets a segment where that
         // fails (keys that agree on their high digits: small integers in wide keys) runs every pass from then on.
+        // (These lines stand at four sites -- here, segp_sort_one, topk_one, rsx_bucket_sort_kernel: as one helper four kernels compile otherwise.)
         PassPlan pp;
         pp.end = a.passes;
         pp.first = (a.no_skip || !skip_ok) ? 0u : first_digit_for(len, 8u * a.passes, a.passes);
         pp.set_masks(a.key_offset, a.key_bytes);
         const uint32_t first = pp.first;
-        uint32_t* s_flag = reinterpret_cast<uint32_t*>(reinterpret_cast<typename WaveCnt<ES>::T*>(smem + (size_t)cape<ES, KPT, WG>() * sizeof(E)) + (WG / WAVE) * RADIX) + (WG / WAVE);
+        uint32_t* s_flag = LdsTile<ES, KPT, WG>::flag(smem);
         local_sort_skip<ES, KPT, WG>(a, seg, seg, len, smem, pp, s_flag);
         if (pp.first != first) skip_ok = 0;
     }
@@ -76,6 +81,8 @@ constexpr uint32_t SEG_BLOCK = 64;  // segments a workgroup examines at a time: 
 template <int ES, int KPT, int WG, bool MEM>
 __global__ __launch_bounds__(WG) void rsx_segment_sort_kernel(const SmallArgs a, const SegArgs s) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    // (The loop below reads SegWalk alone and is the same, token for token, in rsx_segment_pairs_kernel.  It stays in
+    // both kernels: as one function that takes the body, the through-memory fused kernels gained 8-128 bytes of scratch.)
     // the block's segments as its first wave read and judged them (every thread takes a member's place from here: the
     // offsets are read once, by vector loads, and what was judged is what is sorted)
     __shared__ uint64_t s_beg[SEG_BLOCK];
@@ -83,11 +90,11 @@ __global__ __launch_bounds__(WG) void rsx_segment_sort_kernel(const SmallArgs a,
     __shared__ uint64_t s_members;
     using E = Elem<ES>;
     const uint32_t tid = threadIdx.x;
-    const bool rows = s.offsets == nullptr;
-    const uint32_t team = rows ? 1u : s.team;
+    const bool rows = s.w.offsets == nullptr;
+    const uint32_t team = rows ? 1u : s.w.team;
     const uint32_t r = blockIdx.x & (team - 1u);
     const uint64_t step = gridDim.x / team;
-    const uint64_t nblocks = rows ? s.nseg : (s.nseg + SEG_BLOCK - 1) / SEG_BLOCK;
+    const uint64_t nblocks = rows ? s.w.nseg : (s.w.nseg + SEG_BLOCK - 1) / SEG_BLOCK;
     uint32_t skip_ok = 1;
     for (uint64_t blk = blockIdx.x / team; blk < nblocks; blk += step) {
         if (!rows) {
@@ -95,12 +102,12 @@ __global__ __launch_bounds__(WG) void rsx_segment_sort_kernel(const SmallArgs a,
                 const uint64_t i = blk * SEG_BLOCK + tid;
                 bool member = false;
                 uint64_t b = 0, e = 0;
-                if (i < s.nseg) {
-                    b = s.offsets[i];
-                    e = s.offsets[i + 1];
-                    const bool valid = b <= e && e <= s.n && e - b < (1ull << 32);
-                    if (!valid) __hip_atomic_store(s.error, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    member = valid && e - b > s.lo && e - b <= s.hi;
+                if (i < s.w.nseg) {
+                    b = s.w.offsets[i];
+                    e = s.w.offsets[i + 1];
+                    const bool valid = b <= e && e <= s.w.n && e - b < (1ull << 32);
+                    if (!valid) __hip_atomic_store(s.w.error, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    member = valid && e - b > s.w.lo && e - b <= s.w.hi;
                 }
                 s_beg[tid] = b;
                 s_len[tid] = member ? (uint32_t)(e - b) : 0u;
@@ -117,8 +124,8 @@ __global__ __launch_bounds__(WG) void rsx_segment_sort_kernel(const SmallArgs a,
         uint32_t k = 0;  // members of the block so far (uniform, as everything from here on)
         for (; m != 0; m &= m - 1ull) {
             if ((k++ & (team - 1u)) != r) continue;
-            uint64_t beg = blk * s.row_len;
-            uint32_t len = (uint32_t)s.row_len;
+            uint64_t beg = blk * s.w.row_len;
+            uint32_t len = (uint32_t)s.w.row_len;
             if (!rows) {
                 const uint32_t bit = (uint32_t)__builtin_ctzll(m);
                 const uint64_t v = s_beg[bit];

@@ -27,13 +27,7 @@ struct SegPairsArgs {
     uint8_t* values;          // SEGP_VALUES: n values; SEGP_LOCAL: n indices of ib bytes; SEGP_GLOBAL: n proxies of ES bytes
     void* w0;                 // MEM: the two workspace arrays of n joined elements
     void* w1;
-    uint64_t n;
-    const uint64_t* offsets;  // nseg + 1 element offsets, or nullptr: segment i = [i * row_len, (i + 1) * row_len)
-    uint64_t nseg;
-    uint64_t row_len;
-    uint64_t lo, hi;          // this launch sorts the segments of lo < length <= hi
-    uint32_t team;
-    uint32_t* error;          // host-visible error word of the context
+    SegWalk w;                // n: of keys, values and workspace elements
     uint32_t kind, desc, mode, ib;
 };
 
@@ -119,7 +113,7 @@ __device__ __forceinline__ void segp_passes_skip(const SmallArgs& a, Elem<ES> (&
     if (!mended) mended = local_mend_listed<ES, KPT, WG>(n, smem, pp, s_flag, ties);
     if (!mended) {
         pp.first = 0;
-        const uint32_t kp = (n + WG - 1) / WG, seg = (threadIdx.x >> 6) * (WAVE * kp) + (threadIdx.x & 63u);
+        const uint32_t kp = (n + WG - 1) / WG, seg = (threadIdx.x >> 6) * (WAVE * kp) + (threadIdx.x & 63u);  // (as in local_sort_skip)
 #pragma unroll
         for (int j = 0; j < KPT; ++j)
             if ((uint32_t)j < kp) e[j] = reinterpret_cast<const E*>(smem)[seg + (uint32_t)j * WAVE];
@@ -152,7 +146,7 @@ __device__ __forceinline__ void segp_sort_one(const SmallArgs& a, const SegPairs
         for (uint32_t i = threadIdx.x; i < len; i += WG) segp_split<ES, KB, VB>(s, beg, i, src[i]);
     } else {
         E e[KPT];
-        {   // the slot order of local_load
+        {   // the slot order: slots_of(len), written out (through the call three of these kernels are scheduled otherwise)
             const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
             const uint32_t kp = (len + WG - 1) / WG;
             const uint32_t seg = wave * (WAVE * kp) + lane;
@@ -173,7 +167,7 @@ __device__ __forceinline__ void segp_sort_one(const SmallArgs& a, const SegPairs
             pp.first = (a.no_skip || !skip_ok) ? 0u : first_digit_for(len, 8u * a.passes, a.passes);
             pp.set_masks(0u, (uint32_t)KB);
             const uint32_t first = pp.first;
-            uint32_t* s_flag = reinterpret_cast<uint32_t*>(reinterpret_cast<typename WaveCnt<ES>::T*>(smem + (size_t)cape<ES, KPT, WG>() * sizeof(E)) + (WG / WAVE) * RADIX) + (WG / WAVE);
+            uint32_t* s_flag = LdsTile<ES, KPT, WG>::flag(smem);
             segp_passes_skip<ES, KPT, WG>(a, e, len, smem, pp, s_flag);
             if (pp.first != first) skip_ok = 0;
         }
@@ -185,16 +179,16 @@ __device__ __forceinline__ void segp_sort_one(const SmallArgs& a, const SegPairs
 template <int ES, int KB, int VB, int KPT, int WG, bool MEM>
 __global__ __launch_bounds__(WG) void rsx_segment_pairs_kernel(const SmallArgs a, const SegPairsArgs s) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    // (the dispatch loop of rsx_segment_sort_kernel)
+    // (the dispatch loop of rsx_segment_sort_kernel, which says why it is written out twice)
     __shared__ uint64_t s_beg[SEG_BLOCK];
     __shared__ uint32_t s_len[SEG_BLOCK];
     __shared__ uint64_t s_members;
     const uint32_t tid = threadIdx.x;
-    const bool rows = s.offsets == nullptr;
-    const uint32_t team = rows ? 1u : s.team;
+    const bool rows = s.w.offsets == nullptr;
+    const uint32_t team = rows ? 1u : s.w.team;
     const uint32_t r = blockIdx.x & (team - 1u);
     const uint64_t step = gridDim.x / team;
-    const uint64_t nblocks = rows ? s.nseg : (s.nseg + SEG_BLOCK - 1) / SEG_BLOCK;
+    const uint64_t nblocks = rows ? s.w.nseg : (s.w.nseg + SEG_BLOCK - 1) / SEG_BLOCK;
     uint32_t skip_ok = 1;
     for (uint64_t blk = blockIdx.x / team; blk < nblocks; blk += step) {
         if (!rows) {
@@ -202,12 +196,12 @@ __global__ __launch_bounds__(WG) void rsx_segment_pairs_kernel(const SmallArgs a
                 const uint64_t i = blk * SEG_BLOCK + tid;
                 bool member = false;
                 uint64_t b = 0, e = 0;
-                if (i < s.nseg) {
-                    b = s.offsets[i];
-                    e = s.offsets[i + 1];
-                    const bool valid = b <= e && e <= s.n && e - b < (1ull << 32);
-                    if (!valid) __hip_atomic_store(s.error, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    member = valid && e - b > s.lo && e - b <= s.hi;
+                if (i < s.w.nseg) {
+                    b = s.w.offsets[i];
+                    e = s.w.offsets[i + 1];
+                    const bool valid = b <= e && e <= s.w.n && e - b < (1ull << 32);
+                    if (!valid) __hip_atomic_store(s.w.error, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    member = valid && e - b > s.w.lo && e - b <= s.w.hi;
                 }
                 s_beg[tid] = b;
                 s_len[tid] = member ? (uint32_t)(e - b) : 0u;
@@ -224,8 +218,8 @@ __global__ __launch_bounds__(WG) void rsx_segment_pairs_kernel(const SmallArgs a
         uint32_t k = 0;
         for (; m != 0; m &= m - 1ull) {
             if ((k++ & (team - 1u)) != r) continue;
-            uint64_t beg = blk * s.row_len;
-            uint32_t len = (uint32_t)s.row_len;
+            uint64_t beg = blk * s.w.row_len;
+            uint32_t len = (uint32_t)s.w.row_len;
             if (!rows) {
                 const uint32_t bit = (uint32_t)__builtin_ctzll(m);
                 const uint64_t v = s_beg[bit];

@@ -23,6 +23,7 @@
 // stable sort by the whole key).
 #pragma once
 #include "rsx_device.hpp"
+#include "rsx_internal.hpp"  // the tile geometry: bucket_cape, lds_tile_bytes
 
 namespace rsx {
 
@@ -104,22 +105,40 @@ struct WaveCnt {
         }
     }
 };
-// What a workgroup of WG threads x KPT registers holds in LDS: WG * KPT elements, or what 160 KiB leave beside the wave
-// counters and the 3 KiB of the sort through memory (1024 threads of 16-byte elements: 9020 of 9216 slots).
+// What a workgroup of WG threads x KPT registers holds in LDS (bucket_cape: WG * KPT elements, or what 160 KiB leave).
 template <int ES, int KPT, int WG>
 __host__ __device__ constexpr uint32_t cape() {
-    constexpr uint32_t slots = (uint32_t)WG * KPT;
-    constexpr uint32_t room = ((163840u - 1024u - (uint32_t)(WG / WAVE) * RADIX * (uint32_t)sizeof(typename WaveCnt<ES>::T) - 64u - 3u * RADIX * 4u) / (uint32_t)ES) & ~3u;  // (1 KiB for the kernels' static LDS)
-    return slots < room ? slots : room;
+    constexpr uint32_t c = rsxh::bucket_cape(ES, KPT, WG);
+    return c;
 }
+// The dynamic LDS of such a workgroup (lds_tile_bytes() of them), carved:
+template <int ES, int KPT, int WG>
+struct LdsTile {
+    using C = typename WaveCnt<ES>::T;
+    static_assert(sizeof(C) == rsxh::bucket_cnt_bytes(), "host and device agree on the wave counters");
+    static constexpr int NWAVE = WG / WAVE;
+    __host__ __device__ static constexpr size_t bytes() { return rsxh::lds_tile_bytes(ES, KPT, WG); }
+    static __device__ __forceinline__ Elem<ES>* elems(unsigned char* smem) { return reinterpret_cast<Elem<ES>*>(smem); }  // [cape()]
+    static __device__ __forceinline__ C* cnt(unsigned char* smem) { return reinterpret_cast<C*>(smem + (size_t)cape<ES, KPT, WG>() * ES); }  // [NWAVE][256]
+    static __device__ __forceinline__ uint32_t* misc(unsigned char* smem) { return reinterpret_cast<uint32_t*>(cnt(smem) + NWAVE * RADIX); }  // [NWAVE] (16 words)
+    // the mend's verdict and, four words on, top-k's chosen bin; stream_pass, which mends nothing, has its 3 KiB here
+    static __device__ __forceinline__ uint32_t* flag(unsigned char* smem) { return misc(smem) + NWAVE; }
+};
 
 // The elements of a workgroup's array [0, n) as its threads hold them: wave w holds [w*64*kp, (w+1)*64*kp), round j at
 // +j*64 -- (wave, round, lane) order == index order, so ranks are stable.  kp = ceil(n / WG) rounds are in use.
-template <int ES, int KPT, int WG>
-__device__ __forceinline__ void local_load(const SmallArgs& a, const Elem<ES>* __restrict__ src, const uint32_t n, Elem<ES> (&e)[KPT]) {
+struct Slots { uint32_t kp, seg; };  // rounds in use, 1..KPT; this thread's slot of round 0 (round j: + j * 64)
+template <int WG>
+__device__ __forceinline__ Slots slots_of(const uint32_t n) {
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t kp = (n + WG - 1) / WG;
-    const uint32_t seg = wave * (WAVE * kp) + lane;
+    return Slots{kp, wave * (WAVE * kp) + lane};
+}
+// (The loops over the slots stay at their sites: through one loader with a callable the fused, top-k and 8-byte kernels spilled more.)
+template <int ES, int KPT, int WG>
+__device__ __forceinline__ void local_load(const SmallArgs& a, const Elem<ES>* __restrict__ src, const uint32_t n, Elem<ES> (&e)[KPT]) {
+    const Slots sl = slots_of<WG>(n);
+    const uint32_t kp = sl.kp, seg = sl.seg;
 #pragma unroll
     for (int j = 0; j < KPT; ++j) {
         e[j] = Elem<ES>{};
@@ -140,13 +159,14 @@ __device__ __forceinline__ void local_passes(const SmallArgs& a, Elem<ES> (&e)[K
     const uint32_t stop = end == ~0u ? a.passes : end;
     constexpr int NWAVE = WG / WAVE;
     using E = Elem<ES>;
-    E* s_elems = reinterpret_cast<E*>(smem);                                              // [WG * KPT]
     using C = WaveCnt<ES>;
-    typename C::T* s_cnt = reinterpret_cast<typename C::T*>(smem + (size_t)cape<ES, KPT, WG>() * sizeof(E));  // [NWAVE][256]
-    uint32_t* s_misc = reinterpret_cast<uint32_t*>(s_cnt + NWAVE * RADIX);                         // [NWAVE]
+    using Tile = LdsTile<ES, KPT, WG>;
+    E* s_elems = Tile::elems(smem);
+    typename C::T* s_cnt = Tile::cnt(smem);
+    uint32_t* s_misc = Tile::misc(smem);
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t kp = (n + WG - 1) / WG;          // rounds in use, 1..KPT (wave-uniform, the same for all)
-    const uint32_t seg = wave * (WAVE * kp) + lane;
+    const Slots sl = slots_of<WG>(n);
+    const uint32_t kp = sl.kp, seg = sl.seg;  // rounds in use, 1..KPT (wave-uniform, the same for all); this thread's first slot
     typename C::T* my = s_cnt + wave * RADIX;
     for (uint32_t pass = first; pass < stop; ++pass) {
         const DigitSpec spec = a.spec[pass];
@@ -248,10 +268,11 @@ __device__ __forceinline__ void stream_pass(const SmallArgs& a, const Elem<ES>* 
     constexpr int NWAVE = WG / WAVE;
     constexpr uint32_t CH = cape<ES, KPT, WG>();
     using E = Elem<ES>;
-    E* s_elems = reinterpret_cast<E*>(smem);
     using C = WaveCnt<ES>;
-    typename C::T* s_cnt = reinterpret_cast<typename C::T*>(smem + (size_t)cape<ES, KPT, WG>() * sizeof(E));
-    uint32_t* s_misc = reinterpret_cast<uint32_t*>(s_cnt + NWAVE * RADIX);  // [NWAVE]
+    using Tile = LdsTile<ES, KPT, WG>;
+    E* s_elems = Tile::elems(smem);
+    typename C::T* s_cnt = Tile::cnt(smem);
+    uint32_t* s_misc = Tile::misc(smem);
     uint32_t* s_gbase = s_misc + NWAVE;        // [256] where the next element of each digit goes, relative to the array
     uint32_t* s_dstart = s_gbase + RADIX;      // [256] start of each digit's run in the sorted chunk
     uint32_t* s_dcount = s_dstart + RADIX;     // [256] its length
@@ -278,8 +299,8 @@ __device__ __forceinline__ void stream_pass(const SmallArgs& a, const Elem<ES>* 
     __syncthreads();
     for (uint32_t c0 = 0; c0 < m; c0 += CH) {  // scatter (mod.rs:121-168), chunk by chunk in order
         const uint32_t n = m - c0 < CH ? m - c0 : CH;
-        const uint32_t kp = (n + WG - 1) / WG;
-        const uint32_t seg = wave * (WAVE * kp) + lane;
+        const Slots sl = slots_of<WG>(n);
+        const uint32_t kp = sl.kp, seg = sl.seg;
         E e[KPT];
 #pragma unroll
         for (int j = 0; j < KPT; ++j) {
@@ -396,7 +417,7 @@ __device__ __forceinline__ bool agree(const PassPlan& pp, const Elem<ES>& x, con
 constexpr uint32_t MEND_LIST = 192;
 template <int ES, int KPT, int WG>
 __device__ __forceinline__ uint32_t* mend_count(unsigned char* smem) {
-    return reinterpret_cast<uint32_t*>(smem + (size_t)cape<ES, KPT, WG>() * sizeof(Elem<ES>));  // [0] heads listed, [1 ..] the list
+    return reinterpret_cast<uint32_t*>(LdsTile<ES, KPT, WG>::cnt(smem));  // [0] heads listed, [1 ..] the list
 }
 // The check ahead of the list mend (local_finish after a run of three or more was seen; the fused key / value kernels
 // after every array): the sorted tile is read back in store order together with every element's predecessor (true if
@@ -605,6 +626,7 @@ __device__ __forceinline__ void local_sort_skip(const SmallArgs& a, const Elem<E
         local_store<ES, KPT, WG>(a, dst, n, smem);
     } else if (!local_finish<ES, KPT, WG, PAIRS>(a, dst, n, smem, pp, s_flag)) {
         pp.first = 0;
+        // (slots_of(n), written out: as a call, or with segp_passes_skip's copy in one helper, seven kernels compile otherwise)
         const uint32_t kp = (n + WG - 1) / WG, seg = (threadIdx.x >> 6) * (WAVE * kp) + (threadIdx.x & 63u);
 #pragma unroll
         for (int j = 0; j < KPT; ++j)
@@ -671,7 +693,7 @@ __global__ __launch_bounds__(WG) void rsx_bucket_sort_kernel(const SmallArgs a) 
         pp.end = a.passes;
         pp.first = a.no_skip ? 0u : first_digit_for((uint32_t)count, 8u * a.passes, a.passes);
         pp.set_masks(a.key_offset, a.key_bytes);
-        uint32_t* s_flag = reinterpret_cast<uint32_t*>(reinterpret_cast<typename WaveCnt<ES>::T*>(smem + (size_t)cape<ES, KPT, WG>() * sizeof(Elem<ES>)) + (WG / WAVE) * RADIX) + (WG / WAVE);
+        uint32_t* s_flag = LdsTile<ES, KPT, WG>::flag(smem);
         local_sort_skip<ES, KPT, WG>(a, static_cast<const Elem<ES>*>(a.src) + start, static_cast<Elem<ES>*>(a.data) + start, (uint32_t)count, smem, pp,
                                      s_flag);
     }
@@ -685,7 +707,7 @@ __global__ __launch_bounds__(WG, RSX_B16_WAVES(WG)) void rsx_bucket16_kernel(con
     if (!gate_open(gate)) return;
     using E = Elem<ES>;
     constexpr int NWAVE = WG / WAVE;
-    uint32_t* s_flag = reinterpret_cast<uint32_t*>(reinterpret_cast<typename WaveCnt<ES>::T*>(smem + (size_t)cape<ES, KPT, WG>() * sizeof(E)) + NWAVE * RADIX) + NWAVE;  // (s_misc is [NWAVE]; 16 words there)
+    uint32_t* s_flag = LdsTile<ES, KPT, WG>::flag(smem);  // (s_misc is [NWAVE]; 16 words there)
     // A bucket of m elements that agree on their window (and everything above it) is, as a rule, told apart by the next
     // 2 log2(m) bits or so: the passes start at the digit that leaves them 2 log2(m) - 6 variable bits (first_digit_for:
     // three passes for the 16384-key buckets of 2^30 u64), the neighbours that still agree afterwards are put right --
@@ -782,7 +804,7 @@ __global__ __launch_bounds__(WG, RSX_B16_WAVES(WG)) void rsx_bucket16_medium_ker
     using E = Elem<ES>;
     constexpr int NWAVE = WG / WAVE;
     constexpr uint32_t CAPE = cape<ES, KPT, WG>();
-    uint32_t* s_flag = reinterpret_cast<uint32_t*>(reinterpret_cast<typename WaveCnt<ES>::T*>(smem + (size_t)CAPE * sizeof(E)) + NWAVE * RADIX) + NWAVE;
+    uint32_t* s_flag = LdsTile<ES, KPT, WG>::flag(smem);
     const uint32_t tid = threadIdx.x;
     const uint32_t form = plan->verdict & VERDICT_FORM_MASK;
     const uint64_t handled = form == VERDICT_WG256 ? cap256 : form == VERDICT_WG1024 ? cap1024 : cap512;  // what the other kernel took
@@ -972,8 +994,8 @@ __global__ __launch_bounds__(WG, RSX_B16_WAVES(WG)) void rsx_bucket16_direct_ker
     constexpr uint32_t B = direct_bits<WG>(), NB = 1u << B;
     static_assert(NB == (uint32_t)NWAVE * RADIX && NB == 4u * WG && sizeof(typename WaveCnt<ES>::T) == 4, "the counters take the wave counters' place, four to a thread");
     static_assert((CAPE * ES) % 16 == 0, "the counters are read and written as uint4");
-    E* s = reinterpret_cast<E*>(smem);                                                // [CAPE]
-    uint32_t* s_cnt = reinterpret_cast<uint32_t*>(smem + (size_t)CAPE * sizeof(E));  // [NB] counts, then starts; [NB] = n
+    E* s = LdsTile<ES, KPT, WG>::elems(smem);           // [CAPE]
+    uint32_t* s_cnt = LdsTile<ES, KPT, WG>::cnt(smem);  // [NB] counts, then starts; [NB] = n
     uint32_t* s_tot = s_cnt + NB + 4;                                                 // [NWAVE] the waves' sums of counts
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     // the digit: the BC bits below the window (all b_lo of them if there are fewer), of the mapped key == the element

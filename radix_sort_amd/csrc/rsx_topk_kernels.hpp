@@ -68,20 +68,21 @@ __device__ __forceinline__ void topk_one(const SmallArgs& a, const TopkArgs& t, 
     using K = typename PairsKey<KB>::type;
     constexpr int NWAVE = WG / WAVE;
     constexpr int VOFF = (int)pairs_voff(KB, 4);
-    E* s_elems = reinterpret_cast<E*>(smem);
-    uint32_t* s_cnt = reinterpret_cast<uint32_t*>(smem + (size_t)cape<ES, KPT, WG>() * sizeof(E));  // [NWAVE][256]
-    uint32_t* s_misc = s_cnt + NWAVE * RADIX;                                                      // [NWAVE]
-    uint32_t* s_flag = s_misc + NWAVE;  // (where the bucket kernels keep theirs)
-    uint32_t* s_sel = s_flag + 4;       // [3] the chosen bin, the live elements below it, the live elements in it
+    using Tile = LdsTile<ES, KPT, WG>;
+    E* s_elems = Tile::elems(smem);
+    uint32_t* s_cnt = Tile::cnt(smem);
+    uint32_t* s_misc = Tile::misc(smem);
+    uint32_t* s_flag = Tile::flag(smem);
+    uint32_t* s_sel = s_flag + 4;  // [3] the chosen bin, the live elements below it, the live elements in it
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t c0 = c * t.chunk;
     const uint32_t len = t.m - c0 < t.chunk ? t.m - c0 : t.chunk;
     const uint32_t kk = t.k < len ? t.k : len;
     uint32_t n = len;  // what the passes sort
     E e[KPT];
-    {   // the slot order of local_load
-        const uint32_t kp = (len + WG - 1) / WG;
-        const uint32_t seg = wave * (WAVE * kp) + lane;
+    {   // the slot order (slots_of)
+        const Slots sl = slots_of<WG>(len);
+        const uint32_t kp = sl.kp, seg = sl.seg;
         uint32_t live = 0;
         if (t.keys) {
             SegPairsArgs s{};
@@ -197,8 +198,8 @@ __device__ __forceinline__ void topk_one(const SmallArgs& a, const TopkArgs& t, 
                     }
                 __syncthreads();
                 n = kk;
-                const uint32_t kp2 = (n + WG - 1) / WG;
-                const uint32_t seg2 = wave * (WAVE * kp2) + lane;
+                const Slots sl2 = slots_of<WG>(n);
+                const uint32_t kp2 = sl2.kp, seg2 = sl2.seg;
 #pragma unroll
                 for (int j = 0; j < KPT; ++j) {
                     e[j] = E{};
