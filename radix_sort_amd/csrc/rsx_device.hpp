@@ -332,27 +332,16 @@ struct WidePlan {
 };
 
 // --------------------------------------------------------------- histogram --
-#ifndef RSX_HIST_NT
 // The count kernel reads its input with the streaming hint: it arrives behind a sort whose output still sits,
 // dirty, in the caches, and plain loads allocate there (evicting dirty lines while reading): 256M u32
 // 0.218 -> 0.190 ms (5.66 TB/s), 1B u64 1.48 -> 1.36 ms.  The first sweep then finds a little less of its input
 // cached (+0.5 %); net -0.9 % per 256M-key sort.  (The same hint on the sweep's loads costs 1-4 %, on its
-// stores 80 %: partial lines are then not merged.)
-#define RSX_HIST_NT 1
-#endif
-#ifndef RSX_HIST_UNROLL
-#define RSX_HIST_UNROLL 1  // more loads in flight per thread measured slower (0.217 -> 0.228 ms per 2^28 u32 at 4)
-#endif
-// rsx_count16top_kernel starts behind a sort as well (8- and 16-byte elements): its chunk in 16-byte words
-// (RSX_COUNT16_VEC; 0 = one element per load), with the streaming hint (RSX_COUNT16_NT), RSX_COUNT16_UNROLL of them in
-// flight per thread.  2^30 u64: 1.59 ms with 8-byte plain loads, 1.42 with 16-byte plain ones, 1.37 streaming
-// (4 in flight: the same bytes per CU as before; 8: the same time, 2: 1.44).
-#ifndef RSX_COUNT16_VEC
-#define RSX_COUNT16_VEC 1
-#endif
-#ifndef RSX_COUNT16_NT
-#define RSX_COUNT16_NT 1
-#endif
+// stores 80 %: partial lines are then not merged.)  One pack in flight per thread: more measured slower
+// (0.217 -> 0.228 ms per 2^28 u32 at 4).
+// rsx_count16top_kernel starts behind a sort as well (8- and 16-byte elements): its chunk in 16-byte words, with the
+// streaming hint, RSX_COUNT16_UNROLL of them in flight per thread.  2^30 u64: 1.59 ms with 8-byte plain loads (one
+// element per load), 1.42 with 16-byte plain ones, 1.37 streaming (4 in flight: the same bytes per CU as before; 8: the
+// same time, 2: 1.44).
 #ifndef RSX_COUNT16_NT_BYTES
 #define RSX_COUNT16_NT_BYTES (256ull << 20)  // the memory-side cache
 #endif
@@ -449,13 +438,13 @@ __global__ __launch_bounds__(512) void rsx_hist_kernel(const Elem<ES>* __restric
     const uint64_t nvec = (end - begin - head) / VEC;
     const Pack* vsrc = reinterpret_cast<const Pack*>(src + begin + head);
     const uint64_t stride = (uint64_t)blocks_per_region * blockDim.x;
-    constexpr int UNR = RSX_HIST_UNROLL;
+    constexpr int UNR = 1;  // (left as arrays and loops of one: written plain, the 12- to 32-byte forms allot their SGPRs differently)
     for (uint64_t i = (uint64_t)sub * blockDim.x + tid; i < nvec; i += stride * UNR) {
         Pack p[UNR];
 #pragma unroll
         for (int u = 0; u < UNR; ++u)
             if (i + u * stride < nvec) {
-                if constexpr (RSX_HIST_NT != 0 && sizeof(Pack) == 16 && alignof(Pack) >= 16) {  // streaming 16-byte loads
+                if constexpr (sizeof(Pack) == 16 && alignof(Pack) >= 16) {  // streaming 16-byte loads
                     typedef uint32_t v4u __attribute__((ext_vector_type(4)));  // (12-, 24-byte elements in pieces: +1 %, left plain)
                     const v4u v = __builtin_nontemporal_load(reinterpret_cast<const v4u*>(vsrc + i + u * stride));
                     __builtin_memcpy(&p[u], &v, 16);
@@ -556,6 +545,9 @@ struct SweepArgs {
     uint32_t dbg;                 // RSX_TUNING builds: timing-only ablation switches (0 in production)
     unsigned long long* dbg_cnt;  // [8] diagnostic counters (RSX_TUNING, dbg & 0x100)
 };
+// Whether the sweep's per-wave digit counters are 32 bit (else 16): narrow elements in deep tiles, where the workgroup
+// runs 2 per CU anyway.  Decides the kernel's LDS layout AND the dynamic LDS size its launcher asks for.
+constexpr bool sweep_wide_cnt(int es, int kpt, int wg) { return es <= 4 && kpt >= 16 && wg <= 512; }
 constexpr uint32_t SWEEP_OPT_DYNAMIC = 1u;       // ticketed tiles, no roll call
 constexpr uint32_t SWEEP_OPT_NO_XCD_MAJOR = 2u;  // workgroups numbered by plain blockIdx
 constexpr uint32_t SWEEP_OPT_AGENT_STATUS = 4u;  // agent-scope status stores on every chain
@@ -593,12 +585,6 @@ constexpr uint32_t SWEEP_OPT_PREREAD = 16u;      // 4-byte and narrower elements
 #ifndef RSX_WO_PREREAD
 #define RSX_WO_PREREAD 16  // elements of the write-out read from LDS ahead of the look-back (4-byte and narrower elements)
 #endif
-#ifndef RSX_WO_PREREAD8
-#define RSX_WO_PREREAD8 0  // the same for 8-byte elements
-#endif
-#ifndef RSX_LB_WINDOW
-#define RSX_LB_WINDOW 1  // look-back words requested per round trip: 2 / 4 / 8 measured +0.4 / +1.9 / +5.7 % per 256M-key sort
-#endif
 #ifndef RSX_START_STAGGER
 #define RSX_START_STAGGER 224
 #endif
@@ -611,38 +597,14 @@ constexpr uint32_t SWEEP_OPT_PREREAD = 16u;      // 4-byte and narrower elements
 #ifndef RSX_MINW_BIG
 #define RSX_MINW_BIG 4  // waves/SIMD asked of the compiler for 64-byte-per-thread tiles (u32 x 16)
 #endif
-#ifndef RSX_WIDE_CNT
-#define RSX_WIDE_CNT 1
-#endif
 #ifndef RSX_WO_GROUP
 #define RSX_WO_GROUP 4  // write-out: elements in flight between scheduling barriers
-#endif
-#ifndef RSX_EARLY_HOP
-#define RSX_EARLY_HOP 2  // 0 off, 1 on, 2 = where measured faster (elements of <= 4 bytes)
 #endif
 #ifndef RSX_MINW_1024
 #define RSX_MINW_1024 8
 #endif
-#ifndef RSX_LDS_SWIZZLE
-#define RSX_LDS_SWIZZLE 1
-#endif
-#ifndef RSX_DPP_SCAN
-#define RSX_DPP_SCAN 2  // 0 off, 1 on, 2 = where measured faster (elements of <= 4 bytes)
-#endif
 #ifndef RSX_ROLLCALL_TICKS
 #define RSX_ROLLCALL_TICKS 40000  // s_memtime ticks (shader cycles) a workgroup waits for the full grid
-#endif
-#ifndef RSX_LB_OVERLAP
-#define RSX_LB_OVERLAP 0  // 1: walk the look-back chain beside the LDS reorder (measured slower, see below)
-#endif
-#ifndef RSX_LB_EVERY
-#define RSX_LB_EVERY 4    // elements a wave reorders between two look-back steps
-#endif
-#ifndef RSX_HOT_MBCNT
-#define RSX_HOT_MBCNT 1  // dominant-digit ranks: the running count rides in v_mbcnt's addend
-#endif
-#ifndef RSX_PREFETCH_ALL
-#define RSX_PREFETCH_ALL 3  // 0 off, 1 before/after the look-back, 2 behind it, 3 = 2 where measured faster (>= 12-byte elements)
 #endif
 
 // Makes the compiler forget what it knows about the element registers: digits derived from them
@@ -736,8 +698,8 @@ __attribute__((amdgpu_num_sgpr(RSX_NUM_SGPR))) void rsx_sweep_kernel(const Sweep
     constexpr int TILE = WG * KPT;
     // next-tile prefetch keeps the element registers live through the write-out: only where that fits
     // the VGPR budget without spilling (u32 x 16 keys does not at 80 VGPRs, and is VALU-bound anyway)
-    constexpr bool EARLY_HOP = RSX_EARLY_HOP == 1 || (RSX_EARLY_HOP == 2 && ES <= 4);
-    constexpr bool PREFETCH = RSX_PREFETCH_ALL != 0 && (RSX_PREFETCH_ALL != 3 || ES >= 12);
+    constexpr bool PREFETCH = ES >= 12;
+    constexpr bool EARLY_HOP = ES <= 4;  // the look-back's first hop is requested ahead of the reorder: where measured faster
     static_assert(WG >= RADIX, "need one thread per digit");
     static_assert(TILE <= 65536 / 2, "wave counters are 16 bit");
     using E = Elem<ES>;
@@ -747,7 +709,7 @@ __attribute__((amdgpu_num_sgpr(RSX_NUM_SGPR))) void rsx_sweep_kernel(const Sweep
     E* s_elems = reinterpret_cast<E*>(smem);                                           // [TILE]
     // per-wave digit counters: 32-bit where LDS allows (narrow elements run 2 workgroups/CU), else
     // two 16-bit counters per word (saves 4 KiB, costs ~6 VALU per element for shifts and masks)
-    constexpr bool WIDE_CNT = RSX_WIDE_CNT && ES <= 4 && KPT >= 16 && WG <= 512;  // where the workgroup runs 2 per CU anyway
+    constexpr bool WIDE_CNT = sweep_wide_cnt(ES, KPT, WG);
     using Cnt = typename std::conditional<WIDE_CNT, uint32_t, uint16_t>::type;
     uint32_t* s_whist2 = reinterpret_cast<uint32_t*>(smem + TILE_BYTES);               // the counters as LDS words
     Cnt* s_whist = reinterpret_cast<Cnt*>(s_whist2);                                   // [NWAVE][256]
@@ -1220,7 +1182,6 @@ __attribute__((amdgpu_num_sgpr(RSX_NUM_SGPR))) void rsx_sweep_kernel(const Sweep
                         // is still returning into, and every round waits for its LDS atomic (s_waitcnt lgkmcnt(0)
                         // per round).  Zipf u32 -1.7 %; 8-byte elements measured 2 % slower this way, so they keep
                         // the branch.
-#if RSX_HOT_MBCNT
                         // ... and that hot value is already the lane's rank: v_mbcnt takes an addend, so
                         // hot_run + (hot lanes below me) is two VALU with the running count as the addend -- no select, no
                         // separate `below` (the other lanes' atomic return overwrites it)
@@ -1228,12 +1189,6 @@ __attribute__((amdgpu_num_sgpr(RSX_NUM_SGPR))) void rsx_sweep_kernel(const Sweep
                         if (d != hotd) w = atomicAdd(&my_hist2[WIDE_CNT ? d : (d >> 1)], 1u << sh[r]);
                         word[r] = w;
                         below[r] = 0u;
-#else
-                        uint32_t w = hot_run << sh[r];
-                        if (d != hotd) w = atomicAdd(&my_hist2[WIDE_CNT ? d : (d >> 1)], 1u << sh[r]);
-                        word[r] = w;
-                        below[r] = d == hotd ? mbcnt64(h) : 0u;
-#endif
                     } else if (d == hotd) {
                         below[r] = mbcnt64(h);
                         word[r] = hot_run << sh[r];
@@ -1291,63 +1246,50 @@ __attribute__((amdgpu_num_sgpr(RSX_NUM_SGPR))) void rsx_sweep_kernel(const Sweep
         // The walk back over the chain's earlier tiles is a series of dependent round trips (~500 cycles
         // each from the chain's L2).  Its first hop is requested now and looked at after the LDS reorder
         // (an aggregate or inclusive word stays true however old it is; an empty one is read again); the
-        // rest of the walk follows the reorder.  RSX_LB_OVERLAP = 1 takes further steps of the walk BESIDE
-        // the reorder (one after every RSX_LB_EVERY elements a wave has put into LDS) and publishes the
-        // inclusive prefix the moment the walk ends: measured slower on 4-byte keys (256M u32: 0.468 ->
-        // 0.485-0.498 ms per pass at every step spacing tried) and no different on 8- and 16-byte elements --
-        // the waves that walk stall inside the reorder on each word, and the other four wait for them at
-        // the barrier either way.
-        constexpr int LBW = RSX_LB_WINDOW;  // words requested per round trip (the chain's earlier tiles, nearest first)
-        S lb_pend[LBW];        // the words in flight
-        uint32_t lb_n = 0;     // how many of them were requested
+        // rest of the walk follows the reorder.  Taking further steps of the walk BESIDE the reorder (one
+        // after every few elements a wave has put into LDS) and publishing the inclusive prefix the
+        // moment the walk ends measured slower on 4-byte keys (256M u32: 0.468 -> 0.485-0.498 ms per pass
+        // at every step spacing tried) and no different on 8- and 16-byte elements -- the waves that walk
+        // stall inside the reorder on each word, and the other four wait for them at the barrier either
+        // way.  One word is requested per round trip: 2 / 4 / 8 measured +0.4 / +1.9 / +5.7 % per 256M-key sort.
+        S lb_pend = 0;         // the word in flight
+        uint32_t lb_n = 0;     // 1: it was requested -- wherever lb_left != 0 (left in: without it the sweeps allot their registers differently)
         S lb_excl = 0;         // sum of the predecessors' counts so far (region-relative: fits S)
         uint32_t lb_left = 0;  // predecessors not yet summed (tiles kt-1 .. 0 of the chain); 0 = walk finished
-#pragma unroll
-        for (int i = 0; i < LBW; ++i) lb_pend[i] = 0;
-        // request up to `want` words starting with the nearest predecessor not yet summed
-        auto lb_request = [&](uint32_t want) __attribute__((always_inline)) {
+        // request the nearest predecessor not yet summed
+        auto lb_request = [&]() __attribute__((always_inline)) {
             const uint32_t dist = kt - lb_left + 1u;  // 1 = the tile right before this one
-            lb_n = lb_left < want ? lb_left : want;
-#pragma unroll
-            for (int i = 0; i < LBW; ++i)
-                if ((uint32_t)i < lb_n)
-                    lb_pend[i] = __hip_atomic_load(&status[stat_row - (uint64_t)(dist + (uint32_t)i) * RADIX + tid], __ATOMIC_RELAXED,
-                                                   __HIP_MEMORY_SCOPE_AGENT);
+            lb_n = lb_left < 1u ? lb_left : 1u;
+            if (0u < lb_n) lb_pend = __hip_atomic_load(&status[stat_row - (uint64_t)dist * RADIX + tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         };
-        if ((EARLY_HOP || RSX_LB_OVERLAP) && tid < RADIX && kt > 0) {
+        if (EARLY_HOP && tid < RADIX && kt > 0) {
             lb_left = kt;
-            lb_request(1u);  // early: only the nearest (the words behind it are worth more when read later)
+            lb_request();  // early
         }
-        // one step of the walk: take the words in flight (in order, up to the first empty one), request the next
-        // window.  false = the first word was still empty.
+        // one step of the walk: take the word in flight, request the next one.  false = the word was still empty.
         auto lb_step = [&]() __attribute__((always_inline)) -> bool {
             if (lb_left == 0) return true;
-            bool progressed = false, stalled = false;
-#pragma unroll
-            for (int i = 0; i < LBW; ++i) {
-                if ((uint32_t)i < lb_n && !stalled && lb_left != 0) {
-                    const uint32_t f = (uint32_t)(lb_pend[i] >> Status<S>::SHIFT);
-                    if (f != 0) {
-                        lb_excl += (S)(lb_pend[i] & Status<S>::MASK);
-                        lb_left = f == 2 ? 0u : lb_left - 1u;
-                        progressed = true;
-                    } else {
-                        stalled = true;
-                    }
+            bool progressed = false;
+            if (0u < lb_n) {
+                const uint32_t f = (uint32_t)(lb_pend >> Status<S>::SHIFT);
+                if (f != 0) {
+                    lb_excl += (S)(lb_pend & Status<S>::MASK);
+                    lb_left = f == 2 ? 0u : lb_left - 1u;
+                    progressed = true;
                 }
             }
             if (lb_left == 0) {
                 const uint32_t real = (tid == 255) ? tcount - pad : tcount;
                 publish(&status[stat_row + tid], ((S)2 << Status<S>::SHIFT) | (S)((lb_excl + (S)real) & Status<S>::MASK));
             } else {
-                lb_request((uint32_t)LBW);
+                lb_request();
             }
             return progressed;
         };
         // exclusive scan of tcount over the 256 digits -> start of each digit's run in the tile
         uint32_t incl = tcount;
         if (tid < RADIX) {
-            incl = wave_incl_scan<(RSX_DPP_SCAN == 1 || (RSX_DPP_SCAN == 2 && ES <= 4))>(incl);
+            incl = wave_incl_scan<(ES <= 4)>(incl);  // the DPP form where measured faster
             if (lane == 63) s_misc[12 + wave] = incl;
         }
         __syncthreads();
@@ -1372,24 +1314,23 @@ __attribute__((amdgpu_num_sgpr(RSX_NUM_SGPR))) void rsx_sweep_kernel(const Sweep
 #pragma unroll
         for (int j = 0; j < KPT; ++j) {
             const uint32_t d = (!full && seg + j * WAVE >= valid) ? 255u : sweep_digit<ES, STR>(e[j], spec);
-            // bank swizzle (RSX_LDS_SWIZZLE): slot p lives at p ^ ((p >> 5) & 31).  Digit runs that start
+            // bank swizzle: slot p lives at p ^ ((p >> 5) & 31).  Digit runs that start
             // a multiple of 32 slots apart -- every pass over already sorted input, key = index -- would
             // otherwise put all 64 lanes of a wave on one bank
             const uint32_t pos = my_hist[d] + ((pk[j / 2] >> (16 * (j & 1))) & 0xFFFFu);
-            s_elems[RSX_LDS_SWIZZLE ? (pos ^ ((pos >> 5) & 31u)) : pos] = e[j];
-            if (RSX_LB_OVERLAP && j % RSX_LB_EVERY == RSX_LB_EVERY - 1 && j + 1 < KPT && tid < RADIX) lb_step();  // (wave-uniform)
+            s_elems[pos ^ ((pos >> 5) & 31u)] = e[j];
         }
         __syncthreads();  // s_whist is dead from here: s_base takes its place
         RSX_STAMP(4);
         // physical LDS slot of logical slot i*WG + tid (see the swizzle at the reorder): only the low
         // five bits change, by (i*WG/32 + tid/32) & 31 -- two values per thread when WG % 512 == 0
-        static_assert(!RSX_LDS_SWIZZLE || WG % 512 == 0, "swizzle constants assume WG % 512 == 0");
-        const uint32_t sw0 = RSX_LDS_SWIZZLE ? (tid ^ ((tid >> 5) & 31u)) : tid;
-        const uint32_t sw1 = RSX_LDS_SWIZZLE ? (tid ^ (((tid >> 5) + (WG >> 5)) & 31u)) : tid;
+        static_assert(WG % 512 == 0, "swizzle constants assume WG % 512 == 0");
+        const uint32_t sw0 = tid ^ ((tid >> 5) & 31u);
+        const uint32_t sw1 = tid ^ (((tid >> 5) + (WG >> 5)) & 31u);
         auto slot_of = [&](int i) __attribute__((always_inline)) { return (uint32_t)(i * WG) + ((i & 1) ? sw1 : sw0); };
         // The elements a thread will write out are read from LDS NOW, ahead of the look-back: the reads are in
         // flight while the digit threads walk the chain and the other waves would only wait at the barrier.
-        constexpr int PREREAD_WANT = ES <= 4 ? RSX_WO_PREREAD : ES == 8 ? RSX_WO_PREREAD8 : 0;
+        constexpr int PREREAD_WANT = ES <= 4 ? RSX_WO_PREREAD : 0;
         constexpr int PREREAD = PREFETCH ? 0 : (PREREAD_WANT < KPT ? PREREAD_WANT : KPT);  // elements read ahead
         // (256M u32 -2.3 %, 512M -0.7 %, 1B +1.0 %: the host switches it on up to 2 GiB of data; 8-byte elements lose at
         // any count.)
@@ -1400,10 +1341,9 @@ __attribute__((amdgpu_num_sgpr(RSX_NUM_SGPR))) void rsx_sweep_kernel(const Sweep
                 for (int i = 0; i < PREREAD; ++i) e[i] = s_elems[slot_of(i)];
             }
         }
-        // static mode knows its next tile: its loads are issued as soon as the element registers
-        // are free and fly during the look-back and the write-out.  The waves that do the look-back
-        // issue theirs AFTER it: memory operations return in order, so a status word requested
-        // behind 16 HBM loads would wait for all of them.
+        // static mode knows its next tile: its loads are issued once the element registers are free
+        // and fly during the write-out.  All waves issue theirs AFTER the look-back: memory operations
+        // return in order, so a status word requested behind 16 HBM loads would wait for all of them.
         const bool prefetch = static_mode && PREFETCH && st_k < st_nt;
         auto issue_next = [&]() {
             const uint64_t tb = ((uint64_t)home << a.g.region_shift) + (uint64_t)st_k * TILE;
@@ -1412,13 +1352,12 @@ __attribute__((amdgpu_num_sgpr(RSX_NUM_SGPR))) void rsx_sweep_kernel(const Sweep
             load_tile<ES, KPT>(e, src + tb, seg, fl ? (uint32_t)TILE : (uint32_t)(re - tb), fl);
         };
         preloaded = prefetch;
-        if (prefetch && RSX_PREFETCH_ALL == 1 && tid >= RADIX) issue_next();
 
         // ---- what is left of the look-back ------------------------------------------------------
         if (tid < RADIX) {
-            if (!(EARLY_HOP || RSX_LB_OVERLAP) && kt > 0) {  // nothing requested yet
+            if (!EARLY_HOP && kt > 0) {  // nothing requested yet
                 lb_left = kt;
-                lb_request((uint32_t)LBW);
+                lb_request();
             }
             uint32_t spins = 0;
 #ifdef RSX_STAMPS
@@ -1445,11 +1384,10 @@ __attribute__((amdgpu_num_sgpr(RSX_NUM_SGPR))) void rsx_sweep_kernel(const Sweep
 #endif
             // element index of LDS slot 0 if it belonged to this digit's run (wrap-safe in u64)
             s_base[tid] = rbase + (uint64_t)lb_excl - (uint64_t)tstart;
-            if (prefetch && RSX_PREFETCH_ALL == 1) issue_next();
         }
         __syncthreads();
         RSX_STAMP(5);
-        if (prefetch && RSX_PREFETCH_ALL >= 2) issue_next();  // all waves, behind the look-back: flies during the write-out
+        if (prefetch) issue_next();  // all waves, behind the look-back: flies during the write-out
 
         // ---- write runs: consecutive threads -> consecutive addresses within a run;
         // ---- count the NEXT pass's digit per destination region on the way out

@@ -141,7 +141,7 @@ int launch_sweep_t(rsx_ctx* ctx, const SortRun& run, const SweepPass& pass, cons
     a.rank_atomic = rank_atomic_of(ctx);
     a.hot_lanes = (ctx->options & OPT_ATOMIC_RANKS) ? 65u : ctx->hot_lanes;
     a.dbg_cnt = reinterpret_cast<unsigned long long*>(ctx->aux + OFF_DBG);
-    const size_t lds = (size_t)TILE * ES + (SWEEP_WG / WAVE) * RADIX * ((RSX_WIDE_CNT && ES <= 4 && KPT >= 16 && SWEEP_WG <= 512) ? sizeof(uint32_t) : sizeof(uint16_t)) +
+    const size_t lds = (size_t)TILE * ES + (SWEEP_WG / WAVE) * RADIX * (sweep_wide_cnt(ES, KPT, SWEEP_WG) ? sizeof(uint32_t) : sizeof(uint16_t)) +
                        (NEXT ? (size_t)g.num_regions * RADIX * sizeof(uint32_t) : 0) + 128;
     auto kern = rsx_sweep_kernel<ES, KPT, SWEEP_WG, S, XF, NEXT, MID, STR>;
     // resident workgroups per CU for this kernel at this LDS size (the count matrix of the next pass

@@ -333,7 +333,7 @@ __global__ __launch_bounds__(1024) void rsx_count16top_kernel(const Elem<ES>* __
     };
     constexpr int UNR = ES <= 8 ? 8 : ES <= 16 ? 4 : 2;  // loads in flight per thread (one workgroup per CU: 16 waves)
     uint64_t i = p0 + tid;
-    if constexpr (RSX_COUNT16_VEC != 0 && (ES == 8 || ES == 16)) {
+    if constexpr (ES == 8 || ES == 16) {
         // Order inside a chunk does not matter for a count, its membership does: the chunk [p0, p1) is read in 16-byte
         // words with the streaming hint (as rsx_hist_kernel reads its region), two 8-byte elements or one 16-byte
         // element each.  The C-ABI promises element alignment only, the multi-GPU drivers pass interior pointers and p0
@@ -350,7 +350,7 @@ __global__ __launch_bounds__(1024) void rsx_count16top_kernel(const Elem<ES>* __
             const v4u* vsrc = reinterpret_cast<const v4u*>(src + p0 + head);
             // (the streaming hint from RSX_COUNT16_NT_BYTES on: a smaller array is still in the memory-side cache when the
             // first sweep reads it again, and stays there only under plain loads; the same for every thread of the launch)
-            const bool stream = RSX_COUNT16_NT != 0 && n * (uint64_t)ES >= (uint64_t)RSX_COUNT16_NT_BYTES;
+            const bool stream = n * (uint64_t)ES >= (uint64_t)RSX_COUNT16_NT_BYTES;
             auto count_word = [&](const v4u& v) {
                 if constexpr (ES == 8) {
                     Elem<ES> a, b;

@@ -456,16 +456,13 @@ __device__ __forceinline__ bool local_check(const PassPlan& pp, const uint32_t n
 }
 // (Not inlined: inside the bucket kernels' loop its registers cost the 1024- and 512-thread forms 70-86 spilled ones and
 // 2^30 u64 8 %.  It takes what it needs by value -- no argument block, which would go to scratch.)
-#ifndef RSX_MEND_INLINE
-#define RSX_MEND_INLINE __forceinline__
-#endif
 template <int ES>
 struct MendMasks {
     uint32_t hi[ES / 4], lo[ES / 4];
 };
 template <int ES>
-__device__ RSX_MEND_INLINE uint32_t mend_listed(Elem<ES>* s_elems, uint32_t* s_list, uint32_t* s_flag, const uint32_t n, const uint32_t wg,
-                                                          uint32_t ties, const MendMasks<ES> mm) {
+__device__ __forceinline__ uint32_t mend_listed(Elem<ES>* s_elems, uint32_t* s_list, uint32_t* s_flag, const uint32_t n, const uint32_t wg,
+                                                        uint32_t ties, const MendMasks<ES> mm) {
     using E = Elem<ES>;
     constexpr uint32_t MAX_RUN = 48;
     auto same = [&](const E& u, const E& v) {
@@ -891,20 +888,12 @@ __global__ __launch_bounds__(WG, RSX_B16_WAVES(WG)) void rsx_bucket16_medium_ker
 // about 7 to about 5 on uniform keys, and the rank loop with it.  Two lanes meet on a word as often as they met on a
 // counter.  The hand-over rule stays on the B-bit sub-buckets -- the two halves of a word together (where the keys have
 // no more than B bits below the window the digit is all of them, and a half is such a sub-bucket by itself).
-// (RSX_DIRECT_PACKED=0: one 32-bit counter per B-bit digit, the form before, for A/B builds.)
-#ifndef RSX_DIRECT_PACKED
-#define RSX_DIRECT_PACKED 1
-#endif
-// (RSX_DIRECT_LOAD16=0: one 8-byte element per global load of the bucket, the form before, for A/B builds.)
-#ifndef RSX_DIRECT_LOAD16
-#define RSX_DIRECT_LOAD16 1
-#endif
 constexpr uint32_t DIRECT_LIMIT = 24;
 template <int WG>
 __host__ __device__ constexpr uint32_t direct_bits() {
     return WG >= 1024 ? 12u : WG >= 512 ? 11u : 10u;
 }
-constexpr uint32_t DIRECT_EXTRA_BITS = RSX_DIRECT_PACKED ? 1u : 0u;  // digit bits of the counting pass beyond direct_bits()
+constexpr uint32_t DIRECT_EXTRA_BITS = 1u;  // digit bits of the counting pass beyond direct_bits()
 template <int ES>
 __device__ __forceinline__ bool key_less(const Elem<ES>& x, const Elem<ES>& y) {  // the element as ONE number, highest dword first
     static_assert(ES == 8 || ES == 16, "key-only elements of 8 and 16 bytes");
@@ -999,7 +988,6 @@ __global__ __launch_bounds__(WG, RSX_B16_WAVES(WG)) void rsx_bucket16_direct_ker
     uint32_t* s_tot = s_cnt + NB + 4;                                                 // [NWAVE] the waves' sums of counts
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     // the digit: the BC bits below the window (all b_lo of them if there are fewer), of the mapped key == the element
-    constexpr bool PACKED = DIRECT_EXTRA_BITS != 0;
     constexpr uint32_t BC = B + DIRECT_EXTRA_BITS;
     static_assert(CAPE < (1u << 16), "a count and a start fit a half");
     const uint32_t b_lo = plan->window_top - 15u;
@@ -1012,8 +1000,7 @@ __global__ __launch_bounds__(WG, RSX_B16_WAVES(WG)) void rsx_bucket16_direct_ker
         return (uint32_t)(((((uint64_t)hi << 32) | lo) >> dsh)) & dmask;
     };
     auto start_of = [&](const uint32_t d) -> uint32_t {  // (after the scan; d = number of digits: n)
-        if constexpr (PACKED) return reinterpret_cast<const uint16_t*>(s_cnt)[d];
-        else return s_cnt[d];
+        return reinterpret_cast<const uint16_t*>(s_cnt)[d];
     };
     // Bucket g and all later ones of this workgroup are left to the old kernel: marked by all threads at once (one after
     // the other a workgroup's 85-256 buckets took 0.8 us each: 2^28 keys of 2^20 distinct values +75 us, 1.3 %).  Returns
@@ -1051,7 +1038,7 @@ __global__ __launch_bounds__(WG, RSX_B16_WAVES(WG)) void rsx_bucket16_direct_ker
         // 8-byte elements, 512 and 1024 threads: a thread takes KPT / 2 16-byte words of two neighbours each (and an odd
         // KPT's last element by itself).  A bucket starts on an 8-byte boundary only; gfx950 takes 16-byte loads at that
         // alignment.  (The 256-thread form, three workgroups per CU, measured slower with them: 2^27 u64 1.79 -> 1.81 ms.)
-        constexpr bool LOAD16 = RSX_DIRECT_LOAD16 != 0 && ES == 8 && WG >= 512;
+        constexpr bool LOAD16 = ES == 8 && WG >= 512;
         constexpr int NPAIR = LOAD16 ? KPT / 2 : 0;
         auto pos_of = [&](const int j) -> uint32_t {  // which element of the bucket e[j] is
             if (j < 2 * NPAIR) return 2u * ((uint32_t)(j >> 1) * WG + tid) + (uint32_t)(j & 1);
@@ -1085,31 +1072,21 @@ __global__ __launch_bounds__(WG, RSX_B16_WAVES(WG)) void rsx_bucket16_direct_ker
             rk[j] = 0;
             if (pos_of(j) < n) {
                 const uint32_t d = digit_of(e[j]);
-                if constexpr (PACKED) {
-                    const uint32_t sh = (d & 1u) << 4;
-                    rk[j] = (atomicAdd(&s_cnt[d >> 1], 1u << sh) >> sh) & 0xFFFFu;
-                } else {
-                    rk[j] = atomicAdd(&s_cnt[d], 1u);
-                }
+                const uint32_t sh = (d & 1u) << 4;
+                rk[j] = (atomicAdd(&s_cnt[d >> 1], 1u << sh) >> sh) & 0xFFFFu;
             }
         }
         __syncthreads();
         // counts -> starts: every thread four consecutive words of counters, a wave scan, the waves before mine
         const uint4 c = reinterpret_cast<const uint4*>(s_cnt)[tid];
-        uint32_t p0 = c.x, p1 = c.y, p2 = c.z, p3 = c.w;  // the words' sums, and the largest B-bit sub-bucket among them
-        uint32_t big;
-        if constexpr (PACKED) {
-            auto low = [](uint32_t v) { return v & 0xFFFFu; };
-            auto larger = [](uint32_t u, uint32_t v) { return u > v ? u : v; };
-            p0 = low(c.x) + (c.x >> 16), p1 = low(c.y) + (c.y >> 16), p2 = low(c.z) + (c.z >> 16), p3 = low(c.w) + (c.w >> 16);
-            const uint32_t pairs = larger(larger(p0, p1), larger(p2, p3));
-            const uint32_t halves = larger(larger(larger(low(c.x), c.x >> 16), larger(low(c.y), c.y >> 16)),
-                                           larger(larger(low(c.z), c.z >> 16), larger(low(c.w), c.w >> 16)));
-            big = b_lo > B ? pairs : halves;  // (no more than B bits below the window: a half IS a B-bit sub-bucket)
-        } else {
-            const uint32_t m01 = c.x > c.y ? c.x : c.y, m23 = c.z > c.w ? c.z : c.w;
-            big = m01 > m23 ? m01 : m23;
-        }
+        auto low = [](uint32_t v) { return v & 0xFFFFu; };
+        auto larger = [](uint32_t u, uint32_t v) { return u > v ? u : v; };
+        // the words' sums, and the largest B-bit sub-bucket among them
+        const uint32_t p0 = low(c.x) + (c.x >> 16), p1 = low(c.y) + (c.y >> 16), p2 = low(c.z) + (c.z >> 16), p3 = low(c.w) + (c.w >> 16);
+        const uint32_t pairs = larger(larger(p0, p1), larger(p2, p3));
+        const uint32_t halves = larger(larger(larger(low(c.x), c.x >> 16), larger(low(c.y), c.y >> 16)),
+                                       larger(larger(low(c.z), c.z >> 16), larger(low(c.w), c.w >> 16)));
+        const uint32_t big = b_lo > B ? pairs : halves;  // (no more than B bits below the window: a half IS a B-bit sub-bucket)
         const uint32_t sum = p0 + p1 + p2 + p3;
         const uint32_t incl = wave_incl_scan<true>(sum);
         if (lane == 63) s_tot[wave] = incl;
@@ -1119,12 +1096,9 @@ __global__ __launch_bounds__(WG, RSX_B16_WAVES(WG)) void rsx_bucket16_direct_ker
         }
         uint32_t run = incl - sum;
         for (uint32_t w = 0; w < wave; ++w) run += s_tot[w];
-        if constexpr (PACKED) {  // a word: the start of its first digit in both halves, plus the first digit's count in the high one
-            const uint32_t r1 = run + p0, r2 = r1 + p1, r3 = r2 + p2;
-            reinterpret_cast<uint4*>(s_cnt)[tid] = uint4{(c.x << 16) + run * 0x10001u, (c.y << 16) + r1 * 0x10001u, (c.z << 16) + r2 * 0x10001u, (c.w << 16) + r3 * 0x10001u};
-        } else {
-            reinterpret_cast<uint4*>(s_cnt)[tid] = uint4{run, run + c.x, run + c.x + c.y, run + c.x + c.y + c.z};
-        }
+        // a word: the start of its first digit in both halves, plus the first digit's count in the high one
+        const uint32_t r1 = run + p0, r2 = r1 + p1, r3 = r2 + p2;
+        reinterpret_cast<uint4*>(s_cnt)[tid] = uint4{(c.x << 16) + run * 0x10001u, (c.y << 16) + r1 * 0x10001u, (c.z << 16) + r2 * 0x10001u, (c.w << 16) + r3 * 0x10001u};
         if (tid == 0) s_cnt[NB] = n;
         __syncthreads();
 #pragma unroll
