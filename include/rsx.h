@@ -199,6 +199,8 @@ enum {
                                  any sort of the needles, bit 8 is set when they were sorted first, bits 9-23 are 0),
                                  11 merge (rsx_merge_device: bits 0-7 are then the kernels launched, bit 8 is set on the
                                  wide-value route, bits 9-23 are 0),
+                                 12 set operation (rsx_setop_device: bits 0-7 are then the kernels launched, bits 8-23
+                                 are 0),
                                  bits 28-29 the route of a layout without kernels of its own: 0 direct, 1 packed
                                  re-layout, 2 key-index proxy (bits 0-27 then describe the sort of the re-laid-out
                                  elements / of the proxies) */
@@ -579,6 +581,66 @@ int rsx_ctx_reserve_merge(rsx_ctx *ctx, size_t n_total, uint32_t key_bytes, uint
 /* Host-only, needs no device: *tile = the output positions one workgroup takes (256 threads; tile * (key_bytes + 2) + 16
  * bytes of LDS at most, which leaves more than two workgroups per CU). */
 int rsx_merge_caps(uint32_t key_bytes, uint32_t value_bytes, uint32_t *tile);
+
+/* -- set operations on two sorted key arrays ---------------------------------- */
+/* Union, intersection, difference and symmetric difference of two sorted key arrays as MULTISETS (the rules of
+ * std::set_union and its siblings): which ids are in both, which only in the first, the deduplicated union of two
+ * rsx_unique_device results -- in one merge-path pass, where the chain of searches, a mask and a compaction moves the keys
+ * several times and reads a count back.  Let M be the key mapping of rsx_argsort_device for (key_bytes, key_kind),
+ * complemented when `order` is descending, N_a = na, or min(na, *d_a_num) when that pointer is given (one device word, such
+ * as the d_out_num of rsx_unique_device, read on the device), and N_b likewise.  PRECONDITION: a[0 .. N_a) and b[0 .. N_b)
+ * are each non-decreasing under M.  For a key k let A_lo(k) = #{ i < N_a : M(a[i]) < M(k) } and B_lo(k) the same count in
+ * b.  The rank of a[i] in its run of equal keys is r = i - A_lo(a[i]), that of b[j] is s = j - B_lo(b[j]).
+ *     a[i] is MATCHED when B_lo(a[i]) + r < N_b and b[B_lo(a[i]) + r] has the same bit pattern (the key occurs more than r
+ *          times in b);
+ *     b[j] is MATCHED when A_lo(b[j]) + s < N_a and a[A_lo(b[j]) + s] equals it.
+ * The operation keeps
+ *     RSX_SETOP_UNION                 every a[i]; the unmatched b[j]
+ *     RSX_SETOP_INTERSECTION          the matched a[i]
+ *     RSX_SETOP_DIFFERENCE            the unmatched a[i]
+ *     RSX_SETOP_SYMMETRIC_DIFFERENCE  the unmatched a[i]; the unmatched b[j]
+ * and the output is the kept elements in the order of the stable merge of a ++ b, equal keys of a first (the order of
+ * rsx_merge_device): for t < *d_out_num,
+ *     d_out_keys[t]    the key, as raw key bytes
+ *     d_out_values[t]  the value of that very element, moved bitwise
+ *     d_out_index[t]   its position in the concatenation: i for a[i], na + j for b[j] -- the offset is the HOST's na, so
+ *                      that index - na always indexes the b array
+ *     *d_out_num       the number kept; entries at t >= *d_out_num are not written.
+ * The caller provides cap(op) rows in every output it asks for: na + nb for union and symmetric difference, na for
+ * difference, min(na, nb) for intersection.  Each of keys, values, index is optional through a NULL pointer, at least one
+ * must be given; d_out_num is required and 8-byte aligned (so are d_a_num and d_b_num when given).  Key widths, kinds and
+ * alignments are those of rsx_argsort_device (1, 2, 4, 8, 16 bytes); value_bytes is 0, 1, 2, 4, 8 or 16 with the value
+ * alignment of rsx_sort_pairs_device, and any other width up to RSX_MAX_ELEM_BYTES returns RSX_ERR_UNSUPPORTED: ask for
+ * d_out_index and gather.  value_bytes == 0 goes with all three value pointers NULL; d_b_values is looked at only by the
+ * two operations that can emit from b.  index_bytes is 4 or 8 and is looked at only when d_out_index is given.
+ * RSX_ERR_ARG: a bad op, widths, kinds, order, index_bytes or alignments; a NULL input with a nonzero count; values missing
+ * on a side that can be emitted; all outputs NULL; d_out_num NULL; index_bytes == 4 with na + nb > 2^32; an output range
+ * (cap(op) rows, or the word of d_out_num) that overlaps an input range, a count word or another output.
+ * RSX_ERR_UNSUPPORTED: na + nb of 2^31 tiles or more.  na + nb == 0 stores *d_out_num = 0, launches no kernel and looks at
+ * no other pointer; one empty side goes through the same kernels.  Stream-ordered, no synchronisation; the host reads
+ * nothing.  If the precondition does not hold, every read stays inside the two inputs, every write inside cap(op) rows of
+ * the outputs, *d_out_num <= cap(op) and every d_out_index[t] is below na + nb; nothing else is promised.
+ *
+ * Three launches over tiles of `tile` consecutive positions of the MERGE of a and b (rsx_setop_caps): a count launch, a
+ * one-workgroup scan, a write launch; no workgroup waits for another one and there are no atomics.  A workgroup finds its
+ * tile's two cuts on the merge path and merges in LDS as rsx_merge_device does, and decides every element while it
+ * merges, by one probe of the other array at the element's rank.  Workspace, per tile: a 4-byte count, an 8-byte base and
+ * 32 bytes the first launch saves for the second; it is made on first use or by rsx_ctx_reserve_setop, and under capture
+ * without a sufficient reserve the call returns RSX_ERR_WORKSPACE and enqueues nothing.  RSX_INFO_LAST_PASSES reports
+ * path 12. */
+enum { RSX_SETOP_UNION = 0, RSX_SETOP_INTERSECTION = 1, RSX_SETOP_DIFFERENCE = 2, RSX_SETOP_SYMMETRIC_DIFFERENCE = 3 };
+int rsx_setop_device(rsx_ctx *ctx, uint32_t op,
+                     const void *d_a_keys, const void *d_a_values, size_t na, const uint64_t *d_a_num,
+                     const void *d_b_keys, const void *d_b_values, size_t nb, const uint64_t *d_b_num,
+                     uint32_t key_bytes, uint32_t key_kind, uint32_t value_bytes, int order,
+                     void *d_out_keys, void *d_out_values, void *d_out_index, uint32_t index_bytes,
+                     uint64_t *d_out_num, void *stream);
+/* Workspace (and the context's first-call set-up) of a set operation on up to n_total = na + nb keys of this width, so that
+ * the call allocates nothing (stream capture). */
+int rsx_ctx_reserve_setop(rsx_ctx *ctx, size_t n_total, uint32_t key_bytes);
+/* Host-only, needs no device: *tile = the merge positions one workgroup takes (256 threads; tile * (key_bytes + 2) + 64
+ * bytes of LDS at most, which leaves more than two workgroups per CU; tile <= 4096). */
+int rsx_setop_caps(uint32_t key_bytes, uint32_t *tile);
 
 /* -- several key columns ----------------------------------------------------- */
 /* Sorting a table by (a, b descending, c): ncols key columns of n keys each, column 0 the MOST significant (the opposite

@@ -30,6 +30,7 @@ UNITS = (
     ("rsx_lex.hip", "rsx_lex.o", ()),        # the join of several key columns: rsx_lexsort_device, rsx_sort_columns_device
     ("rsx_search.hip", "rsx_search.o", ()),  # the kernel of rsx_search_sorted_device
     ("rsx_merge.hip", "rsx_merge.o", ()),    # the kernels of rsx_merge_device
+    ("rsx_setops.hip", "rsx_setops.o", ()),  # the kernel of rsx_setop_device
 ) + tuple(("rsx_es.hip", f"rsx_es{es}.o", (f"-DRSX_ES={es}",)) for es in ELEM_SIZES)  # the sort kernels, once per element size
 # what the library is stale against: every unit, every header beside them, and the public header
 DEPS = sorted({src for src, _obj, _flags in UNITS}) + sorted(f for f in os.listdir(CSRC) if f.endswith(".hpp")) + \

@@ -25,6 +25,7 @@ SYMBOLS = [
     "rsx_lexsort_device", "rsx_sort_columns_device", "rsx_ctx_reserve_lex", "rsx_lex_plan",
     "rsx_search_sorted_device", "rsx_ctx_reserve_search", "rsx_search_caps",
     "rsx_merge_device", "rsx_ctx_reserve_merge", "rsx_merge_caps",
+    "rsx_setop_device", "rsx_ctx_reserve_setop", "rsx_setop_caps",
 ]
 SEG_CLASSES = 2  # RSX_SEG_CLASSES
 LEX_MAX_COLUMNS = 16  # RSX_LEX_MAX_COLUMNS
@@ -41,6 +42,7 @@ INFO_RANK_ATOMIC, INFO_L2_LOCAL, INFO_NUM_CU, INFO_DEVICE, INFO_LAST_PASSES, INF
 ORDER_ASCENDING, ORDER_DESCENDING = 0, 1
 REDUCE_SUM, REDUCE_MIN, REDUCE_MAX = 0, 1, 2
 SEARCH_PRESORT = 1
+SETOP_UNION, SETOP_INTERSECTION, SETOP_DIFFERENCE, SETOP_SYMMETRIC_DIFFERENCE = 0, 1, 2, 3
 SHARD_EXCHANGE_FIRST, SHARD_SORT_FIRST = 0, 1
 
 
@@ -161,6 +163,9 @@ def load():
     L.rsx_merge_device.argtypes = [vp, vp, vp, sz, vp, vp, sz, u32, u32, u32, i, vp, vp, vp, u32, vp]
     L.rsx_ctx_reserve_merge.argtypes = [vp, sz, u32, u32]
     L.rsx_merge_caps.argtypes = [u32, u32, pu32]
+    L.rsx_setop_device.argtypes = [vp, u32, vp, vp, sz, vp, vp, vp, sz, vp, u32, u32, u32, i, vp, vp, vp, u32, vp, vp]
+    L.rsx_ctx_reserve_setop.argtypes = [vp, sz, u32]
+    L.rsx_setop_caps.argtypes = [u32, pu32]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("rsx_last_error", "rsx_strerror"):

@@ -338,6 +338,23 @@ class Context:
                                              key_bytes, key_kind, value_bytes, 1 if descending else 0, d_out_keys or None,
                                              d_out_values or None, d_out_index or None, index_bytes, stream))
 
+    def reserve_setop(self, n_total: int, key_bytes: int):
+        """rsx_ctx_reserve_setop: the context's first-call set-up and the workspace of setop_device on up to n_total =
+        na + nb keys of this width, so that the call allocates nothing and can be captured."""
+        self._check(self._L.rsx_ctx_reserve_setop(self._h, n_total, key_bytes))
+
+    def setop_device(self, op: int, d_a_keys: int, d_a_values: int, na: int, d_a_num: int, d_b_keys: int, d_b_values: int, nb: int,
+                     d_b_num: int, key_bytes: int, key_kind: int, value_bytes: int, d_out_keys: int, d_out_values: int, d_out_index: int,
+                     index_bytes: int, d_out_num: int, descending: bool = False, stream: int = 0):
+        """rsx_setop_device: union (op 0), intersection (1), difference (2) or symmetric difference (3) of two sorted key
+        arrays as multisets -- the kept keys in merge order, their values, their positions in a ++ b (each output may be
+        0: not produced) and their number into d_out_num; d_a_num / d_b_num (0: none) are device words that bound the
+        inputs.  The inputs are only read and no output may overlap them."""
+        self._check(self._L.rsx_setop_device(self._h, op, d_a_keys or None, d_a_values or None, na, d_a_num or None, d_b_keys or None,
+                                             d_b_values or None, nb, d_b_num or None, key_bytes, key_kind, value_bytes,
+                                             1 if descending else 0, d_out_keys or None, d_out_values or None, d_out_index or None,
+                                             index_bytes, d_out_num or None, stream))
+
     def reserve_reduce(self, n: int, key_bytes: int, value_bytes: int):
         """rsx_ctx_reserve_reduce: the context's first-call set-up and the workspace of reduce_by_key_device on up to n keys
         of these widths, so that the call allocates nothing and can be captured."""
@@ -1326,6 +1343,156 @@ def radix_merge_pairs(a_keys, a_values, b_keys, b_values, descending: bool = Fal
             c.merge_device(a_keys.data_ptr() if na else 0, a_values.data_ptr() if na else 0, na, b_keys.data_ptr() if nb else 0,
                            b_values.data_ptr() if nb else 0, nb, kb, kind, va, out_keys.data_ptr(), out_values.data_ptr(), 0, 8, descending, stream)
     return out_keys, out_values
+
+
+def setop_caps(key_bytes: int):
+    """rsx_setop_caps -> tile: the positions of the merge one workgroup of the set-operation kernel takes for this key
+    width.  Needs no device."""
+    L = _lib.load()
+    tile = ctypes.c_uint32()
+    _check_rc(L, L.rsx_setop_caps(key_bytes, ctypes.byref(tile)))
+    return int(tile.value)
+
+
+SetResult = namedtuple("SetResult", ["keys", "index", "num"])
+SetPairsResult = namedtuple("SetPairsResult", ["keys", "values", "num"])
+_SET_OPS = {"union": _lib.SETOP_UNION, "intersection": _lib.SETOP_INTERSECTION, "difference": _lib.SETOP_DIFFERENCE,
+            "symmetric_difference": _lib.SETOP_SYMMETRIC_DIFFERENCE}
+_SET_FUSED = (1, 2, 4, 8, 16)
+
+
+def _set_op(op):
+    if op not in _SET_OPS:
+        raise ValueError(f'op must be "union", "intersection", "difference" or "symmetric_difference", not {op!r}')
+    return _SET_OPS[op]
+
+
+def _set_cap(op: int, na: int, nb: int) -> int:
+    """Rows of every output of a set operation."""
+    return min(na, nb) if op == _lib.SETOP_INTERSECTION else na if op == _lib.SETOP_DIFFERENCE else na + nb
+
+
+def _set_num(num, keys, what: str):
+    """a_num= / b_num= of radix_set_op: None, or a one-element int64 tensor on the keys' device."""
+    import torch
+    if num is None:
+        return
+    if not isinstance(num, torch.Tensor) or num.dtype != torch.int64 or num.numel() != 1:
+        raise TypeError(f"{what} must be a one-element int64 tensor")
+    if num.device != keys.device:
+        raise ValueError(f"the keys and {what} must live on the same device")
+
+
+def radix_set_op(a, b, op: str, descending: bool = False, return_index: bool = False, index_dtype=None, out=None,
+                 a_num=None, b_num=None, ctx: Optional[Context] = None, key_kind: Optional[int] = None):
+    """A set operation on two sorted key tensors as multisets (rsx_setop_device), the rules of std::set_union and its
+    siblings: a key that occurs m times in `a` and n times in `b` occurs max(m, n) times in the "union", min(m, n) times
+    in the "intersection", max(m - n, 0) times in the "difference" and |m - n| times in the "symmetric_difference".  The
+    kept keys come in sorted order, equal keys of `a` in front of equal keys of `b`.  Returns SetResult(keys, index, num)
+    without synchronising:
+
+    keys   a tensor like `a` of the capacity len(a) + len(b) (union, symmetric difference), len(a) (difference) or
+           min(len(a), len(b)) (intersection); its first num entries are the result, the rest is not written.
+    index  None, or with return_index=True the position of every kept key in the concatenation: below len(a) a position in
+           `a`, otherwise index - len(a) a position in `b`; index_dtype torch.int64 (default) or torch.int32.
+    num    a 0-d int64 device tensor: the number of kept keys.
+
+    a, b: as in radix_merge.  a_num, b_num: one-element int64 device tensors such as radix_group(...).num; only the first
+    min(len(a), a_num) keys of `a` count (`b` likewise), read on the device: two radix_group results combine without a
+    host read.  out: the keys tensor to fill (with return_index: a pair (keys, index)), of the capacity above; it must not
+    overlap an input.  If an input is not sorted the result is unspecified but nothing outside the outputs is written.
+    Enqueued on the current stream."""
+    import torch
+    kb, kind, na, nb = _merge_keys(a, b, key_kind)
+    code = _set_op(op)
+    cap = _set_cap(code, na, nb)
+    out_keys, out_index = out, None
+    if return_index and out is not None:
+        if not isinstance(out, (tuple, list)) or len(out) != 2:
+            raise TypeError("out must be a pair (keys, index) with return_index=True")
+        out_keys, out_index = out
+    if out_keys is not None:
+        _merge_out(out_keys, a, cap, "keys")
+    if out_index is not None:
+        _index_out(out_index, (cap,), "the kept keys")
+        if out_index.device != a.device:
+            raise ValueError("the keys and out (index) must live on the same device")
+        index_dtype = out_index.dtype
+    index_dtype = _index_dtype(index_dtype)
+    _set_num(a_num, a, "a_num")
+    _set_num(b_num, a, "b_num")
+    _pairs_device(a, None, "")
+    if return_index and index_dtype == torch.int32 and na + nb > 1 << 32:
+        raise ValueError("more than 2^32 keys need int64 indices")
+    if out_keys is None:
+        out_keys = torch.empty((cap,) + tuple(a.shape[1:]), dtype=a.dtype, device=a.device)
+    if return_index and out_index is None:
+        out_index = torch.empty(cap, dtype=index_dtype, device=a.device)
+    num = torch.empty((), dtype=torch.int64, device=a.device)
+    if na + nb == 0 or cap == 0:  # (empty outputs have no address to hand to the C call: nothing can be kept)
+        num.zero_()
+        return SetResult(out_keys, out_index, num)
+    with _on_device(a, ctx) as (c, stream):
+        c.setop_device(code, a.data_ptr() if na else 0, 0, na, a_num.data_ptr() if a_num is not None else 0, b.data_ptr() if nb else 0, 0, nb,
+                       b_num.data_ptr() if b_num is not None else 0, kb, kind, 0, out_keys.data_ptr(), 0,
+                       out_index.data_ptr() if return_index else 0, out_index.element_size() if return_index else 8, num.data_ptr(),
+                       descending, stream)
+    return SetResult(out_keys, out_index, num)
+
+
+def radix_set_op_pairs(a_keys, a_values, b_keys, b_values, op: str, descending: bool = False, out=None, a_num=None, b_num=None,
+                       ctx: Optional[Context] = None, key_kind: Optional[int] = None):
+    """radix_set_op with values (rsx_setop_device): returns SetPairsResult(keys, values, num); values[t] is the value of the
+    very element keys[t] came from (for a key in both inputs: `a`'s, except the surplus occurrences of `b` in a union).
+
+    a_values, b_values: contiguous GPU tensors of one dtype with one row per key and the same trailing dimensions; a row
+    is one value of 1, 2, 4, 8 or 16 bytes, moved bitwise.  b_values may be None for "intersection" and "difference",
+    which never emit from `b`.  Other widths raise ValueError: use radix_set_op(..., return_index=True) and gather.
+    out: a pair (keys, values) of the capacity of radix_set_op.  Enqueued on the current stream, not synchronised."""
+    import torch
+    kb, kind, na, nb = _merge_keys(a_keys, b_keys, key_kind)
+    code = _set_op(op)
+    cap = _set_cap(code, na, nb)
+    emits_b = code in (_lib.SETOP_UNION, _lib.SETOP_SYMMETRIC_DIFFERENCE)
+    va = _value_bytes(a_values, (na,), "a_keys")
+    if a_values is None:
+        raise TypeError("a_values must be a torch tensor (keys alone: radix_set_op)")
+    if b_values is None and emits_b:
+        raise TypeError(f'b_values must be a torch tensor for "{op}", which can emit from b')
+    if b_values is not None:
+        vb = _value_bytes(b_values, (nb,), "b_keys")
+        if a_values.dtype != b_values.dtype:
+            raise TypeError(f"both value tensors must have one dtype, not {a_values.dtype} and {b_values.dtype}")
+        if tuple(a_values.shape[1:]) != tuple(b_values.shape[1:]) or va != vb:
+            raise ValueError(f"both value tensors must have the same trailing shape, not {tuple(a_values.shape)} and {tuple(b_values.shape)}")
+    if va not in _SET_FUSED:
+        raise ValueError(f"one value must have 1, 2, 4, 8 or 16 bytes, not {va}: use radix_set_op(..., return_index=True) and gather")
+    out_keys = out_values = None
+    if out is not None:
+        if not isinstance(out, (tuple, list)) or len(out) != 2:
+            raise TypeError("out must be a pair (keys, values)")
+        out_keys, out_values = out
+        _merge_out(out_keys, a_keys, cap, "keys")
+        _merge_out(out_values, a_values, cap, "values")
+    for v, what in ((a_values, "a_values"), (b_values, "b_values")):
+        if v is not None and v.device != a_keys.device:
+            raise ValueError(f"keys and {what} must live on the same device")
+    _set_num(a_num, a_keys, "a_num")
+    _set_num(b_num, a_keys, "b_num")
+    _pairs_device(a_keys, None, "")
+    if out_keys is None:
+        out_keys = torch.empty((cap,) + tuple(a_keys.shape[1:]), dtype=a_keys.dtype, device=a_keys.device)
+        out_values = torch.empty((cap,) + tuple(a_values.shape[1:]), dtype=a_values.dtype, device=a_keys.device)
+    num = torch.empty((), dtype=torch.int64, device=a_keys.device)
+    if na + nb == 0 or cap == 0:
+        num.zero_()
+        return SetPairsResult(out_keys, out_values, num)
+    with _on_device(a_keys, ctx) as (c, stream):
+        c.setop_device(code, a_keys.data_ptr() if na else 0, a_values.data_ptr() if na else 0, na, a_num.data_ptr() if a_num is not None else 0,
+                       b_keys.data_ptr() if nb else 0, b_values.data_ptr() if nb and b_values is not None and emits_b else 0, nb,
+                       b_num.data_ptr() if b_num is not None else 0, kb, kind, va, out_keys.data_ptr(), out_values.data_ptr(), 0, 8,
+                       num.data_ptr(), descending, stream)
+    return SetPairsResult(out_keys, out_values, num)
 
 
 def _segments_common(keys, offsets, max_seg_len):

@@ -1036,6 +1036,7 @@ int rsx_ctx_get_info(rsx_ctx* ctx, int what, uint64_t* out) try {
                     *out = (uint64_t)(ctx->last_sort_passes & 0xFFu) | (uint64_t)ctx->last_path << 24;
                     return RSX_OK;
                 case PATH_SEARCH:  // bits 0-7 the kernels launched after any sort, bit 8 the needles were sorted first
+                case PATH_SETOP:   // bits 0-7 the kernels launched
                 case PATH_MERGE:   // bits 0-7 the kernels launched, bit 8 the wide-value route
                     *out = (uint64_t)(ctx->last_sort_passes & 0x1FFu) | (uint64_t)ctx->last_path << 24;
                     return RSX_OK;
@@ -1840,6 +1841,149 @@ int rsx_ctx_reserve_merge(rsx_ctx* ctx, size_t n_total, uint32_t key_bytes, uint
 int rsx_merge_caps(uint32_t key_bytes, uint32_t value_bytes, uint32_t* tile) {
     if (!tile || !key_widths_ok(key_bytes, RSX_KEY_UNSIGNED) || value_bytes > RSX_MAX_ELEM_BYTES) return RSX_ERR_ARG;
     *tile = merge_tile_elems(key_bytes, value_bytes);
+    return RSX_OK;
+}
+
+// ---- set operations on two sorted key arrays (rsx_setop_kernels.hpp, include/rsx.h) ----
+namespace {
+// The workspace of one rsx_setop_device call, per tile of the merge of up to n keys: the count, the base, what the count
+// launch saves for the write launch; and the scan's sum.
+struct SetopPlan {
+    Carve ws;
+    size_t count_off;  // tile_count [tiles] u32
+    size_t base_off;   // tile_base [tiles] u64
+    size_t save_off;   // tile_save [tiles][setop_save_words()] u64
+    size_t num_off;    // one u64
+};
+SetopPlan setop_plan(size_t n, uint32_t kb) {
+    SetopPlan P{};
+    const uint32_t tile = setop_tile_elems(kb);
+    const size_t tiles = (n + tile - 1) / tile;
+    P.count_off = P.ws.take(tiles * sizeof(uint32_t));
+    P.base_off = P.ws.take(tiles * sizeof(uint64_t));
+    P.save_off = P.ws.take(tiles * setop_save_words() * sizeof(uint64_t));
+    P.num_off = P.ws.take(sizeof(uint64_t));
+    return P;
+}
+bool setop_size_ok(uint64_t n, uint32_t kb) {
+    const uint32_t tile = setop_tile_elems(kb);
+    return (n + tile - 1) / tile < (1ull << 31);
+}
+// rows the caller provides in every output
+uint64_t setop_cap(uint32_t op, uint64_t na, uint64_t nb) {
+    switch (op) {
+        case RSX_SETOP_INTERSECTION: return na < nb ? na : nb;
+        case RSX_SETOP_DIFFERENCE: return na;
+        default: return na + nb;
+    }
+}
+}  // namespace
+
+int rsx_setop_device(rsx_ctx* ctx, uint32_t op, const void* d_a_keys, const void* d_a_values, size_t na, const uint64_t* d_a_num, const void* d_b_keys,
+                     const void* d_b_values, size_t nb, const uint64_t* d_b_num, uint32_t key_bytes, uint32_t key_kind, uint32_t value_bytes, int order,
+                     void* d_out_keys, void* d_out_values, void* d_out_index, uint32_t index_bytes, uint64_t* d_out_num, void* stream) try {
+    if (!ctx) return RSX_ERR_ARG;
+    if (op > RSX_SETOP_SYMMETRIC_DIFFERENCE) return fail(ctx, RSX_ERR_ARG, "invalid set operation");
+    if (!key_widths_ok(key_bytes, key_kind)) return fail(ctx, RSX_ERR_ARG, "invalid key width or kind");
+    if (value_bytes > RSX_MAX_ELEM_BYTES) return fail(ctx, RSX_ERR_ARG, "value wider than RSX_MAX_ELEM_BYTES");
+    if (!setop_value_fused(value_bytes)) return fail(ctx, RSX_ERR_UNSUPPORTED, "values of 1, 2, 4, 8 or 16 bytes only (ask for d_out_index and gather)");
+    uint32_t desc = 0;
+    if (int rc = order_desc(ctx, order, &desc)) return rc;
+    if (!d_out_num) return fail(ctx, RSX_ERR_ARG, "d_out_num is null");
+    if (!aligned(d_out_num, 8) || !aligned(d_a_num, 8) || !aligned(d_b_num, 8)) return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
+    const uint64_t n = (uint64_t)na + (uint64_t)nb;
+    if (n < (uint64_t)na) return fail(ctx, RSX_ERR_UNSUPPORTED, "too many keys for one launch");
+    Entry held(ctx, stream);
+    if (!held.ok) return no_device(ctx);
+    const hipStream_t st = held.st;
+    if (n == 0) return no_group(ctx, PATH_SETOP, d_out_num, nullptr, st);  // nothing kept: no other pointer is looked at
+    if (d_out_index) {
+        if (int rc = check_index_bytes(ctx, index_bytes)) return rc;
+        if (index_bytes == 4 && n > (1ull << 32)) return fail(ctx, RSX_ERR_ARG, "more than 2^32 keys need 8-byte indices");
+    }
+    if (!d_out_keys && !d_out_values && !d_out_index) return fail(ctx, RSX_ERR_ARG, "d_out_keys, d_out_values and d_out_index are all null");
+    if (value_bytes == 0 && (d_a_values || d_b_values || d_out_values)) return fail(ctx, RSX_ERR_ARG, "value pointers and value_bytes disagree");
+    if ((na > 0 && !d_a_keys) || (nb > 0 && !d_b_keys)) return fail(ctx, RSX_ERR_ARG, "null device pointer");
+    const bool emits_b = op == RSX_SETOP_UNION || op == RSX_SETOP_SYMMETRIC_DIFFERENCE;
+    if (!emits_b) d_b_values = nullptr;  // not looked at
+    if (value_bytes != 0 && ((na > 0 && !d_a_values) || (emits_b && nb > 0 && !d_b_values)))
+        return fail(ctx, RSX_ERR_ARG, "values are given on one side only");
+    const uint32_t va = value_bytes ? value_align(value_bytes) : 1u, ia = d_out_index ? index_bytes : 1u;
+    if (!aligned(d_a_keys, key_bytes) || !aligned(d_b_keys, key_bytes) || !aligned(d_out_keys, key_bytes) || !aligned(d_a_values, va) ||
+        !aligned(d_b_values, va) || !aligned(d_out_values, va) || !aligned(d_out_index, ia))
+        return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
+    if (!setop_size_ok(n, key_bytes)) return fail(ctx, RSX_ERR_UNSUPPORTED, "too many keys for one launch");
+    const uint64_t cap = setop_cap(op, na, nb);
+    {  // not in place: no output may share a byte with an input or with another output
+        const void* in_p[6] = {d_a_keys, d_b_keys, d_a_values, d_b_values, d_a_num, d_b_num};
+        const uint64_t in_b[6] = {(uint64_t)na * key_bytes, (uint64_t)nb * key_bytes, (uint64_t)na * value_bytes, (uint64_t)nb * value_bytes, 8, 8};
+        const void* out_p[4] = {d_out_keys, d_out_values, d_out_index, d_out_num};
+        const uint64_t out_b[4] = {cap * key_bytes, cap * value_bytes, cap * (d_out_index ? index_bytes : 0u), 8};
+        for (int o = 0; o < 4; ++o) {
+            for (int i = 0; i < 6; ++i)
+                if (ranges_overlap(out_p[o], out_b[o], in_p[i], in_b[i])) return fail(ctx, RSX_ERR_ARG, "an output overlaps an input");
+            for (int p = o + 1; p < 4; ++p)
+                if (ranges_overlap(out_p[o], out_b[o], out_p[p], out_b[p])) return fail(ctx, RSX_ERR_ARG, "two outputs overlap");
+        }
+    }
+    int rc = pending_error(ctx);
+    if (rc) return rc;
+    const SetopPlan P = setop_plan((size_t)n, key_bytes);
+    rc = ensure_aux(ctx, st);
+    if (rc) return rc;
+    rc = ensure_any(ctx, P.ws.bytes, st);
+    if (rc) return rc;
+    Enqueue enq(ctx, st);  // the workspace arrays belong to this call from the first launch on
+    char* w = reinterpret_cast<char*>(ctx->any_buf);
+    SetopCall c{};
+    c.a_keys = d_a_keys;
+    c.a_values = d_out_values ? d_a_values : nullptr;
+    c.na = na;
+    c.a_num = d_a_num;
+    c.b_keys = d_b_keys;
+    c.b_values = d_out_values ? d_b_values : nullptr;
+    c.nb = nb;
+    c.b_num = d_b_num;
+    c.op = op;
+    c.kb = key_bytes;
+    c.kind = key_kind;
+    c.desc = desc;
+    c.vb = value_bytes;
+    c.ib = index_bytes;
+    c.tile_count = reinterpret_cast<uint32_t*>(w + P.count_off);
+    c.tile_base = reinterpret_cast<uint64_t*>(w + P.base_off);
+    c.tile_save = reinterpret_cast<uint64_t*>(w + P.save_off);
+    c.raw_num = reinterpret_cast<uint64_t*>(w + P.num_off);
+    c.cap = (size_t)cap;
+    c.out_keys = d_out_keys;
+    c.out_values = d_out_values;
+    c.out_index = d_out_index;
+    c.out_num = d_out_num;
+    uint32_t launched = 0;
+    rc = launch_setop(ctx, c, &launched, st);
+    if (rc) return rc;
+    note_path(ctx, PATH_SETOP, launched);
+    return RSX_OK;
+} catch (...) {
+    return RSX_ERR_HIP;
+}
+
+int rsx_ctx_reserve_setop(rsx_ctx* ctx, size_t n_total, uint32_t key_bytes) try {
+    if (!ctx) return RSX_ERR_ARG;
+    if (!key_widths_ok(key_bytes, RSX_KEY_UNSIGNED)) return fail(ctx, RSX_ERR_ARG, "invalid key width");
+    if (!setop_size_ok(n_total, key_bytes)) return fail(ctx, RSX_ERR_UNSUPPORTED, "too many keys for one launch");
+    Entry held(ctx);
+    if (!held.ok) return no_device(ctx);
+    int rc = ensure_aux(ctx, nullptr);
+    if (rc) return rc;
+    return ensure_any(ctx, setop_plan(n_total, key_bytes).ws.bytes, nullptr);
+} catch (...) {
+    return RSX_ERR_NOMEM;
+}
+
+int rsx_setop_caps(uint32_t key_bytes, uint32_t* tile) {
+    if (!tile || !key_widths_ok(key_bytes, RSX_KEY_UNSIGNED)) return RSX_ERR_ARG;
+    *tile = setop_tile_elems(key_bytes);
     return RSX_OK;
 }
 

@@ -1,4 +1,4 @@
-// rsx_internal.hpp -- host-side state and helpers shared by the fifteen translation units of librsx.so:
+// rsx_internal.hpp -- host-side state and helpers shared by the sixteen translation units of librsx.so:
 //   rsx.hip         the C-ABI of include/rsx.h (context, pass loop, multi-GPU driver, harness)
 //   rsx_es.hip      the kernel launchers of ONE element size (compiled once per size with -DRSX_ES=n,
 //                   so the eight sizes build in parallel), reached through that size's EsLaunchers table
@@ -7,6 +7,7 @@
 //   rsx_reduce.hip  those of rsx_reduce_by_key_device
 //   rsx_search.hip  the kernel of rsx_search_sorted_device
 //   rsx_merge.hip   the kernels of rsx_merge_device
+//   rsx_setops.hip  the kernel of rsx_setop_device
 //   rsx_lex.hip     the join of several key columns (rsx_lexsort_device, rsx_sort_columns_device)
 #pragma once
 #include "rsx_device.hpp"
@@ -79,6 +80,7 @@ enum : uint32_t {
     PATH_REDUCE = 9,
     PATH_SEARCH = 10,
     PATH_MERGE = 11,
+    PATH_SETOP = 12,
 };
 
 // option bits (rsx_ctx_set_option): alternative kernel paths, all bit-exact
@@ -597,5 +599,36 @@ int launch_merge(rsx_ctx* ctx, const MergeCall& call, uint32_t* launched, hipStr
 int launch_merge_gather(rsx_ctx* ctx, const MergeCall& call, const uint64_t* pos, void* out_values, void* out_index, hipStream_t st);
 uint32_t merge_tile_elems(uint32_t kb, uint32_t vb);  // outputs per workgroup
 bool merge_value_fused(uint32_t vb);                  // the kernel moves values of this width itself
+
+// What one rsx_setop_device call asks of the set-operation kernel (rsx_setops.hip, rsx_setop_kernels.hpp).
+struct SetopCall {
+    const void* a_keys;          // na keys of kb bytes, sorted by mapped key in the call's order; b likewise
+    const void* a_values;        // na values of vb bytes (read only when out_values is given)
+    size_t na;
+    const uint64_t* a_num;       // null, or one device word: only the first min(na, *a_num) keys count; b_num likewise
+    const void* b_keys;
+    const void* b_values;        // may be null when the operation never emits from b
+    size_t nb;
+    const uint64_t* b_num;
+    uint32_t op;                 // RSX_SETOP_*
+    uint32_t kb, kind, desc;
+    uint32_t vb;                 // a fused width (setop_value_fused)
+    uint32_t ib;                 // bytes of a position in out_index
+    uint32_t* tile_count;        // per tile of setop_tile_elems: its kept elements, ...
+    uint64_t* tile_base;         // ... those in front of it, and ...
+    uint64_t* tile_save;         // ... setop_save_words() words the count launch leaves for the write launch
+    uint64_t* raw_num;           // one word: the scan's sum
+    size_t cap;                  // rows of every output
+    void* out_keys;              // each may be null
+    void* out_values;
+    void* out_index;
+    uint64_t* out_num;           // min(the scan's sum, cap)
+};
+int launch_setop(rsx_ctx* ctx, const SetopCall& call, uint32_t* launched, hipStream_t st);
+uint32_t setop_tile_elems(uint32_t kb);  // merge positions per workgroup
+uint32_t setop_save_words();
+bool setop_value_fused(uint32_t vb);
+// rsx_unique_scan_kernel over another call's per-tile counts (rsx_unique.hip): tile_base[t] and their sum -> out_num[0]
+void launch_run_scan(const uint32_t* tile_count, uint64_t* tile_base, uint64_t tiles, uint64_t* out_num, hipStream_t st);
 
 }  // namespace rsxh

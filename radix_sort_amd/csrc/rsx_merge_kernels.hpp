@@ -2,7 +2,8 @@
 // key arrays a[na] and b[nb] that are sorted by mapped key (complemented for descending order), with optional values and
 // optional source positions.  With c = a ++ b and p the stable permutation that sorts c by mapped key (equal keys of a in
 // front of equal keys of b):  out_keys[t] = c[p[t]],  out_values[t] = (a_values ++ b_values)[p[t]],  out_index[t] = p[t].
-// One kernel, rsx_merge_kernel<KB, VB, IB> (VB 0: no values, IB 0: no positions); one workgroup of MERGE_WG threads per tile
+// One kernel, rsx_merge_kernel<KB, VB, IB> (VB 0: no values, IB 0: no positions; its steps a to c are functions that the
+// set-operation kernel of rsx_setop_kernels.hpp calls too); one workgroup of MERGE_WG threads per tile
 // of merge_tile(KB, VB) consecutive OUTPUT positions [d0, d1):
 //   a. the tile's two cuts on the merge path: cut(d) = the number of elements of a among the first d outputs = the largest
 //      i in [max(0, d - nb), min(d, na)] with i == 0, or d - i >= nb, or M(a[i-1]) <= M(b[d-i]) (monotone in i; the <= is
@@ -86,6 +87,65 @@ __device__ __forceinline__ void merge_clamp(uint64_t a0, uint64_t a1, uint64_t d
     *bcnt = L - (uint32_t)c;
 }
 
+// Step a, the waves 0 and 1 of the workgroup: cut(d0) and cut(d1) -> s_cut[0], s_cut[1] (the caller's barrier follows).
+template <int KB>
+__device__ __forceinline__ void merge_cuts(const uint8_t* __restrict__ a_keys, uint64_t na, const uint8_t* __restrict__ b_keys, uint64_t nb, uint64_t d0,
+                                           uint64_t d1, uint32_t kind, uint32_t desc, uint64_t* s_cut) {
+    using K = typename PairsKey<KB>::type;
+    const uint32_t wave = threadIdx.x / WAVE;
+    if (wave < 2) {
+        const uint64_t d = wave == 0 ? d0 : d1;
+        const uint64_t lo = d > nb ? d - nb : 0, hi = d < na ? d : na;
+        // i = lo + 1 + x for x in [0, hi - lo): a[i-1] = a[lo + x] with lo + x < hi <= na, b[d-i] = b[d - lo - 1 - x] with
+        // 0 <= d - hi <= d - lo - 1 - x <= d - lo - 1 < nb
+        const uint64_t c = search_wave_count(hi - lo, [&](uint64_t x) {
+            const K ka = search_hay<KB>(a_keys, lo + x, kind, desc);
+            const K kb = search_hay<KB>(b_keys, d - lo - 1 - x, kind, desc);
+            return !(kb < ka);
+        });
+        if ((threadIdx.x & (WAVE - 1)) == 0) s_cut[wave] = lo + c;
+    }
+}
+
+// Step c, first part: both ranges -> LDS, a's mapped keys at [0, acnt), b's behind them (L = acnt + bcnt <= IPT * MERGE_WG).
+template <int KB, int IPT>
+__device__ __forceinline__ void merge_stage(const uint8_t* __restrict__ a_keys, uint64_t a0, uint32_t acnt, const uint8_t* __restrict__ b_keys, uint64_t b0,
+                                            uint32_t L, uint32_t kind, uint32_t desc, typename PairsKey<KB>::type* s_key) {
+#pragma unroll
+    for (int j = 0; j < IPT; ++j) {
+        const uint32_t i = threadIdx.x + (uint32_t)j * MERGE_WG;
+        if (i < L) s_key[i] = i < acnt ? search_hay<KB>(a_keys, a0 + i, kind, desc) : search_hay<KB>(b_keys, b0 + (i - acnt), kind, desc);
+    }
+}
+
+// ... second part: the cut of the tile's output dt in LDS, the largest i in [lo, hi] with i == lo or sa[i-1] <= sb[dt-i]
+template <typename K>
+__device__ __forceinline__ void merge_thread_cut(const K* s_key, uint32_t dt, uint32_t acnt, uint32_t bcnt, uint32_t* ai, uint32_t* bi) {
+    uint32_t lo = dt > bcnt ? dt - bcnt : 0, hi = dt < acnt ? dt : acnt;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi + 1) >> 1;  // lo < mid <= hi: mid - 1 < acnt, 0 <= dt - mid < bcnt
+        if (!(s_key[acnt + (dt - mid)] < s_key[mid - 1])) lo = mid;
+        else hi = mid - 1;
+    }
+    *ai = lo;
+    *bi = dt - lo;
+}
+
+// ... third part, one output of the serial merge.  ka = sa[ai] when ai < acnt, kb = sb[bi] when bi < bcnt, and one side at
+// least has an element left: which side gives the output (the <= that puts a first among ties).  One definition for both
+// kernels, as a macro: through a function the 16-byte-key instantiations of the merge kernel took 2 to 4 more SGPRs.
+#define RSX_MERGE_TAKE_A(ka, kb, ai, bi, acnt, bcnt) ((ai) < (acnt) && ((bi) >= (bcnt) || !((kb) < (ka))))
+// ... and the step behind it: the next key of the side taken, one LDS read per output whichever side it is (no divergent branch)
+template <typename K>
+__device__ __forceinline__ void merge_advance(const K* s_key, bool take_a, uint32_t acnt, uint32_t bcnt, uint32_t& ai, uint32_t& bi, K& ka, K& kb) {
+    ai += take_a ? 1u : 0u;
+    bi += take_a ? 0u : 1u;
+    const bool more = take_a ? ai < acnt : bi < bcnt;
+    const K next = s_key[more ? (take_a ? ai : acnt + bi) : 0u];
+    ka = merge_pick<K>(take_a, next, ka);
+    kb = merge_pick<K>(take_a, kb, next);
+}
+
 // VB > 0: a_values (na > 0), b_values (nb > 0) and out_values are given; IB > 0: out_index is; out_keys may be null.
 template <int KB, int VB, int IB>
 __global__ __launch_bounds__(MERGE_WG) void rsx_merge_kernel(const uint8_t* __restrict__ a_keys, const uint8_t* __restrict__ a_values, uint64_t na,
@@ -106,20 +166,8 @@ __global__ __launch_bounds__(MERGE_WG) void rsx_merge_kernel(const uint8_t* __re
     const uint64_t d0 = (uint64_t)blockIdx.x * TILE;  // (the host launches ceil(n / TILE) tiles: d0 < n)
     const uint64_t d1 = d0 + TILE < n ? d0 + TILE : n;
     const uint32_t L = (uint32_t)(d1 - d0);
-    const uint32_t wave = threadIdx.x / WAVE;
     // a. the two cuts
-    if (wave < 2) {
-        const uint64_t d = wave == 0 ? d0 : d1;
-        const uint64_t lo = d > nb ? d - nb : 0, hi = d < na ? d : na;
-        // i = lo + 1 + x for x in [0, hi - lo): a[i-1] = a[lo + x] with lo + x < hi <= na, b[d-i] = b[d - lo - 1 - x] with
-        // 0 <= d - hi <= d - lo - 1 - x <= d - lo - 1 < nb
-        const uint64_t c = search_wave_count(hi - lo, [&](uint64_t x) {
-            const K ka = search_hay<KB>(a_keys, lo + x, kind, desc);
-            const K kb = search_hay<KB>(b_keys, d - lo - 1 - x, kind, desc);
-            return !(kb < ka);
-        });
-        if ((threadIdx.x & (WAVE - 1)) == 0) s_cut[wave] = lo + c;
-    }
+    merge_cuts<KB>(a_keys, na, b_keys, nb, d0, d1, kind, desc, s_cut);
     __syncthreads();
     // b. the clamp
     const uint64_t a0 = s_cut[0];
@@ -127,25 +175,12 @@ __global__ __launch_bounds__(MERGE_WG) void rsx_merge_kernel(const uint8_t* __re
     uint32_t acnt, bcnt;
     merge_clamp(a0, s_cut[1], d0, L, na, nb, &b0, &acnt, &bcnt);
     // c. both ranges -> LDS: a's keys at [0, acnt), b's behind them
-#pragma unroll
-    for (int j = 0; j < IPT; ++j) {
-        const uint32_t i = threadIdx.x + (uint32_t)j * MERGE_WG;
-        if (i < L) s_key[i] = i < acnt ? search_hay<KB>(a_keys, a0 + i, kind, desc) : search_hay<KB>(b_keys, b0 + (i - acnt), kind, desc);
-    }
+    merge_stage<KB, IPT>(a_keys, a0, acnt, b_keys, b0, L, kind, desc, s_key);
     __syncthreads();
-    // this thread's outputs [dt, dt + IPT) of the tile and their cut: the largest i in [lo, hi] with i == lo or sa[i-1] <= sb[dt-i]
+    // this thread's outputs [dt, dt + IPT) of the tile and their cut
     const uint32_t dt = threadIdx.x * IPT < L ? threadIdx.x * IPT : L;
     uint32_t ai, bi;
-    {
-        uint32_t lo = dt > bcnt ? dt - bcnt : 0, hi = dt < acnt ? dt : acnt;
-        while (lo < hi) {
-            const uint32_t mid = (lo + hi + 1) >> 1;  // lo < mid <= hi: mid - 1 < acnt, 0 <= dt - mid < bcnt
-            if (!(s_key[acnt + (dt - mid)] < s_key[mid - 1])) lo = mid;
-            else hi = mid - 1;
-        }
-        ai = lo;
-        bi = dt - lo;
-    }
+    merge_thread_cut<K>(s_key, dt, acnt, bcnt, &ai, &bi);
     K key[IPT];
     K ka{}, kb{};
     if (ai < acnt) ka = s_key[ai];
@@ -154,17 +189,11 @@ __global__ __launch_bounds__(MERGE_WG) void rsx_merge_kernel(const uint8_t* __re
     for (int k = 0; k < IPT; ++k) {
         key[k] = K{};
         if (dt + k < L) {  // ai + bi = dt + k < acnt + bcnt: one side at least has an element left
-            const bool take_a = ai < acnt && (bi >= bcnt || !(kb < ka));
+            const bool take_a = RSX_MERGE_TAKE_A(ka, kb, ai, bi, acnt, bcnt);
             key[k] = merge_pick<K>(take_a, ka, kb);
             // (the slots have an array of their own that nobody reads before the barriers below: stored at once, in output order)
             if constexpr (SLOTS) s_slot[dt + k] = (uint16_t)(take_a ? ai : acnt + bi);
-            // the next key of the side taken: one LDS read per output whichever side it is (no divergent branch)
-            ai += take_a ? 1u : 0u;
-            bi += take_a ? 0u : 1u;
-            const bool more = take_a ? ai < acnt : bi < bcnt;
-            const K next = s_key[more ? (take_a ? ai : acnt + bi) : 0u];
-            ka = merge_pick<K>(take_a, next, ka);
-            kb = merge_pick<K>(take_a, kb, next);
+            merge_advance<K>(s_key, take_a, acnt, bcnt, ai, bi, ka, kb);
         }
     }
     __syncthreads();

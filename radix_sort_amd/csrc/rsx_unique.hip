@@ -31,6 +31,12 @@ void unique_kb(const UniqueCall& c, uint32_t tiles, bool write, hipStream_t st) 
 uint32_t unique_tile_elems(uint32_t kb, bool pos) { return unique_tile(unique_elem(kb, pos)); }
 uint32_t unique_scan_span() { return UNIQUE_SCAN_SPAN; }
 
+// the scan kernel alone, for another call's per-tile counts (rsx_setops.hip): at most 4096 per tile
+void launch_run_scan(const uint32_t* tile_count, uint64_t* tile_base, uint64_t tiles, uint64_t* out_num, hipStream_t st) {
+    hipLaunchKernelGGL(rsx_unique_scan_kernel, dim3(1), dim3(UNIQUE_SCAN_WG), 0, st, tile_count, tile_base, tiles, (uint64_t)0, out_num,
+                       static_cast<uint64_t*>(nullptr));
+}
+
 // the three run kernels over c.n >= 1 sorted joined elements; the write kernel only when it has an output
 int launch_unique(rsx_ctx* ctx, const UniqueCall& c, uint32_t* launched, hipStream_t st) {
     const uint32_t es = pairs_elem_bytes(c.kb, c.pos ? 4u : 0u);

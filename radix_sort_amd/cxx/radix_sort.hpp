@@ -18,6 +18,8 @@
 //     rsx::search_sorted(const K* d_sorted, size_t n, const K* d_needles, size_t m, I* lower, I* upper, bool descending, const uint64_t* d_sorted_num, bool presort, hipStream_t)
 //     rsx::merge(const K* d_a_keys, size_t na, const K* d_b_keys, size_t nb, K* d_out_keys, bool descending, hipStream_t)   // two sorted arrays
 //     rsx::merge_pairs(const K* d_a_keys, const V* d_a_values, size_t na, const K* d_b_keys, const V* d_b_values, size_t nb, K* keys, V* values[, I* index], bool descending, hipStream_t)
+//     rsx::set_op(int op, const K* d_a_keys, size_t na, const K* d_b_keys, size_t nb, K* d_out_keys, uint64_t* d_out_num[, I* index], bool descending, const uint64_t* d_a_num, const uint64_t* d_b_num, hipStream_t)   // RSX_SETOP_*
+//     rsx::set_op_pairs(int op, const K* d_a_keys, const V* d_a_values, size_t na, const K* d_b_keys, const V* d_b_values, size_t nb, K* keys, V* values, uint64_t* d_out_num, bool descending, const uint64_t* d_a_num, const uint64_t* d_b_num, hipStream_t)
 //     rsx::lexsort({rsx::key_column(d_a), rsx::key_column(d_b, true)}, I* d_index, size_t n, hipStream_t)   // several key columns
 //     rsx::sort_columns({rsx::key_column(d_a), rsx::key_column(d_b, true)}, V* d_values, size_t n, hipStream_t)
 // Errors: the reference panics (mod.rs:68,106); here std::runtime_error is thrown.
@@ -305,6 +307,47 @@ void merge(const K* d_a_keys, size_t na, const K* d_b_keys, size_t nb, K* d_out_
     ctx.check(rsx_merge_device(ctx.get(), d_a_keys, nullptr, na, d_b_keys, nullptr, nb, L.key_bytes, L.key_kind, 0u,
                                descending ? RSX_ORDER_DESCENDING : RSX_ORDER_ASCENDING, d_out_keys, nullptr, nullptr, 8u, stream),
               "rsx_merge_device");
+}
+
+// A set operation on two key arrays that are each sorted in that order, as multisets (rsx_setop_device; op: RSX_SETOP_UNION,
+// _INTERSECTION, _DIFFERENCE, _SYMMETRIC_DIFFERENCE): the kept keys in merge order into d_out_keys, equal keys of a first, and
+// their number into the device word d_out_num.  Every output holds na + nb rows (union, symmetric difference), na
+// (difference) or min(na, nb) (intersection); rows from *d_out_num on are not written.  d_out_index: the position of every
+// kept key in a ++ b (below na a position in a, else that minus na a position in b).  d_a_num / d_b_num, when given, are
+// device words such as the d_out_num of unique: only the first min(na, *d_a_num) keys of a count.  set_op_pairs moves the
+// values with their keys (V of 1, 2, 4, 8 or 16 bytes; d_b_values may be nullptr for intersection and difference).  The
+// inputs are only read and no output may overlap them; rsx_ctx_reserve_setop before a stream capture.  Stream-ordered,
+// never synchronised.
+template <typename K, typename I>
+void set_op(int op, const K* d_a_keys, size_t na, const K* d_b_keys, size_t nb, K* d_out_keys, uint64_t* d_out_num, I* d_out_index,
+            bool descending = false, const uint64_t* d_a_num = nullptr, const uint64_t* d_b_num = nullptr, void* stream = nullptr,
+            Context& ctx = default_context()) {
+    static_assert(std::is_integral<I>::value && (sizeof(I) == 4 || sizeof(I) == 8), "indices are 4- or 8-byte integers");
+    const rsx_layout L = RadixDigits<K>::layout();
+    if (L.key_offset != 0 || L.key_bytes != L.elem_bytes) throw std::invalid_argument("set_op: the key type must be its own key");
+    ctx.check(rsx_setop_device(ctx.get(), (uint32_t)op, d_a_keys, nullptr, na, d_a_num, d_b_keys, nullptr, nb, d_b_num, L.key_bytes, L.key_kind, 0u,
+                               descending ? RSX_ORDER_DESCENDING : RSX_ORDER_ASCENDING, d_out_keys, nullptr, d_out_index, (uint32_t)sizeof(I),
+                               d_out_num, stream),
+              "rsx_setop_device");
+}
+template <typename K>
+void set_op(int op, const K* d_a_keys, size_t na, const K* d_b_keys, size_t nb, K* d_out_keys, uint64_t* d_out_num, bool descending = false,
+            const uint64_t* d_a_num = nullptr, const uint64_t* d_b_num = nullptr, void* stream = nullptr, Context& ctx = default_context()) {
+    set_op(op, d_a_keys, na, d_b_keys, nb, d_out_keys, d_out_num, static_cast<uint64_t*>(nullptr), descending, d_a_num, d_b_num, stream, ctx);
+}
+template <typename K, typename V>
+void set_op_pairs(int op, const K* d_a_keys, const V* d_a_values, size_t na, const K* d_b_keys, const V* d_b_values, size_t nb, K* d_out_keys,
+                  V* d_out_values, uint64_t* d_out_num, bool descending = false, const uint64_t* d_a_num = nullptr,
+                  const uint64_t* d_b_num = nullptr, void* stream = nullptr, Context& ctx = default_context()) {
+    static_assert(std::is_trivially_copyable<V>::value, "values are moved bitwise");
+    static_assert(sizeof(V) == 1 || sizeof(V) == 2 || sizeof(V) == 4 || sizeof(V) == 8 || sizeof(V) == 16,
+                  "values of 1, 2, 4, 8 or 16 bytes move with their keys; for other widths ask set_op for the index and gather");
+    const rsx_layout L = RadixDigits<K>::layout();
+    if (L.key_offset != 0 || L.key_bytes != L.elem_bytes) throw std::invalid_argument("set_op_pairs: the key type must be its own key");
+    ctx.check(rsx_setop_device(ctx.get(), (uint32_t)op, d_a_keys, d_a_values, na, d_a_num, d_b_keys, d_b_values, nb, d_b_num, L.key_bytes,
+                               L.key_kind, (uint32_t)sizeof(V), descending ? RSX_ORDER_DESCENDING : RSX_ORDER_ASCENDING, d_out_keys,
+                               d_out_values, nullptr, 8u, d_out_num, stream),
+              "rsx_setop_device");
 }
 
 // Several key columns (rsx_lexsort_device, rsx_sort_columns_device): rows sorted by (column 0, column 1, ...), column 0

@@ -84,6 +84,16 @@ extern "C" {
                             d_out_index: *mut c_void, index_bytes: u32, stream: *mut c_void) -> c_int;
     pub fn rsx_ctx_reserve_merge(ctx: *mut RsxCtx, n_total: usize, key_bytes: u32, value_bytes: u32) -> c_int;
     pub fn rsx_merge_caps(key_bytes: u32, value_bytes: u32, tile: *mut u32) -> c_int;
+    // set operations on two sorted key arrays (include/rsx.h, "set operations on two sorted key arrays"): op is
+    // RSX_SETOP_UNION (0), _INTERSECTION (1), _DIFFERENCE (2), _SYMMETRIC_DIFFERENCE (3); d_a_num / d_b_num are null or
+    // one device word that bounds the input; the number kept goes to d_out_num, the outputs hold cap(op) rows
+    pub fn rsx_setop_device(ctx: *mut RsxCtx, op: u32, d_a_keys: *const c_void, d_a_values: *const c_void, na: usize,
+                            d_a_num: *const u64, d_b_keys: *const c_void, d_b_values: *const c_void, nb: usize,
+                            d_b_num: *const u64, key_bytes: u32, key_kind: u32, value_bytes: u32, order: c_int,
+                            d_out_keys: *mut c_void, d_out_values: *mut c_void, d_out_index: *mut c_void, index_bytes: u32,
+                            d_out_num: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn rsx_ctx_reserve_setop(ctx: *mut RsxCtx, n_total: usize, key_bytes: u32) -> c_int;
+    pub fn rsx_setop_caps(key_bytes: u32, tile: *mut u32) -> c_int;
     pub fn rsx_sort_sharded(ctxs: *const *mut RsxCtx, ndev: u32, d_slices: *const *mut c_void,
                             d_tmps: *const *mut c_void, n_per_dev: *const usize,
                             layout: *const RsxLayout) -> c_int;
