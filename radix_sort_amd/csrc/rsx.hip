@@ -411,7 +411,13 @@ int sort_wide(rsx_ctx* ctx, const EsLaunchers& K, void* d_data, void* d_tmp, siz
     rc = K.sweep(ctx, hyb, SweepPass{0, false, 0}, d_data, d_tmp, geom, L, D - 2, J_of(ctx, hyb, 0), J_of(ctx, hyb, 1), nullptr, 1, st);  // keys mapped on load
     if (rc) return rc;
     hyb.spec_dev = &plan->specs[1];
-    rc = K.sweep(ctx, hyb, SweepPass{1, true, 0}, d_tmp, d_data, geom, L, D - 1, J_of(ctx, hyb, 1), nullptr, nullptr, 0, st);  // ... and stay mapped
+    // The second sweep counts nothing, and spends the LDS its count matrix would take on a deeper tile (hyb_geom: 8-byte
+    // elements; the forced mode keeps the one geometry).  Its count matrix, cursors and tickets are per region and do not
+    // know the tile; its status rows are among those the first sweep zeroed.
+    const RegionGeom geom2 = ctx->wide_mode == 2 ? geom : hyb_geom(geom, es);
+    if (status_rows_used(geom2) > status_rows_used(geom) || tiles_per_region(geom2) > tiles_per_region(geom))
+        return fail(ctx, RSX_ERR_INTERNAL, "sort_wide: the second sweep's status rows are not among those the first one zeroes");
+    rc = K.sweep(ctx, hyb, SweepPass{1, true, 0}, d_tmp, d_data, geom2, L, D - 1, J_of(ctx, hyb, 1), nullptr, nullptr, 0, st);  // ... and stay mapped
     if (rc) return rc;
     rc = K.bucket16(ctx, hyb, d_data, d_tmp, n, L, starts, plan, st);
     if (rc) return rc;

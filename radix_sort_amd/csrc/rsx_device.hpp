@@ -600,6 +600,9 @@ constexpr uint32_t SWEEP_OPT_PREREAD = 16u;      // 4-byte and narrower elements
 #ifndef RSX_WO_GROUP
 #define RSX_WO_GROUP 4  // write-out: elements in flight between scheduling barriers
 #endif
+#ifndef RSX_WO_STORES
+#define RSX_WO_STORES 3  // write-out of the hybrid's sweeps of 8-byte elements: stores in flight per wave (WO_THROTTLE)
+#endif
 #ifndef RSX_MINW_1024
 #define RSX_MINW_1024 8
 #endif
@@ -700,6 +703,9 @@ __attribute__((amdgpu_num_sgpr(RSX_NUM_SGPR))) void rsx_sweep_kernel(const Sweep
     // the VGPR budget without spilling (u32 x 16 keys does not at 80 VGPRs, and is VALU-bound anyway)
     constexpr bool PREFETCH = ES >= 12;
     constexpr bool EARLY_HOP = ES <= 4;  // the look-back's first hop is requested ahead of the reorder: where measured faster
+    // The hybrid's two sweeps of 8-byte elements (nothing prefetched: stores are the only vector memory operations of their
+    // write-out) keep at most RSX_WO_STORES stores in flight per wave: see the write-out.
+    constexpr bool WO_THROTTLE = ES == 8 && STR && !MID && !PREFETCH;
     static_assert(WG >= RADIX, "need one thread per digit");
     static_assert(TILE <= 65536 / 2, "wave counters are 16 bit");
     using E = Elem<ES>;
@@ -1452,6 +1458,13 @@ __attribute__((amdgpu_num_sgpr(RSX_NUM_SGPR))) void rsx_sweep_kernel(const Sweep
                         }
                         // (element by element on purpose: issuing a group's LDS reads ahead of its atomics was
                         // measured no faster on u32 and slower on 8/16-byte elements)
+                        // A wave that has issued all its stores at once -- the count-free write-out otherwise does, 14 or 18
+                        // per lane -- fills the CU's memory pipeline with scattered partial lines, and the tile loads of the
+                        // other workgroup on the CU queue behind them: the sweep that counts nothing ran 0.15 ms per 2^30 u64
+                        // SLOWER than the one that counts, on the same input.  At most RSX_WO_STORES in flight per wave:
+                        // second sweep 3.62 -> 3.40-3.47 ms, first 3.47 -> 3.40 ms (1 / 2 / 4 / 6 measured within 0.05 ms
+                        // of 3, no limit at all and looser scheduling barriers slower: DESIGN, "Hybrid sweeps: store pacing").
+                        if constexpr (WO_THROTTLE) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(RSX_WO_STORES) : "memory");
                         if (i % RSX_WO_GROUP == RSX_WO_GROUP - 1) __builtin_amdgcn_sched_barrier(0);
                     }
                     if constexpr (NEXT && CROWD) hot_flush();

@@ -312,6 +312,15 @@ constexpr uint64_t mid_max_elems(int es) { return es == 1 ? 0 : es == 8 ? (1ull 
 constexpr int kpt_for(int es) { return es <= 2 ? RSX_KPT2 : es <= 4 ? RSX_KPT4 : es == 8 ? RSX_KPT8 : es == 12 ? RSX_KPT12 : es == 16 ? RSX_KPT16 : es == 24 ? RSX_KPT24 : RSX_KPT32; }
 constexpr int wg_for(int es) { return es <= 4 ? RSX_WG4 : es == 8 ? RSX_WG8 : 512; }
 constexpr uint32_t tile_elems(int es) { return wg_for(es) * kpt_for(es); }
+// The wide-key hybrid's SECOND sweep counts for no next pass (the bucket kernel follows), so the 16 KiB that the count
+// matrix s_jn[16][256] takes beside a 512 x 14 tile of 8-byte elements hold four more keys per thread there:
+// 512 x 18 x 8 + 4096 (wave counters) + 128 = 77952 B, to the byte what the first sweep asks for, still two workgroups
+// per CU (19 does not fit).  Other element sizes keep kpt_for: 16-byte elements are capped at 80 VGPRs.
+#ifndef RSX_HYB_KPT8
+#define RSX_HYB_KPT8 18
+#endif
+constexpr int hyb_kpt_for(int es) { return es == 8 ? RSX_HYB_KPT8 : kpt_for(es); }
+static_assert((size_t)RSX_WG8 * RSX_HYB_KPT8 * 8 + (RSX_WG8 / 64) * 256 * 2 + 128 <= LDS_PER_CU / 2, "the deep tile leaves no room for two workgroups per CU");
 // The bucket split of a middle-size sort (rsx_mid_kernels.hpp) works on SMALL tiles, one workgroup each (a tile is one
 // workgroup's serial work: 13 us for 14336 u32 keys, and 2^16 keys are five of those): 512 x 8 4-byte, 512 x 4 8-byte,
 // 512 x 2 16-byte elements.
@@ -334,7 +343,9 @@ inline RegionGeom make_geom(const rsx_ctx* ctx, uint64_t n, uint32_t es, bool sm
     // 109 -> 87 us, 2^22 u32 148 -> 134 us, 2^18 u64 249 -> 166 us, 2^22 u64 360 -> 275 us; large inputs are
     // bounded by `cap` as before.
     k += small_tiles ? 3 : RSX_REGION_FLOOR;
-    // the next pass's count matrix costs 1 KiB of LDS per region: 8 where the tile needs the room
+    // the next pass's count matrix costs 1 KiB of LDS per region: 8 where the tile needs the room.  (True of every sweep
+    // that counts for a next pass -- all LSD passes but the last, the hybrid's first sweep; a last pass and the hybrid's
+    // second sweep have no such matrix, and the latter spends the room on a deeper tile: hyb_geom.)
     const uint64_t cap = small_tiles ? MID_MAX_REGIONS : ctx->max_regions ? ctx->max_regions : (es == 8 || es == 32) ? 16 : 8;
     while (((n + (1ull << k) - 1) >> k) > cap) ++k;
     g.region_shift = k;
@@ -347,6 +358,22 @@ inline uint64_t tiles_per_region(const RegionGeom& g) {
 }
 inline uint64_t status_rows(const RegionGeom& g) {
     return (uint64_t)g.num_regions * tiles_per_region(g);
+}
+// The geometry of the hybrid's second sweep: the regions of `g` (same n, region_shift, num_regions) cut into the deeper
+// tiles of hyb_kpt_for.  Its status rows are reg * tiles_per_region(deep) + kt, and they have to be rows that the first
+// sweep zeroed (each of ITS tiles zeroes row reg * tiles_per_region(g) + kt of the next pass's half).  They are: every
+// region but the last is full, so the first sweep zeroes all tiles_per_region(g) rows of it and, for the last, as many as
+// that region has tiles -- one unbroken range [0, (NR - 1) * tpr + tiles(last)) --, and a deeper tile makes neither
+// number larger, so the second sweep's rows are a prefix of that range (sort_wide checks the two numbers).
+inline RegionGeom hyb_geom(const RegionGeom& g, uint32_t es) {
+    RegionGeom d = g;
+    d.tile = (uint32_t)wg_for((int)es) * (uint32_t)hyb_kpt_for((int)es);
+    return d;
+}
+// rows of a sweep's status array in use: up to the last tile of the last region
+inline uint64_t status_rows_used(const RegionGeom& g) {
+    const uint64_t last = g.n - ((uint64_t)(g.num_regions - 1) << g.region_shift);
+    return (uint64_t)(g.num_regions - 1) * tiles_per_region(g) + (last + g.tile - 1) / g.tile;
 }
 // chain prefixes are relative to the region: 30 value bits suffice up to 2^30-element regions
 inline bool status32(const RegionGeom& g) { return g.region_shift <= 30; }

@@ -90,11 +90,13 @@ inline KeyXform make_xform(const rsx_layout* L) {
     return x;
 }
 
-template <int ES, typename S, int XF, bool NEXT, bool MID = false, bool STR = false>
+// KPT: keys per thread of the tile; the geometry has to be one of that tile size (every sweep at kpt_for(ES) but the
+// hybrid's second, at hyb_kpt_for(ES): launch_sweep_n).  The dynamic LDS size and the occupancy cached with it follow it.
+template <int ES, typename S, int XF, bool NEXT, bool MID = false, bool STR = false, int KPT = kpt_for(ES)>
 int launch_sweep_t(rsx_ctx* ctx, const SortRun& run, const SweepPass& pass, const void* src, void* dst, const RegionGeom& g, const rsx_layout* L,
                    uint32_t digit, const unsigned long long* J, unsigned long long* jnext, unsigned long long* jzero,
                    hipStream_t st) {
-    constexpr int KPT = kpt_for(ES);
+    static_assert(KPT == kpt_for(ES) || (STR && !NEXT && !MID), "only the hybrid's sweep that counts nothing has room for a deeper tile");
     if (g.tile != (uint32_t)(wg_for(ES) * KPT)) return fail(ctx, RSX_ERR_INTERNAL, "launch_sweep: geometry of another tile size");
     constexpr int SWEEP_WG = wg_for(ES);
     constexpr int TILE = SWEEP_WG * KPT;
@@ -213,7 +215,13 @@ int launch_sweep_n(rsx_ctx* ctx, const SortRun& run, const SweepPass& pass, cons
     if (run.spec_dev != nullptr) {  // the hybrid's two sweeps: window digits at any bit offset (the STR instantiation)
         if constexpr (ES >= 8 && (XF & 2) == 0) {
             if (jnext) return launch_sweep_t<ES, S, XF, true, false, true>(ctx, run, pass, src, dst, g, L, digit, J, jnext, jzero, st);
-            if constexpr (XF == 0) return launch_sweep_t<ES, S, 0, false, false, true>(ctx, run, pass, src, dst, g, L, digit, J, nullptr, jzero, st);
+            if constexpr (XF == 0) {  // the second sweep: a geometry of the deeper tile (hyb_geom) picks the deeper kernel
+                if constexpr (hyb_kpt_for(ES) != kpt_for(ES)) {
+                    if (g.tile == (uint32_t)(wg_for(ES) * hyb_kpt_for(ES)))
+                        return launch_sweep_t<ES, S, 0, false, false, true, hyb_kpt_for(ES)>(ctx, run, pass, src, dst, g, L, digit, J, nullptr, jzero, st);
+                }
+                return launch_sweep_t<ES, S, 0, false, false, true>(ctx, run, pass, src, dst, g, L, digit, J, nullptr, jzero, st);
+            }
         }
         return fail(ctx, RSX_ERR_INTERNAL, "launch_sweep: no kernel for this pass of the hybrid");
     }
