@@ -201,6 +201,8 @@ enum {
                                  wide-value route, bits 9-23 are 0),
                                  12 set operation (rsx_setop_device: bits 0-7 are then the kernels launched, bits 8-23
                                  are 0),
+                                 13 join (rsx_join_device: bits 0-7 are then the kernels launched -- 0, 2 for the
+                                 count-only form, 3 otherwise -- and bits 8-23 are 0),
                                  bits 28-29 the route of a layout without kernels of its own: 0 direct, 1 packed
                                  re-layout, 2 key-index proxy (bits 0-27 then describe the sort of the re-laid-out
                                  elements / of the proxies) */
@@ -641,6 +643,69 @@ int rsx_ctx_reserve_setop(rsx_ctx *ctx, size_t n_total, uint32_t key_bytes);
 /* Host-only, needs no device: *tile = the merge positions one workgroup takes (256 threads; tile * (key_bytes + 2) + 64
  * bytes of LDS at most, which leaves more than two workgroups per CU; tile <= 4096). */
 int rsx_setop_caps(uint32_t key_bytes, uint32_t *tile);
+
+/* -- sort-merge join of two sorted key arrays --------------------------------- */
+/* Which rows of table A match which rows of table B on a key: the row pairs of the join, in one read of the keys and one
+ * write of the pairs, where rsx_search_sorted_device (the probe) leaves the expansion -- counts, their running sum, a
+ * repeat and the right-hand positions -- to the caller.  The set operations do not cover it: they keep min(m, n) copies
+ * of a key, a join emits m * n pairs.  Let M be the key mapping of rsx_argsort_device for (key_bytes, key_kind),
+ * complemented when `order` is descending, N_a = na, or min(na, *d_a_num) when that pointer is given (one device word,
+ * read on the device), and N_b likewise.  PRECONDITION: a[0 .. N_a) and b[0 .. N_b) are each non-decreasing under M.
+ * For i < N_a let
+ *     lo(i) = #{ j < N_b : M(b[j]) <  M(a[i]) }      hi(i) = #{ j < N_b : M(b[j]) <= M(a[i]) }      m(i) = hi(i) - lo(i),
+ * the number of keys of b that equal a[i] in every bit.  a[i] contributes c(i) rows, row r of them (0 <= r < c(i)) being
+ *     RSX_JOIN_INNER  c(i) = m(i)               (i, lo(i) + r)
+ *     RSX_JOIN_LEFT   c(i) = max(m(i), 1)       (i, lo(i) + r), or (i, NONE) when m(i) == 0
+ *     RSX_JOIN_SEMI   c(i) = m(i) > 0 ? 1 : 0   (i)
+ *     RSX_JOIN_ANTI   c(i) = m(i) == 0 ? 1 : 0  (i)
+ * With S(i) = c(0) + ... + c(i - 1) and T = S(N_a), row t = S(i) + r is
+ *     d_out_a[t] = A(i)        d_out_b[t] = B(lo(i) + r), or NONE
+ * where A(i) = d_a_index ? d_a_index[i] : i and B likewise with d_b_index; NONE has all bits of the index set.  So the rows
+ * are ordered by i, then by position in b: the order of the stable sorts.  *d_out_num = T, the FULL number of rows
+ * whatever `capacity` is; rows t >= min(T, capacity) are not written.
+ *
+ * d_a_index / d_b_index are optional arrays of index_bytes-wide words, na / nb entries, moved bitwise: the permutations a
+ * caller got from sorting unsorted tables, so that the rows come out as positions in the ORIGINAL tables with no gather
+ * afterwards.  Key widths, kinds and alignments are those of rsx_argsort_device (1, 2, 4, 8, 16 bytes); index_bytes is 4
+ * or 8; d_out_num is required and 8-byte aligned (so are d_a_num and d_b_num when given).  For SEMI and ANTI d_out_b and
+ * d_b_index must be NULL.  d_out_a == NULL && d_out_b == NULL with capacity == 0 is the COUNT-ONLY form: it launches the
+ * first two kernels, stores T and writes nothing else, and a caller sizes its outputs from it.  Otherwise d_out_a (and,
+ * for INNER and LEFT, d_out_b) is required.
+ * RSX_ERR_ARG: a bad how, widths, kinds, order, index_bytes or alignments; a NULL input with a nonzero count; d_out_num
+ * NULL; a NULL output outside the count-only form; d_out_b or d_b_index given to SEMI or ANTI; an output range
+ * (min(capacity, bound(how)) rows, or the word of d_out_num) that overlaps an input, an index array, a count word or
+ * another output.  bound(how) is na * nb for INNER, na * max(nb, 1) for LEFT and na for SEMI and ANTI.
+ * RSX_ERR_UNSUPPORTED: na >= 2^32 or nb >= 2^32 (so that T < 2^64 and a position in b fits 32 bits next to NONE); more
+ * than 2^31 write workgroups (min(capacity, bound(how)) / rows of rsx_join_caps).  The write grid is sized from
+ * min(capacity, bound(how)), so a generous capacity costs only workgroups that read T and leave.
+ * na == 0 stores *d_out_num = 0 stream-ordered, launches nothing and looks at no other pointer; nb == 0 goes through the
+ * kernels (LEFT and ANTI emit N_a rows).  Stream-ordered, no synchronisation; the host reads nothing.  If the precondition
+ * does not hold, every read stays inside the inputs and index arrays, every write inside min(capacity, bound(how)) rows,
+ * every d_out_a[t] comes from [0, na) or the index array, every d_out_b[t] from [0, nb), the index array or NONE, and
+ * *d_out_num <= bound(how); nothing else is promised.
+ *
+ * Three launches, no workgroup waits for another one and there are no atomics, so the same input gives the same bytes on
+ * every call: a count launch over tiles of `tile` keys of a (the kernel of rsx_search_sorted_device with a's keys as
+ * ordered needles, then the rows of every key and their sums inside the tile), a one-workgroup scan of the tiles' sums,
+ * and a write launch over tiles of `rows` OUTPUT rows, each row finding its key by a search in the sums -- a workgroup's
+ * work is bounded by its rows, not by any key's fan-out.  Workspace: 12 bytes per key of a and 16 per count tile; it is
+ * made on first use or by rsx_ctx_reserve_join, and under capture without a sufficient reserve the call returns
+ * RSX_ERR_WORKSPACE and enqueues nothing.  RSX_INFO_LAST_PASSES reports path 13. */
+enum { RSX_JOIN_INNER = 0, RSX_JOIN_LEFT = 1, RSX_JOIN_SEMI = 2, RSX_JOIN_ANTI = 3 };
+int rsx_join_device(rsx_ctx *ctx, uint32_t how,
+                    const void *d_a_keys, size_t na, const uint64_t *d_a_num, const void *d_a_index,
+                    const void *d_b_keys, size_t nb, const uint64_t *d_b_num, const void *d_b_index,
+                    uint32_t key_bytes, uint32_t key_kind, int order,
+                    void *d_out_a, void *d_out_b, uint32_t index_bytes, size_t capacity,
+                    uint64_t *d_out_num, void *stream);
+/* Workspace (and the context's first-call set-up) of a join whose left side has up to na keys of this width, so that the
+ * call allocates nothing (stream capture). */
+int rsx_ctx_reserve_join(rsx_ctx *ctx, size_t na, uint32_t key_bytes);
+/* Host-only, needs no device: *tile = the keys of a one count workgroup takes, *window = the keys of b it stages in LDS at
+ * most, *rows = the output rows one write workgroup stores (256 threads each).  Static LDS: the count kernel window *
+ * key_bytes + 8 * key_bytes + 160 bytes at most, the write kernel 8 * rows + 32 bytes at most, the scan kernel 32 bytes;
+ * every one leaves more than two workgroups per CU. */
+int rsx_join_caps(uint32_t key_bytes, uint32_t *tile, uint32_t *window, uint32_t *rows);
 
 /* -- several key columns ----------------------------------------------------- */
 /* Sorting a table by (a, b descending, c): ncols key columns of n keys each, column 0 the MOST significant (the opposite

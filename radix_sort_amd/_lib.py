@@ -26,6 +26,7 @@ SYMBOLS = [
     "rsx_search_sorted_device", "rsx_ctx_reserve_search", "rsx_search_caps",
     "rsx_merge_device", "rsx_ctx_reserve_merge", "rsx_merge_caps",
     "rsx_setop_device", "rsx_ctx_reserve_setop", "rsx_setop_caps",
+    "rsx_join_device", "rsx_ctx_reserve_join", "rsx_join_caps",
 ]
 SEG_CLASSES = 2  # RSX_SEG_CLASSES
 LEX_MAX_COLUMNS = 16  # RSX_LEX_MAX_COLUMNS
@@ -43,6 +44,7 @@ ORDER_ASCENDING, ORDER_DESCENDING = 0, 1
 REDUCE_SUM, REDUCE_MIN, REDUCE_MAX = 0, 1, 2
 SEARCH_PRESORT = 1
 SETOP_UNION, SETOP_INTERSECTION, SETOP_DIFFERENCE, SETOP_SYMMETRIC_DIFFERENCE = 0, 1, 2, 3
+JOIN_INNER, JOIN_LEFT, JOIN_SEMI, JOIN_ANTI = 0, 1, 2, 3
 SHARD_EXCHANGE_FIRST, SHARD_SORT_FIRST = 0, 1
 
 
@@ -166,6 +168,9 @@ def load():
     L.rsx_setop_device.argtypes = [vp, u32, vp, vp, sz, vp, vp, vp, sz, vp, u32, u32, u32, i, vp, vp, vp, u32, vp, vp]
     L.rsx_ctx_reserve_setop.argtypes = [vp, sz, u32]
     L.rsx_setop_caps.argtypes = [u32, pu32]
+    L.rsx_join_device.argtypes = [vp, u32, vp, sz, vp, vp, vp, sz, vp, vp, u32, u32, i, vp, vp, u32, sz, vp, vp]
+    L.rsx_ctx_reserve_join.argtypes = [vp, sz, u32]
+    L.rsx_join_caps.argtypes = [u32, pu32, pu32, pu32]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("rsx_last_error", "rsx_strerror"):

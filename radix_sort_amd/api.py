@@ -355,6 +355,22 @@ class Context:
                                              1 if descending else 0, d_out_keys or None, d_out_values or None, d_out_index or None,
                                              index_bytes, d_out_num or None, stream))
 
+    def reserve_join(self, na: int, key_bytes: int):
+        """rsx_ctx_reserve_join: the context's first-call set-up and the workspace of join_device with up to na keys of this
+        width on its left side, so that the call allocates nothing and can be captured."""
+        self._check(self._L.rsx_ctx_reserve_join(self._h, na, key_bytes))
+
+    def join_device(self, how: int, d_a_keys: int, na: int, d_a_num: int, d_a_index: int, d_b_keys: int, nb: int, d_b_num: int,
+                    d_b_index: int, key_bytes: int, key_kind: int, d_out_a: int, d_out_b: int, index_bytes: int, capacity: int,
+                    d_out_num: int, descending: bool = False, stream: int = 0):
+        """rsx_join_device: the inner (how 0), left (1), semi (2) or anti (3) join of two sorted key arrays -- for every row
+        its position in a (d_out_a) and in b (d_out_b; all ones: none), or the words of d_a_index / d_b_index at those
+        positions, up to `capacity` rows, and the FULL number of rows into d_out_num.  Both outputs 0 with capacity 0: the
+        count alone.  d_a_num / d_b_num (0: none) are device words that bound the inputs, which are only read."""
+        self._check(self._L.rsx_join_device(self._h, how, d_a_keys or None, na, d_a_num or None, d_a_index or None, d_b_keys or None, nb,
+                                            d_b_num or None, d_b_index or None, key_bytes, key_kind, 1 if descending else 0,
+                                            d_out_a or None, d_out_b or None, index_bytes, capacity, d_out_num or None, stream))
+
     def reserve_reduce(self, n: int, key_bytes: int, value_bytes: int):
         """rsx_ctx_reserve_reduce: the context's first-call set-up and the workspace of reduce_by_key_device on up to n keys
         of these widths, so that the call allocates nothing and can be captured."""
@@ -1493,6 +1509,152 @@ def radix_set_op_pairs(a_keys, a_values, b_keys, b_values, op: str, descending: 
                        b_num.data_ptr() if b_num is not None else 0, kb, kind, va, out_keys.data_ptr(), out_values.data_ptr(), 0, 8,
                        num.data_ptr(), descending, stream)
     return SetPairsResult(out_keys, out_values, num)
+
+
+def join_caps(key_bytes: int):
+    """rsx_join_caps -> (tile, window, rows): the keys of `a` one count workgroup of the join takes, the keys of `b` it
+    stages in LDS at most, and the output rows one write workgroup stores.  Needs no device."""
+    L = _lib.load()
+    tile, window, rows = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+    _check_rc(L, L.rsx_join_caps(key_bytes, ctypes.byref(tile), ctypes.byref(window), ctypes.byref(rows)))
+    return int(tile.value), int(window.value), int(rows.value)
+
+
+JoinResult = namedtuple("JoinResult", ["left", "right", "num"])
+_JOINS = {"inner": _lib.JOIN_INNER, "left": _lib.JOIN_LEFT, "semi": _lib.JOIN_SEMI, "anti": _lib.JOIN_ANTI}
+
+
+def _join_bound(how: int, na: int, nb: int) -> int:
+    """The most rows a join can have."""
+    return na * nb if how == _lib.JOIN_INNER else na * max(nb, 1) if how == _lib.JOIN_LEFT else na
+
+
+def _join_index(index, keys, n: int, index_dtype, what: str):
+    """a_index= / b_index= of radix_join: None, or one word of the index dtype per key, on the keys' device."""
+    import torch
+    if index is None:
+        return
+    if not isinstance(index, torch.Tensor) or index.dtype != index_dtype:
+        raise TypeError(f"{what} must be a torch tensor of the index dtype {index_dtype}")
+    if tuple(index.shape) != (n,) or not index.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous 1-D tensor with one entry per key ({n})")
+    if index.device != keys.device:
+        raise ValueError(f"the keys and {what} must live on the same device")
+
+
+def radix_join(a, b, how: str = "inner", assume_sorted: bool = False, capacity: Optional[int] = None, descending: bool = False,
+               index_dtype=None, a_num=None, b_num=None, a_index=None, b_index=None, out=None, ctx: Optional[Context] = None,
+               key_kind: Optional[int] = None):
+    """The join of two key tensors (rsx_join_device): which rows of `a` match which rows of `b`.  Returns
+    JoinResult(left, right, num): for t < num, (left[t], right[t]) is one pair of positions with a[left[t]] equal to
+    b[right[t]] in every bit.  A key that occurs m times in `a` and n times in `b` gives m * n pairs.
+
+    how    "inner": the matching pairs.  "left": those, and one row (i, -1) for every a[i] without a match.  "semi": the
+           positions of the a[i] with a match, once each.  "anti": those without.  For "semi" and "anti" `right` is None.
+    num    a 0-d int64 device tensor: the FULL number of rows, whatever the capacity is.
+    index_dtype  torch.int64 (default) or torch.int32, the dtype of left and right (taken from `out` when that is given).
+
+    a, b: contiguous 1-D GPU tensors of one dtype radix_sort knows, or (n, 16) uint8 128-bit keys (key_kind=), fewer than
+    2^32 keys each.  Neither is modified.  Keys match by bit pattern: -0.0 and +0.0 do not, a NaN matches the same NaN.
+
+    assume_sorted=False (the default): both sides are sorted with their positions by radix_sort_pairs on copies, and the
+    positions go into the join, so that left and right index the tensors as given: the result is exactly (pa[L], pb[R]) with
+    pa = radix_argsort(a), pb = radix_argsort(b) and (L, R) the join of a[pa] and b[pb].  Rows are ordered by key, then by
+    position in a, then by position in b.  a_num, b_num, a_index and b_index raise ValueError here.
+    assume_sorted=True: a and b are each in the order radix_sort / radix_sort_pairs(descending=descending) / radix_group
+    leave, and are used as they are.  a_num, b_num: one-element int64 device tensors such as radix_group(...).num; only
+    the first min(len(a), a_num) keys of `a` count (`b` likewise), read on the device.  a_index, b_index: 1-D tensors of the
+    index dtype, one entry per key, whose entries are returned in place of the positions.  If an input is not sorted the
+    result is unspecified but nothing outside the outputs is written.
+
+    capacity=int, or out=(left, right) (for "semi" / "anti" out=left or (left, None)) of one length and dtype: ONE call,
+    never synchronised; rows beyond the capacity are dropped, and num tells.
+    capacity=None without out: the count-only call, ONE host read of num (this synchronises the stream), tensors of exactly
+    num rows, then the full call -- the keys are searched twice on this route.
+
+    Enqueued on the current stream."""
+    import torch
+    if how not in _JOINS:
+        raise ValueError(f'how must be "inner", "left", "semi" or "anti", not {how!r}')
+    code = _JOINS[how]
+    pairs = code in (_lib.JOIN_INNER, _lib.JOIN_LEFT)
+    kb, kind, na, nb = _merge_keys(a, b, key_kind)
+    if not assume_sorted and any(x is not None for x in (a_num, b_num, a_index, b_index)):
+        raise ValueError("a_num, b_num, a_index and b_index go with assume_sorted=True")
+    out_left = out_right = None
+    if out is not None:
+        if isinstance(out, torch.Tensor):
+            out = (out, None)
+        if not isinstance(out, (tuple, list)) or len(out) != 2:
+            raise TypeError("out must be a pair (left, right)")
+        out_left, out_right = out
+        if not pairs and out_right is not None:
+            raise ValueError(f'a "{how}" join has no right-hand output: out must be left or (left, None)')
+        if pairs and out_right is None:
+            raise TypeError(f'out must be a pair (left, right) of tensors for a "{how}" join')
+        rows = out_left.shape[0] if isinstance(out_left, torch.Tensor) and out_left.dim() == 1 else 0
+        for o in (out_left, out_right) if pairs else (out_left,):
+            _index_out(o, (rows,), "each other")
+            if o.device != a.device:
+                raise ValueError("the keys and out must live on the same device")
+        if pairs and out_left.dtype != out_right.dtype:
+            raise TypeError("both tensors of out must have one dtype")
+        if capacity is not None and capacity != rows:
+            raise ValueError(f"capacity ({capacity}) and the length of out ({rows}) disagree")
+        capacity = rows
+        index_dtype = out_left.dtype
+    index_dtype = _index_dtype(index_dtype)
+    if capacity is not None and (not isinstance(capacity, int) or capacity < 0):
+        raise ValueError("capacity must be None or a non-negative int")
+    if na >= 1 << 32 or nb >= 1 << 32:
+        raise ValueError("radix_join takes fewer than 2^32 keys on each side (a position in b, int32 or int64, is kept in 32 bits)")
+    _join_index(a_index, a, na, index_dtype, "a_index")
+    _join_index(b_index, a, nb, index_dtype, "b_index")
+    if not pairs and b_index is not None:
+        raise ValueError(f'a "{how}" join has no right-hand output: b_index must be None')
+    _set_num(a_num, a, "a_num")
+    _set_num(b_num, a, "b_num")
+    _pairs_device(a, None, "")
+    dev = a.device
+    num = torch.empty((), dtype=torch.int64, device=dev)
+
+    def result(rows):
+        left = out_left if out_left is not None else torch.empty(rows, dtype=index_dtype, device=dev)
+        right = (out_right if out_right is not None else torch.empty(rows, dtype=index_dtype, device=dev)) if pairs else None
+        return left, right
+
+    if na == 0:  # no row (and no address to hand to the C call)
+        num.zero_()
+        return JoinResult(*result(capacity or 0), num)
+    if not assume_sorted:  # the keys of both sides sorted on copies, their positions with them
+        def sorted_with_positions(keys, n):
+            k = keys.clone()
+            p = torch.arange(n, dtype=index_dtype, device=dev) if n <= 1 << 31 else torch.arange(n, dtype=torch.int64, device=dev).to(index_dtype)
+            radix_sort_pairs(k, p, descending=descending, ctx=ctx, key_kind=key_kind)
+            return k, p
+
+        a, a_index = sorted_with_positions(a, na)
+        b, b_index = sorted_with_positions(b, nb)
+        if not pairs:
+            b_index = None
+    ib = 8 if index_dtype == torch.int64 else 4
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else 0  # noqa: E731
+
+    def call(c, stream, left, right, rows):
+        c.join_device(code, a.data_ptr(), na, ptr(a_num), ptr(a_index), ptr(b), nb, ptr(b_num), ptr(b_index), kb, kind, ptr(left), ptr(right),
+                      ib, rows, num.data_ptr(), descending, stream)
+
+    with _on_device(a, ctx) as (c, stream):
+        counted = capacity is None
+        if counted:  # the count alone, the one host read, then the exact allocation
+            call(c, stream, None, None, 0)
+            capacity = min(int(num), _join_bound(code, na, nb))
+        left, right = result(capacity)
+        if capacity > 0:
+            call(c, stream, left, right, capacity)
+        elif not counted:  # (empty outputs have no address: the count alone)
+            call(c, stream, None, None, 0)
+    return JoinResult(left, right, num)
 
 
 def _segments_common(keys, offsets, max_seg_len):

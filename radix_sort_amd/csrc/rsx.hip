@@ -1043,6 +1043,7 @@ int rsx_ctx_get_info(rsx_ctx* ctx, int what, uint64_t* out) try {
                     return RSX_OK;
                 case PATH_SEARCH:  // bits 0-7 the kernels launched after any sort, bit 8 the needles were sorted first
                 case PATH_SETOP:   // bits 0-7 the kernels launched
+                case PATH_JOIN:    // bits 0-7 the kernels launched
                 case PATH_MERGE:   // bits 0-7 the kernels launched, bit 8 the wide-value route
                     *out = (uint64_t)(ctx->last_sort_passes & 0x1FFu) | (uint64_t)ctx->last_path << 24;
                     return RSX_OK;
@@ -1990,6 +1991,146 @@ int rsx_ctx_reserve_setop(rsx_ctx* ctx, size_t n_total, uint32_t key_bytes) try 
 int rsx_setop_caps(uint32_t key_bytes, uint32_t* tile) {
     if (!tile || !key_widths_ok(key_bytes, RSX_KEY_UNSIGNED)) return RSX_ERR_ARG;
     *tile = setop_tile_elems(key_bytes);
+    return RSX_OK;
+}
+
+// ---- sort-merge join of two sorted key arrays (rsx_join_kernels.hpp, include/rsx.h) ----
+namespace {
+// The workspace of one rsx_join_device call: per key of a its lower bound in b and the rows in front of it in its count
+// tile; per count tile its rows and (one word more) the rows in front of it.
+struct JoinPlan {
+    Carve ws;
+    size_t lo_off;     // ws_lo [na] u32
+    size_t local_off;  // ws_local [na] u64
+    size_t total_off;  // tile_total [tiles] u64
+    size_t base_off;   // tile_base [tiles + 1] u64
+};
+JoinPlan join_plan(size_t na) {
+    JoinPlan P{};
+    const uint32_t tile = join_tile_elems();
+    const size_t tiles = (na + tile - 1) / tile;
+    P.lo_off = P.ws.take(na * sizeof(uint32_t));
+    P.local_off = P.ws.take(na * sizeof(uint64_t));
+    P.total_off = P.ws.take(tiles * sizeof(uint64_t));
+    P.base_off = P.ws.take((tiles + 1) * sizeof(uint64_t));
+    return P;
+}
+// the most rows a join of na and nb keys (each below 2^32: no overflow) can have
+uint64_t join_bound(uint32_t how, uint64_t na, uint64_t nb) {
+    switch (how) {
+        case RSX_JOIN_INNER: return na * nb;
+        case RSX_JOIN_LEFT: return na * (nb ? nb : 1u);
+        default: return na;
+    }
+}
+// rows * width bytes at p for ranges_overlap; a product that does not fit ends with the address space
+uint64_t join_bytes(const void* p, uint64_t rows, uint32_t width) {
+    const uint64_t room = ~(uint64_t)0 - reinterpret_cast<uintptr_t>(p);
+    return rows > room / width ? room : rows * width;
+}
+}  // namespace
+
+int rsx_join_device(rsx_ctx* ctx, uint32_t how, const void* d_a_keys, size_t na, const uint64_t* d_a_num, const void* d_a_index, const void* d_b_keys,
+                    size_t nb, const uint64_t* d_b_num, const void* d_b_index, uint32_t key_bytes, uint32_t key_kind, int order, void* d_out_a,
+                    void* d_out_b, uint32_t index_bytes, size_t capacity, uint64_t* d_out_num, void* stream) try {
+    if (!ctx) return RSX_ERR_ARG;
+    if (how > RSX_JOIN_ANTI) return fail(ctx, RSX_ERR_ARG, "invalid kind of join");
+    if (!key_widths_ok(key_bytes, key_kind)) return fail(ctx, RSX_ERR_ARG, "invalid key width or kind");
+    uint32_t desc = 0;
+    if (int rc = order_desc(ctx, order, &desc)) return rc;
+    if (int rc = check_index_bytes(ctx, index_bytes)) return rc;
+    if (!d_out_num) return fail(ctx, RSX_ERR_ARG, "d_out_num is null");
+    if (!aligned(d_out_num, 8) || !aligned(d_a_num, 8) || !aligned(d_b_num, 8)) return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
+    if ((uint64_t)na >= (1ull << 32) || (uint64_t)nb >= (1ull << 32)) return fail(ctx, RSX_ERR_UNSUPPORTED, "2^32 or more keys on one side");
+    Entry held(ctx, stream);
+    if (!held.ok) return no_device(ctx);
+    const hipStream_t st = held.st;
+    if (na == 0) return no_group(ctx, PATH_JOIN, d_out_num, nullptr, st);  // no row: no other pointer is looked at
+    const bool pairs = how == RSX_JOIN_INNER || how == RSX_JOIN_LEFT;
+    if (!pairs && (d_out_b || d_b_index)) return fail(ctx, RSX_ERR_ARG, "a semi or anti join has no right-hand output: d_out_b and d_b_index must be null");
+    const bool count_only = !d_out_a && !d_out_b && capacity == 0;
+    if (!count_only && (!d_out_a || (pairs && !d_out_b))) return fail(ctx, RSX_ERR_ARG, "null output (only the count-only form, both outputs null and capacity 0, has none)");
+    if (!d_a_keys || (nb > 0 && !d_b_keys)) return fail(ctx, RSX_ERR_ARG, "null device pointer");
+    if (!aligned(d_a_keys, key_bytes) || !aligned(d_b_keys, key_bytes) || !aligned(d_a_index, index_bytes) || !aligned(d_b_index, index_bytes) ||
+        !aligned(d_out_a, index_bytes) || !aligned(d_out_b, index_bytes))
+        return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
+    const uint64_t bound = join_bound(how, na, nb);
+    const uint64_t rows = (uint64_t)capacity < bound ? (uint64_t)capacity : bound;  // the rows the call may write
+    const uint64_t per = join_rows();
+    const uint64_t groups = rows / per + (rows % per ? 1u : 0u);
+    if (groups > (1ull << 31)) return fail(ctx, RSX_ERR_UNSUPPORTED, "too many rows for one launch: lower the capacity");
+    {  // no output may share a byte with an input or with another output
+        const void* in_p[6] = {d_a_keys, d_b_keys, d_a_index, d_b_index, d_a_num, d_b_num};
+        const uint64_t in_b[6] = {(uint64_t)na * key_bytes, (uint64_t)nb * key_bytes, (uint64_t)na * index_bytes, (uint64_t)nb * index_bytes, 8, 8};
+        const void* out_p[3] = {d_out_a, d_out_b, d_out_num};
+        const uint64_t out_b[3] = {join_bytes(d_out_a, rows, index_bytes), join_bytes(d_out_b, rows, index_bytes), 8};
+        for (int o = 0; o < 3; ++o) {
+            for (int i = 0; i < 6; ++i)
+                if (ranges_overlap(out_p[o], out_b[o], in_p[i], in_b[i])) return fail(ctx, RSX_ERR_ARG, "an output overlaps an input");
+            for (int p = o + 1; p < 3; ++p)
+                if (ranges_overlap(out_p[o], out_b[o], out_p[p], out_b[p])) return fail(ctx, RSX_ERR_ARG, "two outputs overlap");
+        }
+    }
+    int rc = pending_error(ctx);
+    if (rc) return rc;
+    const JoinPlan P = join_plan(na);
+    rc = ensure_aux(ctx, st);
+    if (rc) return rc;
+    rc = ensure_any(ctx, P.ws.bytes, st);
+    if (rc) return rc;
+    Enqueue enq(ctx, st);  // the workspace arrays belong to this call from the first launch on
+    char* w = reinterpret_cast<char*>(ctx->any_buf);
+    JoinCall c{};
+    c.how = how;
+    c.a_keys = d_a_keys;
+    c.na = na;
+    c.a_num = d_a_num;
+    c.a_index = d_a_index;
+    c.b_keys = d_b_keys;
+    c.nb = nb;
+    c.b_num = d_b_num;
+    c.b_index = d_b_index;
+    c.kb = key_bytes;
+    c.kind = key_kind;
+    c.desc = desc;
+    c.ib = index_bytes;
+    c.ws_lo = reinterpret_cast<uint32_t*>(w + P.lo_off);
+    c.ws_local = reinterpret_cast<uint64_t*>(w + P.local_off);
+    c.tile_total = reinterpret_cast<uint64_t*>(w + P.total_off);
+    c.tile_base = reinterpret_cast<uint64_t*>(w + P.base_off);
+    c.write = !count_only;
+    c.write_groups = groups ? groups : 1u;  // (no row can be written: one workgroup that reads the count and leaves)
+    c.out_a = d_out_a;
+    c.out_b = d_out_b;
+    c.capacity = (size_t)rows;
+    c.out_num = d_out_num;
+    uint32_t launched = 0;
+    rc = launch_join(ctx, c, &launched, st);
+    if (rc) return rc;
+    note_path(ctx, PATH_JOIN, launched);
+    return RSX_OK;
+} catch (...) {
+    return RSX_ERR_HIP;
+}
+
+int rsx_ctx_reserve_join(rsx_ctx* ctx, size_t na, uint32_t key_bytes) try {
+    if (!ctx) return RSX_ERR_ARG;
+    if (!key_widths_ok(key_bytes, RSX_KEY_UNSIGNED)) return fail(ctx, RSX_ERR_ARG, "invalid key width");
+    if ((uint64_t)na >= (1ull << 32)) return fail(ctx, RSX_ERR_UNSUPPORTED, "2^32 or more keys on one side");
+    Entry held(ctx);
+    if (!held.ok) return no_device(ctx);
+    int rc = ensure_aux(ctx, nullptr);
+    if (rc) return rc;
+    return ensure_any(ctx, join_plan(na).ws.bytes, nullptr);
+} catch (...) {
+    return RSX_ERR_NOMEM;
+}
+
+int rsx_join_caps(uint32_t key_bytes, uint32_t* tile, uint32_t* window, uint32_t* rows) {
+    if (!tile || !window || !rows || !key_widths_ok(key_bytes, RSX_KEY_UNSIGNED)) return RSX_ERR_ARG;
+    *tile = join_tile_elems();
+    *window = search_window_elems(key_bytes);
+    *rows = join_rows();
     return RSX_OK;
 }
 

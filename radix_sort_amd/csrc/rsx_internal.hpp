@@ -5,7 +5,7 @@
 //   rsx_pairs.hip   the join and split kernels of the key / value calls
 //   rsx_unique.hip  the run kernels of rsx_unique_device
 //   rsx_reduce.hip  those of rsx_reduce_by_key_device
-//   rsx_search.hip  the kernel of rsx_search_sorted_device
+//   rsx_search.hip  the kernel of rsx_search_sorted_device and, built from its functions, those of rsx_join_device
 //   rsx_merge.hip   the kernels of rsx_merge_device
 //   rsx_setops.hip  the kernel of rsx_setop_device
 //   rsx_lex.hip     the join of several key columns (rsx_lexsort_device, rsx_sort_columns_device)
@@ -81,6 +81,7 @@ enum : uint32_t {
     PATH_SEARCH = 10,
     PATH_MERGE = 11,
     PATH_SETOP = 12,
+    PATH_JOIN = 13,
 };
 
 // option bits (rsx_ctx_set_option): alternative kernel paths, all bit-exact
@@ -605,6 +606,34 @@ struct SearchCall {
 int launch_search(rsx_ctx* ctx, const SearchCall& call, uint32_t* launched, hipStream_t st);
 uint32_t search_tile_elems(uint32_t kb);     // needles per workgroup
 uint32_t search_window_elems(uint32_t kb);  // haystack keys a workgroup stages in LDS at most
+
+// What one rsx_join_device call asks of the join kernels (rsx_search.hip, rsx_join_kernels.hpp).
+struct JoinCall {
+    uint32_t how;                // RSX_JOIN_*
+    const void* a_keys;          // na keys of kb bytes, sorted by mapped key in the call's order; b likewise
+    size_t na;                   // 1 .. 2^32 - 1
+    const uint64_t* a_num;       // null, or one device word: only the first min(na, *a_num) keys count; b_num likewise
+    const void* a_index;         // null, or na words of ib bytes to emit in place of positions in a; b_index likewise
+    const void* b_keys;
+    size_t nb;                   // 0 .. 2^32 - 1
+    const uint64_t* b_num;
+    const void* b_index;
+    uint32_t kb, kind, desc;
+    uint32_t ib;                 // bytes of a word of out_a / out_b / a_index / b_index
+    uint32_t* ws_lo;             // per key of a: its lower bound in b (or all ones), ...
+    uint64_t* ws_local;          // ... and the rows of the keys in front of it in its count tile
+    uint64_t* tile_total;        // per count tile of join_tile_elems: its rows, and ...
+    uint64_t* tile_base;         // ... [tiles + 1] those in front of it; the last word is the number of rows
+    bool write;                  // false: the count-only form, two launches
+    uint64_t write_groups;       // workgroups of the write launch (1 .. 2^31)
+    void* out_a;
+    void* out_b;                 // null: semi and anti joins
+    size_t capacity;             // rows of out_a / out_b
+    uint64_t* out_num;           // the number of rows, whatever the capacity
+};
+int launch_join(rsx_ctx* ctx, const JoinCall& call, uint32_t* launched, hipStream_t st);
+uint32_t join_tile_elems();  // keys of a per count workgroup
+uint32_t join_rows();        // output rows per write workgroup
 
 // What one rsx_merge_device call asks of the merge kernel (rsx_merge.hip, rsx_merge_kernels.hpp).
 struct MergeCall {

@@ -20,6 +20,8 @@
 //     rsx::merge_pairs(const K* d_a_keys, const V* d_a_values, size_t na, const K* d_b_keys, const V* d_b_values, size_t nb, K* keys, V* values[, I* index], bool descending, hipStream_t)
 //     rsx::set_op(int op, const K* d_a_keys, size_t na, const K* d_b_keys, size_t nb, K* d_out_keys, uint64_t* d_out_num[, I* index], bool descending, const uint64_t* d_a_num, const uint64_t* d_b_num, hipStream_t)   // RSX_SETOP_*
 //     rsx::set_op_pairs(int op, const K* d_a_keys, const V* d_a_values, size_t na, const K* d_b_keys, const V* d_b_values, size_t nb, K* keys, V* values, uint64_t* d_out_num, bool descending, const uint64_t* d_a_num, const uint64_t* d_b_num, hipStream_t)
+//     rsx::join(int how, const K* d_a_keys, size_t na, const K* d_b_keys, size_t nb, I* d_out_a, I* d_out_b, size_t capacity, uint64_t* d_out_num, bool descending, const uint64_t* d_a_num, const uint64_t* d_b_num, const I* d_a_index, const I* d_b_index, hipStream_t)   // RSX_JOIN_*
+//     rsx::join_count(int how, const K* d_a_keys, size_t na, const K* d_b_keys, size_t nb, uint64_t* d_out_num, bool descending, const uint64_t* d_a_num, const uint64_t* d_b_num, hipStream_t)
 //     rsx::lexsort({rsx::key_column(d_a), rsx::key_column(d_b, true)}, I* d_index, size_t n, hipStream_t)   // several key columns
 //     rsx::sort_columns({rsx::key_column(d_a), rsx::key_column(d_b, true)}, V* d_values, size_t n, hipStream_t)
 // Errors: the reference panics (mod.rs:68,106); here std::runtime_error is thrown.
@@ -348,6 +350,34 @@ void set_op_pairs(int op, const K* d_a_keys, const V* d_a_values, size_t na, con
                                L.key_kind, (uint32_t)sizeof(V), descending ? RSX_ORDER_DESCENDING : RSX_ORDER_ASCENDING, d_out_keys,
                                d_out_values, nullptr, 8u, d_out_num, stream),
               "rsx_setop_device");
+}
+
+// The join of two key arrays that are each sorted in that order (rsx_join_device; how: RSX_JOIN_INNER, _LEFT, _SEMI, _ANTI):
+// row t is a pair of positions (d_out_a[t], d_out_b[t]) of equal keys, ordered by position in a, then in b; a left join
+// writes all ones into d_out_b for a key of a without a match; semi and anti joins take d_out_b == nullptr.  The FULL number
+// of rows goes into the device word d_out_num whatever `capacity` (the rows of d_out_a / d_out_b) is, and rows from
+// min(*d_out_num, capacity) on are not written.  d_a_num / d_b_num, when given, are device words such as the d_out_num of
+// unique: only the first min(na, *d_a_num) keys of a count.  d_a_index / d_b_index, when given, hold one word per key that
+// is written in place of the position (the permutations of two argsorts: rows of the unsorted tables).  join_count stores
+// the number of rows alone, for a caller that sizes its outputs from it.  Fewer than 2^32 keys on each side; the inputs are
+// only read and no output may overlap them; rsx_ctx_reserve_join before a stream capture.  Stream-ordered, never
+// synchronised.
+template <typename K, typename I>
+void join(int how, const K* d_a_keys, size_t na, const K* d_b_keys, size_t nb, I* d_out_a, I* d_out_b, size_t capacity, uint64_t* d_out_num,
+          bool descending = false, const uint64_t* d_a_num = nullptr, const uint64_t* d_b_num = nullptr, const I* d_a_index = nullptr,
+          const I* d_b_index = nullptr, void* stream = nullptr, Context& ctx = default_context()) {
+    static_assert(std::is_integral<I>::value && (sizeof(I) == 4 || sizeof(I) == 8), "indices are 4- or 8-byte integers");
+    const rsx_layout L = RadixDigits<K>::layout();
+    if (L.key_offset != 0 || L.key_bytes != L.elem_bytes) throw std::invalid_argument("join: the key type must be its own key");
+    ctx.check(rsx_join_device(ctx.get(), (uint32_t)how, d_a_keys, na, d_a_num, d_a_index, d_b_keys, nb, d_b_num, d_b_index, L.key_bytes, L.key_kind,
+                              descending ? RSX_ORDER_DESCENDING : RSX_ORDER_ASCENDING, d_out_a, d_out_b, (uint32_t)sizeof(I), capacity, d_out_num,
+                              stream),
+              "rsx_join_device");
+}
+template <typename K>
+void join_count(int how, const K* d_a_keys, size_t na, const K* d_b_keys, size_t nb, uint64_t* d_out_num, bool descending = false,
+                const uint64_t* d_a_num = nullptr, const uint64_t* d_b_num = nullptr, void* stream = nullptr, Context& ctx = default_context()) {
+    join<K, uint64_t>(how, d_a_keys, na, d_b_keys, nb, nullptr, nullptr, 0, d_out_num, descending, d_a_num, d_b_num, nullptr, nullptr, stream, ctx);
 }
 
 // Several key columns (rsx_lexsort_device, rsx_sort_columns_device): rows sorted by (column 0, column 1, ...), column 0

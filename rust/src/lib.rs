@@ -94,6 +94,17 @@ extern "C" {
                             d_out_num: *mut u64, stream: *mut c_void) -> c_int;
     pub fn rsx_ctx_reserve_setop(ctx: *mut RsxCtx, n_total: usize, key_bytes: u32) -> c_int;
     pub fn rsx_setop_caps(key_bytes: u32, tile: *mut u32) -> c_int;
+    // sort-merge join of two sorted key arrays (include/rsx.h, "sort-merge join of two sorted key arrays"): how is
+    // RSX_JOIN_INNER (0), _LEFT (1), _SEMI (2), _ANTI (3); d_a_num / d_b_num are null or one device word that bounds the
+    // input, d_a_index / d_b_index null or the words to emit in place of positions; up to `capacity` rows are written and
+    // the full number of rows goes to d_out_num (both outputs null with capacity 0: the count alone)
+    pub fn rsx_join_device(ctx: *mut RsxCtx, how: u32, d_a_keys: *const c_void, na: usize, d_a_num: *const u64,
+                           d_a_index: *const c_void, d_b_keys: *const c_void, nb: usize, d_b_num: *const u64,
+                           d_b_index: *const c_void, key_bytes: u32, key_kind: u32, order: c_int, d_out_a: *mut c_void,
+                           d_out_b: *mut c_void, index_bytes: u32, capacity: usize, d_out_num: *mut u64,
+                           stream: *mut c_void) -> c_int;
+    pub fn rsx_ctx_reserve_join(ctx: *mut RsxCtx, na: usize, key_bytes: u32) -> c_int;
+    pub fn rsx_join_caps(key_bytes: u32, tile: *mut u32, window: *mut u32, rows: *mut u32) -> c_int;
     pub fn rsx_sort_sharded(ctxs: *const *mut RsxCtx, ndev: u32, d_slices: *const *mut c_void,
                             d_tmps: *const *mut c_void, n_per_dev: *const usize,
                             layout: *const RsxLayout) -> c_int;
