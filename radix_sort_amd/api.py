@@ -1270,6 +1270,61 @@ def _merge_out(out, like, n: int, what: str):
         raise ValueError(f"the keys and out ({what}) must live on the same device")
 
 
+def _merge_out_index(out, return_index: bool, index_dtype, like, rows: int, n: int, what: str):
+    """out= and index_dtype= of radix_merge / radix_set_op -> (keys, index) of `rows` rows: the tensors of `out` checked,
+    a missing one made; index is None without return_index.  n: the keys of both inputs, which an index has to count."""
+    import torch
+    out_keys, out_index = out, None
+    if return_index and out is not None:
+        if not isinstance(out, (tuple, list)) or len(out) != 2:
+            raise TypeError("out must be a pair (keys, index) with return_index=True")
+        out_keys, out_index = out
+    if out_keys is not None:
+        _merge_out(out_keys, like, rows, "keys")
+    if out_index is not None:
+        _index_out(out_index, (rows,), what)
+        if out_index.device != like.device:
+            raise ValueError("the keys and out (index) must live on the same device")
+        index_dtype = out_index.dtype
+    index_dtype = _index_dtype(index_dtype)
+    if return_index and index_dtype == torch.int32 and n > 1 << 32:
+        raise ValueError("more than 2^32 keys need int64 indices")
+    if out_keys is None:
+        out_keys = torch.empty((rows,) + tuple(like.shape[1:]), dtype=like.dtype, device=like.device)
+    if return_index and out_index is None:
+        out_index = torch.empty(rows, dtype=index_dtype, device=like.device)
+    return out_keys, out_index
+
+
+def _merge_out_values(out, keys, values, rows: int):
+    """out= of radix_merge_pairs / radix_set_op_pairs -> (keys, values) of `rows` rows: the pair checked, or made."""
+    import torch
+    if out is None:
+        return (torch.empty((rows,) + tuple(keys.shape[1:]), dtype=keys.dtype, device=keys.device),
+                torch.empty((rows,) + tuple(values.shape[1:]), dtype=values.dtype, device=keys.device))
+    if not isinstance(out, (tuple, list)) or len(out) != 2:
+        raise TypeError("out must be a pair (keys, values)")
+    _merge_out(out[0], keys, rows, "keys")
+    _merge_out(out[1], values, rows, "values")
+    return tuple(out)
+
+
+def _merge_values(keys, a_values, na: int, b_values, nb: int) -> int:
+    """Bytes of one value of radix_merge_pairs / radix_set_op_pairs: the two value tensors checked against their keys and
+    against each other.  b_values None (where the caller lets it be absent): a_values alone."""
+    va = _value_bytes(a_values, (na,), "a_keys")
+    if b_values is not None:
+        vb = _value_bytes(b_values, (nb,), "b_keys")
+        if a_values.dtype != b_values.dtype:
+            raise TypeError(f"both value tensors must have one dtype, not {a_values.dtype} and {b_values.dtype}")
+        if tuple(a_values.shape[1:]) != tuple(b_values.shape[1:]) or va != vb:
+            raise ValueError(f"both value tensors must have the same trailing shape, not {tuple(a_values.shape)} and {tuple(b_values.shape)}")
+    for v, what in ((a_values, "a_values"), (b_values, "b_values")):
+        if v is not None and v.device != keys.device:
+            raise ValueError(f"keys and {what} must live on the same device")
+    return va
+
+
 def radix_merge(a, b, descending: bool = False, return_index: bool = False, index_dtype=None, out=None,
                 ctx: Optional[Context] = None, key_kind: Optional[int] = None):
     """The stable merge of two sorted key tensors (rsx_merge_device): what `torch.sort(torch.cat((a, b)), stable=True,
@@ -1286,29 +1341,10 @@ def radix_merge(a, b, descending: bool = False, return_index: bool = False, inde
 
     If an input is not sorted the result is unspecified but nothing outside the outputs is written.  Enqueued on the
     current stream, not synchronised."""
-    import torch
     kb, kind, na, nb = _merge_keys(a, b, key_kind)
     n = na + nb
-    out_keys, out_index = out, None
-    if return_index and out is not None:
-        if not isinstance(out, (tuple, list)) or len(out) != 2:
-            raise TypeError("out must be a pair (keys, index) with return_index=True")
-        out_keys, out_index = out
-    if out_keys is not None:
-        _merge_out(out_keys, a, n, "keys")
-    if out_index is not None:
-        _index_out(out_index, (n,), "the merged keys")
-        if out_index.device != a.device:
-            raise ValueError("the keys and out (index) must live on the same device")
-        index_dtype = out_index.dtype
-    index_dtype = _index_dtype(index_dtype)
+    out_keys, out_index = _merge_out_index(out, return_index, index_dtype, a, n, n, "the merged keys")
     _pairs_device(a, None, "")
-    if return_index and index_dtype == torch.int32 and n > 1 << 32:
-        raise ValueError("more than 2^32 keys need int64 indices")
-    if out_keys is None:
-        out_keys = torch.empty((n,) + tuple(a.shape[1:]), dtype=a.dtype, device=a.device)
-    if return_index and out_index is None:
-        out_index = torch.empty(n, dtype=index_dtype, device=a.device)
     if n > 0:
         with _on_device(a, ctx) as (c, stream):
             c.merge_device(a.data_ptr() if na else 0, 0, na, b.data_ptr() if nb else 0, 0, nb, kb, kind, 0, out_keys.data_ptr(), 0,
@@ -1329,31 +1365,13 @@ def radix_merge_pairs(a_keys, a_values, b_keys, b_values, descending: bool = Fal
     out: a pair (keys, values) to fill, shaped like the concatenations; it must not overlap an input.
 
     Enqueued on the current stream, not synchronised."""
-    import torch
     kb, kind, na, nb = _merge_keys(a_keys, b_keys, key_kind)
     n = na + nb
-    va = _value_bytes(a_values, (na,), "a_keys")
-    vb = _value_bytes(b_values, (nb,), "b_keys")
     if a_values is None or b_values is None:
         raise TypeError("a_values and b_values must be torch tensors (keys alone: radix_merge)")
-    if a_values.dtype != b_values.dtype:
-        raise TypeError(f"both value tensors must have one dtype, not {a_values.dtype} and {b_values.dtype}")
-    if tuple(a_values.shape[1:]) != tuple(b_values.shape[1:]) or va != vb:
-        raise ValueError(f"both value tensors must have the same trailing shape, not {tuple(a_values.shape)} and {tuple(b_values.shape)}")
-    out_keys = out_values = None
-    if out is not None:
-        if not isinstance(out, (tuple, list)) or len(out) != 2:
-            raise TypeError("out must be a pair (keys, values)")
-        out_keys, out_values = out
-        _merge_out(out_keys, a_keys, n, "keys")
-        _merge_out(out_values, a_values, n, "values")
-    for v, what in ((a_values, "a_values"), (b_values, "b_values")):
-        if v.device != a_keys.device:
-            raise ValueError(f"keys and {what} must live on the same device")
+    va = _merge_values(a_keys, a_values, na, b_values, nb)
+    out_keys, out_values = _merge_out_values(out, a_keys, a_values, n)
     _pairs_device(a_keys, None, "")
-    if out_keys is None:
-        out_keys = torch.empty((n,) + tuple(a_keys.shape[1:]), dtype=a_keys.dtype, device=a_keys.device)
-        out_values = torch.empty((n,) + tuple(a_values.shape[1:]), dtype=a_values.dtype, device=a_keys.device)
     if n > 0:
         with _on_device(a_keys, ctx) as (c, stream):
             c.merge_device(a_keys.data_ptr() if na else 0, a_values.data_ptr() if na else 0, na, b_keys.data_ptr() if nb else 0,
@@ -1422,28 +1440,10 @@ def radix_set_op(a, b, op: str, descending: bool = False, return_index: bool = F
     kb, kind, na, nb = _merge_keys(a, b, key_kind)
     code = _set_op(op)
     cap = _set_cap(code, na, nb)
-    out_keys, out_index = out, None
-    if return_index and out is not None:
-        if not isinstance(out, (tuple, list)) or len(out) != 2:
-            raise TypeError("out must be a pair (keys, index) with return_index=True")
-        out_keys, out_index = out
-    if out_keys is not None:
-        _merge_out(out_keys, a, cap, "keys")
-    if out_index is not None:
-        _index_out(out_index, (cap,), "the kept keys")
-        if out_index.device != a.device:
-            raise ValueError("the keys and out (index) must live on the same device")
-        index_dtype = out_index.dtype
-    index_dtype = _index_dtype(index_dtype)
+    out_keys, out_index = _merge_out_index(out, return_index, index_dtype, a, cap, na + nb, "the kept keys")
     _set_num(a_num, a, "a_num")
     _set_num(b_num, a, "b_num")
     _pairs_device(a, None, "")
-    if return_index and index_dtype == torch.int32 and na + nb > 1 << 32:
-        raise ValueError("more than 2^32 keys need int64 indices")
-    if out_keys is None:
-        out_keys = torch.empty((cap,) + tuple(a.shape[1:]), dtype=a.dtype, device=a.device)
-    if return_index and out_index is None:
-        out_index = torch.empty(cap, dtype=index_dtype, device=a.device)
     num = torch.empty((), dtype=torch.int64, device=a.device)
     if na + nb == 0 or cap == 0:  # (empty outputs have no address to hand to the C call: nothing can be kept)
         num.zero_()
@@ -1470,35 +1470,17 @@ def radix_set_op_pairs(a_keys, a_values, b_keys, b_values, op: str, descending: 
     code = _set_op(op)
     cap = _set_cap(code, na, nb)
     emits_b = code in (_lib.SETOP_UNION, _lib.SETOP_SYMMETRIC_DIFFERENCE)
-    va = _value_bytes(a_values, (na,), "a_keys")
     if a_values is None:
         raise TypeError("a_values must be a torch tensor (keys alone: radix_set_op)")
     if b_values is None and emits_b:
         raise TypeError(f'b_values must be a torch tensor for "{op}", which can emit from b')
-    if b_values is not None:
-        vb = _value_bytes(b_values, (nb,), "b_keys")
-        if a_values.dtype != b_values.dtype:
-            raise TypeError(f"both value tensors must have one dtype, not {a_values.dtype} and {b_values.dtype}")
-        if tuple(a_values.shape[1:]) != tuple(b_values.shape[1:]) or va != vb:
-            raise ValueError(f"both value tensors must have the same trailing shape, not {tuple(a_values.shape)} and {tuple(b_values.shape)}")
+    va = _merge_values(a_keys, a_values, na, b_values, nb)
     if va not in _SET_FUSED:
         raise ValueError(f"one value must have 1, 2, 4, 8 or 16 bytes, not {va}: use radix_set_op(..., return_index=True) and gather")
-    out_keys = out_values = None
-    if out is not None:
-        if not isinstance(out, (tuple, list)) or len(out) != 2:
-            raise TypeError("out must be a pair (keys, values)")
-        out_keys, out_values = out
-        _merge_out(out_keys, a_keys, cap, "keys")
-        _merge_out(out_values, a_values, cap, "values")
-    for v, what in ((a_values, "a_values"), (b_values, "b_values")):
-        if v is not None and v.device != a_keys.device:
-            raise ValueError(f"keys and {what} must live on the same device")
+    out_keys, out_values = _merge_out_values(out, a_keys, a_values, cap)
     _set_num(a_num, a_keys, "a_num")
     _set_num(b_num, a_keys, "b_num")
     _pairs_device(a_keys, None, "")
-    if out_keys is None:
-        out_keys = torch.empty((cap,) + tuple(a_keys.shape[1:]), dtype=a_keys.dtype, device=a_keys.device)
-        out_values = torch.empty((cap,) + tuple(a_values.shape[1:]), dtype=a_values.dtype, device=a_keys.device)
     num = torch.empty((), dtype=torch.int64, device=a_keys.device)
     if na + nb == 0 or cap == 0:
         num.zero_()

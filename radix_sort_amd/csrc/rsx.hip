@@ -209,8 +209,7 @@ struct DeviceGuard {
 };
 
 // What an entry point holds from its argument checks to its return: the context's mutex, the context's device as the
-// current one, and the caller's stream.  !ok: the device could not be set (the entries that sort refuse to go on, see
-// no_device; the older ones never looked and still do not).
+// current one, and the caller's stream.  !ok: the device could not be set.
 struct Entry {
     std::lock_guard<std::mutex> lk;
     DeviceGuard dev;
@@ -219,6 +218,10 @@ struct Entry {
     explicit Entry(rsx_ctx* ctx, void* stream = nullptr) : lk(ctx->mu), dev(ctx->device), ok(dev.ok), st(static_cast<hipStream_t>(stream)) {}
 };
 int no_device(rsx_ctx* ctx) { return fail(ctx, RSX_ERR_NODEVICE, "hipSetDevice failed"); }
+// How every entry point that needs the device takes it: declares `held`, and leaves where the device could not be set.
+#define RSX_ENTER(stream)     \
+    Entry held(ctx, stream);  \
+    if (!held.ok) return no_device(ctx)
 
 // the checks of an `order` and an `index_bytes` argument
 int order_desc(rsx_ctx* ctx, int order, uint32_t* desc) {
@@ -733,6 +736,17 @@ int reserve_joined(rsx_ctx* ctx, const JoinedPlan& P, hipStream_t st) {
     if (rc) return rc;
     return ensure_any(ctx, P.ws.bytes, st);
 }
+// a reserve entry's body once its arguments are checked: a joined sort's two workspaces, or `bytes` of the second alone
+int reserve_joined_entry(rsx_ctx* ctx, const JoinedPlan& P) {
+    RSX_ENTER(nullptr);
+    return reserve_joined(ctx, P, nullptr);
+}
+int reserve_any_entry(rsx_ctx* ctx, size_t bytes) {
+    RSX_ENTER(nullptr);
+    int rc = ensure_aux(ctx, nullptr);
+    if (rc) return rc;
+    return ensure_any(ctx, bytes, nullptr);
+}
 // Joins keys and values (gen: every key's position) into the first array and sorts them there; *w0 receives the sorted
 // elements.  The caller has reserved P (reserve_joined) and opened its Enqueue, in that order.
 int joined_sort(rsx_ctx* ctx, const JoinedPlan& P, const void* d_keys, const void* d_values, bool gen, uint32_t kind, uint32_t desc, hipStream_t st,
@@ -768,10 +782,9 @@ bool key_widths_ok(uint32_t kb, uint32_t kind) {  // the key array as a layout o
     return layout_ok(&L);
 }
 // ---- the segmented forms of those calls (rsx_segment_pairs_kernels.hpp): values with a fused kernel, or positions ----
-bool typed_value_width(uint32_t vb) { return vb == 0 || vb == 1 || vb == 2 || vb == 4 || vb == 8 || vb == 16; }
 // the joined element the fused kernels sort: the value itself, or a four-byte position (argsort; values too wide to join)
 uint32_t segment_pairs_elem(uint32_t kb, uint32_t vb, bool argsort) {
-    return pairs_elem_bytes(kb, (!argsort && typed_value_width(vb)) ? vb : 4u);
+    return pairs_elem_bytes(kb, (!argsort && value_width_fused(vb)) ? vb : 4u);
 }
 uint32_t value_align(uint32_t vb) {
     uint32_t a = 1;
@@ -923,7 +936,7 @@ int rsx_ctx_destroy(rsx_ctx* ctx) try {
 int rsx_ctx_reserve(rsx_ctx* ctx, size_t n, const rsx_layout* layout) try {
     int rc = check_any(ctx, layout);
     if (rc) return rc;
-    Entry held(ctx);
+    RSX_ENTER(nullptr);
     if (!direct_layout(layout)) return reserve_any(ctx, n, layout, nullptr);
     return ensure_workspace(ctx, n, layout, nullptr);
 } catch (...) {
@@ -932,7 +945,7 @@ int rsx_ctx_reserve(rsx_ctx* ctx, size_t n, const rsx_layout* layout) try {
 
 int rsx_ctx_check(rsx_ctx* ctx, void* stream) try {
     if (!ctx) return RSX_ERR_ARG;
-    Entry held(ctx);
+    RSX_ENTER(nullptr);
     RSX_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
     if (!ctx->host_err) return RSX_OK;
     if (host_word(ctx, HV_ERROR)) {
@@ -1026,7 +1039,7 @@ int rsx_ctx_set_option(rsx_ctx* ctx, int option, uint64_t value) try {
 
 int rsx_ctx_get_info(rsx_ctx* ctx, int what, uint64_t* out) try {
     if (!ctx || !out) return RSX_ERR_ARG;
-    Entry held(ctx);
+    RSX_ENTER(nullptr);
     if (what == RSX_INFO_RANK_ATOMIC || what == RSX_INFO_L2_LOCAL) {
         int rc = ensure_aux(ctx, nullptr);  // runs the self-tests on first use
         if (rc) return rc;
@@ -1092,7 +1105,7 @@ int rsx_ctx_get_info(rsx_ctx* ctx, int what, uint64_t* out) try {
 // Diagnostic counters of the sweep kernel (RSX_TUNING builds, RSX_DEBUG & 0x100); not part of include/rsx.h.
 int rsx_debug_counters(rsx_ctx* ctx, unsigned long long* out128, int reset) try {
     if (!ctx || !out128 || !ctx->aux) return RSX_ERR_ARG;
-    Entry held(ctx);
+    RSX_ENTER(nullptr);
     RSX_HIP(hipDeviceSynchronize());
     RSX_HIP(hipMemcpy(out128, ctx->aux + OFF_DBG, 1024, hipMemcpyDeviceToHost));  // caller passes 128 u64
     if (reset) RSX_HIP(hipMemset(ctx->aux + OFF_DBG, 0, 1024));
@@ -1136,7 +1149,7 @@ int rsx_debug_sweep_times(rsx_ctx* ctx, float* out, int max) try {
 
 int rsx_ctx_profile_read(rsx_ctx* ctx, double* ms, uint64_t* launches) try {
     if (!ctx || !ms || !launches) return RSX_ERR_ARG;
-    Entry held(ctx);
+    RSX_ENTER(nullptr);
     for (int k = 0; k < RSX_PROF_KINDS; ++k) {
         for (auto& e : ctx->prof_pending[k]) {
             RSX_HIP(hipEventSynchronize(e.second));
@@ -1165,8 +1178,7 @@ int rsx_sort_device(rsx_ctx* ctx, void* d_data, void* d_tmp, size_t n, const rsx
         const uint32_t al = elem_align(L->elem_bytes);
         if (!aligned(d_data, al) || !aligned(d_tmp, al)) return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
     }
-    Entry held(ctx, stream);
-    if (!held.ok) return no_device(ctx);
+    RSX_ENTER(stream);
     return sort_any_locked(ctx, d_data, d_tmp, n, L, held.st);
 } catch (...) {
     return RSX_ERR_HIP;
@@ -1175,13 +1187,12 @@ int rsx_sort_device(rsx_ctx* ctx, void* d_data, void* d_tmp, size_t n, const rsx
 int rsx_ctx_reserve_pairs(rsx_ctx* ctx, size_t n, uint32_t key_bytes, uint32_t value_bytes) try {
     if (!ctx) return RSX_ERR_ARG;
     if (!key_widths_ok(key_bytes, RSX_KEY_UNSIGNED) || value_bytes > RSX_MAX_ELEM_BYTES) return fail(ctx, RSX_ERR_ARG, "invalid key or value width");
-    Entry held(ctx);
-    if (!held.ok) return no_device(ctx);
+    RSX_ENTER(nullptr);
     int rc = reserve_joined(ctx, pairs_plan(n, key_bytes, value_bytes).j, nullptr);
     // an argsort with 8-byte indices joins 4-byte positions while n < 2^32: another element size
     if (!rc && value_bytes == 8 && (uint64_t)n < (1ull << 32)) rc = reserve_joined(ctx, pairs_plan(n, key_bytes, 4).j, nullptr);
     // the segmented calls keep values without a fused kernel behind four-byte positions, whatever their width
-    if (!rc && !typed_value_width(value_bytes)) rc = ensure_any(ctx, proxy_plan(n, key_bytes, value_bytes).j.ws.bytes, nullptr);
+    if (!rc && !value_width_fused(value_bytes)) rc = ensure_any(ctx, proxy_plan(n, key_bytes, value_bytes).j.ws.bytes, nullptr);
     return rc;
 } catch (...) {
     return RSX_ERR_NOMEM;
@@ -1199,8 +1210,7 @@ int rsx_sort_pairs_device(rsx_ctx* ctx, void* d_keys, void* d_values, size_t n, 
     if (!d_keys) return fail(ctx, RSX_ERR_ARG, "null device pointer");
     if (!aligned(d_keys, key_bytes) || (value_bytes && !aligned(d_values, value_align(value_bytes)))) return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
     if (n == 1) return RSX_OK;
-    Entry held(ctx, stream);
-    if (!held.ok) return no_device(ctx);
+    RSX_ENTER(stream);
     return pairs_locked(ctx, d_keys, d_values, nullptr, n, key_bytes, key_kind, value_bytes, 0, desc, held.st);
 } catch (...) {
     return RSX_ERR_HIP;
@@ -1216,8 +1226,7 @@ int rsx_argsort_device(rsx_ctx* ctx, const void* d_keys, void* d_index, size_t n
     if (n == 0) return RSX_OK;
     if (!d_keys || !d_index) return fail(ctx, RSX_ERR_ARG, "null device pointer");
     if (!aligned(d_keys, key_bytes) || !aligned(d_index, index_bytes)) return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
-    Entry held(ctx, stream);
-    if (!held.ok) return no_device(ctx);
+    RSX_ENTER(stream);
     const hipStream_t st = held.st;
     if (n == 1) {  // the one position
         RSX_HIP(hipMemsetAsync(d_index, 0, index_bytes, st));
@@ -1245,8 +1254,7 @@ int sort_segments_common(rsx_ctx* ctx, void* d_data, void* d_tmp, size_t n, cons
     if (!d_data || !d_tmp) return fail(ctx, RSX_ERR_ARG, "null device pointer");
     const uint32_t al = elem_align(L->elem_bytes);
     if (!aligned(d_data, al) || !aligned(d_tmp, al) || !aligned(d_offsets, 8)) return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
-    Entry held(ctx, stream);
-    if (!held.ok) return no_device(ctx);
+    RSX_ENTER(stream);
     const hipStream_t st = held.st;
     const uint64_t cap = segment_cap((int)L->elem_bytes, RSX_SEG_CLASSES - 1);
     if (!d_offsets && rows_one_by_one(ctx, nseg, row_len, cap)) {
@@ -1307,14 +1315,13 @@ int segments_pairs_common(rsx_ctx* ctx, void* d_keys, void* d_values, void* d_in
     if (!d_keys || (argsort && !d_index)) return fail(ctx, RSX_ERR_ARG, "null device pointer");
     if (!aligned(d_keys, kb) || (argsort && !aligned(d_index, ib)) || (vb && !aligned(d_values, value_align(vb))) || !aligned(d_offsets, 8))
         return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
-    Entry held(ctx, stream);
-    if (!held.ok) return no_device(ctx);
+    RSX_ENTER(stream);
     const hipStream_t st = held.st;
     if (rows && row_len == 1) {  // argsort: every row's one position
         RSX_HIP(hipMemsetAsync(d_index, 0, n * (size_t)ib, st));
         return RSX_OK;
     }
-    const bool wide = !argsort && !typed_value_width(vb);  // route B: positions and a gather
+    const bool wide = !argsort && !value_width_fused(vb);  // route B: positions and a gather
     const uint32_t es = segment_pairs_elem(kb, vb, argsort);
     if (es == 0 || !launchers_for(es)) return fail(ctx, RSX_ERR_INTERNAL, "no joined element for these widths");
     if (wide && (uint64_t)n >= (1ull << 32)) return fail(ctx, RSX_ERR_UNSUPPORTED, "2^32 or more pairs with values too wide to join");
@@ -1461,8 +1468,7 @@ int rsx_topk_rows_device(rsx_ctx* ctx, const void* d_keys, void* d_out_keys, voi
     if (!d_keys) return fail(ctx, RSX_ERR_ARG, "null device pointer");
     if (!aligned(d_keys, key_bytes) || !aligned(d_out_keys, key_bytes) || !aligned(d_out_index, index_bytes))
         return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
-    Entry held(ctx, stream);
-    if (!held.ok) return no_device(ctx);
+    RSX_ENTER(stream);
     const hipStream_t st = held.st;
     rc = pending_error(ctx);
     if (rc) return rc;
@@ -1499,12 +1505,7 @@ int rsx_ctx_reserve_topk(rsx_ctx* ctx, size_t rows, size_t row_len, size_t k, ui
     uint32_t es = 0;
     int rc = topk_shape(ctx, rows, row_len, k, key_bytes, &es);
     if (rc) return rc;
-    Entry held(ctx);
-    if (!held.ok) return no_device(ctx);
-    rc = ensure_aux(ctx, nullptr);
-    const size_t half = (rows == 0 || k == 0) ? 0 : topk_workspace_half(es, rows, row_len, k);
-    if (!rc && half) rc = ensure_any(ctx, 2 * half, nullptr);
-    return rc;
+    return reserve_any_entry(ctx, (rows == 0 || k == 0) ? 0 : 2 * topk_workspace_half(es, rows, row_len, k));
 } catch (...) {
     return RSX_ERR_NOMEM;
 }
@@ -1536,12 +1537,6 @@ UniquePlan unique_plan(size_t n, uint32_t kb, bool pos) {
     return P;
 }
 bool unique_size_ok(size_t n) { return (uint64_t)n < (1ull << 32); }
-// a reserve entry's body once its arguments are checked
-int reserve_joined_entry(rsx_ctx* ctx, const JoinedPlan& P) {
-    Entry held(ctx);
-    if (!held.ok) return no_device(ctx);
-    return reserve_joined(ctx, P, nullptr);
-}
 // rsx_unique_device and rsx_reduce_by_key_device on no keys: no group, so two memsets and no kernel
 int no_group(rsx_ctx* ctx, uint32_t path, uint64_t* d_out_num, uint64_t* d_out_offsets, hipStream_t st) {
     RSX_HIP(hipMemsetAsync(d_out_num, 0, sizeof(uint64_t), st));
@@ -1567,8 +1562,7 @@ int rsx_unique_device(rsx_ctx* ctx, const void* d_keys, size_t n, uint32_t key_b
         (pos && (!aligned(d_out_perm, index_bytes) || !aligned(d_out_inverse, index_bytes))))
         return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
     if (!unique_size_ok(n)) return fail(ctx, RSX_ERR_UNSUPPORTED, "2^32 or more keys");
-    Entry held(ctx, stream);
-    if (!held.ok) return no_device(ctx);
+    RSX_ENTER(stream);
     const hipStream_t st = held.st;
     if (n == 0) return no_group(ctx, PATH_UNIQUE, d_out_num, d_out_offsets, st);
     const UniquePlan P = unique_plan(n, key_bytes, pos);
@@ -1635,7 +1629,8 @@ int rsx_search_sorted_device(rsx_ctx* ctx, const void* d_sorted, size_t n, const
     if (flags & ~(uint32_t)RSX_SEARCH_PRESORT) return fail(ctx, RSX_ERR_ARG, "unknown flag bits");
     if (index_bytes == 4 && (uint64_t)n >= (1ull << 32)) return fail(ctx, RSX_ERR_ARG, "2^32 or more sorted keys need 8-byte indices");
     const bool presort = (flags & RSX_SEARCH_PRESORT) != 0;
-    std::lock_guard<std::mutex> lk(ctx->mu);
+    RSX_ENTER(stream);
+    const hipStream_t st = held.st;
     if (m == 0) {  // nothing asked: no pointer is looked at
         note_path(ctx, PATH_SEARCH, 0);
         return RSX_OK;
@@ -1646,10 +1641,7 @@ int rsx_search_sorted_device(rsx_ctx* ctx, const void* d_sorted, size_t n, const
         !aligned(d_out_upper, index_bytes))
         return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
     if (presort && (uint64_t)m >= (1ull << 32)) return fail(ctx, RSX_ERR_UNSUPPORTED, "2^32 or more needles to sort first");
-    if (((uint64_t)m + search_tile_elems(key_bytes) - 1) / search_tile_elems(key_bytes) >= (1ull << 31)) return fail(ctx, RSX_ERR_UNSUPPORTED, "too many needles for one launch");
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return fail(ctx, RSX_ERR_NODEVICE, "hipSetDevice failed");
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!tiles_fit(m, search_tile_elems(key_bytes))) return fail(ctx, RSX_ERR_UNSUPPORTED, "too many needles for one launch");
     if (n == 0) {  // an empty haystack: every count is zero
         if (d_out_lower) RSX_HIP(hipMemsetAsync(d_out_lower, 0, m * (size_t)index_bytes, st));
         if (d_out_upper) RSX_HIP(hipMemsetAsync(d_out_upper, 0, m * (size_t)index_bytes, st));
@@ -1727,19 +1719,50 @@ struct MergePlan {
 };
 MergePlan merge_plan(size_t n, uint32_t vb) {
     MergePlan P{};
-    P.wide = !merge_value_fused(vb);
+    P.wide = !value_width_fused(vb);
     if (P.wide) P.pos_off = P.ws.take(n * sizeof(uint64_t));
     return P;
-}
-bool merge_size_ok(uint64_t n, uint32_t kb, uint32_t vb) {
-    const uint32_t tile = merge_tile_elems(kb, vb);
-    return (n + tile - 1) / tile < (1ull << 31);
 }
 // [p, p + bytes) and [q, q + qbytes) share a byte (an absent or empty range shares none)
 bool ranges_overlap(const void* p, uint64_t bytes, const void* q, uint64_t qbytes) {
     if (!p || !q || bytes == 0 || qbytes == 0) return false;
     const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
     return a < b + qbytes && b < a + bytes;
+}
+// The calls on two sorted arrays are not in place: no output may share a byte with an input or with another output.
+struct ByteRange {
+    const void* p;
+    uint64_t bytes;
+};
+int check_disjoint(rsx_ctx* ctx, std::initializer_list<ByteRange> in, std::initializer_list<ByteRange> out) {
+    for (const ByteRange* o = out.begin(); o != out.end(); ++o) {
+        for (const ByteRange& i : in)
+            if (ranges_overlap(o->p, o->bytes, i.p, i.bytes)) return fail(ctx, RSX_ERR_ARG, "an output overlaps an input");
+        for (const ByteRange* p = o + 1; p != out.end(); ++p)
+            if (ranges_overlap(o->p, o->bytes, p->p, p->bytes)) return fail(ctx, RSX_ERR_ARG, "two outputs overlap");
+    }
+    return RSX_OK;
+}
+// The checks rsx_merge_device and rsx_setop_device share, of na + nb >= 1 keys, their values and the three outputs.
+// need_b_values false: b's values are not asked for, and not looked at beyond their agreement with value_bytes.
+int check_merge_args(rsx_ctx* ctx, const void* d_a_keys, const void* d_a_values, size_t na, const void* d_b_keys, const void* d_b_values, size_t nb,
+                     bool need_b_values, uint32_t key_bytes, uint32_t value_bytes, const void* d_out_keys, const void* d_out_values,
+                     const void* d_out_index, uint32_t index_bytes) {
+    if (d_out_index) {
+        if (int rc = check_index_bytes(ctx, index_bytes)) return rc;
+        if (index_bytes == 4 && (uint64_t)na + (uint64_t)nb > (1ull << 32)) return fail(ctx, RSX_ERR_ARG, "more than 2^32 keys need 8-byte indices");
+    }
+    if (!d_out_keys && !d_out_values && !d_out_index) return fail(ctx, RSX_ERR_ARG, "d_out_keys, d_out_values and d_out_index are all null");
+    if (value_bytes == 0 && (d_a_values || d_b_values || d_out_values)) return fail(ctx, RSX_ERR_ARG, "value pointers and value_bytes disagree");
+    if ((na > 0 && !d_a_keys) || (nb > 0 && !d_b_keys)) return fail(ctx, RSX_ERR_ARG, "null device pointer");
+    if (!need_b_values) d_b_values = nullptr;
+    if (value_bytes != 0 && ((na > 0 && !d_a_values) || (need_b_values && nb > 0 && !d_b_values)))
+        return fail(ctx, RSX_ERR_ARG, "values are given on one side only");
+    const uint32_t va = value_bytes ? value_align(value_bytes) : 1u, ia = d_out_index ? index_bytes : 1u;
+    if (!aligned(d_a_keys, key_bytes) || !aligned(d_b_keys, key_bytes) || !aligned(d_out_keys, key_bytes) || !aligned(d_a_values, va) ||
+        !aligned(d_b_values, va) || !aligned(d_out_values, va) || !aligned(d_out_index, ia))
+        return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
+    return RSX_OK;
 }
 }  // namespace
 
@@ -1753,39 +1776,22 @@ int rsx_merge_device(rsx_ctx* ctx, const void* d_a_keys, const void* d_a_values,
     if (int rc = order_desc(ctx, order, &desc)) return rc;
     const uint64_t n = (uint64_t)na + (uint64_t)nb;
     if (n < (uint64_t)na) return fail(ctx, RSX_ERR_UNSUPPORTED, "too many keys for one launch");
-    Entry held(ctx, stream);
-    if (!held.ok) return no_device(ctx);
+    RSX_ENTER(stream);
     const hipStream_t st = held.st;
     if (n == 0) {  // nothing asked: no pointer is looked at
         note_path(ctx, PATH_MERGE, 0);
         return RSX_OK;
     }
-    if (d_out_index) {
-        if (int rc = check_index_bytes(ctx, index_bytes)) return rc;
-        if (index_bytes == 4 && n > (1ull << 32)) return fail(ctx, RSX_ERR_ARG, "more than 2^32 keys need 8-byte indices");
-    }
-    if (!d_out_keys && !d_out_values && !d_out_index) return fail(ctx, RSX_ERR_ARG, "d_out_keys, d_out_values and d_out_index are all null");
-    if (value_bytes == 0 && (d_a_values || d_b_values || d_out_values)) return fail(ctx, RSX_ERR_ARG, "value pointers and value_bytes disagree");
-    if ((na > 0 && !d_a_keys) || (nb > 0 && !d_b_keys)) return fail(ctx, RSX_ERR_ARG, "null device pointer");
-    if (value_bytes != 0 && ((na > 0 && !d_a_values) || (nb > 0 && !d_b_values))) return fail(ctx, RSX_ERR_ARG, "values are given on one side only");
-    const uint32_t va = value_bytes ? value_align(value_bytes) : 1u, ia = d_out_index ? index_bytes : 1u;
-    if (!aligned(d_a_keys, key_bytes) || !aligned(d_b_keys, key_bytes) || !aligned(d_out_keys, key_bytes) || !aligned(d_a_values, va) ||
-        !aligned(d_b_values, va) || !aligned(d_out_values, va) || !aligned(d_out_index, ia))
-        return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
-    if (!merge_size_ok(n, key_bytes, value_bytes)) return fail(ctx, RSX_ERR_UNSUPPORTED, "too many keys for one launch");
-    {  // the merge is not in place: no output may share a byte with an input or with another output
-        const void* in_p[4] = {d_a_keys, d_b_keys, d_a_values, d_b_values};
-        const uint64_t in_b[4] = {(uint64_t)na * key_bytes, (uint64_t)nb * key_bytes, (uint64_t)na * value_bytes, (uint64_t)nb * value_bytes};
-        const void* out_p[3] = {d_out_keys, d_out_values, d_out_index};
-        const uint64_t out_b[3] = {n * key_bytes, n * value_bytes, n * (d_out_index ? index_bytes : 0u)};
-        for (int o = 0; o < 3; ++o) {
-            for (int i = 0; i < 4; ++i)
-                if (ranges_overlap(out_p[o], out_b[o], in_p[i], in_b[i])) return fail(ctx, RSX_ERR_ARG, "an output overlaps an input");
-            for (int p = o + 1; p < 3; ++p)
-                if (ranges_overlap(out_p[o], out_b[o], out_p[p], out_b[p])) return fail(ctx, RSX_ERR_ARG, "two outputs overlap");
-        }
-    }
-    int rc = pending_error(ctx);
+    int rc = check_merge_args(ctx, d_a_keys, d_a_values, na, d_b_keys, d_b_values, nb, true, key_bytes, value_bytes, d_out_keys, d_out_values,
+                              d_out_index, index_bytes);
+    if (rc) return rc;
+    if (!tiles_fit(n, merge_tile_elems(key_bytes, value_bytes))) return fail(ctx, RSX_ERR_UNSUPPORTED, "too many keys for one launch");
+    rc = check_disjoint(ctx,
+                        {{d_a_keys, (uint64_t)na * key_bytes}, {d_b_keys, (uint64_t)nb * key_bytes}, {d_a_values, (uint64_t)na * value_bytes},
+                         {d_b_values, (uint64_t)nb * value_bytes}},
+                        {{d_out_keys, n * key_bytes}, {d_out_values, n * value_bytes}, {d_out_index, n * (d_out_index ? index_bytes : 0u)}});
+    if (rc) return rc;
+    rc = pending_error(ctx);
     if (rc) return rc;
     MergeCall c{};
     c.a_keys = d_a_keys;
@@ -1835,12 +1841,8 @@ int rsx_merge_device(rsx_ctx* ctx, const void* d_a_keys, const void* d_a_values,
 int rsx_ctx_reserve_merge(rsx_ctx* ctx, size_t n_total, uint32_t key_bytes, uint32_t value_bytes) try {
     if (!ctx) return RSX_ERR_ARG;
     if (!key_widths_ok(key_bytes, RSX_KEY_UNSIGNED) || value_bytes > RSX_MAX_ELEM_BYTES) return fail(ctx, RSX_ERR_ARG, "invalid key or value width");
-    if (!merge_size_ok(n_total, key_bytes, value_bytes)) return fail(ctx, RSX_ERR_UNSUPPORTED, "too many keys for one launch");
-    Entry held(ctx);
-    if (!held.ok) return no_device(ctx);
-    int rc = ensure_aux(ctx, nullptr);
-    if (rc) return rc;
-    return ensure_any(ctx, merge_plan(n_total, value_bytes).ws.bytes, nullptr);
+    if (!tiles_fit(n_total, merge_tile_elems(key_bytes, value_bytes))) return fail(ctx, RSX_ERR_UNSUPPORTED, "too many keys for one launch");
+    return reserve_any_entry(ctx, merge_plan(n_total, value_bytes).ws.bytes);
 } catch (...) {
     return RSX_ERR_NOMEM;
 }
@@ -1872,10 +1874,6 @@ SetopPlan setop_plan(size_t n, uint32_t kb) {
     P.num_off = P.ws.take(sizeof(uint64_t));
     return P;
 }
-bool setop_size_ok(uint64_t n, uint32_t kb) {
-    const uint32_t tile = setop_tile_elems(kb);
-    return (n + tile - 1) / tile < (1ull << 31);
-}
 // rows the caller provides in every output
 uint64_t setop_cap(uint32_t op, uint64_t na, uint64_t nb) {
     switch (op) {
@@ -1893,47 +1891,30 @@ int rsx_setop_device(rsx_ctx* ctx, uint32_t op, const void* d_a_keys, const void
     if (op > RSX_SETOP_SYMMETRIC_DIFFERENCE) return fail(ctx, RSX_ERR_ARG, "invalid set operation");
     if (!key_widths_ok(key_bytes, key_kind)) return fail(ctx, RSX_ERR_ARG, "invalid key width or kind");
     if (value_bytes > RSX_MAX_ELEM_BYTES) return fail(ctx, RSX_ERR_ARG, "value wider than RSX_MAX_ELEM_BYTES");
-    if (!setop_value_fused(value_bytes)) return fail(ctx, RSX_ERR_UNSUPPORTED, "values of 1, 2, 4, 8 or 16 bytes only (ask for d_out_index and gather)");
+    if (!value_width_fused(value_bytes)) return fail(ctx, RSX_ERR_UNSUPPORTED, "values of 1, 2, 4, 8 or 16 bytes only (ask for d_out_index and gather)");
     uint32_t desc = 0;
     if (int rc = order_desc(ctx, order, &desc)) return rc;
     if (!d_out_num) return fail(ctx, RSX_ERR_ARG, "d_out_num is null");
     if (!aligned(d_out_num, 8) || !aligned(d_a_num, 8) || !aligned(d_b_num, 8)) return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
     const uint64_t n = (uint64_t)na + (uint64_t)nb;
     if (n < (uint64_t)na) return fail(ctx, RSX_ERR_UNSUPPORTED, "too many keys for one launch");
-    Entry held(ctx, stream);
-    if (!held.ok) return no_device(ctx);
+    RSX_ENTER(stream);
     const hipStream_t st = held.st;
     if (n == 0) return no_group(ctx, PATH_SETOP, d_out_num, nullptr, st);  // nothing kept: no other pointer is looked at
-    if (d_out_index) {
-        if (int rc = check_index_bytes(ctx, index_bytes)) return rc;
-        if (index_bytes == 4 && n > (1ull << 32)) return fail(ctx, RSX_ERR_ARG, "more than 2^32 keys need 8-byte indices");
-    }
-    if (!d_out_keys && !d_out_values && !d_out_index) return fail(ctx, RSX_ERR_ARG, "d_out_keys, d_out_values and d_out_index are all null");
-    if (value_bytes == 0 && (d_a_values || d_b_values || d_out_values)) return fail(ctx, RSX_ERR_ARG, "value pointers and value_bytes disagree");
-    if ((na > 0 && !d_a_keys) || (nb > 0 && !d_b_keys)) return fail(ctx, RSX_ERR_ARG, "null device pointer");
     const bool emits_b = op == RSX_SETOP_UNION || op == RSX_SETOP_SYMMETRIC_DIFFERENCE;
+    int rc = check_merge_args(ctx, d_a_keys, d_a_values, na, d_b_keys, d_b_values, nb, emits_b, key_bytes, value_bytes, d_out_keys, d_out_values,
+                              d_out_index, index_bytes);
+    if (rc) return rc;
     if (!emits_b) d_b_values = nullptr;  // not looked at
-    if (value_bytes != 0 && ((na > 0 && !d_a_values) || (emits_b && nb > 0 && !d_b_values)))
-        return fail(ctx, RSX_ERR_ARG, "values are given on one side only");
-    const uint32_t va = value_bytes ? value_align(value_bytes) : 1u, ia = d_out_index ? index_bytes : 1u;
-    if (!aligned(d_a_keys, key_bytes) || !aligned(d_b_keys, key_bytes) || !aligned(d_out_keys, key_bytes) || !aligned(d_a_values, va) ||
-        !aligned(d_b_values, va) || !aligned(d_out_values, va) || !aligned(d_out_index, ia))
-        return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
-    if (!setop_size_ok(n, key_bytes)) return fail(ctx, RSX_ERR_UNSUPPORTED, "too many keys for one launch");
+    if (!tiles_fit(n, setop_tile_elems(key_bytes))) return fail(ctx, RSX_ERR_UNSUPPORTED, "too many keys for one launch");
     const uint64_t cap = setop_cap(op, na, nb);
-    {  // not in place: no output may share a byte with an input or with another output
-        const void* in_p[6] = {d_a_keys, d_b_keys, d_a_values, d_b_values, d_a_num, d_b_num};
-        const uint64_t in_b[6] = {(uint64_t)na * key_bytes, (uint64_t)nb * key_bytes, (uint64_t)na * value_bytes, (uint64_t)nb * value_bytes, 8, 8};
-        const void* out_p[4] = {d_out_keys, d_out_values, d_out_index, d_out_num};
-        const uint64_t out_b[4] = {cap * key_bytes, cap * value_bytes, cap * (d_out_index ? index_bytes : 0u), 8};
-        for (int o = 0; o < 4; ++o) {
-            for (int i = 0; i < 6; ++i)
-                if (ranges_overlap(out_p[o], out_b[o], in_p[i], in_b[i])) return fail(ctx, RSX_ERR_ARG, "an output overlaps an input");
-            for (int p = o + 1; p < 4; ++p)
-                if (ranges_overlap(out_p[o], out_b[o], out_p[p], out_b[p])) return fail(ctx, RSX_ERR_ARG, "two outputs overlap");
-        }
-    }
-    int rc = pending_error(ctx);
+    rc = check_disjoint(ctx,
+                        {{d_a_keys, (uint64_t)na * key_bytes}, {d_b_keys, (uint64_t)nb * key_bytes}, {d_a_values, (uint64_t)na * value_bytes},
+                         {d_b_values, (uint64_t)nb * value_bytes}, {d_a_num, 8}, {d_b_num, 8}},
+                        {{d_out_keys, cap * key_bytes}, {d_out_values, cap * value_bytes}, {d_out_index, cap * (d_out_index ? index_bytes : 0u)},
+                         {d_out_num, 8}});
+    if (rc) return rc;
+    rc = pending_error(ctx);
     if (rc) return rc;
     const SetopPlan P = setop_plan((size_t)n, key_bytes);
     rc = ensure_aux(ctx, st);
@@ -1978,12 +1959,8 @@ int rsx_setop_device(rsx_ctx* ctx, uint32_t op, const void* d_a_keys, const void
 int rsx_ctx_reserve_setop(rsx_ctx* ctx, size_t n_total, uint32_t key_bytes) try {
     if (!ctx) return RSX_ERR_ARG;
     if (!key_widths_ok(key_bytes, RSX_KEY_UNSIGNED)) return fail(ctx, RSX_ERR_ARG, "invalid key width");
-    if (!setop_size_ok(n_total, key_bytes)) return fail(ctx, RSX_ERR_UNSUPPORTED, "too many keys for one launch");
-    Entry held(ctx);
-    if (!held.ok) return no_device(ctx);
-    int rc = ensure_aux(ctx, nullptr);
-    if (rc) return rc;
-    return ensure_any(ctx, setop_plan(n_total, key_bytes).ws.bytes, nullptr);
+    if (!tiles_fit(n_total, setop_tile_elems(key_bytes))) return fail(ctx, RSX_ERR_UNSUPPORTED, "too many keys for one launch");
+    return reserve_any_entry(ctx, setop_plan(n_total, key_bytes).ws.bytes);
 } catch (...) {
     return RSX_ERR_NOMEM;
 }
@@ -2042,8 +2019,7 @@ int rsx_join_device(rsx_ctx* ctx, uint32_t how, const void* d_a_keys, size_t na,
     if (!d_out_num) return fail(ctx, RSX_ERR_ARG, "d_out_num is null");
     if (!aligned(d_out_num, 8) || !aligned(d_a_num, 8) || !aligned(d_b_num, 8)) return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
     if ((uint64_t)na >= (1ull << 32) || (uint64_t)nb >= (1ull << 32)) return fail(ctx, RSX_ERR_UNSUPPORTED, "2^32 or more keys on one side");
-    Entry held(ctx, stream);
-    if (!held.ok) return no_device(ctx);
+    RSX_ENTER(stream);
     const hipStream_t st = held.st;
     if (na == 0) return no_group(ctx, PATH_JOIN, d_out_num, nullptr, st);  // no row: no other pointer is looked at
     const bool pairs = how == RSX_JOIN_INNER || how == RSX_JOIN_LEFT;
@@ -2059,19 +2035,12 @@ int rsx_join_device(rsx_ctx* ctx, uint32_t how, const void* d_a_keys, size_t na,
     const uint64_t per = join_rows();
     const uint64_t groups = rows / per + (rows % per ? 1u : 0u);
     if (groups > (1ull << 31)) return fail(ctx, RSX_ERR_UNSUPPORTED, "too many rows for one launch: lower the capacity");
-    {  // no output may share a byte with an input or with another output
-        const void* in_p[6] = {d_a_keys, d_b_keys, d_a_index, d_b_index, d_a_num, d_b_num};
-        const uint64_t in_b[6] = {(uint64_t)na * key_bytes, (uint64_t)nb * key_bytes, (uint64_t)na * index_bytes, (uint64_t)nb * index_bytes, 8, 8};
-        const void* out_p[3] = {d_out_a, d_out_b, d_out_num};
-        const uint64_t out_b[3] = {join_bytes(d_out_a, rows, index_bytes), join_bytes(d_out_b, rows, index_bytes), 8};
-        for (int o = 0; o < 3; ++o) {
-            for (int i = 0; i < 6; ++i)
-                if (ranges_overlap(out_p[o], out_b[o], in_p[i], in_b[i])) return fail(ctx, RSX_ERR_ARG, "an output overlaps an input");
-            for (int p = o + 1; p < 3; ++p)
-                if (ranges_overlap(out_p[o], out_b[o], out_p[p], out_b[p])) return fail(ctx, RSX_ERR_ARG, "two outputs overlap");
-        }
-    }
-    int rc = pending_error(ctx);
+    int rc = check_disjoint(ctx,
+                            {{d_a_keys, (uint64_t)na * key_bytes}, {d_b_keys, (uint64_t)nb * key_bytes}, {d_a_index, (uint64_t)na * index_bytes},
+                             {d_b_index, (uint64_t)nb * index_bytes}, {d_a_num, 8}, {d_b_num, 8}},
+                            {{d_out_a, join_bytes(d_out_a, rows, index_bytes)}, {d_out_b, join_bytes(d_out_b, rows, index_bytes)}, {d_out_num, 8}});
+    if (rc) return rc;
+    rc = pending_error(ctx);
     if (rc) return rc;
     const JoinPlan P = join_plan(na);
     rc = ensure_aux(ctx, st);
@@ -2117,11 +2086,7 @@ int rsx_ctx_reserve_join(rsx_ctx* ctx, size_t na, uint32_t key_bytes) try {
     if (!ctx) return RSX_ERR_ARG;
     if (!key_widths_ok(key_bytes, RSX_KEY_UNSIGNED)) return fail(ctx, RSX_ERR_ARG, "invalid key width");
     if ((uint64_t)na >= (1ull << 32)) return fail(ctx, RSX_ERR_UNSUPPORTED, "2^32 or more keys on one side");
-    Entry held(ctx);
-    if (!held.ok) return no_device(ctx);
-    int rc = ensure_aux(ctx, nullptr);
-    if (rc) return rc;
-    return ensure_any(ctx, join_plan(na).ws.bytes, nullptr);
+    return reserve_any_entry(ctx, join_plan(na).ws.bytes);
 } catch (...) {
     return RSX_ERR_NOMEM;
 }
@@ -2176,8 +2141,7 @@ int rsx_reduce_by_key_device(rsx_ctx* ctx, const void* d_keys, const void* d_val
         !aligned(d_out_offsets, 8) || !aligned(d_out_num, 8))
         return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
     if (!unique_size_ok(n)) return fail(ctx, RSX_ERR_UNSUPPORTED, "2^32 or more keys");
-    Entry held(ctx, stream);
-    if (!held.ok) return no_device(ctx);
+    RSX_ENTER(stream);
     const hipStream_t st = held.st;
     if (n == 0) return no_group(ctx, PATH_REDUCE, d_out_num, d_out_offsets, st);
     const ReducePlan P = reduce_plan(n, key_bytes, value_bytes);
@@ -2374,8 +2338,7 @@ int rsx_ctx_reserve_lex(rsx_ctx* ctx, size_t n, const rsx_key_column* cols, uint
     if (rc) return lex_fail_columns(ctx, rc);
     if (value_bytes > RSX_MAX_ELEM_BYTES) return fail(ctx, RSX_ERR_ARG, "value wider than RSX_MAX_ELEM_BYTES");
     if (!unique_size_ok(n)) return fail(ctx, RSX_ERR_UNSUPPORTED, "2^32 or more keys");
-    Entry held(ctx);
-    if (!held.ok) return no_device(ctx);
+    RSX_ENTER(nullptr);
     const LexPlan P = lex_plan(cols, ncols);
     return reserve_lex_one(ctx, n, P, lex_space(n, P, std::max(P.max_kb, value_bytes)), nullptr);
 } catch (...) {
@@ -2395,8 +2358,7 @@ int rsx_lexsort_device(rsx_ctx* ctx, const rsx_key_column* cols, uint32_t ncols,
     if (!aligned(d_index, index_bytes)) return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
     rc = lex_check_pointers(ctx, cols, ncols);
     if (rc) return rc;
-    Entry held(ctx, stream);
-    if (!held.ok) return no_device(ctx);
+    RSX_ENTER(stream);
     const hipStream_t st = held.st;
     if (n == 1) {  // the one position
         RSX_HIP(hipMemsetAsync(d_index, 0, index_bytes, st));
@@ -2432,8 +2394,7 @@ int rsx_sort_columns_device(rsx_ctx* ctx, const rsx_key_column* cols, uint32_t n
     if (rc) return rc;
     if (value_bytes && !aligned(d_values, value_align(value_bytes))) return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
     if (n == 1) return RSX_OK;
-    Entry held(ctx, stream);
-    if (!held.ok) return no_device(ctx);
+    RSX_ENTER(stream);
     const hipStream_t st = held.st;
     const LexPlan P = lex_plan(cols, ncols);
     const LexSpace S = lex_space(n, P, std::max(P.max_kb, value_bytes));
@@ -2545,8 +2506,7 @@ int rsx_sort_host(rsx_ctx* ctx, void* data, size_t n, const rsx_layout* L) try {
     if (n <= 1) return RSX_OK;
     if (!data) return fail(ctx, RSX_ERR_ARG, "null host pointer");
     const size_t bytes = n * (size_t)L->elem_bytes;
-    Entry held(ctx);  // one lock across copy-in, sort and copy-out: the staging buffers are the context's
-    if (!held.ok) return no_device(ctx);
+    RSX_ENTER(nullptr);  // one lock across copy-in, sort and copy-out: the staging buffers are the context's
     if (bytes > ctx->host_bytes) {
         if (ctx->busy) RSX_HIP(hipEventSynchronize(ctx->last_event));
         for (void*& p : ctx->host_buf) {
@@ -2582,7 +2542,7 @@ int rsx_histogram_device(rsx_ctx* ctx, const void* d_src, size_t n, const rsx_la
     int rc = check_common(ctx, L);
     if (rc) return rc;
     if (digit >= L->key_bytes || !d_hist) return fail(ctx, RSX_ERR_ARG, "bad digit / null histogram");
-    Entry held(ctx, stream);
+    RSX_ENTER(stream);
     const hipStream_t st = held.st;
     if (n == 0) {
         RSX_HIP(hipMemsetAsync(d_hist, 0, RADIX * sizeof(uint64_t), st));
@@ -2635,7 +2595,7 @@ int rsx_partition_device(rsx_ctx* ctx, const void* d_src, void* d_dst, size_t n,
     int rc = check_common(ctx, L);
     if (rc) return rc;
     if (digit >= L->key_bytes) return fail(ctx, RSX_ERR_ARG, "bad digit");
-    Entry held(ctx, stream);
+    RSX_ENTER(stream);
     const hipStream_t st = held.st;
     if (n == 0) {
         if (d_hist) RSX_HIP(hipMemsetAsync(d_hist, 0, RADIX * sizeof(uint64_t), st));
@@ -2659,7 +2619,7 @@ int rsx_partition_count_device(rsx_ctx* ctx, const void* d_src, size_t n, const 
     if (rc) return rc;
     if (digit >= L->key_bytes) return fail(ctx, RSX_ERR_ARG, "bad digit");
     if (nsub == 0 || nsub > PART_MAX_SUB || !d_hist) return fail(ctx, RSX_ERR_ARG, "1..16 sub-ranges, non-null histogram");
-    Entry held(ctx, stream);
+    RSX_ENTER(stream);
     const hipStream_t st = held.st;
     if (n && (!d_src || !aligned(d_src, elem_align(L->elem_bytes)))) return fail(ctx, RSX_ERR_ARG, "bad source pointer");
     rc = ensure_aux(ctx, st);
@@ -2696,7 +2656,7 @@ int rsx_partition_scatter_device(rsx_ctx* ctx, const void* d_src, void* d_dst, s
     if (rc) return rc;
     if (digit >= L->key_bytes) return fail(ctx, RSX_ERR_ARG, "bad digit");
     if (nsub == 0 || nsub > PART_MAX_SUB || k >= nsub) return fail(ctx, RSX_ERR_ARG, "bad sub-range");
-    Entry held(ctx, stream);
+    RSX_ENTER(stream);
     const hipStream_t st = held.st;
     const uint64_t beg = sub_start(n, nsub, k), nk = sub_start(n, nsub, k + 1) - beg;
     if (nk == 0) return RSX_OK;
@@ -2727,7 +2687,7 @@ int rsx_splitter_count_device(rsx_ctx* ctx, const void* d_data, size_t n, const 
     if (!layout_ok(L)) return fail(ctx, RSX_ERR_ARG, "invalid rsx_layout");
     if (nb == 0) return RSX_OK;
     if (digit >= L->key_bytes || !d_ranges || !d_prefix || !d_less || (n && !d_data)) return fail(ctx, RSX_ERR_ARG, "bad digit / null pointer");
-    Entry held(ctx);
+    RSX_ENTER(nullptr);
     hipLaunchKernelGGL(rsx_splitter_count_kernel, dim3(nb), dim3(RADIX), 0, static_cast<hipStream_t>(stream),
                        static_cast<const uint8_t*>(d_data), (uint64_t)n, L->elem_bytes, L->key_offset, L->key_bytes, L->key_kind,
                        d_ranges, d_prefix, digit, d_less);
@@ -2742,7 +2702,7 @@ int rsx_splitter_pick_device(rsx_ctx* ctx, const uint64_t* d_total, const uint64
     if (!ctx) return RSX_ERR_ARG;
     if (nb == 0) return RSX_OK;
     if (digit >= 16 || !d_total || !d_rank || !d_prefix) return fail(ctx, RSX_ERR_ARG, "bad digit / null pointer");
-    Entry held(ctx);
+    RSX_ENTER(nullptr);
     hipLaunchKernelGGL(rsx_splitter_pick_kernel, dim3(nb), dim3(RADIX), 0, static_cast<hipStream_t>(stream), d_total, d_rank,
                        d_prefix, digit);
     RSX_HIP(hipGetLastError());
@@ -2758,7 +2718,7 @@ int rsx_segmented_copy_device(rsx_ctx* ctx, const void* d_src, void* d_dst, uint
     if (nseg == 0) return RSX_OK;
     if (!d_src || !d_dst || !d_src_off || !d_dst_off || !d_len) return fail(ctx, RSX_ERR_ARG, "null pointer");
     if (!size_supported(elem_bytes)) return fail(ctx, RSX_ERR_UNSUPPORTED, "element size has no device kernel");
-    Entry held(ctx, stream);
+    RSX_ENTER(stream);
     const hipStream_t st = held.st;
     return launchers_for(elem_bytes)->segcopy(ctx, d_src, d_dst, d_src_off, d_dst_off, d_len, nseg, st);
 } catch (...) {
@@ -2776,7 +2736,7 @@ int rsx_bounds_ranges_device(rsx_ctx* ctx, const void* d_sorted, size_t n, const
     if (!layout_ok(L)) return fail(ctx, RSX_ERR_ARG, "invalid rsx_layout");
     if (nq == 0) return RSX_OK;
     if (!d_queries || !d_out || (n && !d_sorted)) return fail(ctx, RSX_ERR_ARG, "null pointer");
-    Entry held(ctx, stream);
+    RSX_ENTER(stream);
     const hipStream_t st = held.st;
     hipLaunchKernelGGL(rsx_bounds_kernel, dim3((nq + 255) / 256), dim3(256), 0, st, static_cast<const uint8_t*>(d_sorted),
                        (uint64_t)n, L->elem_bytes, L->key_offset, L->key_bytes, L->key_kind, d_queries, nq, d_out,
@@ -3173,7 +3133,7 @@ int rsx_generate_device(rsx_ctx* ctx, void* d_data, size_t n, const rsx_layout* 
     } else if (gen == RSX_GEN_ZIPF) {
         if (!(param > 0.0)) return fail(ctx, RSX_ERR_ARG, "Zipf generator needs param > 0");
     }
-    Entry held(ctx, stream);
+    RSX_ENTER(stream);
     const hipStream_t st = held.st;
     uint64_t blocks = (n + 255) / 256;
     const uint64_t cap = (uint64_t)ctx->num_cu * 16;
@@ -3193,7 +3153,7 @@ int rsx_verify_device(rsx_ctx* ctx, const void* d_data, size_t n, const rsx_layo
     if (!layout_ok(L, true)) return fail(ctx, RSX_ERR_ARG, "invalid rsx_layout");
     if (L->elem_bytes > RSX_MAX_ELEM_BYTES) return fail(ctx, RSX_ERR_UNSUPPORTED, "element larger than RSX_MAX_ELEM_BYTES");
     if (!d_out) return fail(ctx, RSX_ERR_ARG, "null pointer");
-    Entry held(ctx, stream);
+    RSX_ENTER(stream);
     const hipStream_t st = held.st;
     RSX_HIP(hipMemsetAsync(d_out, 0, 3 * sizeof(uint64_t), st));
     if (n == 0) return RSX_OK;

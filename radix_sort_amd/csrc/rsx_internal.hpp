@@ -9,6 +9,8 @@
 //   rsx_merge.hip   the kernels of rsx_merge_device
 //   rsx_setops.hip  the kernel of rsx_setop_device
 //   rsx_lex.hip     the join of several key columns (rsx_lexsort_device, rsx_sort_columns_device)
+// and what they agree on before a kernel is picked: the dispatch on a key width (for_key_width) and on the value and
+// index widths of the merge and set-operation kernels, the fused value widths, and the tile count of one launch.
 #pragma once
 #include "rsx_device.hpp"
 
@@ -22,6 +24,7 @@
 #include <algorithm>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -522,6 +525,45 @@ struct EsLaunchers {
 template <int ES>
 const EsLaunchers& es_launchers();  // specialised in rsx_es.hip
 
+// ---- what the launcher units and rsx.hip agree on before a kernel is picked ----
+template <int N>
+using Width = std::integral_constant<int, N>;
+// The key widths with kernels: calls f(Width<KB>{}) for kb = 1, 2, 4, 8, 16 and returns true; any other width: false, f
+// is not called.  A launcher reads KB off its generic lambda's argument (decltype(kb)::value) as a template argument.
+template <class F>
+bool for_key_width(uint32_t kb, F&& f) {
+    switch (kb) {
+        case 1: f(Width<1>{}); return true;
+        case 2: f(Width<2>{}); return true;
+        case 4: f(Width<4>{}); return true;
+        case 8: f(Width<8>{}); return true;
+        case 16: f(Width<16>{}); return true;
+        default: return false;
+    }
+}
+// a value width that the typed kernels of the pairs, segment, merge and set-operation calls move themselves (0: no values)
+constexpr bool value_width_fused(uint32_t vb) { return vb == 0 || vb == 1 || vb == 2 || vb == 4 || vb == 8 || vb == 16; }
+// The merge and set-operation write kernels, per fused value width (taken as 16 when it is none of the others) and index
+// width (0: no index; else 4 or 8): calls f(Width<VB>{}, Width<IB>{}).
+template <class F>
+void for_value_index_width(uint32_t vb, uint32_t ib, F&& f) {
+    auto index = [&](auto v) {
+        if (ib == 0) f(v, Width<0>{});
+        else if (ib == 4) f(v, Width<4>{});
+        else f(v, Width<8>{});
+    };
+    switch (vb) {
+        case 0: index(Width<0>{}); break;
+        case 1: index(Width<1>{}); break;
+        case 2: index(Width<2>{}); break;
+        case 4: index(Width<4>{}); break;
+        case 8: index(Width<8>{}); break;
+        default: index(Width<16>{}); break;
+    }
+}
+// whether ceil(n / tile) tiles, one workgroup each, fit one launch
+constexpr bool tiles_fit(uint64_t n, uint32_t tile) { return (n + tile - 1) / tile < (1ull << 31); }
+
 // separate key and value arrays <-> joined elements (rsx_pairs.hip, rsx_pairs_kernels.hpp); split modes: 0 keys and
 // values, 1 keys only, 2 the position alone as ib bytes
 int launch_pairs_join(rsx_ctx* ctx, const void* keys, const void* values, void* elems, size_t n, uint32_t kb, uint32_t vb, bool gen,
@@ -644,7 +686,7 @@ struct MergeCall {
     const void* b_values;
     size_t nb;
     uint32_t kb, kind, desc;
-    uint32_t vb;                 // launch_merge: a fused width (merge_value_fused) when out_values is given
+    uint32_t vb;                 // launch_merge: a fused width (value_width_fused) when out_values is given
     uint32_t ib;                 // bytes of a position in out_index
     void* out_keys;              // each may be null
     void* out_values;
@@ -654,7 +696,6 @@ int launch_merge(rsx_ctx* ctx, const MergeCall& call, uint32_t* launched, hipStr
 // the values of any other width: out_values row r = row pos[r] of a_values ++ b_values; out_index (or null) receives pos
 int launch_merge_gather(rsx_ctx* ctx, const MergeCall& call, const uint64_t* pos, void* out_values, void* out_index, hipStream_t st);
 uint32_t merge_tile_elems(uint32_t kb, uint32_t vb);  // outputs per workgroup
-bool merge_value_fused(uint32_t vb);                  // the kernel moves values of this width itself
 
 // What one rsx_setop_device call asks of the set-operation kernel (rsx_setops.hip, rsx_setop_kernels.hpp).
 struct SetopCall {
@@ -668,7 +709,7 @@ struct SetopCall {
     const uint64_t* b_num;
     uint32_t op;                 // RSX_SETOP_*
     uint32_t kb, kind, desc;
-    uint32_t vb;                 // a fused width (setop_value_fused)
+    uint32_t vb;                 // a fused width (value_width_fused)
     uint32_t ib;                 // bytes of a position in out_index
     uint32_t* tile_count;        // per tile of setop_tile_elems: its kept elements, ...
     uint64_t* tile_base;         // ... those in front of it, and ...
@@ -683,7 +724,6 @@ struct SetopCall {
 int launch_setop(rsx_ctx* ctx, const SetopCall& call, uint32_t* launched, hipStream_t st);
 uint32_t setop_tile_elems(uint32_t kb);  // merge positions per workgroup
 uint32_t setop_save_words();
-bool setop_value_fused(uint32_t vb);
 // rsx_unique_scan_kernel over another call's per-tile counts (rsx_unique.hip): tile_base[t] and their sum -> out_num[0]
 void launch_run_scan(const uint32_t* tile_count, uint64_t* tile_base, uint64_t tiles, uint64_t* out_num, hipStream_t st);
 

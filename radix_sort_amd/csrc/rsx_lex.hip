@@ -43,14 +43,8 @@ int launch_lex_join(rsx_ctx* ctx, const LexJoinCall& c, hipStream_t st) {
         return fail(ctx, RSX_ERR_INTERNAL, "launch_lex_join: elements misplaced");
     a.ncols = c.ncols;
     LaunchTimer lt(ctx, RSX_PROF_OTHER, st);
-    switch (c.w) {
-        case 1: lex_join_w<1>(a, c, st); break;
-        case 2: lex_join_w<2>(a, c, st); break;
-        case 4: lex_join_w<4>(a, c, st); break;
-        case 8: lex_join_w<8>(a, c, st); break;
-        case 16: lex_join_w<16>(a, c, st); break;
-        default: return fail(ctx, RSX_ERR_INTERNAL, "launch_lex_join: compound key width without a kernel");
-    }
+    if (!for_key_width(c.w, [&](auto w) { lex_join_w<decltype(w)::value>(a, c, st); }))
+        return fail(ctx, RSX_ERR_INTERNAL, "launch_lex_join: compound key width without a kernel");
     RSX_HIP(hipGetLastError());
     return RSX_OK;
 }

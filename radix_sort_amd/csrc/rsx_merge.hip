@@ -7,8 +7,6 @@ namespace rsxh {
 
 namespace {
 
-bool key_width_has_kernel(uint32_t kb) { return kb == 1 || kb == 2 || kb == 4 || kb == 8 || kb == 16; }
-
 template <int KB, int VB, int IB>
 void merge_typed(const MergeCall& c, uint32_t tiles, hipStream_t st) {
     hipLaunchKernelGGL((rsx_merge_kernel<KB, VB, IB>), dim3(tiles), dim3(MERGE_WG), 0, st, static_cast<const uint8_t*>(c.a_keys),
@@ -16,46 +14,26 @@ void merge_typed(const MergeCall& c, uint32_t tiles, hipStream_t st) {
                        static_cast<const uint8_t*>(c.b_values), (uint64_t)c.nb, static_cast<uint8_t*>(c.out_keys), static_cast<uint8_t*>(c.out_values),
                        static_cast<uint8_t*>(c.out_index), c.kind, c.desc);
 }
-template <int KB, int VB>
-void merge_vb(const MergeCall& c, uint32_t tiles, hipStream_t st) {
-    if (!c.out_index) merge_typed<KB, VB, 0>(c, tiles, st);
-    else if (c.ib == 4) merge_typed<KB, VB, 4>(c, tiles, st);
-    else merge_typed<KB, VB, 8>(c, tiles, st);
-}
-template <int KB>
-void merge_kb(const MergeCall& c, uint32_t tiles, hipStream_t st) {
-    switch (c.out_values ? c.vb : 0u) {
-        case 0: merge_vb<KB, 0>(c, tiles, st); break;
-        case 1: merge_vb<KB, 1>(c, tiles, st); break;
-        case 2: merge_vb<KB, 2>(c, tiles, st); break;
-        case 4: merge_vb<KB, 4>(c, tiles, st); break;
-        case 8: merge_vb<KB, 8>(c, tiles, st); break;
-        default: merge_vb<KB, 16>(c, tiles, st); break;
-    }
-}
 
 }  // namespace
 
 uint32_t merge_tile_elems(uint32_t kb, uint32_t vb) { return merge_tile(kb, vb); }
 static_assert(2u * merge_lds_bytes(16, 16) <= 160u * 1024u && 2u * merge_lds_bytes(8, 16) <= 160u * 1024u, "two workgroups per CU at least");
-bool merge_value_fused(uint32_t vb) { return vb == 0 || vb == 1 || vb == 2 || vb == 4 || vb == 8 || vb == 16; }
 
 // one launch over c.na + c.nb >= 1 outputs (fewer than 2^31 tiles of them); c.vb is a fused width when c.out_values is given
 int launch_merge(rsx_ctx* ctx, const MergeCall& c, uint32_t* launched, hipStream_t st) {
     const uint32_t tile = merge_tile(c.kb, c.vb);
     const uint64_t n = (uint64_t)c.na + c.nb;
-    const uint64_t tiles = (n + tile - 1) / tile;
-    if (n == 0 || !key_width_has_kernel(c.kb) || tiles >= (1ull << 31) || (c.out_index && c.ib != 4 && c.ib != 8) ||
-        (c.out_values && !merge_value_fused(c.vb)))
+    const uint32_t tiles = (uint32_t)((n + tile - 1) / tile);
+    if (n == 0 || !tiles_fit(n, tile) || (c.out_index && c.ib != 4 && c.ib != 8) || (c.out_values && !value_width_fused(c.vb)))
         return fail(ctx, RSX_ERR_INTERNAL, "launch_merge: no kernel for this call");
     LaunchTimer lt(ctx, RSX_PROF_OTHER, st);
-    switch (c.kb) {
-        case 1: merge_kb<1>(c, (uint32_t)tiles, st); break;
-        case 2: merge_kb<2>(c, (uint32_t)tiles, st); break;
-        case 4: merge_kb<4>(c, (uint32_t)tiles, st); break;
-        case 8: merge_kb<8>(c, (uint32_t)tiles, st); break;
-        default: merge_kb<16>(c, (uint32_t)tiles, st); break;
-    }
+    const bool known = for_key_width(c.kb, [&](auto kb) {
+        for_value_index_width(c.out_values ? c.vb : 0u, c.out_index ? c.ib : 0u, [&](auto vb, auto ib) {
+            merge_typed<decltype(kb)::value, decltype(vb)::value, decltype(ib)::value>(c, tiles, st);
+        });
+    });
+    if (!known) return fail(ctx, RSX_ERR_INTERNAL, "launch_merge: no kernel for this call");
     RSX_HIP(hipGetLastError());
     *launched = 1u;
     return RSX_OK;

@@ -8,7 +8,6 @@ namespace rsxh {
 namespace {
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-bool typed_width(uint32_t vb) { return vb == 0 || vb == 1 || vb == 2 || vb == 4 || vb == 8 || vb == 16; }
 uint32_t blocks_for(uint64_t n, uint32_t per_thread) { return (uint32_t)((n + (uint64_t)per_thread * 256 - 1) / ((uint64_t)per_thread * 256)); }
 
 template <int KB, int VB, bool GEN>
@@ -88,16 +87,6 @@ void split_any(uint32_t vb, uint32_t mode, uint32_t ib, const uint8_t* elems, ui
                            es, mode, ib, kind, desc);
 }
 
-#define RSX_PAIRS_KB(kb, CALL)                    \
-    switch (kb) {                                 \
-        case 1: { constexpr int KB = 1; CALL; } break;   \
-        case 2: { constexpr int KB = 2; CALL; } break;   \
-        case 4: { constexpr int KB = 4; CALL; } break;   \
-        case 8: { constexpr int KB = 8; CALL; } break;   \
-        case 16: { constexpr int KB = 16; CALL; } break; \
-        default: return fail(ctx, RSX_ERR_ARG, "key width without a join kernel"); \
-    }
-
 }  // namespace
 
 // keys (and values, or the position when gen) -> n joined elements of pairs_elem(kb, vb) bytes at `elems` (16-byte aligned)
@@ -107,11 +96,12 @@ int launch_pairs_join(rsx_ctx* ctx, const void* keys, const void* values, void* 
     const uint8_t* k = static_cast<const uint8_t*>(keys);
     const uint8_t* v = gen ? nullptr : static_cast<const uint8_t*>(values);
     uint8_t* e = static_cast<uint8_t*>(elems);
-    const bool typed = typed_width(vb) && aligned16(k) && aligned16(v) && aligned16(e);
+    const bool typed = value_width_fused(vb) && aligned16(k) && aligned16(v) && aligned16(e);
     LaunchTimer lt(ctx, RSX_PROF_OTHER, st);
     bool done = false;
-    if (typed) RSX_PAIRS_KB(kb, done = join_kb<KB>(vb, gen, k, v, e, (uint64_t)n, kind, desc, st))
-    if (!done) RSX_PAIRS_KB(kb, join_any<KB>(vb, k, v, e, (uint64_t)n, kind, desc, st))
+    if (typed) for_key_width(kb, [&](auto w) { done = join_kb<decltype(w)::value>(vb, gen, k, v, e, (uint64_t)n, kind, desc, st); });
+    if (!done && !for_key_width(kb, [&](auto w) { join_any<decltype(w)::value>(vb, k, v, e, (uint64_t)n, kind, desc, st); }))
+        return fail(ctx, RSX_ERR_ARG, "key width without a join kernel");
     RSX_HIP(hipGetLastError());
     return RSX_OK;
 }
@@ -124,11 +114,12 @@ int launch_pairs_split(rsx_ctx* ctx, const void* elems, void* keys, void* values
     const uint8_t* e = static_cast<const uint8_t*>(elems);
     uint8_t* k = mode == PAIRS_SPLIT_INDEX ? nullptr : static_cast<uint8_t*>(keys);
     uint8_t* v = mode == PAIRS_SPLIT_KEYS ? nullptr : static_cast<uint8_t*>(values);
-    const bool typed = typed_width(vb) && aligned16(k) && aligned16(v) && aligned16(e);
+    const bool typed = value_width_fused(vb) && aligned16(k) && aligned16(v) && aligned16(e);
     LaunchTimer lt(ctx, RSX_PROF_OTHER, st);
     bool done = false;
-    if (typed) RSX_PAIRS_KB(kb, done = split_kb<KB>(vb, mode, ib, e, k, v, (uint64_t)n, kind, desc, st))
-    if (!done) RSX_PAIRS_KB(kb, split_any<KB>(vb, mode, ib, e, k, v, (uint64_t)n, kind, desc, st))
+    if (typed) for_key_width(kb, [&](auto w) { done = split_kb<decltype(w)::value>(vb, mode, ib, e, k, v, (uint64_t)n, kind, desc, st); });
+    if (!done && !for_key_width(kb, [&](auto w) { split_any<decltype(w)::value>(vb, mode, ib, e, k, v, (uint64_t)n, kind, desc, st); }))
+        return fail(ctx, RSX_ERR_ARG, "key width without a join kernel");
     RSX_HIP(hipGetLastError());
     return RSX_OK;
 }

@@ -48,14 +48,7 @@ int launch_reduce(rsx_ctx* ctx, const ReduceCall& c, uint32_t* launched, hipStre
     const uint32_t tiles = (uint32_t)(((uint64_t)c.n + tile - 1) / tile);
     LaunchTimer lt(ctx, RSX_PROF_SCAN, st);  // (count, scan, write: the three phases of one scan, timed as one)
     bool ok = false;
-    switch (c.kb) {
-        case 1: ok = reduce_kb<1>(c, tiles, st); break;
-        case 2: ok = reduce_kb<2>(c, tiles, st); break;
-        case 4: ok = reduce_kb<4>(c, tiles, st); break;
-        case 8: ok = reduce_kb<8>(c, tiles, st); break;
-        case 16: ok = reduce_kb<16>(c, tiles, st); break;
-        default: break;
-    }
+    for_key_width(c.kb, [&](auto kb) { ok = reduce_kb<decltype(kb)::value>(c, tiles, st); });
     if (!ok) return fail(ctx, RSX_ERR_ARG, "key width or value type without run kernels");
     RSX_HIP(hipGetLastError());
     *launched = 3u;

@@ -9,8 +9,6 @@ namespace rsxh {
 
 namespace {
 
-bool key_width_has_kernel(uint32_t kb) { return kb == 1 || kb == 2 || kb == 4 || kb == 8 || kb == 16; }
-
 template <int KB, bool POS, int IB>
 void search_typed(const SearchCall& c, uint32_t tiles, hipStream_t st) {
     hipLaunchKernelGGL((rsx_search_kernel<KB, POS, IB>), dim3(tiles), dim3(SEARCH_WG), 0, st, static_cast<const uint8_t*>(c.sorted), (uint64_t)c.n,
@@ -48,17 +46,11 @@ uint32_t search_window_elems(uint32_t kb) { return search_window(kb); }
 // one launch over c.m >= 1 needles (fewer than 2^32 tiles of them)
 int launch_search(rsx_ctx* ctx, const SearchCall& c, uint32_t* launched, hipStream_t st) {
     const uint32_t tile = search_tile(c.kb);
-    const uint64_t tiles = ((uint64_t)c.m + tile - 1) / tile;
-    if (c.m == 0 || !key_width_has_kernel(c.kb) || tiles >= (1ull << 31) || (c.ib != 4 && c.ib != 8)) return fail(ctx, RSX_ERR_INTERNAL, "launch_search: no kernel for this call");
+    const uint32_t tiles = (uint32_t)(((uint64_t)c.m + tile - 1) / tile);
+    if (c.m == 0 || !tiles_fit(c.m, tile) || (c.ib != 4 && c.ib != 8)) return fail(ctx, RSX_ERR_INTERNAL, "launch_search: no kernel for this call");
     LaunchTimer lt(ctx, RSX_PROF_OTHER, st);
-    switch (c.kb) {
-        case 1: search_kb<1>(c, (uint32_t)tiles, st); break;
-        case 2: search_kb<2>(c, (uint32_t)tiles, st); break;
-        case 4: search_kb<4>(c, (uint32_t)tiles, st); break;
-        case 8: search_kb<8>(c, (uint32_t)tiles, st); break;
-        case 16: search_kb<16>(c, (uint32_t)tiles, st); break;
-        default: return fail(ctx, RSX_ERR_ARG, "key width without a search kernel");
-    }
+    if (!for_key_width(c.kb, [&](auto kb) { search_kb<decltype(kb)::value>(c, tiles, st); }))
+        return fail(ctx, RSX_ERR_INTERNAL, "launch_search: no kernel for this call");
     RSX_HIP(hipGetLastError());
     *launched = 1u;
     return RSX_OK;
@@ -70,17 +62,12 @@ uint32_t join_rows() { return JOIN_ROWS; }
 // the count launch, the scan and (c.write) the write launch over c.na >= 1 keys of a
 int launch_join(rsx_ctx* ctx, const JoinCall& c, uint32_t* launched, hipStream_t st) {
     const uint64_t tiles = ((uint64_t)c.na + JOIN_TILE - 1) / JOIN_TILE;
-    if (c.na == 0 || (uint64_t)c.na >= (1ull << 32) || (uint64_t)c.nb >= (1ull << 32) || !key_width_has_kernel(c.kb) || c.how > JOIN_ANTI ||
+    if (c.na == 0 || (uint64_t)c.na >= (1ull << 32) || (uint64_t)c.nb >= (1ull << 32) || c.how > JOIN_ANTI ||
         (c.write && (c.write_groups == 0 || c.write_groups > (1ull << 31) || !c.out_a || (c.ib != 4 && c.ib != 8))))
         return fail(ctx, RSX_ERR_INTERNAL, "launch_join: no kernel for this call");
     LaunchTimer lt(ctx, RSX_PROF_OTHER, st);
-    switch (c.kb) {
-        case 1: join_count_typed<1>(c, (uint32_t)tiles, st); break;
-        case 2: join_count_typed<2>(c, (uint32_t)tiles, st); break;
-        case 4: join_count_typed<4>(c, (uint32_t)tiles, st); break;
-        case 8: join_count_typed<8>(c, (uint32_t)tiles, st); break;
-        default: join_count_typed<16>(c, (uint32_t)tiles, st); break;
-    }
+    if (!for_key_width(c.kb, [&](auto kb) { join_count_typed<decltype(kb)::value>(c, (uint32_t)tiles, st); }))
+        return fail(ctx, RSX_ERR_INTERNAL, "launch_join: no kernel for this call");
     RSX_HIP(hipGetLastError());
     hipLaunchKernelGGL(rsx_join_scan_kernel, dim3(1), dim3(JOIN_WG), 0, st, c.tile_total, c.tile_base, tiles, c.out_num);
     RSX_HIP(hipGetLastError());

@@ -45,14 +45,8 @@ int launch_unique(rsx_ctx* ctx, const UniqueCall& c, uint32_t* launched, hipStre
     const uint32_t tiles = (uint32_t)(((uint64_t)c.n + tile - 1) / tile);
     const bool write = c.out_keys || c.out_offsets || c.out_perm || c.out_inverse;
     LaunchTimer lt(ctx, RSX_PROF_SCAN, st);  // (count, scan, write: the three phases of one scan, timed as one)
-    switch (c.kb) {
-        case 1: unique_kb<1>(c, tiles, write, st); break;
-        case 2: unique_kb<2>(c, tiles, write, st); break;
-        case 4: unique_kb<4>(c, tiles, write, st); break;
-        case 8: unique_kb<8>(c, tiles, write, st); break;
-        case 16: unique_kb<16>(c, tiles, write, st); break;
-        default: return fail(ctx, RSX_ERR_ARG, "key width without run kernels");
-    }
+    if (!for_key_width(c.kb, [&](auto kb) { unique_kb<decltype(kb)::value>(c, tiles, write, st); }))
+        return fail(ctx, RSX_ERR_ARG, "key width without run kernels");
     RSX_HIP(hipGetLastError());
     *launched = write ? 3u : 2u;
     return RSX_OK;
