@@ -203,6 +203,8 @@ enum {
                                  are 0),
                                  13 join (rsx_join_device: bits 0-7 are then the kernels launched -- 0, 2 for the
                                  count-only form, 3 otherwise -- and bits 8-23 are 0),
+                                 14 scan by key (rsx_scan_by_key_device: bits 0-7 are then the kernels launched after
+                                 any sort, bit 8 is set under RSX_SCAN_RUNS, bits 9-23 are 0),
                                  bits 28-29 the route of a layout without kernels of its own: 0 direct, 1 packed
                                  re-layout, 2 key-index proxy (bits 0-27 then describe the sort of the re-laid-out
                                  elements / of the proxies) */
@@ -494,6 +496,65 @@ int rsx_ctx_reserve_reduce(rsx_ctx *ctx, size_t n, uint32_t key_bytes, uint32_t 
 /* Host-only, needs no device: *tile = the elements one workgroup of the run kernels takes for these widths (256 threads,
  * each a whole number of 16-byte words), *scan_span = the tiles one sweep of the scan kernel's loop takes. */
 int rsx_reduce_caps(uint32_t key_bytes, uint32_t value_bytes, uint32_t *tile, uint32_t *scan_span);
+
+/* -- scan by key ------------------------------------------------------------- */
+/* The other thing callers do with a group: a result for EVERY row -- the running sum, minimum or maximum of a column
+ * inside the row's group, or the row's number inside it (groupby().cumsum() / cummax() / cumcount(), row_number() over
+ * (partition by ...), inclusive_scan_by_key).
+ *
+ * Groups.  Two keys are equal when all their bits are equal, the rule of rsx_unique_device (-0.0 and +0.0 are two keys).
+ *     default (grouped)  the group of position q is every position with q's key, anywhere in the array;
+ *     RSX_SCAN_RUNS      the group of q is the maximal run of CONSECUTIVE positions with q's key: the keys are taken as
+ *                        they lie, nothing is sorted, and a key that appears again later starts a new group.
+ * Inclusive result.  Let q_1 < q_2 < ... be the positions of q's group that are <= q and (+) the operator `op`
+ * (RSX_REDUCE_SUM / MIN / MAX with the operators, value types and order rules of rsx_reduce_by_key_device):
+ *     d_out[q] = d_values[q_1] (+) d_values[q_2] (+) ... (+) d_values[q]                (n entries of value_bytes)
+ * The result stands at the INPUT position q; the order in which groups are processed is not observable, so the call has
+ * no `order` argument.
+ * RSX_SCAN_EXCLUSIVE.  d_out[q] is the inclusive result at q's predecessor in its group; the first position of every
+ * group receives the low value_bytes bytes of `first`, which is stored, never combined (no identity element is ever
+ * added, as everywhere in this library).
+ * d_values == NULL, the count form.  Every value is the integer 1 of the stated value type; accepted only with
+ * RSX_REDUCE_SUM and an integer value_kind.  Inclusive gives the 1-based rank of q in its group, exclusive with first = 0
+ * the 0-based rank (cumcount, row_number).
+ * d_out_num (optional) receives the number of groups -- of runs under RSX_SCAN_RUNS -- as uint64: a by-product of the
+ * tile scan, never read by the host.
+ * Float sums.  The association is fixed by the tiling: a function of (n, the widths, the flags, the group's start and
+ * the rank) alone.  The same input gives the same bytes on every call and every context; there are no atomics.
+ * Aliasing.  d_out may be d_values (a thread of the write kernel stores only positions whose values it has itself
+ * already loaded; in the grouped form the values were gathered into the workspace by the launch before).  d_out must
+ * not overlap d_keys.
+ *
+ * Keys: every width and kind of rsx_argsort_device.  Values: 4 or 8 bytes of kind unsigned, signed or float.  Natural
+ * alignment suffices for all four pointers; under RSX_SCAN_RUNS columns that are not 16-byte aligned are loaded and
+ * stored element by element and give the same bytes.  RSX_ERR_ARG: bad widths, kinds, op, unknown flag bits or
+ * misalignment, d_out or d_keys NULL with n > 0, the count form with a float kind or an op other than RSX_REDUCE_SUM,
+ * d_out or d_out_num sharing a byte with d_keys or with each other.
+ * n >= 2^32 is RSX_ERR_UNSUPPORTED.  n == 0 writes d_out_num[0] = 0 where given, by a stream-ordered memset, and launches
+ * nothing.  Stream-ordered, never synchronised.
+ *
+ * Three kernels, none of which waits for another workgroup: per tile (rsx_scan_by_key_caps) the heads and the value of
+ * the open tail; the tile scan of rsx_reduce_by_key_device; and the write, in which every element stores its result.
+ * Under RSX_SCAN_RUNS they read the caller's columns directly (keys and values twice, one write: no element workspace).
+ * The grouped form first joins and sorts the (mapped key, u32 position) elements of rsx_argsort_device in the context's
+ * workspace; the first kernel gathers d_values[position] into a workspace column and the write scatters d_out[position].
+ * The workspace -- the per-tile arrays, one word, and for the grouped form the two element arrays and the value column
+ * -- is made on first use or by rsx_ctx_reserve_scan_by_key; under capture without a sufficient reserve the call returns
+ * RSX_ERR_WORKSPACE and enqueues nothing.  RSX_INFO_LAST_PASSES reports path 14: bits 0-7 the kernels launched after any
+ * sort, bit 8 set under RSX_SCAN_RUNS, bits 9-23 zero (the sort of the grouped form is described as for path 8).
+ * RSX_INFO_LAST_PAIRS reports route 1 and the joined element's size for the grouped form and keeps its previous value
+ * under RSX_SCAN_RUNS. */
+enum { RSX_SCAN_EXCLUSIVE = 1, RSX_SCAN_RUNS = 2 };
+int rsx_scan_by_key_device(rsx_ctx *ctx, const void *d_keys, const void *d_values, size_t n, uint32_t key_bytes,
+                           uint32_t key_kind, uint32_t value_bytes, uint32_t value_kind, int op, uint32_t flags,
+                           uint64_t first, void *d_out, uint64_t *d_out_num, void *stream);
+/* Workspace (and the context's first-call set-up) for rsx_scan_by_key_device on up to n keys of these widths with these
+ * flags (only RSX_SCAN_RUNS matters), so that the call allocates nothing (stream capture). */
+int rsx_ctx_reserve_scan_by_key(rsx_ctx *ctx, size_t n, uint32_t key_bytes, uint32_t value_bytes, uint32_t flags);
+/* Host-only, needs no device: *tile = the elements one workgroup of the count and write kernels takes (256 threads; under
+ * RSX_SCAN_RUNS each a whole number of 16-byte words of both columns), *scan_span = the tiles one sweep of the scan
+ * kernel's loop takes. */
+int rsx_scan_by_key_caps(uint32_t key_bytes, uint32_t value_bytes, uint32_t flags, uint32_t *tile, uint32_t *scan_span);
 
 /* -- bounds of many needles in a sorted key array ---------------------------- */
 /* The other thing callers do with a sorted array: look keys up in it (searchsorted / bucketize, membership, the probe side

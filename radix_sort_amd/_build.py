@@ -26,14 +26,16 @@ UNITS = (
     ("rsx.hip", "rsx.o", ()),                # the C-ABI and the size-independent kernels
     ("rsx_pairs.hip", "rsx_pairs.o", ()),    # the join and split kernels of the key / value calls
     ("rsx_unique.hip", "rsx_unique.o", ()),  # the run kernels of rsx_unique_device
-    ("rsx_reduce.hip", "rsx_reduce.o", ()),  # those of rsx_reduce_by_key_device
+    ("rsx_scan.hip", "rsx_scan.o", ()),      # those of rsx_scan_by_key_device and, through rsx_reduce.hip, which it includes,
+                                             # of rsx_reduce_by_key_device: one unit, the tile scan both calls launch built once
     ("rsx_lex.hip", "rsx_lex.o", ()),        # the join of several key columns: rsx_lexsort_device, rsx_sort_columns_device
     ("rsx_search.hip", "rsx_search.o", ()),  # the kernel of rsx_search_sorted_device
     ("rsx_merge.hip", "rsx_merge.o", ()),    # the kernels of rsx_merge_device
     ("rsx_setops.hip", "rsx_setops.o", ()),  # the kernel of rsx_setop_device
 ) + tuple(("rsx_es.hip", f"rsx_es{es}.o", (f"-DRSX_ES={es}",)) for es in ELEM_SIZES)  # the sort kernels, once per element size
-# what the library is stale against: every unit, every header beside them, and the public header
-DEPS = sorted({src for src, _obj, _flags in UNITS}) + sorted(f for f in os.listdir(CSRC) if f.endswith(".hpp")) + \
+# what the library is stale against: every unit, every file beside them that one of them includes (the headers and
+# rsx_reduce.hip), and the public header
+DEPS = sorted({src for src, _obj, _flags in UNITS} | {"rsx_reduce.hip"}) + sorted(f for f in os.listdir(CSRC) if f.endswith(".hpp")) + \
     [os.path.join("..", "..", "include", "rsx.h")]
 CXXFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

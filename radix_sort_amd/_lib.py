@@ -22,6 +22,7 @@ SYMBOLS = [
     "rsx_topk_rows_device", "rsx_ctx_reserve_topk", "rsx_topk_caps",
     "rsx_unique_device", "rsx_ctx_reserve_unique", "rsx_unique_caps",
     "rsx_reduce_by_key_device", "rsx_ctx_reserve_reduce", "rsx_reduce_caps",
+    "rsx_scan_by_key_device", "rsx_ctx_reserve_scan_by_key", "rsx_scan_by_key_caps",
     "rsx_lexsort_device", "rsx_sort_columns_device", "rsx_ctx_reserve_lex", "rsx_lex_plan",
     "rsx_search_sorted_device", "rsx_ctx_reserve_search", "rsx_search_caps",
     "rsx_merge_device", "rsx_ctx_reserve_merge", "rsx_merge_caps",
@@ -42,6 +43,7 @@ GEN_PAYLOAD_ZERO = 0x100
 INFO_RANK_ATOMIC, INFO_L2_LOCAL, INFO_NUM_CU, INFO_DEVICE, INFO_LAST_PASSES, INFO_LAST_PAIRS, INFO_LAST_DIRECT, INFO_LAST_LEX = 1, 2, 3, 4, 5, 6, 7, 8
 ORDER_ASCENDING, ORDER_DESCENDING = 0, 1
 REDUCE_SUM, REDUCE_MIN, REDUCE_MAX = 0, 1, 2
+SCAN_EXCLUSIVE, SCAN_RUNS = 1, 2
 SEARCH_PRESORT = 1
 SETOP_UNION, SETOP_INTERSECTION, SETOP_DIFFERENCE, SETOP_SYMMETRIC_DIFFERENCE = 0, 1, 2, 3
 JOIN_INNER, JOIN_LEFT, JOIN_SEMI, JOIN_ANTI = 0, 1, 2, 3
@@ -154,6 +156,9 @@ def load():
     L.rsx_reduce_by_key_device.argtypes = [vp, vp, vp, sz, u32, u32, u32, u32, i, i, vp, vp, vp, vp, vp]
     L.rsx_ctx_reserve_reduce.argtypes = [vp, sz, u32, u32]
     L.rsx_reduce_caps.argtypes = [u32, u32, ctypes.POINTER(u32), ctypes.POINTER(u32)]
+    L.rsx_scan_by_key_device.argtypes = [vp, vp, vp, sz, u32, u32, u32, u32, i, u32, u64, vp, vp, vp]
+    L.rsx_ctx_reserve_scan_by_key.argtypes = [vp, sz, u32, u32, u32]
+    L.rsx_scan_by_key_caps.argtypes = [u32, u32, u32, ctypes.POINTER(u32), ctypes.POINTER(u32)]
     kc, pu32 = ctypes.POINTER(KeyColumn), ctypes.POINTER(u32)
     L.rsx_lexsort_device.argtypes = [vp, kc, u32, vp, sz, u32, vp]
     L.rsx_sort_columns_device.argtypes = [vp, kc, u32, vp, u32, sz, vp]

@@ -387,6 +387,21 @@ class Context:
                                                      value_kind, op, 1 if descending else 0, d_out_keys or None, d_out_values or None,
                                                      d_out_offsets or None, d_out_num or None, stream))
 
+    def reserve_scan_by_key(self, n: int, key_bytes: int, value_bytes: int, runs: bool = False):
+        """rsx_ctx_reserve_scan_by_key: the context's first-call set-up and the workspace of scan_by_key_device on up to n
+        keys of these widths under this group rule, so that the call allocates nothing and can be captured."""
+        self._check(self._L.rsx_ctx_reserve_scan_by_key(self._h, n, key_bytes, value_bytes, _lib.SCAN_RUNS if runs else 0))
+
+    def scan_by_key_device(self, d_keys: int, d_values: int, n: int, key_bytes: int, key_kind: int, value_bytes: int, value_kind: int,
+                           op: int, flags: int, first: int, d_out: int, d_out_num: int = 0, stream: int = 0):
+        """rsx_scan_by_key_device: for every position the running sum (op 0), minimum (1) or maximum (2) of the values of
+        its group up to it, into d_out at that position -- the group being every position with the same key, or under
+        SCAN_RUNS the run of consecutive equal keys; SCAN_EXCLUSIVE: the result of the predecessor in the group, the low
+        value_bytes bytes of `first` at a group's first position.  d_values 0: every value is 1 (ranks).  d_out_num (0:
+        none) receives the number of groups.  d_keys and d_values are only read; d_out may be d_values."""
+        self._check(self._L.rsx_scan_by_key_device(self._h, d_keys or None, d_values or None, n, key_bytes, key_kind, value_bytes, value_kind,
+                                                   op, flags, first & 0xFFFFFFFFFFFFFFFF, d_out or None, d_out_num or None, stream))
+
 
     @staticmethod
     def _key_columns(columns):
@@ -1113,6 +1128,114 @@ def radix_reduce_by_key(keys, values, op: str = "sum", descending: bool = False,
         c.reduce_by_key_device(keys.data_ptr(), values.data_ptr(), n, kb, kind, vt[0], vt[1], _REDUCE_OPS[op], out_keys.data_ptr(),
                                out_values.data_ptr(), out_offsets.data_ptr() if offsets else 0, num.data_ptr(), descending, stream)
     return Reduced(num, out_keys, out_values, out_offsets)
+
+
+def scan_by_key_caps(key_bytes: int, value_bytes: int, runs: bool = False):
+    """rsx_scan_by_key_caps -> (tile, scan_span): the elements one workgroup of the count and write kernels of
+    radix_scan_by_key takes for these widths and this group rule, and the tiles one sweep of the scan kernel takes.
+    Needs no device."""
+    L = _lib.load()
+    tile, span = ctypes.c_uint32(), ctypes.c_uint32()
+    rc = L.rsx_scan_by_key_caps(key_bytes, value_bytes, _lib.SCAN_RUNS if runs else 0, ctypes.byref(tile), ctypes.byref(span))
+    _check_rc(L, rc)
+    return int(tile.value), int(span.value)
+
+
+def _scan_first_bits(first, op: str, dtype) -> int:
+    """The bit pattern, as an unsigned integer, of what an exclusive scan stores at a group's first position: `first`, or
+    for None 0 ("sum"), the type's largest value ("min", +inf for floats) or its smallest ("max", -inf)."""
+    import torch
+    name = str(dtype).split(".")[-1]
+    nd = np.dtype(name)
+    if first is None:
+        if op == "sum":
+            first = 0
+        elif nd.kind == "f":
+            first = float("inf") if op == "min" else float("-inf")
+        else:
+            info = np.iinfo(nd)
+            first = info.max if op == "min" else info.min
+    elif isinstance(first, torch.Tensor):
+        raise TypeError("first must be a Python number (it is an argument of the launch, not a device value)")
+    if nd.kind != "f" and (isinstance(first, bool) or not isinstance(first, (int, np.integer))):
+        raise TypeError(f"first must be an integer for {name} values, not {first!r}")
+    if nd.kind != "f" and not (np.iinfo(nd).min <= int(first) <= np.iinfo(nd).max):
+        raise ValueError(f"first={first} does not fit {name}")
+    word = np.array([first], dtype=nd).view(np.uint32 if nd.itemsize == 4 else np.uint64)
+    return int(word[0])
+
+
+def radix_scan_by_key(keys, values, op: str = "sum", exclusive: bool = False, first=None, runs: bool = False, out=None,
+                      return_num: bool = False, index_dtype=None, ctx: Optional[Context] = None, key_kind: Optional[int] = None):
+    """The running `op` of `values` inside every group of `keys` (rsx_scan_by_key_device), one result per row at the
+    row's own position, without synchronising: groupby().cumsum() / cummin() / cummax() and, with values=None,
+    cumcount() / row_number().
+
+    runs=False  the group of a row is every row with the same key, anywhere in `keys` (a stable sort of (key, position)
+                elements in the workspace finds them; rows of a group are taken in input order).
+    runs=True   the group of a row is the run of CONSECUTIVE rows with its key: nothing is sorted, the call streams the two
+                columns, and a key that appears again later starts a new group.
+    exclusive   a row receives the result of its predecessor in the group, and the first row of every group `first`,
+                which is stored and never combined: None is 0 for "sum", the dtype's largest value for "min" (+inf for
+                floats) and its smallest for "max" (-inf).
+    values=None every value is 1: the result, int64 or with index_dtype=torch.int32 int32, is the 1-based rank of the row
+                in its group, or exclusive the 0-based rank.  Only with op="sum".
+
+    Returns a tensor like `values`, or `out` when given (same dtype, shape and device as `values`; it may be `values`
+    itself); with return_num=True the pair (out, num), num a 0-d int64 device tensor: the number of groups (runs).
+    `keys` follows the rules of radix_group (bit-pattern equality: -0.0 and +0.0 are two keys) and is not modified; `values`
+    and the operators follow radix_reduce_by_key: integer sums wrap, float minima and maxima follow the total order on bit
+    patterns, and a float sum is added in an order fixed by the input's size, the group's start and the row's rank alone,
+    so the same input gives the same bits on every call (there are no atomics)."""
+    import torch
+    kb, kind, n = _pairs_keys(keys, key_kind)
+    if op not in _REDUCE_OPS:
+        raise ValueError(f"op must be 'sum', 'min' or 'max', not {op!r}")
+    if values is None:
+        if op != "sum":
+            raise ValueError(f"values=None (the count form) takes op='sum', not {op!r}")
+        dtype = _index_dtype(index_dtype)
+        vt = _reduce_value_types()[dtype]
+    else:
+        if not isinstance(values, torch.Tensor):
+            raise TypeError("values must be a torch tensor on a GPU or None")
+        if index_dtype is not None:
+            raise ValueError("index_dtype= is for values=None; the result has the dtype of values")
+        vt = _reduce_value_types().get(values.dtype)
+        if vt is None:
+            raise ValueError(f"values must be int32, int64, float32, float64, uint32 or uint64, not {values.dtype}")
+        if values.dim() != 1 or values.shape[0] != n:
+            raise ValueError(f"values must be 1-D with one entry per key ({n}), not of shape {tuple(values.shape)}")
+        if not values.is_contiguous():
+            raise ValueError("values must be contiguous")
+        if values.device != keys.device:
+            raise ValueError(f"keys and values must be on the same device ({keys.device}, {values.device})")
+        dtype = values.dtype
+    if out is not None:
+        if not isinstance(out, torch.Tensor):
+            raise TypeError("out must be a torch tensor on a GPU")
+        if out.dtype != dtype or out.dim() != 1 or out.shape[0] != n:
+            raise ValueError(f"out must be 1-D of dtype {dtype} with one entry per key ({n}), not {out.dtype} of shape {tuple(out.shape)}")
+        if not out.is_contiguous():
+            raise ValueError("out must be contiguous")
+        if out.device != keys.device:
+            raise ValueError(f"keys and out must be on the same device ({keys.device}, {out.device})")
+    bits = _scan_first_bits(first, op, dtype)
+    _pairs_device(keys, None, "")
+    if n >= 1 << 32:
+        raise ValueError("radix_scan_by_key takes fewer than 2^32 keys")
+    if out is None:
+        out = torch.empty(n, dtype=dtype, device=keys.device)
+    num = torch.empty((), dtype=torch.int64, device=keys.device) if return_num else None
+    if n == 0:  # (empty tensors have no address to hand to the C call)
+        if return_num:
+            num.zero_()
+        return (out, num) if return_num else out
+    flags = (_lib.SCAN_EXCLUSIVE if exclusive else 0) | (_lib.SCAN_RUNS if runs else 0)
+    with _on_device(keys, ctx) as (c, stream):
+        c.scan_by_key_device(keys.data_ptr(), values.data_ptr() if values is not None else 0, n, kb, kind, vt[0], vt[1], _REDUCE_OPS[op],
+                             flags, bits, out.data_ptr(), num.data_ptr() if return_num else 0, stream)
+    return (out, num) if return_num else out
 
 
 def radix_unique(keys, return_inverse: bool = False, return_counts: bool = False, descending: bool = False,

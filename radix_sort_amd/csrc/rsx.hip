@@ -1058,6 +1058,7 @@ int rsx_ctx_get_info(rsx_ctx* ctx, int what, uint64_t* out) try {
                 case PATH_SETOP:   // bits 0-7 the kernels launched
                 case PATH_JOIN:    // bits 0-7 the kernels launched
                 case PATH_MERGE:   // bits 0-7 the kernels launched, bit 8 the wide-value route
+                case PATH_SCAN:    // bits 0-7 the kernels launched after any sort, bit 8 RSX_SCAN_RUNS
                     *out = (uint64_t)(ctx->last_sort_passes & 0x1FFu) | (uint64_t)ctx->last_path << 24;
                     return RSX_OK;
                 default: break;
@@ -2194,6 +2195,130 @@ int rsx_ctx_reserve_reduce(rsx_ctx* ctx, size_t n, uint32_t key_bytes, uint32_t 
 int rsx_reduce_caps(uint32_t key_bytes, uint32_t value_bytes, uint32_t* tile, uint32_t* scan_span) {
     if (!tile || !scan_span || !key_widths_ok(key_bytes, RSX_KEY_UNSIGNED) || !reduce_value_ok(value_bytes, RSX_KEY_UNSIGNED)) return RSX_ERR_ARG;
     *tile = reduce_tile_elems(key_bytes, value_bytes);
+    *scan_span = reduce_scan_span();
+    return RSX_OK;
+}
+
+// ---- scan by key (rsx_scan_kernels.hpp, include/rsx.h) ----
+namespace {
+// The workspace of one rsx_scan_by_key_device call: for the grouped form the two arrays of joined (mapped key, u32
+// position) elements and the column of gathered values; the four per-tile arrays; one word for the number of groups.
+struct ScanPlan {
+    JoinedPlan j;       // RSX_SCAN_RUNS: only its ws, nothing is joined
+    size_t column_off;  // values [n] in sorted order (grouped form)
+    size_t heads_off;   // tile_heads [tiles] u32
+    size_t base_off;    // tile_base [tiles] u64
+    size_t tail_off;    // tile_tail [tiles] u64
+    size_t carry_off;   // tile_carry [tiles] u64
+    size_t num_off;     // one u64
+};
+ScanPlan scan_plan(size_t n, uint32_t kb, uint32_t vb, bool runs) {
+    ScanPlan P{};
+    if (!runs) {
+        P.j = joined_plan(n, kb, 4);
+        P.column_off = P.j.ws.take(n * (size_t)vb);
+    }
+    const uint32_t tile = scan_tile_elems(kb, runs);
+    const size_t tiles = (n + tile - 1) / tile;
+    P.heads_off = P.j.ws.take(tiles * sizeof(uint32_t));
+    P.base_off = P.j.ws.take(tiles * sizeof(uint64_t));
+    P.tail_off = P.j.ws.take(tiles * sizeof(uint64_t));
+    P.carry_off = P.j.ws.take(tiles * sizeof(uint64_t));
+    P.num_off = P.j.ws.take(sizeof(uint64_t));
+    return P;
+}
+constexpr uint32_t SCAN_FLAGS = RSX_SCAN_EXCLUSIVE | RSX_SCAN_RUNS;
+}  // namespace
+
+int rsx_scan_by_key_device(rsx_ctx* ctx, const void* d_keys, const void* d_values, size_t n, uint32_t key_bytes, uint32_t key_kind,
+                           uint32_t value_bytes, uint32_t value_kind, int op, uint32_t flags, uint64_t first, void* d_out, uint64_t* d_out_num,
+                           void* stream) try {
+    if (!ctx) return RSX_ERR_ARG;
+    if (!key_widths_ok(key_bytes, key_kind)) return fail(ctx, RSX_ERR_ARG, "invalid key width or kind");
+    if (!reduce_value_ok(value_bytes, value_kind)) return fail(ctx, RSX_ERR_ARG, "invalid value width or kind");
+    if (op != RSX_REDUCE_SUM && op != RSX_REDUCE_MIN && op != RSX_REDUCE_MAX) return fail(ctx, RSX_ERR_ARG, "invalid operator");
+    if (flags & ~SCAN_FLAGS) return fail(ctx, RSX_ERR_ARG, "unknown flag bits");
+    if (!d_values && (op != RSX_REDUCE_SUM || value_kind == RSX_KEY_FLOAT))
+        return fail(ctx, RSX_ERR_ARG, "the count form (d_values NULL) takes RSX_REDUCE_SUM and an integer value kind");
+    if (n > 0 && (!d_keys || !d_out)) return fail(ctx, RSX_ERR_ARG, "null device pointer");
+    if (!aligned(d_keys, key_bytes) || !aligned(d_values, value_bytes) || !aligned(d_out, value_bytes) || !aligned(d_out_num, 8))
+        return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
+    if (!unique_size_ok(n)) return fail(ctx, RSX_ERR_UNSUPPORTED, "2^32 or more keys");
+    // (d_out may be d_values; the key in front of a thread's rows is read while other threads store)
+    if (int rc = check_disjoint(ctx, {{d_keys, (uint64_t)n * key_bytes}}, {{d_out, (uint64_t)n * value_bytes}, {d_out_num, d_out_num ? 8u : 0u}})) return rc;
+    const bool runs = (flags & RSX_SCAN_RUNS) != 0;
+    const uint32_t runs_bit = runs ? 0x100u : 0u;
+    RSX_ENTER(stream);
+    const hipStream_t st = held.st;
+    if (n == 0) {  // no group: one memset and no kernel
+        if (d_out_num) RSX_HIP(hipMemsetAsync(d_out_num, 0, sizeof(uint64_t), st));
+        note_path(ctx, PATH_SCAN, runs_bit);
+        return RSX_OK;
+    }
+    const ScanPlan P = scan_plan(n, key_bytes, d_values ? value_bytes : 0u, runs);
+    if (!runs && (P.j.inner.elem_bytes == 0 || !launchers_for(P.j.inner.elem_bytes)))
+        return fail(ctx, RSX_ERR_INTERNAL, "no joined element for this key width");
+    int rc = pending_error(ctx);
+    if (rc) return rc;
+    if (runs) {
+        rc = ensure_aux(ctx, st);
+        if (rc) return rc;
+        rc = ensure_any(ctx, P.j.ws.bytes, st);
+    } else {
+        rc = reserve_joined(ctx, P.j, st);
+    }
+    if (rc) return rc;
+    Enqueue enq(ctx, st);  // the workspace arrays belong to this call from the first launch on
+    char* w0 = ctx->any_buf;
+    if (!runs) {
+        // the join of rsx_argsort_device: ascending (mapped key, u32 position), so every group in input order
+        rc = joined_sort(ctx, P.j, d_keys, nullptr, true, key_kind, 0, st, &w0);
+        if (rc) return rc;
+    }
+    ScanCall c{};
+    c.runs = runs;
+    c.keys = runs ? d_keys : static_cast<const void*>(w0);
+    c.values = d_values;
+    c.column = (!runs && d_values) ? w0 + P.column_off : nullptr;
+    c.tile_heads = reinterpret_cast<uint32_t*>(w0 + P.heads_off);
+    c.tile_base = reinterpret_cast<uint64_t*>(w0 + P.base_off);
+    c.tile_tail = reinterpret_cast<uint64_t*>(w0 + P.tail_off);
+    c.tile_carry = reinterpret_cast<uint64_t*>(w0 + P.carry_off);
+    c.n = n;
+    c.kb = key_bytes;
+    c.vb = value_bytes;
+    c.vkind = value_kind;
+    c.op = (uint32_t)op;
+    c.exclusive = (flags & RSX_SCAN_EXCLUSIVE) != 0;
+    c.first = first;
+    c.out = d_out;
+    c.out_num = d_out_num ? d_out_num : reinterpret_cast<uint64_t*>(w0 + P.num_off);
+    uint32_t launched = 0;
+    rc = launch_scan_by_key(ctx, c, &launched, st);
+    if (rc) return rc;
+    note_path(ctx, PATH_SCAN, launched | runs_bit);
+    return RSX_OK;
+} catch (...) {
+    return RSX_ERR_HIP;
+}
+
+int rsx_ctx_reserve_scan_by_key(rsx_ctx* ctx, size_t n, uint32_t key_bytes, uint32_t value_bytes, uint32_t flags) try {
+    if (!ctx) return RSX_ERR_ARG;
+    if (!key_widths_ok(key_bytes, RSX_KEY_UNSIGNED)) return fail(ctx, RSX_ERR_ARG, "invalid key width");
+    if (!reduce_value_ok(value_bytes, RSX_KEY_UNSIGNED)) return fail(ctx, RSX_ERR_ARG, "invalid value width");
+    if (flags & ~SCAN_FLAGS) return fail(ctx, RSX_ERR_ARG, "unknown flag bits");
+    if (!unique_size_ok(n)) return fail(ctx, RSX_ERR_UNSUPPORTED, "2^32 or more keys");
+    const bool runs = (flags & RSX_SCAN_RUNS) != 0;
+    const ScanPlan P = scan_plan(n, key_bytes, value_bytes, runs);
+    return runs ? reserve_any_entry(ctx, P.j.ws.bytes) : reserve_joined_entry(ctx, P.j);
+} catch (...) {
+    return RSX_ERR_NOMEM;
+}
+
+int rsx_scan_by_key_caps(uint32_t key_bytes, uint32_t value_bytes, uint32_t flags, uint32_t* tile, uint32_t* scan_span) {
+    if (!tile || !scan_span || !key_widths_ok(key_bytes, RSX_KEY_UNSIGNED) || !reduce_value_ok(value_bytes, RSX_KEY_UNSIGNED) || (flags & ~SCAN_FLAGS))
+        return RSX_ERR_ARG;
+    *tile = scan_tile_elems(key_bytes, (flags & RSX_SCAN_RUNS) != 0);
     *scan_span = reduce_scan_span();
     return RSX_OK;
 }

@@ -4,7 +4,8 @@
 //                   so the eight sizes build in parallel), reached through that size's EsLaunchers table
 //   rsx_pairs.hip   the join and split kernels of the key / value calls
 //   rsx_unique.hip  the run kernels of rsx_unique_device
-//   rsx_reduce.hip  those of rsx_reduce_by_key_device
+//   rsx_scan.hip    the kernels of rsx_scan_by_key_device and, through rsx_reduce.hip, which it includes, the run kernels
+//                   of rsx_reduce_by_key_device
 //   rsx_search.hip  the kernel of rsx_search_sorted_device and, built from its functions, those of rsx_join_device
 //   rsx_merge.hip   the kernels of rsx_merge_device
 //   rsx_setops.hip  the kernel of rsx_setop_device
@@ -85,6 +86,7 @@ enum : uint32_t {
     PATH_MERGE = 11,
     PATH_SETOP = 12,
     PATH_JOIN = 13,
+    PATH_SCAN = 14,      // scan by key
 };
 
 // option bits (rsx_ctx_set_option): alternative kernel paths, all bit-exact
@@ -631,6 +633,27 @@ struct ReduceCall {
 int launch_reduce(rsx_ctx* ctx, const ReduceCall& call, uint32_t* launched, hipStream_t st);
 uint32_t reduce_tile_elems(uint32_t kb, uint32_t vb);  // elements per workgroup of the count and write kernels
 uint32_t reduce_scan_span();                           // tiles per sweep of the scan kernel's loop
+
+// What one rsx_scan_by_key_device call asks of the scan kernels (rsx_scan.hip, rsx_scan_kernels.hpp).
+struct ScanCall {
+    bool runs;                // RSX_SCAN_RUNS: the keys as they lie; else the sorted elements of the grouped form
+    const void* keys;         // runs: the caller's n keys; else n sorted joined (mapped key, u32 position) elements
+    const void* values;       // the caller's n values, only read; null: the count form, every value the integer 1
+    void* column;             // grouped form with values: the workspace column of n values in sorted order
+    uint32_t* tile_heads;     // per tile of scan_tile_elems, with the meaning they have in ReduceCall
+    uint64_t* tile_base;
+    uint64_t* tile_tail;
+    uint64_t* tile_carry;
+    size_t n;
+    uint32_t kb;
+    uint32_t vb, vkind, op;
+    bool exclusive;
+    uint64_t first;           // its low vb bytes: what the first element of every group receives (exclusive)
+    void* out;                // n results of vb bytes by input position; may be `values`
+    uint64_t* out_num;        // the number of groups (runs): the caller's word or a workspace word
+};
+int launch_scan_by_key(rsx_ctx* ctx, const ScanCall& call, uint32_t* launched, hipStream_t st);
+uint32_t scan_tile_elems(uint32_t kb, bool runs);  // elements per workgroup of the count and write kernels
 
 // What one rsx_search_sorted_device call asks of the search kernel (rsx_search.hip, rsx_search_kernels.hpp).
 struct SearchCall {

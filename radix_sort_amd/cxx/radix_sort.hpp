@@ -15,6 +15,7 @@
 //     rsx::radix_argsort(const K* d_keys, I* d_index, size_t n, bool descending, hipStream_t)
 //     rsx::unique(const K* d_keys, size_t n, K* keys, uint64_t* offsets, I* perm, I* inverse, uint64_t* num, bool descending, hipStream_t)
 //     rsx::reduce_by_key(const K* d_keys, const V* d_values, size_t n, int op, K* keys, V* values, uint64_t* offsets, uint64_t* num, bool descending, hipStream_t)
+//     rsx::scan_by_key(const K* d_keys, const V* d_values, size_t n, int op, V* d_out, bool exclusive, V first, bool runs, uint64_t* num, hipStream_t)
 //     rsx::search_sorted(const K* d_sorted, size_t n, const K* d_needles, size_t m, I* lower, I* upper, bool descending, const uint64_t* d_sorted_num, bool presort, hipStream_t)
 //     rsx::merge(const K* d_a_keys, size_t na, const K* d_b_keys, size_t nb, K* d_out_keys, bool descending, hipStream_t)   // two sorted arrays
 //     rsx::merge_pairs(const K* d_a_keys, const V* d_a_values, size_t na, const K* d_b_keys, const V* d_b_values, size_t nb, K* keys, V* values[, I* index], bool descending, hipStream_t)
@@ -258,6 +259,29 @@ void reduce_by_key(const K* d_keys, const V* d_values, size_t n, int op, K* d_ou
                                        descending ? RSX_ORDER_DESCENDING : RSX_ORDER_ASCENDING, d_out_keys, d_out_values, d_out_offsets,
                                        d_out_num, stream),
               "rsx_reduce_by_key_device");
+}
+
+// One result per ROW (rsx_scan_by_key_device): d_out[q] the running sum (RSX_REDUCE_SUM), minimum or maximum of the values
+// of q's group up to and including q -- the group being every row with q's key or, with runs, the run of consecutive
+// rows with it (nothing is sorted then).  exclusive: the result of q's predecessor in the group, and `first`, stored and
+// never combined, at a group's first row.  d_values == nullptr is the count form: every value is V(1) (V an integer, op
+// RSX_REDUCE_SUM), the results are 1-based ranks, or exclusive with first = 0 the 0-based ones.  d_out_num (optional)
+// receives the number of groups.  V and the operators as in reduce_by_key; d_out may be d_values and must not overlap
+// d_keys.  Stream-ordered, never synchronised (rsx_ctx_reserve_scan_by_key before a stream capture).
+template <typename K, typename V>
+void scan_by_key(const K* d_keys, const V* d_values, size_t n, int op, V* d_out, bool exclusive = false, V first = V(), bool runs = false,
+                 uint64_t* d_out_num = nullptr, void* stream = nullptr, Context& ctx = default_context()) {
+    static_assert(std::is_arithmetic<V>::value && !std::is_same<V, bool>::value && (sizeof(V) == 4 || sizeof(V) == 8),
+                  "values are 4- or 8-byte integers or floats");
+    const rsx_layout L = RadixDigits<K>::layout();
+    if (L.key_offset != 0 || L.key_bytes != L.elem_bytes) throw std::invalid_argument("scan_by_key: the key type must be its own key");
+    const uint32_t vkind = std::is_floating_point<V>::value ? RSX_KEY_FLOAT : std::is_signed<V>::value ? RSX_KEY_SIGNED : RSX_KEY_UNSIGNED;
+    uint64_t bits = 0;
+    std::memcpy(&bits, &first, sizeof(V));  // (little-endian: the low sizeof(V) bytes)
+    ctx.check(rsx_scan_by_key_device(ctx.get(), d_keys, d_values, n, L.key_bytes, L.key_kind, (uint32_t)sizeof(V), vkind, op,
+                                     (exclusive ? (uint32_t)RSX_SCAN_EXCLUSIVE : 0u) | (runs ? (uint32_t)RSX_SCAN_RUNS : 0u), bits, d_out, d_out_num,
+                                     stream),
+              "rsx_scan_by_key_device");
 }
 
 // Where m needles fall in n keys sorted in that order (rsx_search_sorted_device): d_out_lower[i] the number of the sorted

@@ -105,6 +105,14 @@ extern "C" {
                            stream: *mut c_void) -> c_int;
     pub fn rsx_ctx_reserve_join(ctx: *mut RsxCtx, na: usize, key_bytes: u32) -> c_int;
     pub fn rsx_join_caps(key_bytes: u32, tile: *mut u32, window: *mut u32, rows: *mut u32) -> c_int;
+    // scan by key (include/rsx.h, "scan by key"): op is RSX_REDUCE_SUM (0), _MIN (1), _MAX (2); flags RSX_SCAN_EXCLUSIVE (1)
+    // and RSX_SCAN_RUNS (2); one result per row at the row's position; d_values null: every value is 1 (ranks);
+    // `first` is what the first row of every group receives in an exclusive scan; d_out_num may be null
+    pub fn rsx_scan_by_key_device(ctx: *mut RsxCtx, d_keys: *const c_void, d_values: *const c_void, n: usize, key_bytes: u32,
+                                  key_kind: u32, value_bytes: u32, value_kind: u32, op: c_int, flags: u32, first: u64,
+                                  d_out: *mut c_void, d_out_num: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn rsx_ctx_reserve_scan_by_key(ctx: *mut RsxCtx, n: usize, key_bytes: u32, value_bytes: u32, flags: u32) -> c_int;
+    pub fn rsx_scan_by_key_caps(key_bytes: u32, value_bytes: u32, flags: u32, tile: *mut u32, scan_span: *mut u32) -> c_int;
     pub fn rsx_sort_sharded(ctxs: *const *mut RsxCtx, ndev: u32, d_slices: *const *mut c_void,
                             d_tmps: *const *mut c_void, n_per_dev: *const usize,
                             layout: *const RsxLayout) -> c_int;
