@@ -970,6 +970,53 @@ __device__ __forceinline__ void direct_rank(const unsigned char* smem, const uin
     }
 }
 
+// How a thread of the direct kernel takes its KPT elements of a bucket, and in how many steps.
+// 8-byte elements, 512 and 1024 threads: a thread takes KPT / 2 16-byte words of two neighbours each (and an odd KPT's last
+// element by itself).  A bucket starts on an 8-byte boundary only; gfx950 takes 16-byte loads at that alignment.  (The
+// 256-thread form, three workgroups per CU, measured slower with them: 2^27 u64 1.79 -> 1.81 ms.)  Those forms PIPELINE the
+// load (see the kernel): part 0 is the first PRE words, part 1 everything else; the other forms have part 1 only.
+// PRE = 3 is measured (2^30 u64, the kernel's ms per launch): none ahead of the rank loop 4.39, 1: 4.28, 2: 4.19, 3: 4.17,
+// 4: 4.28, 5: 4.41, 6: 4.54, all: 4.75, where the load at the top of the trip took 4.50 -- registers allow them all.
+template <int ES, int KPT, int WG>
+struct DirectLoad {
+    using E = Elem<ES>;
+    static constexpr bool LOAD16 = ES == 8 && WG >= 512;
+    static constexpr int NPAIR = LOAD16 ? KPT / 2 : 0;
+    static constexpr bool PIPE = LOAD16;
+    static constexpr int PRE = PIPE ? 3 : 0;
+    static_assert(PRE <= NPAIR, "part 0 is 16-byte words");
+    static __device__ __forceinline__ uint32_t pos_of(const int j, const uint32_t tid) {  // which element of the bucket e[j] is
+        if (j < 2 * NPAIR) return 2u * ((uint32_t)(j >> 1) * WG + tid) + (uint32_t)(j & 1);
+        return (uint32_t)j * WG + tid;
+    }
+    // Part PART of the n elements at `bucket` into e[]: the slots of the part past n are zero, the others are not touched.
+    // Reads nothing outside [bucket, bucket + n).
+    template <int PART>
+    static __device__ __forceinline__ void load(const E* __restrict__ bucket, const uint32_t n, const uint32_t tid, E (&e)[KPT]) {
+        typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+        typedef v4u v4u_a8 __attribute__((aligned(8)));
+#pragma unroll
+        for (int jj = (PART == 0 ? 0 : PRE); jj < (PART == 0 ? PRE : NPAIR); ++jj) {  // (two ifs, no else: the loads of all rounds stay in flight together)
+            const uint32_t i = pos_of(2 * jj, tid);
+            e[2 * jj] = E{};
+            e[2 * jj + 1] = E{};
+            if (i + 1u < n) {
+                const v4u v = *reinterpret_cast<const v4u_a8*>(bucket + i);
+                e[2 * jj].w[0] = v.x, e[2 * jj].w[1] = v.y, e[2 * jj + 1].w[0] = v.z, e[2 * jj + 1].w[1] = v.w;
+            }
+            if (i + 1u == n) e[2 * jj] = bucket[i];  // the bucket's last element, alone in its word
+        }
+        if constexpr (PART == 1) {
+#pragma unroll
+            for (int j = 2 * NPAIR; j < KPT; ++j) {  // plain store order: nothing rests on which thread holds what
+                const uint32_t i = (uint32_t)j * WG + tid;
+                e[j] = E{};
+                if (i < n) e[j] = bucket[i];
+            }
+        }
+    }
+};
+
 template <int ES, int KPT, int WG>
 __global__ __launch_bounds__(WG, RSX_B16_WAVES(WG)) void rsx_bucket16_direct_kernel(const SmallArgs a, const uint64_t* __restrict__ starts,
                                                                                 const WidePlan* __restrict__ plan, unsigned char* __restrict__ done,
@@ -1023,47 +1070,51 @@ __global__ __launch_bounds__(WG, RSX_B16_WAVES(WG)) void rsx_bucket16_direct_ker
         if (tid == 0 && left_here != 0) atomicAdd(left, left_here);
         return;
     }
-    for (uint32_t g = blockIdx.x; g < 65536u; g += gridDim.x) {
-        const uint64_t start = starts[g];
-        const uint64_t count = starts[g + 1] - start;  // (the same for every thread: uniform control flow below)
-        if (count == 0 || count > (uint64_t)CAPE) {
+    // THE PIPELINED LOAD (8-byte elements, 512 and 1024 threads).  e[], the registers that receive a bucket, are dead from the
+    // scatter to LDS on -- the rank loop works from LDS alone -- so the loads of the NEXT bucket this workgroup sorts are
+    // issued once the scatter is behind its barrier: the first PRE 16-byte words ahead of the rank loop, the rest directly
+    // behind it, and the next trip finds e[] filled and goes straight to the counting pass.  No LDS is added.  There is ONE
+    // place in the loop where a bucket is loaded and so one set of registers for it: `next_sorted` walks past the buckets
+    // that are left (empty, above cape(): marked and counted as they always were) to the next one that is sorted here, or
+    // to the end, and only that bucket is fetched -- no byte is read twice or for nothing, and a trip never starts on a
+    // bucket that is not in e[].  The hand-over's `break` comes before its trip has issued anything, so no load is in
+    // flight then; what it abandons is the bucket in e[], which the kernels behind this one read again (as they did when
+    // that bucket was loaded at the top of its trip).
+    // Why the early read is safe: the bucket is sorted by this workgroup only, the sweeps that wrote it finished before the
+    // launch, and rsx_bucket16_kernel runs after it -- nobody writes those bytes between the read and their use.
+    using L = DirectLoad<ES, KPT, WG>;
+    auto pos_of = [&](const int j) -> uint32_t { return L::pos_of(j, tid); };
+    // The first of g, g + gridDim.x, ... that this kernel sorts (65536 or more: none), where it lies and how many it holds;
+    // the ones passed over are marked and counted.  The same in every thread.
+    auto next_sorted = [&](uint32_t g, E*& bucket, uint32_t& n) -> uint32_t {
+        for (; g < 65536u; g += gridDim.x) {
+            const uint64_t start = starts[g];
+            const uint64_t count = starts[g + 1] - start;
+            if (count != 0 && count <= (uint64_t)CAPE) {
+                bucket = static_cast<E*>(a.data) + start;
+                n = (uint32_t)count;
+                break;
+            }
             if (tid == 0) done[g] = 0;
             left_here += count != 0 ? 1u : 0u;
-            continue;
         }
-        const uint32_t n = (uint32_t)count;
-        E* bucket = static_cast<E*>(a.data) + start;
+        return g;
+    };
+    E e[KPT];
+    E* bucket = nullptr;
+    uint32_t n = 0;
+    uint32_t g = next_sorted(blockIdx.x, bucket, n);
+    if constexpr (L::PIPE) {
+        if (g < 65536u) {  // the workgroup's first bucket
+            L::template load<0>(bucket, n, tid, e);
+            L::template load<1>(bucket, n, tid, e);
+        }
+    }
+    while (g < 65536u) {
         reinterpret_cast<uint4*>(s_cnt)[tid] = uint4{0u, 0u, 0u, 0u};
-        E e[KPT];
-        // 8-byte elements, 512 and 1024 threads: a thread takes KPT / 2 16-byte words of two neighbours each (and an odd
-        // KPT's last element by itself).  A bucket starts on an 8-byte boundary only; gfx950 takes 16-byte loads at that
-        // alignment.  (The 256-thread form, three workgroups per CU, measured slower with them: 2^27 u64 1.79 -> 1.81 ms.)
-        constexpr bool LOAD16 = ES == 8 && WG >= 512;
-        constexpr int NPAIR = LOAD16 ? KPT / 2 : 0;
-        auto pos_of = [&](const int j) -> uint32_t {  // which element of the bucket e[j] is
-            if (j < 2 * NPAIR) return 2u * ((uint32_t)(j >> 1) * WG + tid) + (uint32_t)(j & 1);
-            return (uint32_t)j * WG + tid;
-        };
-        if constexpr (LOAD16) {
-            typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-            typedef v4u v4u_a8 __attribute__((aligned(8)));
-#pragma unroll
-            for (int jj = 0; jj < NPAIR; ++jj) {  // (two ifs, no else: the loads of all rounds stay in flight together)
-                const uint32_t i = pos_of(2 * jj);
-                e[2 * jj] = E{};
-                e[2 * jj + 1] = E{};
-                if (i + 1u < n) {
-                    const v4u v = *reinterpret_cast<const v4u_a8*>(bucket + i);
-                    e[2 * jj].w[0] = v.x, e[2 * jj].w[1] = v.y, e[2 * jj + 1].w[0] = v.z, e[2 * jj + 1].w[1] = v.w;
-                }
-                if (i + 1u == n) e[2 * jj] = bucket[i];  // the bucket's last element, alone in its word
-            }
-        }
-#pragma unroll
-        for (int j = 2 * NPAIR; j < KPT; ++j) {  // plain store order: nothing rests on which thread holds what
-            const uint32_t i = (uint32_t)j * WG + tid;
-            e[j] = E{};
-            if (i < n) e[j] = bucket[i];
+        if constexpr (!L::PIPE) {
+            L::template load<0>(bucket, n, tid, e);
+            L::template load<1>(bucket, n, tid, e);
         }
         __syncthreads();
         uint32_t rk[KPT];
@@ -1105,6 +1156,13 @@ __global__ __launch_bounds__(WG, RSX_B16_WAVES(WG)) void rsx_bucket16_direct_ker
         for (int j = 0; j < KPT; ++j)
             if (pos_of(j) < n) s[start_of(digit_of(e[j])) + rk[j]] = e[j];
         __syncthreads();
+        // e[] is free: the next bucket's first words, in flight during the rank loop
+        E* next = nullptr;
+        uint32_t n_next = 0;
+        const uint32_t g_next = next_sorted(g + gridDim.x, next, n_next);
+        if constexpr (L::PIPE) {
+            if (g_next < 65536u) L::template load<0>(next, n_next, tid, e);
+        }
         // the exact rank, one 16-byte word of the tile per thread and round
         const uint32_t words = (n + G - 1) / G;
         auto rank_word = [&](const uint32_t q0, const bool live, const uint32_t q, E (&x)[G], uint32_t (&r)[G]) {
@@ -1147,8 +1205,12 @@ __global__ __launch_bounds__(WG, RSX_B16_WAVES(WG)) void rsx_bucket16_direct_ker
                     if (r[h] < n) bucket[r[h]] = y;  // (always: a place outside the bucket is never written, whatever the ranks)
                 }
         }
+        if constexpr (L::PIPE) {
+            if (g_next < 65536u) L::template load<1>(next, n_next, tid, e);  // the rest of the next bucket
+        }
         if (tid == 0) done[g] = 1;
         __syncthreads();  // smem belongs to the next bucket
+        g = g_next, bucket = next, n = n_next;
     }
     if (tid == 0 && left_here != 0) atomicAdd(left, left_here);
 }
