@@ -205,6 +205,9 @@ enum {
                                  count-only form, 3 otherwise -- and bits 8-23 are 0),
                                  14 scan by key (rsx_scan_by_key_device: bits 0-7 are then the kernels launched after
                                  any sort, bit 8 is set under RSX_SCAN_RUNS, bits 9-23 are 0),
+                                 15 order statistics (rsx_select_device: bits 0-7 are then the kernels launched, bits
+                                 8-11 are 0 when the candidates were never compacted, else 1 + the level after which
+                                 they were -- read from the device, so this waits for the call --, bits 12-23 are 0),
                                  bits 28-29 the route of a layout without kernels of its own: 0 direct, 1 packed
                                  re-layout, 2 key-index proxy (bits 0-27 then describe the sort of the re-laid-out
                                  elements / of the proxies) */
@@ -767,6 +770,43 @@ int rsx_ctx_reserve_join(rsx_ctx *ctx, size_t na, uint32_t key_bytes);
  * key_bytes + 8 * key_bytes + 160 bytes at most, the write kernel 8 * rows + 32 bytes at most, the scan kernel 32 bytes;
  * every one leaves more than two workgroups per CU. */
 int rsx_join_caps(uint32_t key_bytes, uint32_t *tile, uint32_t *window, uint32_t *rows);
+
+/* -- order statistics of an unsorted key array -------------------------------- */
+/* The elements at given ranks of the stable sort, without sorting.  With p the permutation rsx_argsort_device produces for
+ * these keys in `order` (by mapped key, complemented for descending order; equal keys in input order; floats by the total
+ * order on bit patterns), for every q < nranks
+ *     d_out_keys[q]  = keys[p[ranks[q]]]     (the raw key bytes)
+ *     d_out_index[q] = p[ranks[q]]           (index_bytes 4 or 8; 4 with n >= 2^32: RSX_ERR_UNSUPPORTED)
+ * -- column ranks[q] of the full stable sort, byte for byte, the rule of rsx_topk_rows_device.  Key widths, kinds and
+ * alignment as rsx_argsort_device; d_keys is only read.  `ranks` is a HOST array, read during the call and handed to the
+ * kernels by value (no copy is enqueued, so the call can be captured into a graph); ranks may repeat and come in any
+ * order, every one below n, and nranks <= max_ranks of rsx_select_caps.  Either output may be null, not both.
+ * nranks == 0 succeeds, launches nothing and looks at no pointer.  Stream-ordered, no synchronisation, the host reads
+ * nothing from the device; nothing outside the nranks output keys and nranks indices is written.
+ *
+ * A counting select: levels of digit_bits bits run over the mapped key from the top.  Each level counts one digit of the
+ * keys under the prefixes the ranks have reached (LDS counters per workgroup and per distinct prefix, flushed into
+ * global bins with integer atomics: the sums do not depend on the order), then one workgroup picks every rank's bin.
+ * Nothing is moved -- except once: as soon as the keys still under some prefix number at most
+ * cand_cap(n) = n / cand_div + cand_floor, a gated kernel copies them (keys only, in arbitrary order) into a buffer of
+ * that capacity and the later levels count the buffer; if that never happens (all keys equal, heavy skew) every level
+ * counts the whole array, which is correct and slower.  The host enqueues every level, the device decides what runs.
+ * With d_out_index the wanted occurrence of the value is then found in three launches without atomics over tiles of
+ * `tile` keys (count per tile, scan per rank, find inside one tile); no workgroup waits for another.
+ * Workspace: the bins, cand_cap(n) keys and 4 * max_ranks bytes per tile; it is made on first use or by
+ * rsx_ctx_reserve_select, and under capture without a sufficient reserve the call returns RSX_ERR_WORKSPACE and enqueues
+ * nothing.  RSX_INFO_LAST_PASSES reports path 15. */
+int rsx_select_device(rsx_ctx *ctx, const void *d_keys, size_t n, uint32_t key_bytes, uint32_t key_kind,
+                      const uint64_t *ranks /* HOST array */, uint32_t nranks, void *d_out_keys, void *d_out_index,
+                      uint32_t index_bytes, int order, void *stream);
+/* Workspace (and the context's first-call set-up) of a select over up to n keys of this width, so that the call
+ * allocates nothing (stream capture). */
+int rsx_ctx_reserve_select(rsx_ctx *ctx, size_t n, uint32_t key_bytes);
+/* Host-only, needs no device: *max_ranks = the ranks one call takes, *digit_bits = the bits of a level, *tile = the keys
+ * per workgroup of the index launches, *cand_div and *cand_floor as in cand_cap(n) above.  The count kernel keeps
+ * max_ranks * 2^digit_bits four-byte counters in LDS, at most 80 KiB: two workgroups per CU. */
+int rsx_select_caps(uint32_t key_bytes, uint32_t *max_ranks, uint32_t *digit_bits, uint32_t *tile,
+                    uint32_t *cand_div, uint32_t *cand_floor);
 
 /* -- several key columns ----------------------------------------------------- */
 /* Sorting a table by (a, b descending, c): ncols key columns of n keys each, column 0 the MOST significant (the opposite

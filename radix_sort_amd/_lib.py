@@ -28,6 +28,7 @@ SYMBOLS = [
     "rsx_merge_device", "rsx_ctx_reserve_merge", "rsx_merge_caps",
     "rsx_setop_device", "rsx_ctx_reserve_setop", "rsx_setop_caps",
     "rsx_join_device", "rsx_ctx_reserve_join", "rsx_join_caps",
+    "rsx_select_device", "rsx_ctx_reserve_select", "rsx_select_caps",
 ]
 SEG_CLASSES = 2  # RSX_SEG_CLASSES
 LEX_MAX_COLUMNS = 16  # RSX_LEX_MAX_COLUMNS
@@ -176,6 +177,9 @@ def load():
     L.rsx_join_device.argtypes = [vp, u32, vp, sz, vp, vp, vp, sz, vp, vp, u32, u32, i, vp, vp, u32, sz, vp, vp]
     L.rsx_ctx_reserve_join.argtypes = [vp, sz, u32]
     L.rsx_join_caps.argtypes = [u32, pu32, pu32, pu32]
+    L.rsx_select_device.argtypes = [vp, vp, sz, u32, u32, ctypes.POINTER(u64), u32, vp, vp, u32, i, vp]
+    L.rsx_ctx_reserve_select.argtypes = [vp, sz, u32]
+    L.rsx_select_caps.argtypes = [u32, pu32, pu32, pu32, pu32, pu32]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("rsx_last_error", "rsx_strerror"):

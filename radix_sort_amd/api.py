@@ -13,6 +13,7 @@ torch is used for device memory and streams only.
 from __future__ import annotations
 
 import ctypes
+import math
 import operator
 import threading
 from collections import namedtuple
@@ -292,6 +293,20 @@ class Context:
         positions in the row into d_out_index (either may be 0: not produced); d_keys is only read."""
         self._check(self._L.rsx_topk_rows_device(self._h, d_keys, d_out_keys or None, d_out_index or None, rows, row_len, k, key_bytes,
                                                  key_kind, index_bytes, 1 if descending else 0, stream))
+
+    def reserve_select(self, n: int, key_bytes: int):
+        """rsx_ctx_reserve_select: the context's first-call set-up and the workspace of select_device on up to n keys of this
+        width, so that the call allocates nothing and can be captured."""
+        self._check(self._L.rsx_ctx_reserve_select(self._h, n, key_bytes))
+
+    def select_device(self, d_keys: int, n: int, key_bytes: int, key_kind: int, ranks, d_out_keys: int, d_out_index: int,
+                      index_bytes: int, descending: bool = False, stream: int = 0):
+        """rsx_select_device: for every rank of `ranks` (host integers, at most select_caps(key_bytes)[0] of them) the key
+        at that position of the stable sort of the n keys into d_out_keys and its input position into d_out_index (either
+        may be 0: not produced); d_keys is only read."""
+        host = (ctypes.c_uint64 * max(1, len(ranks)))(*ranks)
+        self._check(self._L.rsx_select_device(self._h, d_keys or None, n, key_bytes, key_kind, host, len(ranks), d_out_keys or None,
+                                              d_out_index or None, index_bytes, 1 if descending else 0, stream))
 
     def reserve_unique(self, n: int, key_bytes: int, with_positions: bool = True):
         """rsx_ctx_reserve_unique: the context's first-call set-up and the workspace of unique_device on up to n keys of this
@@ -1008,6 +1023,166 @@ def radix_topk(keys, k: int, largest: bool = True, index_dtype=None, ctx: Option
         c.topk_rows_device(keys.data_ptr(), values.data_ptr(), indices.data_ptr(), rows, row_len, k, kb, kind,
                            indices.element_size(), largest, stream)
     return values, indices
+
+
+def select_caps(key_bytes: int):
+    """rsx_select_caps -> (max_ranks, digit_bits, tile, cand_div, cand_floor): the ranks one rsx_select_device call takes,
+    the bits of one level's digit, the keys per workgroup of its index launches, and the capacity of its candidate
+    buffer, n // cand_div + cand_floor keys.  Needs no device."""
+    L = _lib.load()
+    out = [ctypes.c_uint32() for _ in range(5)]
+    rc = L.rsx_select_caps(key_bytes, *[ctypes.byref(o) for o in out])
+    _check_rc(L, rc)
+    return tuple(int(o.value) for o in out)
+
+
+# Shapes radix_select hands to radix_argsort although rsx_select_device takes them: (no entry: no crossover measured)
+def _select_by_sort(n: int, key_bytes: int) -> bool:
+    return False
+
+
+def _select_ranks(ranks, n: int):
+    """(list of ranks in 0 .. n - 1, scalar?) of the ranks argument of radix_select: negative ranks count from the end."""
+    scalar = False
+    try:
+        ranks = [operator.index(ranks)]
+        scalar = True
+    except TypeError:
+        ranks = [operator.index(r) for r in ranks]
+    out = []
+    for r in ranks:
+        if r < -n or r >= n:
+            raise ValueError(f"rank {r} is out of range for {n} keys")
+        out.append(r + n if r < 0 else r)
+    return out, scalar
+
+
+def _select_flat(keys, kb: int, kind: int, n: int, ranks, descending: bool, want_index: bool, index_dtype, ctx):
+    """values (and indices, or None) of the ranks of one flat key array, in batches of select_caps(kb)[0] ranks."""
+    import torch
+    m = len(ranks)
+    values = torch.empty((m,) + tuple(keys.shape[1:]), dtype=keys.dtype, device=keys.device)
+    indices = torch.empty(m, dtype=index_dtype, device=keys.device) if want_index else None
+    if m == 0:
+        return values, indices
+    with _on_device(keys, ctx) as (c, stream):
+        if _select_by_sort(n, kb):
+            perm = radix_argsort(keys, descending=descending, ctx=c, key_kind=kind if kb == 16 else None)
+            at = perm[torch.tensor(ranks, dtype=torch.int64, device=keys.device)]
+            bits = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64, 16: torch.uint8}[kb]
+            values.view(bits).copy_(keys.view(bits)[at])
+            if want_index:
+                indices.copy_(at)
+            return values, indices
+        step = select_caps(kb)[0]
+        ib = indices.element_size() if want_index else 0
+        for b in range(0, m, step):
+            c.select_device(keys.data_ptr(), n, kb, kind, ranks[b:b + step], values.data_ptr() + b * kb,
+                            indices.data_ptr() + b * ib if want_index else 0, ib, descending, stream)
+    return values, indices
+
+
+def radix_select(keys, ranks, descending: bool = False, return_index: bool = False, index_dtype=None, ctx: Optional[Context] = None,
+                 key_kind: Optional[int] = None):
+    """The elements at sorted positions `ranks` of `keys`, without sorting them (rsx_select_device): with p =
+    radix_argsort(keys, descending=descending), the values keys[p[ranks]] and, with return_index, the positions p[ranks]
+    -- column `ranks` of the full stable sort, byte for byte, so equal keys count in input order and the call agrees
+    with radix_topk wherever the two overlap.
+
+    keys: a contiguous 1-D GPU tensor of a dtype radix_argsort takes, or an (n, 16) uint8 tensor of 128-bit keys
+       (key_kind= as there); it is not modified.
+    ranks: an int (the results are 0-d, or (16,) for 128-bit keys) or a sequence of ints (1-D results); negative ranks
+       count from the end; ranks may repeat and come in any order.  More than select_caps(key_bytes)[0] go in batches.
+    Returns values, or (values, indices) with indices of index_dtype (torch.int64, the default, or torch.int32).
+    The order is radix_argsort's total order on bit patterns.  A counting select: about two reads of the keys on
+    spread-out keys and a third for the index, against the passes of a sort.  Enqueued on the current stream, not
+    synchronised."""
+    kb, kind, n = _pairs_keys(keys, key_kind)
+    ranks, scalar = _select_ranks(ranks, n)
+    index_dtype = _index_dtype(index_dtype)
+    _pairs_device(keys, None, "")
+    values, indices = _select_flat(keys, kb, kind, n, ranks, descending, return_index, index_dtype, ctx)
+    if scalar:
+        values = values[0]
+        indices = indices[0] if return_index else None
+    return (values, indices) if return_index else values
+
+
+def radix_kthvalue(keys, k: int, largest: bool = False, index_dtype=None, ctx: Optional[Context] = None):
+    """(values, indices) of the k-th smallest (largest=True: largest) key along the last dimension, k counted from 1 as
+    in `torch.kthvalue(keys, k)` -- with the tie index specified: column k - 1 of the stable sort
+    `radix_argsort_rows(keys, descending=largest)`, so among equal keys the one at the lowest position comes first.
+
+    keys: a contiguous GPU tensor of at least one dimension, of a dtype radix_sort knows; it is not modified.
+    Returns tensors of shape keys.shape[:-1].  Rows of at most topk_caps(key_bytes)[0][-1] keys take radix_topk(k) and its
+    last column, one launch for all rows; longer rows take radix_select once per row.  Enqueued on the current stream,
+    not synchronised."""
+    import torch
+    kb, kind, rows, row_len = _rows_keys(keys)
+    k = operator.index(k)
+    if k < 1 or k > row_len:
+        raise ValueError(f"k must be in 1 .. {row_len} (the last dimension), not {k}")
+    index_dtype = _index_dtype(index_dtype)
+    _pairs_device(keys, None, "")
+    shape = tuple(keys.shape[:-1])
+    if row_len <= topk_caps(kb)[0][-1]:
+        v, i = radix_topk(keys, k, largest=largest, index_dtype=index_dtype, ctx=ctx)
+        return v[..., k - 1].contiguous(), i[..., k - 1].contiguous()
+    values = torch.empty(rows, dtype=keys.dtype, device=keys.device)
+    indices = torch.empty(rows, dtype=index_dtype, device=keys.device)
+    flat = keys.reshape(rows, row_len)
+    for r in range(rows):
+        v, i = _select_flat(flat[r], kb, kind, row_len, [k - 1], largest, True, index_dtype, ctx)
+        values[r:r + 1].copy_(v)
+        indices[r:r + 1].copy_(i)
+    return values.reshape(shape), indices.reshape(shape)
+
+
+def radix_median(keys, index_dtype=None, ctx: Optional[Context] = None):
+    """(value, index) of the lower median of a 1-D key tensor, rank (n - 1) // 2 of its stable sort, as `torch.median`
+    picks -- with the tie index specified (radix_select)."""
+    kb, kind, n = _pairs_keys(keys, None)
+    if n == 0:
+        raise ValueError("the median of no keys")
+    return radix_select(keys, (n - 1) // 2, return_index=True, index_dtype=index_dtype, ctx=ctx)
+
+
+_QUANTILE_METHODS = ("lower", "higher", "nearest")
+
+
+def _quantile_ranks(n: int, q, method: str):
+    """numpy's rules on the virtual index q * (n - 1), on the host: lower floor, higher ceil, nearest round-half-even."""
+    out = []
+    for x in q:
+        v = x * (n - 1)
+        lo = math.floor(v)
+        if method == "lower":
+            r = lo
+        elif method == "higher":
+            r = math.ceil(v)
+        else:
+            d = v - lo
+            r = lo + 1 if d > 0.5 or (d == 0.5 and lo % 2 == 1) else lo
+        out.append(min(max(int(r), 0), n - 1))
+    return out
+
+
+def radix_quantile(keys, q, method: str = "lower", ctx: Optional[Context] = None):
+    """The q-quantiles of a 1-D key tensor by one of numpy's non-interpolating methods ("lower", "higher", "nearest" on
+    the virtual index q * (n - 1), computed on the host): always one of the keys (radix_select), so integer keys and floats
+    by bit pattern work, with no limit on n.  q: a float (0-d result) or a sequence of floats in [0, 1] (1-D result)."""
+    kb, kind, n = _pairs_keys(keys, None)
+    scalar = isinstance(q, (int, float))
+    qs = [float(q)] if scalar else [float(x) for x in q]
+    for x in qs:
+        if not 0.0 <= x <= 1.0:  # (NaN too)
+            raise ValueError(f"q must lie in [0, 1], not {x}")
+    if method not in _QUANTILE_METHODS:
+        raise ValueError(f"method must be one of {_QUANTILE_METHODS}, not {method!r}")
+    if n == 0:
+        raise ValueError("a quantile of no keys")
+    ranks = _quantile_ranks(n, qs, method)
+    return radix_select(keys, ranks[0] if scalar else ranks, ctx=ctx)
 
 
 def unique_caps(key_bytes: int, with_positions: bool = True):

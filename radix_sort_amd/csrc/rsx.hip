@@ -6,6 +6,7 @@
 #include "rsx_internal.hpp"
 #include "rsx_misc_kernels.hpp"
 #include "rsx_any_kernels.hpp"
+#include "rsx_select_kernels.hpp"
 
 #include <cmath>
 
@@ -1061,6 +1062,15 @@ int rsx_ctx_get_info(rsx_ctx* ctx, int what, uint64_t* out) try {
                 case PATH_SCAN:    // bits 0-7 the kernels launched after any sort, bit 8 RSX_SCAN_RUNS
                     *out = (uint64_t)(ctx->last_sort_passes & 0x1FFu) | (uint64_t)ctx->last_path << 24;
                     return RSX_OK;
+                case PATH_SELECT: {  // bits 0-7 the kernels launched, bits 8-11 what the device's plan says of the compaction
+                    uint32_t compacted = 0;
+                    if (ctx->last_sort_passes && ctx->any_buf) {
+                        if (ctx->busy) RSX_HIP(hipEventSynchronize(ctx->last_event));
+                        RSX_HIP(hipMemcpy(&compacted, ctx->any_buf + offsetof(SelectState, compacted), sizeof compacted, hipMemcpyDeviceToHost));
+                    }
+                    *out = (uint64_t)(ctx->last_sort_passes & 0xFFu) | (uint64_t)(compacted & 0xFu) << 8 | (uint64_t)ctx->last_path << 24;
+                    return RSX_OK;
+                }
                 default: break;
             }
             *out = (uint64_t)ctx->last_path << 24 | (uint64_t)ctx->last_route << 28;
@@ -1706,6 +1716,153 @@ int rsx_search_caps(uint32_t key_bytes, int with_positions, uint32_t* tile, uint
     if (!tile || !window || !key_widths_ok(key_bytes, RSX_KEY_UNSIGNED)) return RSX_ERR_ARG;
     *tile = search_tile_elems(key_bytes);
     *window = search_window_elems(key_bytes);
+    return RSX_OK;
+}
+
+// ---- order statistics of an unsorted key array (rsx_select_kernels.hpp, include/rsx.h) ----
+namespace {
+// The workspace of one rsx_select_device call: the state and the bins (zeroed together before level 0), the candidate
+// buffer and the per-tile counts of the index launches.
+struct SelectPlan {
+    size_t bins_off;   // [SELECT_MAX_RANKS][SELECT_BINS] u64, right behind the state
+    size_t cand_off;   // cand_cap mapped keys
+    size_t tiles_off;  // [SELECT_MAX_RANKS][tiles] u32
+    uint64_t cand_cap, tiles;
+    Carve ws;
+};
+SelectPlan select_plan(size_t n, uint32_t kb) {
+    SelectPlan P{};
+    P.ws.take(sizeof(SelectState));
+    P.bins_off = P.ws.take((size_t)SELECT_MAX_RANKS * SELECT_BINS * sizeof(uint64_t));
+    P.cand_cap = (uint64_t)n / SELECT_CAND_DIV + SELECT_CAND_FLOOR;
+    P.cand_off = P.ws.take((size_t)P.cand_cap * kb);
+    P.tiles = ((uint64_t)n + SELECT_TILE - 1) / SELECT_TILE;
+    P.tiles_off = P.ws.take((size_t)SELECT_MAX_RANKS * P.tiles * sizeof(uint32_t));
+    return P;
+}
+// level l of a key of kb bytes: SELECT_BITS bits from the top down, the last level what is left
+SelectLevel select_level(uint32_t kb, uint32_t l) {
+    const uint32_t top = 8 * kb - SELECT_BITS * l;
+    const uint32_t width = top < SELECT_BITS ? top : SELECT_BITS;
+    return SelectLevel{l, top - width, width, top == width ? 1u : 0u};
+}
+uint32_t select_levels(uint32_t kb) { return (8 * kb + SELECT_BITS - 1) / SELECT_BITS; }
+
+extern "C++" template <int KB>
+int select_launches(rsx_ctx* ctx, const SelectPlan& P, const void* d_keys, size_t n, uint32_t kind, uint32_t desc, const SelectRanks& ranks,
+                    uint32_t nranks, void* d_out_keys, void* d_out_index, uint32_t ib, uint32_t* launched, hipStream_t st) {
+    char* w = ctx->any_buf;
+    SelectState* state = reinterpret_cast<SelectState*>(w);
+    unsigned long long* bins = reinterpret_cast<unsigned long long*>(w + P.bins_off);
+    void* cand = w + P.cand_off;
+    uint32_t* tile_count = reinterpret_cast<uint32_t*>(w + P.tiles_off);
+    const uint32_t stream = (uint64_t)n * KB >= (uint64_t)RSX_COUNT16_NT_BYTES ? 1u : 0u;  // as rsx_count16top_kernel takes the hint
+    uint64_t shares = ((uint64_t)n + SELECT_SHARE - 1) / SELECT_SHARE;
+    const uint64_t count_groups = std::min<uint64_t>(shares, (uint64_t)ctx->num_cu * 2);
+    const uint64_t compact_groups = std::min<uint64_t>(shares, (uint64_t)ctx->num_cu * 8);
+    LaunchTimer lt(ctx, RSX_PROF_OTHER, st);
+    // (a kernel, not a memset node: rsx_zero16_kernel)
+    hipLaunchKernelGGL(rsx_zero16_kernel, dim3(64), dim3(256), 0, st, reinterpret_cast<uint4*>(w),
+                       (uint64_t)((P.bins_off + (size_t)SELECT_MAX_RANKS * SELECT_BINS * sizeof(uint64_t)) / 16));
+    RSX_HIP(hipGetLastError());
+    ++*launched;
+    const uint32_t levels = select_levels(KB);
+    for (uint32_t l = 0; l < levels; ++l) {
+        const SelectLevel lv = select_level(KB, l);
+        hipLaunchKernelGGL(rsx_select_count_kernel<KB>, dim3((uint32_t)count_groups), dim3(SELECT_COUNT_WG), 0, st, d_keys, (uint64_t)n,
+                           static_cast<const void*>(cand), static_cast<const SelectState*>(state), bins, P.cand_cap, lv, kind, desc, stream);
+        RSX_HIP(hipGetLastError());
+        hipLaunchKernelGGL(rsx_select_pick_kernel, dim3(1), dim3(1024), 0, st, state, bins, ranks, nranks, lv, P.cand_cap);
+        RSX_HIP(hipGetLastError());
+        *launched += 2;
+        if (lv.last) break;
+        hipLaunchKernelGGL(rsx_select_compact_kernel<KB>, dim3((uint32_t)compact_groups), dim3(256), 0, st, d_keys, (uint64_t)n, cand, P.cand_cap,
+                           state, lv, kind, desc, stream);
+        RSX_HIP(hipGetLastError());
+        ++*launched;
+    }
+    if (d_out_index) {
+        hipLaunchKernelGGL(rsx_select_tile_kernel<KB>, dim3((uint32_t)P.tiles), dim3(256), 0, st, d_keys, (uint64_t)n,
+                           static_cast<const SelectState*>(state), tile_count, P.tiles, nranks, kind, desc, stream);
+        RSX_HIP(hipGetLastError());
+        hipLaunchKernelGGL(rsx_select_scan_kernel, dim3(nranks), dim3(1024), 0, st, state, static_cast<const uint32_t*>(tile_count), P.tiles);
+        RSX_HIP(hipGetLastError());
+        hipLaunchKernelGGL(rsx_select_find_kernel<KB>, dim3(nranks), dim3(256), 0, st, d_keys, (uint64_t)n, static_cast<const SelectState*>(state),
+                           d_out_keys, d_out_index, ib, kind, desc);
+        RSX_HIP(hipGetLastError());
+        *launched += 3;
+    } else {
+        hipLaunchKernelGGL(rsx_select_write_kernel<KB>, dim3(1), dim3(64), 0, st, static_cast<const SelectState*>(state), d_out_keys, nranks, kind,
+                           desc);
+        RSX_HIP(hipGetLastError());
+        ++*launched;
+    }
+    return RSX_OK;
+}
+}  // namespace
+
+int rsx_select_device(rsx_ctx* ctx, const void* d_keys, size_t n, uint32_t key_bytes, uint32_t key_kind, const uint64_t* ranks, uint32_t nranks,
+                      void* d_out_keys, void* d_out_index, uint32_t index_bytes, int order, void* stream) try {
+    if (!ctx) return RSX_ERR_ARG;
+    if (!key_widths_ok(key_bytes, key_kind)) return fail(ctx, RSX_ERR_ARG, "invalid key width or kind");
+    uint32_t desc = 0;
+    int rc = order_desc(ctx, order, &desc);
+    if (rc) return rc;
+    if (nranks > SELECT_MAX_RANKS) return fail(ctx, RSX_ERR_ARG, "more ranks than rsx_select_caps reports");
+    RSX_ENTER(stream);
+    const hipStream_t st = held.st;
+    if (nranks == 0) {  // nothing asked: no pointer is looked at
+        note_path(ctx, PATH_SELECT, 0);
+        return RSX_OK;
+    }
+    if (!d_out_keys && !d_out_index) return fail(ctx, RSX_ERR_ARG, "d_out_keys and d_out_index are both null");
+    if (d_out_index) {
+        rc = check_index_bytes(ctx, index_bytes);
+        if (rc) return rc;
+    }
+    if (!ranks || !d_keys) return fail(ctx, RSX_ERR_ARG, "null pointer");
+    SelectRanks r{};
+    for (uint32_t q = 0; q < nranks; ++q) {
+        if (ranks[q] >= (uint64_t)n) return fail(ctx, RSX_ERR_ARG, "rank out of range");
+        r.r[q] = ranks[q];
+    }
+    if (!aligned(d_keys, key_bytes) || !aligned(d_out_keys, key_bytes) || (d_out_index && !aligned(d_out_index, index_bytes)))
+        return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
+    if (d_out_index && index_bytes == 4 && (uint64_t)n >= (1ull << 32)) return fail(ctx, RSX_ERR_UNSUPPORTED, "2^32 or more keys need 8-byte indices");
+    if (d_out_index && !tiles_fit(n, SELECT_TILE)) return fail(ctx, RSX_ERR_UNSUPPORTED, "too many keys for one launch of the index kernels");
+    rc = pending_error(ctx);
+    if (rc) return rc;
+    const SelectPlan P = select_plan(n, key_bytes);
+    rc = ensure_aux(ctx, st);
+    if (!rc) rc = ensure_any(ctx, P.ws.bytes, st);
+    if (rc) return rc;
+    Enqueue enq(ctx, st);  // the workspace belongs to this call from the first launch on
+    uint32_t launched = 0;
+    for_key_width(key_bytes, [&](auto kb) {
+        rc = select_launches<decltype(kb)::value>(ctx, P, d_keys, n, key_kind, desc, r, nranks, d_out_keys, d_out_index, index_bytes, &launched, st);
+    });
+    if (rc) return rc;
+    note_path(ctx, PATH_SELECT, launched);
+    return RSX_OK;
+} catch (...) {
+    return RSX_ERR_HIP;
+}
+
+int rsx_ctx_reserve_select(rsx_ctx* ctx, size_t n, uint32_t key_bytes) try {
+    if (!ctx) return RSX_ERR_ARG;
+    if (!key_widths_ok(key_bytes, RSX_KEY_UNSIGNED)) return fail(ctx, RSX_ERR_ARG, "invalid key width");
+    return reserve_any_entry(ctx, select_plan(n, key_bytes).ws.bytes);
+} catch (...) {
+    return RSX_ERR_NOMEM;
+}
+
+int rsx_select_caps(uint32_t key_bytes, uint32_t* max_ranks, uint32_t* digit_bits, uint32_t* tile, uint32_t* cand_div, uint32_t* cand_floor) {
+    if (!max_ranks || !digit_bits || !tile || !cand_div || !cand_floor || !key_widths_ok(key_bytes, RSX_KEY_UNSIGNED)) return RSX_ERR_ARG;
+    *max_ranks = SELECT_MAX_RANKS;
+    *digit_bits = SELECT_BITS;
+    *tile = SELECT_TILE;
+    *cand_div = SELECT_CAND_DIV;
+    *cand_floor = SELECT_CAND_FLOOR;
     return RSX_OK;
 }
 

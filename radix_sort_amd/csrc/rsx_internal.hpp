@@ -87,6 +87,7 @@ enum : uint32_t {
     PATH_SETOP = 12,
     PATH_JOIN = 13,
     PATH_SCAN = 14,      // scan by key
+    PATH_SELECT = 15,    // order statistics (the last value the four bits hold)
 };
 
 // option bits (rsx_ctx_set_option): alternative kernel paths, all bit-exact

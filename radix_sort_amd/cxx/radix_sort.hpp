@@ -23,6 +23,7 @@
 //     rsx::set_op_pairs(int op, const K* d_a_keys, const V* d_a_values, size_t na, const K* d_b_keys, const V* d_b_values, size_t nb, K* keys, V* values, uint64_t* d_out_num, bool descending, const uint64_t* d_a_num, const uint64_t* d_b_num, hipStream_t)
 //     rsx::join(int how, const K* d_a_keys, size_t na, const K* d_b_keys, size_t nb, I* d_out_a, I* d_out_b, size_t capacity, uint64_t* d_out_num, bool descending, const uint64_t* d_a_num, const uint64_t* d_b_num, const I* d_a_index, const I* d_b_index, hipStream_t)   // RSX_JOIN_*
 //     rsx::join_count(int how, const K* d_a_keys, size_t na, const K* d_b_keys, size_t nb, uint64_t* d_out_num, bool descending, const uint64_t* d_a_num, const uint64_t* d_b_num, hipStream_t)
+//     rsx::select(const K* d_keys, size_t n, const uint64_t* ranks /* host */, uint32_t nranks, K* d_out_keys, I* d_out_index, bool descending, hipStream_t)   // order statistics, no sort
 //     rsx::lexsort({rsx::key_column(d_a), rsx::key_column(d_b, true)}, I* d_index, size_t n, hipStream_t)   // several key columns
 //     rsx::sort_columns({rsx::key_column(d_a), rsx::key_column(d_b, true)}, V* d_values, size_t n, hipStream_t)
 // Errors: the reference panics (mod.rs:68,106); here std::runtime_error is thrown.
@@ -402,6 +403,33 @@ template <typename K>
 void join_count(int how, const K* d_a_keys, size_t na, const K* d_b_keys, size_t nb, uint64_t* d_out_num, bool descending = false,
                 const uint64_t* d_a_num = nullptr, const uint64_t* d_b_num = nullptr, void* stream = nullptr, Context& ctx = default_context()) {
     join<K, uint64_t>(how, d_a_keys, na, d_b_keys, nb, nullptr, nullptr, 0, d_out_num, descending, d_a_num, d_b_num, nullptr, nullptr, stream, ctx);
+}
+
+// Order statistics of an UNSORTED key array (rsx_select_device): for every q < nranks, d_out_keys[q] and d_out_index[q]
+// receive the key at position ranks[q] of the stable sort in that order and its input position -- column ranks[q] of
+// radix_argsort, without the sort.  `ranks` is a HOST array of at most select_caps<K>().max_ranks ranks below n, read
+// during the call; either output may be nullptr, not both.  d_keys is only read; rsx_ctx_reserve_select before a stream
+// capture.  Stream-ordered, never synchronised.
+struct SelectCaps {
+    uint32_t max_ranks, digit_bits, tile, cand_div, cand_floor;
+};
+template <typename K>
+SelectCaps select_caps() {
+    SelectCaps c{};
+    const rsx_layout L = RadixDigits<K>::layout();
+    if (rsx_select_caps(L.key_bytes, &c.max_ranks, &c.digit_bits, &c.tile, &c.cand_div, &c.cand_floor) != RSX_OK)
+        throw std::invalid_argument("select_caps: no select for this key width");
+    return c;
+}
+template <typename K, typename I = uint64_t>
+void select(const K* d_keys, size_t n, const uint64_t* ranks, uint32_t nranks, K* d_out_keys, I* d_out_index, bool descending = false,
+            void* stream = nullptr, Context& ctx = default_context()) {
+    static_assert(std::is_integral<I>::value && (sizeof(I) == 4 || sizeof(I) == 8), "indices are 4- or 8-byte integers");
+    const rsx_layout L = RadixDigits<K>::layout();
+    if (L.key_offset != 0 || L.key_bytes != L.elem_bytes) throw std::invalid_argument("select: the key type must be its own key");
+    ctx.check(rsx_select_device(ctx.get(), d_keys, n, L.key_bytes, L.key_kind, ranks, nranks, d_out_keys, d_out_index, (uint32_t)sizeof(I),
+                                descending ? RSX_ORDER_DESCENDING : RSX_ORDER_ASCENDING, stream),
+              "rsx_select_device");
 }
 
 // Several key columns (rsx_lexsort_device, rsx_sort_columns_device): rows sorted by (column 0, column 1, ...), column 0

@@ -105,6 +105,15 @@ extern "C" {
                            stream: *mut c_void) -> c_int;
     pub fn rsx_ctx_reserve_join(ctx: *mut RsxCtx, na: usize, key_bytes: u32) -> c_int;
     pub fn rsx_join_caps(key_bytes: u32, tile: *mut u32, window: *mut u32, rows: *mut u32) -> c_int;
+    // order statistics of an unsorted key array (include/rsx.h, "order statistics of an unsorted key array"): `ranks` is a
+    // HOST array of nranks <= max_ranks ranks below n; the key at each rank of the stable sort and its input position;
+    // either output may be null, not both
+    pub fn rsx_select_device(ctx: *mut RsxCtx, d_keys: *const c_void, n: usize, key_bytes: u32, key_kind: u32,
+                             ranks: *const u64, nranks: u32, d_out_keys: *mut c_void, d_out_index: *mut c_void,
+                             index_bytes: u32, order: c_int, stream: *mut c_void) -> c_int;
+    pub fn rsx_ctx_reserve_select(ctx: *mut RsxCtx, n: usize, key_bytes: u32) -> c_int;
+    pub fn rsx_select_caps(key_bytes: u32, max_ranks: *mut u32, digit_bits: *mut u32, tile: *mut u32, cand_div: *mut u32,
+                           cand_floor: *mut u32) -> c_int;
     // scan by key (include/rsx.h, "scan by key"): op is RSX_REDUCE_SUM (0), _MIN (1), _MAX (2); flags RSX_SCAN_EXCLUSIVE (1)
     // and RSX_SCAN_RUNS (2); one result per row at the row's position; d_values null: every value is 1 (ranks);
     // `first` is what the first row of every group receives in an exclusive scan; d_out_num may be null
