@@ -208,6 +208,9 @@ enum {
                                  15 order statistics (rsx_select_device: bits 0-7 are then the kernels launched, bits
                                  8-11 are 0 when the candidates were never compacted, else 1 + the level after which
                                  they were -- read from the device, so this waits for the call --, bits 12-23 are 0),
+                                 16 keys per bin (rsx_bin_count_device: the four bits are full, so this path is the
+                                 value of bits 24-28, bits 24-27 zero and bit 28 set; bits 0-7 are then the kernels
+                                 launched, every other bit is 0 -- a bin count has no route),
                                  bits 28-29 the route of a layout without kernels of its own: 0 direct, 1 packed
                                  re-layout, 2 key-index proxy (bits 0-27 then describe the sort of the re-laid-out
                                  elements / of the proxies) */
@@ -807,6 +810,51 @@ int rsx_ctx_reserve_select(rsx_ctx *ctx, size_t n, uint32_t key_bytes);
  * max_ranks * 2^digit_bits four-byte counters in LDS, at most 80 KiB: two workgroups per CU. */
 int rsx_select_caps(uint32_t key_bytes, uint32_t *max_ranks, uint32_t *digit_bits, uint32_t *tile,
                     uint32_t *cand_div, uint32_t *cand_floor);
+
+/* -- keys per bin of an unsorted key array ------------------------------------ */
+/* How many keys fall between given cut points (a histogram), or have each small integer value (a bincount), in one read
+ * of the keys.  (rsx_histogram_device above is something else: the 256-bin digit count of the multi-GPU path.)
+ * With N = n, or min(n, *d_num) when d_num is given -- a device word such as the d_out_num of rsx_unique_device, read on
+ * the device as sorted_num is in rsx_search_sorted_device -- and M the mapped key of rsx_argsort_device (complemented
+ * for descending `order`), d_counts holds m + 1 integers of count_bytes (4 or 8) and
+ *     counts[b] = #{ i < N : bin(keys[i]) == b }        for b = 0 .. m
+ * with bin(key) one of
+ *     RSX_BIN_UPPER   #{ j < m : M(edges[j]) <= M(key) }   bins [e[j-1], e[j]): numpy.histogram, bucketize(right=True)
+ *     RSX_BIN_LOWER   #{ j < m : M(edges[j]) <  M(key) }   bins (e[j-1], e[j]]
+ *     RSX_BIN_INDEX   no edges: the key's integer value when 0 <= value < m, else m ("outside")
+ * Without RSX_BIN_ACCUMULATE in `flags` every one of the m + 1 entries is overwritten; with it the counts are added to
+ * what is there.  In the edge modes the result is bincount(upper_or_lower(edges, keys), minlength = m + 1) of
+ * rsx_search_sorted_device with the same edges, order and kind: every key width (1, 2, 4, 8, 16) and kind, by the total
+ * order on bit patterns -- NaN, +-0 and +-inf are keys and edges like any other.  counts[0] and counts[m] are the two open
+ * ends.  The edges (m keys of the keys' width and kind) must be sorted in `order`; otherwise the result is unspecified,
+ * but no access goes out of bounds.  Equal edges give empty bins.  m == 0 is legal: one bin holds N.
+ * The index mode takes integer keys of 1, 2, 4 or 8 bytes, signed or unsigned (negative keys are outside); float kinds
+ * and 16-byte keys return RSX_ERR_UNSUPPORTED; it requires order == 0 and d_edges == NULL (RSX_ERR_ARG otherwise).
+ * RSX_ERR_UNSUPPORTED, with nothing enqueued: an edge mode with m > max_edges of rsx_bin_caps; count_bytes == 4 with
+ * n >= 2^32.  RSX_ERR_ARG: bad widths, kinds, modes, flags, order or count_bytes; m == 2^32 - 1; d_counts NULL; d_keys NULL
+ * with n > 0; d_edges NULL with m > 0 in an edge mode; a pointer not aligned to its element (d_num: 8 bytes).
+ * n == 0 or N == 0 still zeroes the counts (unless accumulating) and counts nothing.  d_keys and d_edges are only read.
+ *
+ * A zeroing kernel (skipped when accumulating) and one counting kernel: a fixed number of persistent workgroups, each
+ * streaming one share of at least `share` keys in 16-byte words.  Edge modes: the mapped edges are staged in LDS beside
+ * m + 1 four-byte counters, every key is mapped and its bin found by a bound search in LDS, several keys of a thread in
+ * step.  Index mode: the same counters without a search, one window of max_index_bins_lds values at a time (a workgroup
+ * walks its share once per window; the outside bin is counted beside the last window's values) while
+ * m <= 16 * max_index_bins_lds, atomics straight into d_counts above.  A wave whose lanes all hold one bin adds once; the LDS counters are flushed into d_counts with integer
+ * atomics (before any could wrap: a workgroup flushes every 2^31 keys), so the counts do not depend on any order.
+ * Stream-ordered, no synchronisation, the host reads nothing.  There is no workspace: the call allocates nothing and can
+ * be captured with no reserve.  RSX_INFO_LAST_PASSES reports path 16 and, in bits 0-7, the kernels launched. */
+#define RSX_BIN_UPPER 0u
+#define RSX_BIN_LOWER 1u
+#define RSX_BIN_INDEX 2u
+#define RSX_BIN_ACCUMULATE 1u  /* flags: add to d_counts instead of overwriting it */
+int rsx_bin_count_device(rsx_ctx *ctx, const void *d_keys, size_t n, const uint64_t *d_num, uint32_t key_bytes,
+                         uint32_t key_kind, const void *d_edges, uint32_t m, uint32_t mode, int order, void *d_counts,
+                         uint32_t count_bytes, uint32_t flags, void *stream);
+/* Host-only, needs no device: *max_edges = the most edges an edge mode takes for this key width (the edges and m + 1
+ * counters share at most 80 KiB of LDS, two workgroups per CU), *max_index_bins_lds = the values, and with m + 1 <=
+ * this all bins, that the index mode counts in LDS in one pass over the keys, *share = the fewest keys worth a workgroup. */
+int rsx_bin_caps(uint32_t key_bytes, uint32_t *max_edges, uint32_t *max_index_bins_lds, uint32_t *share);
 
 /* -- several key columns ----------------------------------------------------- */
 /* Sorting a table by (a, b descending, c): ncols key columns of n keys each, column 0 the MOST significant (the opposite

@@ -29,6 +29,7 @@ SYMBOLS = [
     "rsx_setop_device", "rsx_ctx_reserve_setop", "rsx_setop_caps",
     "rsx_join_device", "rsx_ctx_reserve_join", "rsx_join_caps",
     "rsx_select_device", "rsx_ctx_reserve_select", "rsx_select_caps",
+    "rsx_bin_count_device", "rsx_bin_caps",
 ]
 SEG_CLASSES = 2  # RSX_SEG_CLASSES
 LEX_MAX_COLUMNS = 16  # RSX_LEX_MAX_COLUMNS
@@ -46,6 +47,8 @@ ORDER_ASCENDING, ORDER_DESCENDING = 0, 1
 REDUCE_SUM, REDUCE_MIN, REDUCE_MAX = 0, 1, 2
 SCAN_EXCLUSIVE, SCAN_RUNS = 1, 2
 SEARCH_PRESORT = 1
+BIN_UPPER, BIN_LOWER, BIN_INDEX = 0, 1, 2
+BIN_ACCUMULATE = 1
 SETOP_UNION, SETOP_INTERSECTION, SETOP_DIFFERENCE, SETOP_SYMMETRIC_DIFFERENCE = 0, 1, 2, 3
 JOIN_INNER, JOIN_LEFT, JOIN_SEMI, JOIN_ANTI = 0, 1, 2, 3
 SHARD_EXCHANGE_FIRST, SHARD_SORT_FIRST = 0, 1
@@ -180,6 +183,8 @@ def load():
     L.rsx_select_device.argtypes = [vp, vp, sz, u32, u32, ctypes.POINTER(u64), u32, vp, vp, u32, i, vp]
     L.rsx_ctx_reserve_select.argtypes = [vp, sz, u32]
     L.rsx_select_caps.argtypes = [u32, pu32, pu32, pu32, pu32, pu32]
+    L.rsx_bin_count_device.argtypes = [vp, vp, sz, vp, u32, u32, vp, u32, u32, i, vp, u32, u32, vp]
+    L.rsx_bin_caps.argtypes = [u32, pu32, pu32, pu32]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("rsx_last_error", "rsx_strerror"):

@@ -308,6 +308,14 @@ class Context:
         self._check(self._L.rsx_select_device(self._h, d_keys or None, n, key_bytes, key_kind, host, len(ranks), d_out_keys or None,
                                               d_out_index or None, index_bytes, 1 if descending else 0, stream))
 
+    def bin_count_device(self, d_keys: int, n: int, key_bytes: int, key_kind: int, d_edges: int, m: int, mode: int, d_counts: int,
+                         count_bytes: int, descending: bool = False, d_num: int = 0, flags: int = 0, stream: int = 0):
+        """rsx_bin_count_device: the number of the first n (or min(n, *d_num)) keys in each of the m + 1 bins of `mode`
+        (BIN_UPPER / BIN_LOWER: between the m sorted edges at d_edges; BIN_INDEX: the key's own value, d_edges 0) into the
+        m + 1 counts of count_bytes at d_counts, overwritten unless flags has BIN_ACCUMULATE; no workspace."""
+        self._check(self._L.rsx_bin_count_device(self._h, d_keys or None, n, d_num or None, key_bytes, key_kind, d_edges or None, m, mode,
+                                                 1 if descending else 0, d_counts or None, count_bytes, flags, stream))
+
     def reserve_unique(self, n: int, key_bytes: int, with_positions: bool = True):
         """rsx_ctx_reserve_unique: the context's first-call set-up and the workspace of unique_device on up to n keys of this
         width, by the route with positions (perm or inverse asked for) or keys only, so that the call allocates nothing and
@@ -1527,6 +1535,137 @@ def radix_searchsorted(sorted_keys, needles, side: str = "left", descending: boo
     if side == "both":
         return lower, upper
     return lower if want_lower else upper
+
+
+def bin_caps(key_bytes: int):
+    """rsx_bin_caps -> (max_edges, max_index_bins_lds, share): the most edges rsx_bin_count_device takes for this key
+    width, the values its index mode counts in LDS in one pass over the keys, and the fewest keys worth a workgroup.  Needs no device."""
+    L = _lib.load()
+    out = [ctypes.c_uint32() for _ in range(3)]
+    rc = L.rsx_bin_caps(key_bytes, *[ctypes.byref(o) for o in out])
+    _check_rc(L, rc)
+    return tuple(int(o.value) for o in out)
+
+
+def _bin_args(keys, bins: int, num, out, accumulate: bool, count_dtype):
+    """The checks radix_histogram and radix_bincount share (none needs a context) -> the count dtype."""
+    import torch
+    if accumulate and out is None:
+        raise ValueError("accumulate=True adds to out=, which must be given")
+    if count_dtype is not None and count_dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"count_dtype must be torch.int32 or torch.int64, not {count_dtype}")
+    if out is not None:
+        _index_out(out, (bins,), "the bins")
+        if count_dtype is not None and count_dtype != out.dtype:
+            raise TypeError(f"count_dtype ({count_dtype}) is not the dtype of out ({out.dtype})")
+        if out.device != keys.device:
+            raise ValueError("keys and out must live on the same device")
+        count_dtype = out.dtype
+    if num is not None:
+        if not isinstance(num, torch.Tensor) or num.dtype != torch.int64 or num.numel() != 1:
+            raise TypeError("num must be a one-element int64 tensor")
+        if num.device != keys.device:
+            raise ValueError("keys and num must live on the same device")
+    count_dtype = torch.int64 if count_dtype is None else count_dtype
+    if count_dtype == torch.int32 and keys.numel() >= 1 << 32:
+        raise ValueError("2^32 or more keys need int64 counts")
+    return count_dtype
+
+
+def radix_histogram(keys, edges, side: str = "right", descending: bool = False, num=None, out=None, accumulate: bool = False,
+                    count_dtype=None, ctx: Optional[Context] = None, key_kind: Optional[int] = None):
+    """How many keys fall between the cut points `edges` (rsx_bin_count_device): the m + 1 counts
+    `torch.bincount(radix_searchsorted(edges, keys, side=side, descending=descending).flatten(), minlength=m + 1)` for
+    m = len(edges), in one read of the keys and with no index array.  side="right" (the default, `torch.bucketize(keys,
+    edges, right=True)`) counts in bin b the keys with edges[b - 1] <= key < edges[b]; side="left" those with
+    edges[b - 1] < key <= edges[b].  counts[0] and counts[m] are the two open ends: the keys before the first and from
+    the last edge on (side="left": up to the first and behind the last).
+
+    Against `numpy.histogram(x, edges)[0]` with side="right": it equals counts[1:m], except that numpy closes its last
+    bin on the right, so keys equal to the last edge are in counts[m] here and in the last bin there.
+
+    keys: a contiguous GPU tensor of any shape and of a dtype radix_sort knows (128-bit keys: (..., 16) uint8 with (m, 16)
+       uint8 edges, key_kind= as in radix_argsort); it is not modified.
+    edges: a contiguous 1-D tensor of the same dtype on the same device, sorted in the order radix_sort(descending=
+       descending) leaves -- the total order on bit patterns (-NaN below -inf, -0.0 below +0.0, +NaN above +inf), not
+       torch's; equal edges give empty bins; m = 0 gives one bin.  Unsorted edges give unspecified counts.
+    num: a one-element int64 device tensor such as radix_group(...).num: only the first min(n, num) keys count; it is
+       read on the device.
+    out: a contiguous int32 or int64 tensor of m + 1 counts to write (accumulate=True: to add to); otherwise a new
+       tensor of count_dtype (torch.int64, the default, or torch.int32).
+    More edges than bin_caps(key_bytes)[0] go through radix_searchsorted into an index array and the index form.
+    Enqueued on the current stream, not synchronised; the host reads nothing."""
+    import torch
+    if not isinstance(keys, torch.Tensor) or not isinstance(edges, torch.Tensor):
+        raise TypeError("keys and edges must be torch tensors on a GPU")
+    if edges.dtype != keys.dtype:
+        raise TypeError(f"edges must have the dtype of keys ({keys.dtype}), not {edges.dtype}")
+    if not keys.is_contiguous():
+        raise ValueError("keys must be contiguous")
+    kb, kind, m = _pairs_keys(edges, key_kind)
+    if kb == 16:
+        if keys.dim() < 1 or keys.shape[-1] != 16:
+            raise ValueError("128-bit keys must have shape (..., 16)")
+        n = keys.numel() // 16
+    else:
+        n = keys.numel()
+    if side not in ("left", "right"):
+        raise ValueError(f'side must be "left" or "right", not {side!r}')
+    if edges.device != keys.device:
+        raise ValueError("keys and edges must live on the same device")
+    count_dtype = _bin_args(keys, m + 1, num, out, accumulate, count_dtype)
+    _pairs_device(keys, None, "")
+    if out is None:
+        out = torch.empty(m + 1, dtype=count_dtype, device=keys.device)
+    flags = _lib.BIN_ACCUMULATE if accumulate else 0
+    d_num = num.data_ptr() if num is not None else 0
+    if m > bin_caps(kb)[0]:  # too many edges for LDS: the bin of every key as an index, then the index form
+        flat = keys.reshape(-1, 16) if kb == 16 else keys.reshape(-1)
+        idx = radix_searchsorted(edges, flat, side=side, descending=descending, index_dtype=torch.int32 if m < (1 << 31) - 1 else torch.int64,
+                                 ctx=ctx, key_kind=key_kind)
+        with _on_device(keys, ctx) as (c, stream):
+            c.bin_count_device(idx.data_ptr() if n else 0, n, idx.element_size(), KEY_SIGNED, 0, m, _lib.BIN_INDEX, out.data_ptr(),
+                               out.element_size(), False, d_num, flags, stream)
+        return out
+    with _on_device(keys, ctx) as (c, stream):
+        c.bin_count_device(keys.data_ptr() if n else 0, n, kb, kind, edges.data_ptr() if m else 0, m,
+                           _lib.BIN_UPPER if side == "right" else _lib.BIN_LOWER, out.data_ptr(), out.element_size(), descending, d_num,
+                           flags, stream)
+    return out
+
+
+def radix_bincount(keys, num_bins: int, num=None, out=None, accumulate: bool = False, count_dtype=None, ctx: Optional[Context] = None):
+    """How often every value 0 .. num_bins - 1 occurs among integer `keys` (rsx_bin_count_device, index mode):
+    num_bins + 1 counts, of which [:num_bins] equals `torch.bincount(in-range keys, minlength=num_bins)` and the last
+    entry counts the keys outside -- negative ones and those of num_bins or more, which torch refuses or grows for.
+
+    keys: a contiguous GPU tensor of any shape and an integer dtype (uint8, int8, int16, int32, int64 and, where torch has
+       them, uint16, uint32, uint64); it is not modified.
+    num, out, accumulate, count_dtype: as in radix_histogram; out holds num_bins + 1 counts.
+    Up to bin_caps(key_bytes)[1] values are counted in LDS in one pass over the keys, up to 16 times as many in as many
+    passes, more by atomics straight into the counts.  Enqueued on the
+    current stream, not synchronised; the host reads nothing."""
+    import torch
+    if not isinstance(keys, torch.Tensor):
+        raise TypeError("keys must be a torch tensor on a GPU")
+    if not keys.is_contiguous():
+        raise ValueError("keys must be contiguous")
+    d = _torch_digits(keys, None)
+    if d.key_kind == KEY_FLOAT or d.key_bytes != d.elem_bytes:
+        raise TypeError(f"radix_bincount takes integer keys, not {keys.dtype}")
+    num_bins = operator.index(num_bins)
+    if num_bins < 0 or num_bins >= (1 << 32) - 1:
+        raise ValueError(f"num_bins must be in 0 .. 2^32 - 2, not {num_bins}")
+    count_dtype = _bin_args(keys, num_bins + 1, num, out, accumulate, count_dtype)
+    _pairs_device(keys, None, "")
+    if out is None:
+        out = torch.empty(num_bins + 1, dtype=count_dtype, device=keys.device)
+    n = keys.numel()
+    with _on_device(keys, ctx) as (c, stream):
+        c.bin_count_device(keys.data_ptr() if n else 0, n, d.key_bytes, d.key_kind, 0, num_bins, _lib.BIN_INDEX, out.data_ptr(),
+                           out.element_size(), False, num.data_ptr() if num is not None else 0,
+                           _lib.BIN_ACCUMULATE if accumulate else 0, stream)
+    return out
 
 
 def merge_caps(key_bytes: int, value_bytes: int = 0):

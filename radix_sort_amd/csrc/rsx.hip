@@ -7,6 +7,7 @@
 #include "rsx_misc_kernels.hpp"
 #include "rsx_any_kernels.hpp"
 #include "rsx_select_kernels.hpp"
+#include "rsx_bin_kernels.hpp"
 
 #include <cmath>
 
@@ -1071,6 +1072,9 @@ int rsx_ctx_get_info(rsx_ctx* ctx, int what, uint64_t* out) try {
                     *out = (uint64_t)(ctx->last_sort_passes & 0xFFu) | (uint64_t)(compacted & 0xFu) << 8 | (uint64_t)ctx->last_path << 24;
                     return RSX_OK;
                 }
+                case PATH_BIN:  // bits 0-7 the kernels launched; the path takes bit 28, a bin count has no route
+                    *out = (uint64_t)(ctx->last_sort_passes & 0xFFu) | (uint64_t)ctx->last_path << 24;
+                    return RSX_OK;
                 default: break;
             }
             *out = (uint64_t)ctx->last_path << 24 | (uint64_t)ctx->last_route << 28;
@@ -1863,6 +1867,98 @@ int rsx_select_caps(uint32_t key_bytes, uint32_t* max_ranks, uint32_t* digit_bit
     *tile = SELECT_TILE;
     *cand_div = SELECT_CAND_DIV;
     *cand_floor = SELECT_CAND_FLOOR;
+    return RSX_OK;
+}
+
+// ---- keys per bin of an unsorted key array (rsx_bin_kernels.hpp, include/rsx.h) ----
+namespace {
+struct BinCall {
+    const void* keys;
+    uint64_t n;
+    const uint64_t* num;
+    const void* edges;
+    uint32_t m, mode, kind, desc, cb;
+    void* counts;
+};
+extern "C++" template <int KB>
+int bin_launch(rsx_ctx* ctx, const BinCall& c, hipStream_t st) {
+    const uint32_t stream = c.n * KB >= (uint64_t)RSX_COUNT16_NT_BYTES ? 1u : 0u;  // as rsx_count16top_kernel takes the hint
+    const uint64_t shares = (c.n + SELECT_SHARE - 1) / SELECT_SHARE;
+    const uint32_t groups = c.m == 0 ? 1u : (uint32_t)std::min<uint64_t>(shares, (uint64_t)ctx->num_cu * 2);
+    if (c.mode == RSX_BIN_INDEX) {
+        if constexpr (KB <= 8) {
+            if (c.m <= BIN_INDEX_WINDOWS * BIN_INDEX_LDS)
+                hipLaunchKernelGGL((rsx_bin_index_kernel<KB, true>), dim3(groups), dim3(BIN_WG), 0, st, c.keys, c.n, c.num, c.m, c.counts, c.cb, c.kind,
+                                   stream);
+            else
+                hipLaunchKernelGGL((rsx_bin_index_kernel<KB, false>), dim3(groups), dim3(BIN_WG), 0, st, c.keys, c.n, c.num, c.m, c.counts, c.cb, c.kind,
+                                   stream);
+        } else {
+            return fail(ctx, RSX_ERR_INTERNAL, "no index form for this key width");
+        }
+    } else if (c.mode == RSX_BIN_UPPER) {
+        hipLaunchKernelGGL((rsx_bin_edge_kernel<KB, true>), dim3(groups), dim3(BIN_WG), 0, st, c.keys, c.n, c.num, c.edges, c.m, c.counts, c.cb, c.kind,
+                           c.desc, stream);
+    } else {
+        hipLaunchKernelGGL((rsx_bin_edge_kernel<KB, false>), dim3(groups), dim3(BIN_WG), 0, st, c.keys, c.n, c.num, c.edges, c.m, c.counts, c.cb, c.kind,
+                           c.desc, stream);
+    }
+    RSX_HIP(hipGetLastError());
+    return RSX_OK;
+}
+}  // namespace
+
+int rsx_bin_count_device(rsx_ctx* ctx, const void* d_keys, size_t n, const uint64_t* d_num, uint32_t key_bytes, uint32_t key_kind, const void* d_edges,
+                         uint32_t m, uint32_t mode, int order, void* d_counts, uint32_t count_bytes, uint32_t flags, void* stream) try {
+    if (!ctx) return RSX_ERR_ARG;
+    if (mode != RSX_BIN_UPPER && mode != RSX_BIN_LOWER && mode != RSX_BIN_INDEX) return fail(ctx, RSX_ERR_ARG, "invalid mode");
+    if (flags & ~(uint32_t)RSX_BIN_ACCUMULATE) return fail(ctx, RSX_ERR_ARG, "unknown flag bits");
+    if (count_bytes != 4 && count_bytes != 8) return fail(ctx, RSX_ERR_ARG, "count_bytes must be 4 or 8");
+    if (!key_widths_ok(key_bytes, key_kind)) return fail(ctx, RSX_ERR_ARG, "invalid key width or kind");
+    uint32_t desc = 0;
+    int rc = order_desc(ctx, order, &desc);
+    if (rc) return rc;
+    if (mode == RSX_BIN_INDEX) {
+        if (desc || d_edges) return fail(ctx, RSX_ERR_ARG, "the index mode takes no edges and no order");
+        if (key_bytes == 16 || key_kind == RSX_KEY_FLOAT) return fail(ctx, RSX_ERR_UNSUPPORTED, "the index mode takes integer keys of 1, 2, 4 or 8 bytes");
+    } else if (m > bin_max_edges(key_bytes)) {
+        return fail(ctx, RSX_ERR_UNSUPPORTED, "more edges than rsx_bin_caps reports");
+    }
+    if (m == UINT32_MAX) return fail(ctx, RSX_ERR_ARG, "m + 1 bins do not fit 32 bits");
+    if (count_bytes == 4 && (uint64_t)n >= (1ull << 32)) return fail(ctx, RSX_ERR_UNSUPPORTED, "2^32 or more keys need 8-byte counts");
+    if (!d_counts || (n > 0 && !d_keys) || (mode != RSX_BIN_INDEX && m > 0 && !d_edges)) return fail(ctx, RSX_ERR_ARG, "null device pointer");
+    if (!aligned(d_counts, count_bytes) || !aligned(d_keys, key_bytes) || !aligned(d_edges, key_bytes) || !aligned(d_num, 8))
+        return fail(ctx, RSX_ERR_ARG, "device pointer misaligned");
+    RSX_ENTER(stream);
+    const hipStream_t st = held.st;
+    rc = pending_error(ctx);
+    if (rc) return rc;
+    // No workspace of the context is touched: nothing to make and nothing to order against its other calls.
+    LaunchTimer lt(ctx, RSX_PROF_OTHER, st);
+    uint32_t launched = 0;
+    if (!(flags & RSX_BIN_ACCUMULATE)) {
+        const uint32_t bins = m + 1;
+        hipLaunchKernelGGL(rsx_bin_zero_kernel, dim3(std::min<uint32_t>((bins + 255u) / 256u, 1024u)), dim3(256), 0, st, d_counts, bins, count_bytes);
+        RSX_HIP(hipGetLastError());
+        ++launched;
+    }
+    if (n > 0) {
+        const BinCall c{d_keys, (uint64_t)n, d_num, d_edges, m, mode, key_kind, desc, count_bytes, d_counts};
+        for_key_width(key_bytes, [&](auto kb) { rc = bin_launch<decltype(kb)::value>(ctx, c, st); });
+        if (rc) return rc;
+        ++launched;
+    }
+    note_path(ctx, PATH_BIN, launched);
+    return RSX_OK;
+} catch (...) {
+    return RSX_ERR_HIP;
+}
+
+int rsx_bin_caps(uint32_t key_bytes, uint32_t* max_edges, uint32_t* max_index_bins_lds, uint32_t* share) {
+    if (!max_edges || !max_index_bins_lds || !share || !key_widths_ok(key_bytes, RSX_KEY_UNSIGNED)) return RSX_ERR_ARG;
+    *max_edges = bin_max_edges(key_bytes);
+    *max_index_bins_lds = BIN_INDEX_LDS;
+    *share = SELECT_SHARE;
     return RSX_OK;
 }
 

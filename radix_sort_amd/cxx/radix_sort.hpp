@@ -24,6 +24,7 @@
 //     rsx::join(int how, const K* d_a_keys, size_t na, const K* d_b_keys, size_t nb, I* d_out_a, I* d_out_b, size_t capacity, uint64_t* d_out_num, bool descending, const uint64_t* d_a_num, const uint64_t* d_b_num, const I* d_a_index, const I* d_b_index, hipStream_t)   // RSX_JOIN_*
 //     rsx::join_count(int how, const K* d_a_keys, size_t na, const K* d_b_keys, size_t nb, uint64_t* d_out_num, bool descending, const uint64_t* d_a_num, const uint64_t* d_b_num, hipStream_t)
 //     rsx::select(const K* d_keys, size_t n, const uint64_t* ranks /* host */, uint32_t nranks, K* d_out_keys, I* d_out_index, bool descending, hipStream_t)   // order statistics, no sort
+//     rsx::bin_count(const K* d_keys, size_t n, const K* d_edges, uint32_t m, uint32_t mode, C* d_counts, bool descending, bool accumulate, const uint64_t* d_num, hipStream_t)   // RSX_BIN_*: histogram, bincount
 //     rsx::lexsort({rsx::key_column(d_a), rsx::key_column(d_b, true)}, I* d_index, size_t n, hipStream_t)   // several key columns
 //     rsx::sort_columns({rsx::key_column(d_a), rsx::key_column(d_b, true)}, V* d_values, size_t n, hipStream_t)
 // Errors: the reference panics (mod.rs:68,106); here std::runtime_error is thrown.
@@ -430,6 +431,35 @@ void select(const K* d_keys, size_t n, const uint64_t* ranks, uint32_t nranks, K
     ctx.check(rsx_select_device(ctx.get(), d_keys, n, L.key_bytes, L.key_kind, ranks, nranks, d_out_keys, d_out_index, (uint32_t)sizeof(I),
                                 descending ? RSX_ORDER_DESCENDING : RSX_ORDER_ASCENDING, stream),
               "rsx_select_device");
+}
+
+// Keys per bin of an UNSORTED key array (rsx_bin_count_device): d_counts[b], b = 0 .. m, receives (accumulate: is
+// increased by) the number of the first n -- or min(n, *d_num) -- keys whose bin is b.  mode RSX_BIN_UPPER / RSX_BIN_LOWER:
+// the bin is the number of the m edges, sorted in that order, that are <= / < the key (bins closed on the left / on the
+// right; d_counts[0] and d_counts[m] are the two open ends); RSX_BIN_INDEX: integer keys, the bin is the key's value when
+// it is in 0 .. m - 1, else m, and d_edges is nullptr.  At most bin_caps<K>().max_edges edges.  The keys and edges are
+// only read; there is no workspace, so the call can be captured as it is.  Stream-ordered, never synchronised.
+struct BinCaps {
+    uint32_t max_edges, max_index_bins_lds, share;
+};
+template <typename K>
+BinCaps bin_caps() {
+    BinCaps c{};
+    const rsx_layout L = RadixDigits<K>::layout();
+    if (rsx_bin_caps(L.key_bytes, &c.max_edges, &c.max_index_bins_lds, &c.share) != RSX_OK)
+        throw std::invalid_argument("bin_caps: no bin count for this key width");
+    return c;
+}
+template <typename K, typename C = uint64_t>
+void bin_count(const K* d_keys, size_t n, const K* d_edges, uint32_t m, uint32_t mode, C* d_counts, bool descending = false,
+               bool accumulate = false, const uint64_t* d_num = nullptr, void* stream = nullptr, Context& ctx = default_context()) {
+    static_assert(std::is_integral<C>::value && (sizeof(C) == 4 || sizeof(C) == 8), "counts are 4- or 8-byte integers");
+    const rsx_layout L = RadixDigits<K>::layout();
+    if (L.key_offset != 0 || L.key_bytes != L.elem_bytes) throw std::invalid_argument("bin_count: the key type must be its own key");
+    ctx.check(rsx_bin_count_device(ctx.get(), d_keys, n, d_num, L.key_bytes, L.key_kind, d_edges, m, mode,
+                                   descending ? RSX_ORDER_DESCENDING : RSX_ORDER_ASCENDING, d_counts, (uint32_t)sizeof(C),
+                                   accumulate ? RSX_BIN_ACCUMULATE : 0u, stream),
+              "rsx_bin_count_device");
 }
 
 // Several key columns (rsx_lexsort_device, rsx_sort_columns_device): rows sorted by (column 0, column 1, ...), column 0

@@ -114,6 +114,13 @@ extern "C" {
     pub fn rsx_ctx_reserve_select(ctx: *mut RsxCtx, n: usize, key_bytes: u32) -> c_int;
     pub fn rsx_select_caps(key_bytes: u32, max_ranks: *mut u32, digit_bits: *mut u32, tile: *mut u32, cand_div: *mut u32,
                            cand_floor: *mut u32) -> c_int;
+    // keys per bin of an unsorted key array (include/rsx.h, "keys per bin of an unsorted key array"): mode is RSX_BIN_UPPER
+    // (0), _LOWER (1) between m sorted edges or _INDEX (2, d_edges null, order 0); flags RSX_BIN_ACCUMULATE (1); d_counts
+    // holds m + 1 integers of count_bytes (4 or 8); d_num (may be null) bounds n by a device word; no workspace
+    pub fn rsx_bin_count_device(ctx: *mut RsxCtx, d_keys: *const c_void, n: usize, d_num: *const u64, key_bytes: u32,
+                                key_kind: u32, d_edges: *const c_void, m: u32, mode: u32, order: c_int,
+                                d_counts: *mut c_void, count_bytes: u32, flags: u32, stream: *mut c_void) -> c_int;
+    pub fn rsx_bin_caps(key_bytes: u32, max_edges: *mut u32, max_index_bins_lds: *mut u32, share: *mut u32) -> c_int;
     // scan by key (include/rsx.h, "scan by key"): op is RSX_REDUCE_SUM (0), _MIN (1), _MAX (2); flags RSX_SCAN_EXCLUSIVE (1)
     // and RSX_SCAN_RUNS (2); one result per row at the row's position; d_values null: every value is 1 (ranks);
     // `first` is what the first row of every group receives in an exclusive scan; d_out_num may be null
