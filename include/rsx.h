@@ -211,6 +211,8 @@ enum {
                                  16 keys per bin (rsx_bin_count_device: the four bits are full, so this path is the
                                  value of bits 24-28, bits 24-27 zero and bit 28 set; bits 0-7 are then the kernels
                                  launched, every other bit is 0 -- a bin count has no route),
+                                 17 rows that pass a predicate (rsx_compact_device: reported like 16, bits 24 and 28
+                                 set; bits 0-7 are the kernels launched),
                                  bits 28-29 the route of a layout without kernels of its own: 0 direct, 1 packed
                                  re-layout, 2 key-index proxy (bits 0-27 then describe the sort of the re-laid-out
                                  elements / of the proxies) */
@@ -855,6 +857,59 @@ int rsx_bin_count_device(rsx_ctx *ctx, const void *d_keys, size_t n, const uint6
  * counters share at most 80 KiB of LDS, two workgroups per CU), *max_index_bins_lds = the values, and with m + 1 <=
  * this all bins, that the index mode counts in LDS in one pass over the keys, *share = the fewest keys worth a workgroup. */
 int rsx_bin_caps(uint32_t key_bytes, uint32_t *max_edges, uint32_t *max_index_bins_lds, uint32_t *share);
+
+/* -- rows that pass a predicate, in input order -------------------------------- */
+/* keys[mask], masked_select, nonzero and a stable two-way partition with the count left on the device.
+ * With N = n, or min(n, *d_num) when d_num is given -- a device word, read on the device exactly as in
+ * rsx_bin_count_device -- and M the mapped key of rsx_argsort_device (complemented for descending `order`), row i < N
+ * passes when
+ *     pred(i) = (d_flags == NULL || d_flags[i] != 0)
+ *            && (d_lo == NULL || M(*d_lo) <= M(keys[i]))
+ *            && (d_hi == NULL || M(keys[i]) <  M(*d_hi))
+ * d_lo and d_hi each point to ONE key of key_bytes on the device -- the output of rsx_select_device, a key of
+ * rsx_unique_device, a word the caller wrote --, read by the kernels, never by the host.  The order is the total order on
+ * bit patterns: NaN, +-0 and +-inf are keys and bounds like any other.
+ *     keep(i) = pred(i) XOR (flags & RSX_COMPACT_INVERT)
+ * Let i_0 < ... < i_{m-1} be the kept rows and j_0 < ... < j_{N-m-1} the others.  Every output is optional through NULL
+ * except d_out_num:
+ *     d_out_keys[t]   = keys[i_t]      t < m   the raw key bytes, untouched
+ *     d_out_values[t] = values[i_t]    t < m
+ *     d_out_index[t]  = i_t            t < m   integers of index_bytes (4 or 8)
+ *     d_out_num[0]    = m
+ * With RSX_COMPACT_PARTITION additionally out[m + u] = row j_u for u < N - m in each given output: a stable two-way
+ * partition, the rejected rows in input order too (CUB writes them in reverse).  Without it nothing is written at m and
+ * beyond, with it nothing at N and beyond; nothing but the outputs and the context's workspace is written, the inputs
+ * are only read.
+ * d_keys may be NULL when d_lo, d_hi and d_out_keys are all NULL (a pure mask call; with d_out_index alone: nonzero);
+ * key_bytes and key_kind are then ignored.  All three predicates may be NULL: every row passes, a bounded copy.  Keys of
+ * 1, 2, 4, 8, 16 bytes and every kind.  Values of 1, 2, 4, 8, 16 bytes are moved by the write kernel; any other width up
+ * to RSX_MAX_ELEM_BYTES rides behind positions (d_out_index when given, else n u32 in the workspace) and a row gather
+ * that stops at the device count.  d_values is looked at only when d_out_values is given.
+ * RSX_ERR_ARG: bad widths, kinds, order, flags bits or index_bytes; d_out_num NULL; a needed pointer NULL with n > 0; a
+ * pointer not aligned (keys and bounds: key_bytes; values: as in rsx_sort_pairs_device; index: index_bytes; d_num and
+ * d_out_num: 8); an output pointer equal to (or overlapping) an input.  RSX_ERR_UNSUPPORTED: n >= 2^32.  These are
+ * answered before the context is looked at.  The call is not in place: the tiles of the write launch do not run in order.
+ * n == 0 or N == 0 stores d_out_num[0] = 0 and writes nothing else.
+ *
+ * Three launches, no workgroup waits for another, no atomics -- the same bytes on every call: a count per tile of `tile`
+ * rows (rsx_compact_caps) that streams only the columns the predicate needs, one workgroup's scan over the tile counts
+ * (`scan_span` tiles per sweep; it writes d_out_num), and the write, which ranks the keep bits inside the workgroup,
+ * compacts key, value and source slot in LDS and stores contiguous ranges.  Stream-ordered, no synchronisation, the host
+ * reads nothing.  Workspace: 12 bytes per tile, plus n u32 positions on the wide-value route without d_out_index; made on
+ * first use or by rsx_ctx_reserve_compact (key_bytes, value_bytes, index_bytes: 0 for a column the calls will not have).
+ * Under capture without a sufficient reserve the call returns RSX_ERR_WORKSPACE and enqueues nothing.
+ * RSX_INFO_LAST_PASSES reports path 17 and, in bits 0-7, the kernels launched. */
+#define RSX_COMPACT_INVERT 1u     /* keep the rows the predicate rejects */
+#define RSX_COMPACT_PARTITION 2u  /* write the rejected rows, in input order, behind the kept ones */
+int rsx_compact_device(rsx_ctx *ctx, const void *d_keys, size_t n, const uint64_t *d_num, uint32_t key_bytes,
+                       uint32_t key_kind, int order, const uint8_t *d_flags, const void *d_lo, const void *d_hi,
+                       const void *d_values, uint32_t value_bytes, uint32_t flags, void *d_out_keys, void *d_out_values,
+                       void *d_out_index, uint32_t index_bytes, uint64_t *d_out_num, void *stream);
+int rsx_ctx_reserve_compact(rsx_ctx *ctx, size_t n, uint32_t key_bytes, uint32_t value_bytes, uint32_t index_bytes);
+/* Host-only, needs no device: *tile = the rows one workgroup of the count and write launches takes for these widths (a
+ * multiple of 256; a key, a value and a two-byte slot per row stay within 80 KiB of LDS, two workgroups per CU; a value
+ * width without a typed kernel counts as none), *scan_span = the tiles one sweep of the scan takes. */
+int rsx_compact_caps(uint32_t key_bytes, uint32_t value_bytes, uint32_t index_bytes, uint32_t *tile, uint32_t *scan_span);
 
 /* -- several key columns ----------------------------------------------------- */
 /* Sorting a table by (a, b descending, c): ncols key columns of n keys each, column 0 the MOST significant (the opposite

@@ -25,7 +25,7 @@ ELEM_SIZES = (1, 2, 4, 8, 12, 16, 24, 32)
 UNITS = (
     ("rsx.hip", "rsx.o", ()),                # the C-ABI and the size-independent kernels
     ("rsx_pairs.hip", "rsx_pairs.o", ()),    # the join and split kernels of the key / value calls
-    ("rsx_unique.hip", "rsx_unique.o", ()),  # the run kernels of rsx_unique_device
+    ("rsx_unique.hip", "rsx_unique.o", ()),  # the run kernels of rsx_unique_device and the kernels of rsx_compact_device
     ("rsx_scan.hip", "rsx_scan.o", ()),      # those of rsx_scan_by_key_device and, through rsx_reduce.hip, which it includes,
                                              # of rsx_reduce_by_key_device: one unit, the tile scan both calls launch built once
     ("rsx_lex.hip", "rsx_lex.o", ()),        # the join of several key columns: rsx_lexsort_device, rsx_sort_columns_device

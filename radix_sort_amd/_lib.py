@@ -30,6 +30,7 @@ SYMBOLS = [
     "rsx_join_device", "rsx_ctx_reserve_join", "rsx_join_caps",
     "rsx_select_device", "rsx_ctx_reserve_select", "rsx_select_caps",
     "rsx_bin_count_device", "rsx_bin_caps",
+    "rsx_compact_device", "rsx_ctx_reserve_compact", "rsx_compact_caps",
 ]
 SEG_CLASSES = 2  # RSX_SEG_CLASSES
 LEX_MAX_COLUMNS = 16  # RSX_LEX_MAX_COLUMNS
@@ -49,6 +50,7 @@ SCAN_EXCLUSIVE, SCAN_RUNS = 1, 2
 SEARCH_PRESORT = 1
 BIN_UPPER, BIN_LOWER, BIN_INDEX = 0, 1, 2
 BIN_ACCUMULATE = 1
+COMPACT_INVERT, COMPACT_PARTITION = 1, 2
 SETOP_UNION, SETOP_INTERSECTION, SETOP_DIFFERENCE, SETOP_SYMMETRIC_DIFFERENCE = 0, 1, 2, 3
 JOIN_INNER, JOIN_LEFT, JOIN_SEMI, JOIN_ANTI = 0, 1, 2, 3
 SHARD_EXCHANGE_FIRST, SHARD_SORT_FIRST = 0, 1
@@ -185,6 +187,9 @@ def load():
     L.rsx_select_caps.argtypes = [u32, pu32, pu32, pu32, pu32, pu32]
     L.rsx_bin_count_device.argtypes = [vp, vp, sz, vp, u32, u32, vp, u32, u32, i, vp, u32, u32, vp]
     L.rsx_bin_caps.argtypes = [u32, pu32, pu32, pu32]
+    L.rsx_compact_device.argtypes = [vp, vp, sz, vp, u32, u32, i, vp, vp, vp, vp, u32, u32, vp, vp, vp, u32, vp, vp]
+    L.rsx_ctx_reserve_compact.argtypes = [vp, sz, u32, u32, u32]
+    L.rsx_compact_caps.argtypes = [u32, u32, u32, pu32, pu32]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("rsx_last_error", "rsx_strerror"):

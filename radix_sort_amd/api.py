@@ -316,6 +316,24 @@ class Context:
         self._check(self._L.rsx_bin_count_device(self._h, d_keys or None, n, d_num or None, key_bytes, key_kind, d_edges or None, m, mode,
                                                  1 if descending else 0, d_counts or None, count_bytes, flags, stream))
 
+    def reserve_compact(self, n: int, key_bytes: int = 0, value_bytes: int = 0, index_bytes: int = 0):
+        """rsx_ctx_reserve_compact: the context's first-call set-up and the workspace of compact_device on up to n rows with
+        keys, values and indices of these widths (0: the calls have no such column), so that the call allocates nothing
+        and can be captured."""
+        self._check(self._L.rsx_ctx_reserve_compact(self._h, n, key_bytes, value_bytes, index_bytes))
+
+    def compact_device(self, d_keys: int, n: int, key_bytes: int, key_kind: int, d_flags: int, d_lo: int, d_hi: int, d_values: int,
+                       value_bytes: int, d_out_keys: int, d_out_values: int, d_out_index: int, index_bytes: int, d_out_num: int,
+                       descending: bool = False, d_num: int = 0, flags: int = 0, stream: int = 0):
+        """rsx_compact_device: of the first n (or min(n, *d_num)) rows those whose flag byte at d_flags is non-zero and whose
+        key lies in [*d_lo, *d_hi) (each of the three may be 0: no such condition; flags COMPACT_INVERT: the others), in
+        input order -- keys, values and positions into the outputs that are not 0, their number into d_out_num; flags
+        COMPACT_PARTITION: the remaining rows behind them, in input order too.  Not in place."""
+        self._check(self._L.rsx_compact_device(self._h, d_keys or None, n, d_num or None, key_bytes, key_kind, 1 if descending else 0,
+                                               d_flags or None, d_lo or None, d_hi or None, d_values or None, value_bytes, flags,
+                                               d_out_keys or None, d_out_values or None, d_out_index or None, index_bytes, d_out_num or None,
+                                               stream))
+
     def reserve_unique(self, n: int, key_bytes: int, with_positions: bool = True):
         """rsx_ctx_reserve_unique: the context's first-call set-up and the workspace of unique_device on up to n keys of this
         width, by the route with positions (perm or inverse asked for) or keys only, so that the call allocates nothing and
@@ -1666,6 +1684,164 @@ def radix_bincount(keys, num_bins: int, num=None, out=None, accumulate: bool = F
                            out.element_size(), False, num.data_ptr() if num is not None else 0,
                            _lib.BIN_ACCUMULATE if accumulate else 0, stream)
     return out
+
+
+def compact_caps(key_bytes: int = 0, value_bytes: int = 0, index_bytes: int = 0):
+    """rsx_compact_caps -> (tile, scan_span): the rows one workgroup of rsx_compact_device's count and write launches takes
+    for these key, value and index widths (0: no such column), and the tiles one sweep of its scan takes.  Needs no
+    device."""
+    L = _lib.load()
+    out = [ctypes.c_uint32() for _ in range(2)]
+    _check_rc(L, L.rsx_compact_caps(key_bytes, value_bytes, index_bytes, *[ctypes.byref(o) for o in out]))
+    return tuple(int(o.value) for o in out)
+
+
+Compacted = namedtuple("Compacted", ["keys", "values", "index", "num"])
+
+
+def _compact_bound(bound, keys, kb: int, what: str):
+    """lo= / hi= of radix_compact -> None or a one-key tensor of the keys' dtype; a Python scalar is placed beside the
+    keys with torch.tensor (a copy to the device, no read from it)."""
+    import torch
+    if bound is None:
+        return None
+    if keys is None:
+        raise ValueError(f"{what} needs keys to compare with")
+    if not isinstance(bound, torch.Tensor):
+        if kb == 16 or isinstance(bound, (bool, str, bytes)) or not isinstance(bound, (int, float)):
+            raise TypeError(f"{what} must be a one-element tensor of the keys' dtype or a Python number")
+        return torch.tensor([bound], dtype=keys.dtype, device=keys.device)
+    if bound.dtype != keys.dtype:
+        raise TypeError(f"{what} must have the dtype of keys ({keys.dtype}), not {bound.dtype}")
+    if bound.numel() != (16 if kb == 16 else 1) or not bound.is_contiguous():
+        raise ValueError(f"{what} must hold one key: a one-element tensor" + (" ((16,) or (1, 16) uint8 for 128-bit keys)" if kb == 16 else ""))
+    if bound.device != keys.device:
+        raise ValueError(f"keys and {what} must live on the same device")
+    return bound
+
+
+def radix_compact(keys, mask=None, lo=None, hi=None, values=None, descending: bool = False, invert: bool = False,
+                  partition: bool = False, return_index: bool = False, index_dtype=None, num=None, out=None,
+                  ctx: Optional[Context] = None, key_kind: Optional[int] = None):
+    """The rows that pass a mask and / or a key range, in input order, with their number left on the device
+    (rsx_compact_device): `keys[mask]`, `torch.masked_select`, `values[(keys >= lo) & (keys < hi)]` without a host read,
+    so that the call can be captured and chained.  Row i passes when mask[i] is non-zero (mask given), lo <= keys[i] (lo
+    given) and keys[i] < hi (hi given), compared in the order radix_sort(descending=descending) leaves -- the total order
+    on bit patterns (-NaN below -inf, -0.0 below +0.0, +NaN above +inf), not torch's; descending=True turns both
+    comparisons round (lo is then the largest key that passes).  invert=True keeps the rows that do not pass.
+
+    Returns Compacted(keys, values, index, num): tensors of n rows like the inputs (None for an input that was not given,
+    index only with return_index=True: the input position of every output row, index_dtype torch.int64 or torch.int32)
+    and num, a 0-d int64 device tensor.  Only the first num rows are defined; partition=True writes the other rows
+    behind them, in input order too (a stable two-way partition), so that all min(n, num_in) rows are.
+
+    keys: a contiguous 1-D GPU tensor of a dtype radix_sort knows, or (n, 16) uint8 128-bit keys (key_kind=); or None
+       with a mask (then values and / or the index are the outputs).
+    mask: a contiguous bool or uint8 tensor of n elements; any non-zero byte passes.
+    lo, hi: one-element tensors of the keys' dtype on the device, such as radix_quantile(keys, [q]) or a slice
+       Group.keys[i:i + 1], read on the device; or Python numbers.
+    values: a contiguous tensor with one row per key; a row (trailing dimensions included) is one value of up to 32768
+       bytes, moved bitwise.  Widths of 1, 2, 4, 8, 16 bytes move in the write kernel, others behind positions.
+    num: a one-element int64 device tensor such as radix_group(...).num: only the first min(n, num) rows count.
+    out: a Compacted of preallocated tensors (keys, values, index of n rows, num of one int64 element; None for an output
+       that is not wanted): nothing is allocated, and after Context.reserve_compact the call can be captured.  No output
+       may overlap an input.
+    Enqueued on the current stream, not synchronised; the host reads nothing."""
+    import torch
+    if keys is None:
+        if mask is None:
+            raise ValueError("keys=None needs a mask")
+        if key_kind is not None:
+            raise ValueError("key_kind= is for (n, 16) uint8 keys")
+        kb, kind = 0, KEY_UNSIGNED
+    else:
+        kb, kind, n = _pairs_keys(keys, key_kind)
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8):
+            raise TypeError("mask must be a torch tensor of dtype bool or uint8")
+        if mask.dim() != 1 or not mask.is_contiguous():
+            raise ValueError("mask must be a contiguous 1-D tensor with one element per row")
+        if keys is None:
+            n = mask.shape[0]
+        elif mask.shape[0] != n:
+            raise ValueError(f"mask must have one element per key ({n}), not {mask.shape[0]}")
+    like = keys if keys is not None else mask
+    lo = _compact_bound(lo, keys, kb, "lo")
+    hi = _compact_bound(hi, keys, kb, "hi")
+    vb = _value_bytes(values, (n,), "keys")
+    for t, what in ((mask, "mask"), (values, "values")):
+        if t is not None and t.device != like.device:
+            raise ValueError(f"keys and {what} must live on the same device")
+    _set_num(num, like, "num")
+    if n >= 1 << 32:
+        raise ValueError("radix_compact takes fewer than 2^32 rows")
+    if out is not None:
+        if not isinstance(out, (tuple, list)) or len(out) != 4:
+            raise TypeError("out must be a Compacted(keys, values, index, num)")
+        out_keys, out_values, out_index, out_num = out
+        if out_keys is not None:
+            if keys is None:
+                raise ValueError("out.keys needs keys")
+            _merge_out(out_keys, keys, n, "keys")
+        if out_values is not None:
+            if values is None:
+                raise ValueError("out.values needs values")
+            _merge_out(out_values, values, n, "values")
+        if out_index is not None:
+            _index_out(out_index, (n,), "the rows")
+            if out_index.device != like.device:
+                raise ValueError("the keys and out (index) must live on the same device")
+            if index_dtype is not None and index_dtype != out_index.dtype:
+                raise TypeError(f"index_dtype ({index_dtype}) is not the dtype of out.index ({out_index.dtype})")
+        elif return_index:
+            raise ValueError("return_index=True with out= needs out.index")
+        if not isinstance(out_num, torch.Tensor) or out_num.dtype != torch.int64 or out_num.numel() != 1:
+            raise TypeError("out.num must be a one-element int64 tensor")
+        if out_num.device != like.device:
+            raise ValueError("the keys and out (num) must live on the same device")
+    else:
+        index_dtype = _index_dtype(index_dtype)
+    if not like.is_cuda:
+        raise ValueError("keys and mask must live on a GPU")
+    if out is None:
+        dev = like.device
+        out_keys = torch.empty_like(keys) if keys is not None else None
+        out_values = torch.empty_like(values) if values is not None else None
+        out_index = torch.empty(n, dtype=index_dtype, device=dev) if return_index else None
+        out_num = torch.empty((), dtype=torch.int64, device=dev)
+    result = Compacted(out_keys, out_values, out_index, out_num)
+    if n == 0:  # (empty tensors have no address to hand to the C call)
+        out_num.zero_()
+        return result
+    flags = (_lib.COMPACT_INVERT if invert else 0) | (_lib.COMPACT_PARTITION if partition else 0)
+    with _on_device(like, ctx) as (c, stream):
+        c.compact_device(keys.data_ptr() if keys is not None else 0, n, kb, kind, mask.data_ptr() if mask is not None else 0,
+                         lo.data_ptr() if lo is not None else 0, hi.data_ptr() if hi is not None else 0,
+                         values.data_ptr() if out_values is not None else 0, vb if out_values is not None else 0,
+                         out_keys.data_ptr() if out_keys is not None else 0, out_values.data_ptr() if out_values is not None else 0,
+                         out_index.data_ptr() if out_index is not None else 0, out_index.element_size() if out_index is not None else 8,
+                         out_num.data_ptr(), descending, num.data_ptr() if num is not None else 0, flags, stream)
+    return result
+
+
+def radix_nonzero(mask, num=None, index_dtype=None, out=None, ctx: Optional[Context] = None):
+    """The positions where a 1-D mask is set, in ascending order, and their number on the device (rsx_compact_device with
+    the index as its only output): returns (index, num); index[:num] equals `torch.nonzero(mask).flatten()`, the rest of
+    its n entries is not written; num is a 0-d int64 device tensor.  No host read, so it can be captured.
+
+    mask: a contiguous 1-D bool or uint8 GPU tensor; any non-zero byte counts.
+    num: a one-element int64 device tensor: only the first min(n, num) elements are looked at.
+    index_dtype: torch.int64 (default) or torch.int32.  out: a pair (index, num) of preallocated tensors."""
+    if out is not None:
+        if not isinstance(out, (tuple, list)) or len(out) != 2:
+            raise TypeError("out must be a pair (index, num)")
+        if out[0] is None:
+            raise TypeError("out must be a pair (index, num) of tensors")
+        out = Compacted(None, None, out[0], out[1])
+    if mask is None:
+        raise TypeError("mask must be a torch tensor of dtype bool or uint8")
+    r = radix_compact(None, mask=mask, return_index=True, index_dtype=index_dtype, num=num, out=out, ctx=ctx)
+    return r.index, r.num
 
 
 def merge_caps(key_bytes: int, value_bytes: int = 0):

@@ -1072,7 +1072,8 @@ int rsx_ctx_get_info(rsx_ctx* ctx, int what, uint64_t* out) try {
                     *out = (uint64_t)(ctx->last_sort_passes & 0xFFu) | (uint64_t)(compacted & 0xFu) << 8 | (uint64_t)ctx->last_path << 24;
                     return RSX_OK;
                 }
-                case PATH_BIN:  // bits 0-7 the kernels launched; the path takes bit 28, a bin count has no route
+                case PATH_BIN:      // bits 0-7 the kernels launched; the path takes bit 28, a bin count has no route
+                case PATH_COMPACT:  // the same: bits 0-7 the kernels launched, the path in bits 24-28
                     *out = (uint64_t)(ctx->last_sort_passes & 0xFFu) | (uint64_t)ctx->last_path << 24;
                     return RSX_OK;
                 default: break;
@@ -2222,6 +2223,156 @@ int rsx_ctx_reserve_setop(rsx_ctx* ctx, size_t n_total, uint32_t key_bytes) try 
 int rsx_setop_caps(uint32_t key_bytes, uint32_t* tile) {
     if (!tile || !key_widths_ok(key_bytes, RSX_KEY_UNSIGNED)) return RSX_ERR_ARG;
     *tile = setop_tile_elems(key_bytes);
+    return RSX_OK;
+}
+
+// ---- rows that pass a predicate, in input order (rsx_compact_kernels.hpp, include/rsx.h) ----
+namespace {
+// The workspace of one rsx_compact_device call: per tile its kept rows and those in front of it; n u32 positions when the
+// values have no typed kernel and the caller's own index cannot serve.
+struct CompactPlan {
+    Carve ws;
+    bool wide;         // the values ride behind positions and a row gather
+    uint32_t kvb;      // the value width of the kernels: 0 on that route
+    size_t count_off;  // tile_count [tiles] u32
+    size_t base_off;   // tile_base [tiles] u64
+    size_t pos_off;    // wide: pos [n] u32
+};
+CompactPlan compact_plan(size_t n, uint32_t kb, uint32_t vb) {
+    CompactPlan P{};
+    P.wide = !value_width_fused(vb);
+    P.kvb = P.wide ? 0u : vb;
+    const uint32_t tile = compact_tile_elems(kb, P.kvb);
+    const size_t tiles = (n + tile - 1) / tile;
+    P.count_off = P.ws.take(tiles * sizeof(uint32_t));
+    P.base_off = P.ws.take(tiles * sizeof(uint64_t));
+    if (P.wide) P.pos_off = P.ws.take(n * sizeof(uint32_t));
+    return P;
+}
+// Every check of rsx_compact_device that needs neither the context nor the device: 0, or the code with *what set.
+int compact_check(const void* d_keys, size_t n, const uint64_t* d_num, uint32_t key_bytes, uint32_t key_kind, int order, const uint8_t* d_flags,
+                  const void* d_lo, const void* d_hi, const void* d_values, uint32_t value_bytes, uint32_t flags, const void* d_out_keys,
+                  const void* d_out_values, const void* d_out_index, uint32_t index_bytes, const uint64_t* d_out_num, const char** what) {
+    const bool keyed = d_lo || d_hi || d_out_keys;
+    *what = "invalid key width or kind";
+    if (keyed && !key_widths_ok(key_bytes, key_kind)) return RSX_ERR_ARG;
+    *what = "invalid order";
+    if (order != RSX_ORDER_ASCENDING && order != RSX_ORDER_DESCENDING) return RSX_ERR_ARG;
+    *what = "unknown flag bits";
+    if (flags & ~(uint32_t)(RSX_COMPACT_INVERT | RSX_COMPACT_PARTITION)) return RSX_ERR_ARG;
+    *what = "value wider than RSX_MAX_ELEM_BYTES";
+    if (value_bytes > RSX_MAX_ELEM_BYTES) return RSX_ERR_ARG;
+    *what = "index_bytes must be 4 or 8";
+    if (d_out_index && index_bytes != 4 && index_bytes != 8) return RSX_ERR_ARG;
+    *what = "d_out_num is null";
+    if (!d_out_num) return RSX_ERR_ARG;
+    *what = "value pointers and value_bytes disagree";
+    if ((value_bytes == 0 && (d_values || d_out_values)) || (d_out_values && !d_values)) return RSX_ERR_ARG;
+    *what = "null device pointer";
+    if (n > 0 && keyed && !d_keys) return RSX_ERR_ARG;  // (values without d_values: refused above)
+    *what = "device pointer misaligned";
+    const uint32_t ka = keyed ? key_bytes : 1u, va = value_bytes ? value_align(value_bytes) : 1u, ia = d_out_index ? index_bytes : 1u;
+    if (!aligned(d_keys, ka) || !aligned(d_lo, ka) || !aligned(d_hi, ka) || !aligned(d_out_keys, ka) || !aligned(d_values, va) ||
+        !aligned(d_out_values, va) || !aligned(d_out_index, ia) || !aligned(d_num, 8) || !aligned(d_out_num, 8))
+        return RSX_ERR_ARG;
+    *what = "an output pointer equals an input pointer";
+    const void* in[] = {d_keys, d_flags, d_lo, d_hi, d_values, d_num};
+    const void* out[] = {d_out_keys, d_out_values, d_out_index, d_out_num};
+    for (const void* o : out)
+        for (const void* i : in)
+            if (o && o == i) return RSX_ERR_ARG;
+    *what = "2^32 or more rows";  // (the last check: what is wrong with the arguments themselves comes first)
+    if ((uint64_t)n >= (1ull << 32)) return RSX_ERR_UNSUPPORTED;
+    *what = "";
+    return RSX_OK;
+}
+}  // namespace
+
+int rsx_compact_device(rsx_ctx* ctx, const void* d_keys, size_t n, const uint64_t* d_num, uint32_t key_bytes, uint32_t key_kind, int order,
+                       const uint8_t* d_flags, const void* d_lo, const void* d_hi, const void* d_values, uint32_t value_bytes, uint32_t flags,
+                       void* d_out_keys, void* d_out_values, void* d_out_index, uint32_t index_bytes, uint64_t* d_out_num, void* stream) try {
+    // the argument checks come first and need no context: a caller's mistake has the same answer with and without one
+    const char* what = "";
+    int rc = compact_check(d_keys, n, d_num, key_bytes, key_kind, order, d_flags, d_lo, d_hi, d_values, value_bytes, flags, d_out_keys, d_out_values,
+                           d_out_index, index_bytes, d_out_num, &what);
+    if (rc) return fail(ctx, rc, what);
+    if (!ctx) return RSX_ERR_ARG;
+    const uint32_t desc = order == RSX_ORDER_DESCENDING ? 1u : 0u;
+    const bool keyed = d_lo || d_hi || d_out_keys;
+    const uint32_t kb = keyed ? key_bytes : 0u;
+    if (!d_out_values) value_bytes = 0;  // the values are not looked at
+    RSX_ENTER(stream);
+    const hipStream_t st = held.st;
+    if (n == 0) return no_group(ctx, PATH_COMPACT, d_out_num, nullptr, st);
+    const uint32_t ib = d_out_index ? index_bytes : 0u;
+    rc = check_disjoint(ctx,
+                        {{d_keys, (uint64_t)n * kb}, {d_flags, (uint64_t)n}, {d_lo, kb}, {d_hi, kb}, {d_values, (uint64_t)n * value_bytes}, {d_num, 8}},
+                        {{d_out_keys, (uint64_t)n * kb}, {d_out_values, (uint64_t)n * value_bytes}, {d_out_index, (uint64_t)n * ib}, {d_out_num, 8}});
+    if (rc) return rc;
+    rc = pending_error(ctx);
+    if (rc) return rc;
+    const CompactPlan P = compact_plan(n, kb, value_bytes);
+    // the positions of the wide route: the index the caller asked for when there is one, else n u32 in the workspace
+    const bool ws_pos = P.wide && !d_out_index;
+    const size_t need = P.wide && !ws_pos ? P.pos_off : P.ws.bytes;  // (without them: the arrays in front of them)
+    rc = ensure_aux(ctx, st);
+    if (rc) return rc;
+    rc = ensure_any(ctx, need, st);
+    if (rc) return rc;
+    Enqueue enq(ctx, st);  // the workspace arrays belong to this call from the first launch on
+    char* w = reinterpret_cast<char*>(ctx->any_buf);
+    CompactCall c{};
+    c.keys = kb ? d_keys : nullptr;
+    c.flags = d_flags;
+    c.lo = d_lo;
+    c.hi = d_hi;
+    c.values = d_values;
+    c.n = n;
+    c.num = d_num;
+    c.kb = kb;
+    c.kind = key_kind;
+    c.desc = desc;
+    c.vb = P.kvb;
+    c.ib = ws_pos ? 4u : (ib ? ib : 4u);
+    c.mode = flags;
+    c.tile_count = reinterpret_cast<uint32_t*>(w + P.count_off);
+    c.tile_base = reinterpret_cast<uint64_t*>(w + P.base_off);
+    c.out_keys = d_out_keys;
+    c.out_values = P.wide ? nullptr : d_out_values;
+    c.out_index = ws_pos ? static_cast<void*>(w + P.pos_off) : d_out_index;
+    c.out_num = d_out_num;
+    uint32_t launched = 0;
+    rc = launch_compact(ctx, c, &launched, st);
+    if (rc) return rc;
+    if (P.wide) {
+        rc = launch_compact_gather(ctx, c, c.out_index, c.ib, value_bytes, d_out_values, st);
+        if (rc) return rc;
+        ++launched;
+    }
+    note_path(ctx, PATH_COMPACT, launched);
+    return RSX_OK;
+} catch (...) {
+    return RSX_ERR_HIP;
+}
+
+int rsx_ctx_reserve_compact(rsx_ctx* ctx, size_t n, uint32_t key_bytes, uint32_t value_bytes, uint32_t index_bytes) try {
+    if (!ctx) return RSX_ERR_ARG;
+    if ((key_bytes != 0 && !key_widths_ok(key_bytes, RSX_KEY_UNSIGNED)) || value_bytes > RSX_MAX_ELEM_BYTES ||
+        (index_bytes != 0 && index_bytes != 4 && index_bytes != 8))
+        return fail(ctx, RSX_ERR_ARG, "invalid key, value or index width");
+    if ((uint64_t)n >= (1ull << 32)) return fail(ctx, RSX_ERR_UNSUPPORTED, "2^32 or more rows");
+    // enough whichever of these columns a call leaves out: a narrower row only widens the tile, so there are fewer of them
+    return reserve_any_entry(ctx, compact_plan(n, key_bytes, value_bytes).ws.bytes);
+} catch (...) {
+    return RSX_ERR_NOMEM;
+}
+
+int rsx_compact_caps(uint32_t key_bytes, uint32_t value_bytes, uint32_t index_bytes, uint32_t* tile, uint32_t* scan_span) {
+    if (!tile || !scan_span || (key_bytes != 0 && !key_widths_ok(key_bytes, RSX_KEY_UNSIGNED)) || value_bytes > RSX_MAX_ELEM_BYTES ||
+        (index_bytes != 0 && index_bytes != 4 && index_bytes != 8))
+        return RSX_ERR_ARG;
+    *tile = compact_tile_elems(key_bytes, value_width_fused(value_bytes) ? value_bytes : 0u);
+    *scan_span = unique_scan_span();
     return RSX_OK;
 }
 

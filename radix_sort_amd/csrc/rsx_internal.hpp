@@ -3,7 +3,7 @@
 //   rsx_es.hip      the kernel launchers of ONE element size (compiled once per size with -DRSX_ES=n,
 //                   so the eight sizes build in parallel), reached through that size's EsLaunchers table
 //   rsx_pairs.hip   the join and split kernels of the key / value calls
-//   rsx_unique.hip  the run kernels of rsx_unique_device
+//   rsx_unique.hip  the run kernels of rsx_unique_device and, around their tile scan, the kernels of rsx_compact_device
 //   rsx_scan.hip    the kernels of rsx_scan_by_key_device and, through rsx_reduce.hip, which it includes, the run kernels
 //                   of rsx_reduce_by_key_device
 //   rsx_search.hip  the kernel of rsx_search_sorted_device and, built from its functions, those of rsx_join_device
@@ -70,7 +70,7 @@ constexpr int HOST_RING = 4;
 // every array carved out of a workspace starts on a 256-byte boundary
 constexpr size_t round256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
-// rsx_ctx::last_path, what the last call ran.  The values are frozen: RSX_INFO_LAST_PASSES reports them in bits 24..27 (PATH_BIN: 24..28).
+// rsx_ctx::last_path, what the last call ran.  The values are frozen: RSX_INFO_LAST_PASSES reports them in bits 24..27 (PATH_BIN, PATH_COMPACT: 24..28).
 enum : uint32_t {
     PATH_LSD = 0,        // general passes
     PATH_SMALL = 1,      // one-launch sort
@@ -89,6 +89,7 @@ enum : uint32_t {
     PATH_SCAN = 14,      // scan by key
     PATH_SELECT = 15,    // order statistics (the last value the four bits hold)
     PATH_BIN = 16,       // keys per bin: it takes bit 28 with it, where the sorts report their route (it has none)
+    PATH_COMPACT = 17,   // rows that pass a predicate: bits 24 and 28, as PATH_BIN
 };
 
 // option bits (rsx_ctx_set_option): alternative kernel paths, all bit-exact
@@ -751,5 +752,30 @@ uint32_t setop_tile_elems(uint32_t kb);  // merge positions per workgroup
 uint32_t setop_save_words();
 // rsx_unique_scan_kernel over another call's per-tile counts (rsx_unique.hip): tile_base[t] and their sum -> out_num[0]
 void launch_run_scan(const uint32_t* tile_count, uint64_t* tile_base, uint64_t tiles, uint64_t* out_num, hipStream_t st);
+
+// What one rsx_compact_device call asks of the compaction kernels (rsx_unique.hip, rsx_compact_kernels.hpp).
+struct CompactCall {
+    const void* keys;            // n keys of kb bytes; null (kb 0) when the call neither compares nor emits keys
+    const uint8_t* flags;        // null, or n flag bytes
+    const void* lo;              // null, or one key on the device: the bounds of the key range
+    const void* hi;
+    const void* values;          // n values of vb bytes (read only when out_values is given)
+    size_t n;                    // 1 .. 2^32 - 1
+    const uint64_t* num;         // null, or one device word: only the first min(n, *num) rows count
+    uint32_t kb, kind, desc;
+    uint32_t vb;                 // 0, or a fused width (value_width_fused): what the write kernel moves itself
+    uint32_t ib;                 // bytes of a position in out_index
+    uint32_t mode;               // RSX_COMPACT_* bits
+    uint32_t* tile_count;        // per tile of compact_tile_elems: its kept rows, and ...
+    uint64_t* tile_base;         // ... those in front of it
+    void* out_keys;              // each may be null
+    void* out_values;
+    void* out_index;
+    uint64_t* out_num;           // the number of kept rows
+};
+int launch_compact(rsx_ctx* ctx, const CompactCall& call, uint32_t* launched, hipStream_t st);
+// out_values row r = row pos[r] (pb bytes each) of `values`, rows of vb bytes, for the rows the call wrote
+int launch_compact_gather(rsx_ctx* ctx, const CompactCall& call, const void* pos, uint32_t pb, uint32_t vb, void* out_values, hipStream_t st);
+uint32_t compact_tile_elems(uint32_t kb, uint32_t vb);  // rows per workgroup of the count and write kernels
 
 }  // namespace rsxh

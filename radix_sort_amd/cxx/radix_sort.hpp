@@ -25,6 +25,7 @@
 //     rsx::join_count(int how, const K* d_a_keys, size_t na, const K* d_b_keys, size_t nb, uint64_t* d_out_num, bool descending, const uint64_t* d_a_num, const uint64_t* d_b_num, hipStream_t)
 //     rsx::select(const K* d_keys, size_t n, const uint64_t* ranks /* host */, uint32_t nranks, K* d_out_keys, I* d_out_index, bool descending, hipStream_t)   // order statistics, no sort
 //     rsx::bin_count(const K* d_keys, size_t n, const K* d_edges, uint32_t m, uint32_t mode, C* d_counts, bool descending, bool accumulate, const uint64_t* d_num, hipStream_t)   // RSX_BIN_*: histogram, bincount
+//     rsx::compact(const K* d_keys, size_t n, const uint8_t* d_flags, const K* d_lo, const K* d_hi, const V* d_values, K* d_out_keys, V* d_out_values, I* d_out_index, uint64_t* d_out_num, uint32_t flags, bool descending, const uint64_t* d_num, hipStream_t)   // RSX_COMPACT_*: select-if, partition, nonzero
 //     rsx::lexsort({rsx::key_column(d_a), rsx::key_column(d_b, true)}, I* d_index, size_t n, hipStream_t)   // several key columns
 //     rsx::sort_columns({rsx::key_column(d_a), rsx::key_column(d_b, true)}, V* d_values, size_t n, hipStream_t)
 // Errors: the reference panics (mod.rs:68,106); here std::runtime_error is thrown.
@@ -460,6 +461,37 @@ void bin_count(const K* d_keys, size_t n, const K* d_edges, uint32_t m, uint32_t
                                    descending ? RSX_ORDER_DESCENDING : RSX_ORDER_ASCENDING, d_counts, (uint32_t)sizeof(C),
                                    accumulate ? RSX_BIN_ACCUMULATE : 0u, stream),
               "rsx_bin_count_device");
+}
+
+// Rows that pass a predicate, in input order (rsx_compact_device): row i of the first n -- or min(n, *d_num) -- passes when
+// d_flags[i] != 0 (d_flags given) and *d_lo <= d_keys[i] < *d_hi in the sort's order (each bound given; ONE key on the
+// device each); flags RSX_COMPACT_INVERT keeps the others.  The kept keys, values and input positions go to the outputs
+// that are not nullptr, their number to *d_out_num; RSX_COMPACT_PARTITION writes the remaining rows behind them, in input
+// order too.  d_keys may be nullptr when neither a bound nor d_out_keys is given (K is then any key type, say uint8_t).
+// Not in place.  Stream-ordered, never synchronised; Context::reserve is not enough for a capture: rsx_ctx_reserve_compact.
+struct CompactCaps {
+    uint32_t tile, scan_span;
+};
+template <typename K, typename V = uint32_t, typename I = uint64_t>
+CompactCaps compact_caps(bool with_values = false, bool with_index = false) {
+    CompactCaps c{};
+    const rsx_layout L = RadixDigits<K>::layout();
+    if (rsx_compact_caps(L.key_bytes, with_values ? (uint32_t)sizeof(V) : 0u, with_index ? (uint32_t)sizeof(I) : 0u, &c.tile, &c.scan_span) != RSX_OK)
+        throw std::invalid_argument("compact_caps: no compaction for these widths");
+    return c;
+}
+template <typename K, typename V = uint32_t, typename I = uint64_t>
+void compact(const K* d_keys, size_t n, const uint8_t* d_flags, const K* d_lo, const K* d_hi, const V* d_values, K* d_out_keys,
+             V* d_out_values, I* d_out_index, uint64_t* d_out_num, uint32_t flags = 0, bool descending = false,
+             const uint64_t* d_num = nullptr, void* stream = nullptr, Context& ctx = default_context()) {
+    static_assert(std::is_integral<I>::value && (sizeof(I) == 4 || sizeof(I) == 8), "indices are 4- or 8-byte integers");
+    static_assert(std::is_trivially_copyable<V>::value, "values are moved bitwise");
+    const rsx_layout L = RadixDigits<K>::layout();
+    if (L.key_offset != 0 || L.key_bytes != L.elem_bytes) throw std::invalid_argument("compact: the key type must be its own key");
+    ctx.check(rsx_compact_device(ctx.get(), d_keys, n, d_num, L.key_bytes, L.key_kind, descending ? RSX_ORDER_DESCENDING : RSX_ORDER_ASCENDING,
+                                 d_flags, d_lo, d_hi, d_values, d_out_values ? (uint32_t)sizeof(V) : 0u, flags, d_out_keys, d_out_values,
+                                 d_out_index, (uint32_t)sizeof(I), d_out_num, stream),
+              "rsx_compact_device");
 }
 
 // Several key columns (rsx_lexsort_device, rsx_sort_columns_device): rows sorted by (column 0, column 1, ...), column 0

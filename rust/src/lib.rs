@@ -121,6 +121,16 @@ extern "C" {
                                 key_kind: u32, d_edges: *const c_void, m: u32, mode: u32, order: c_int,
                                 d_counts: *mut c_void, count_bytes: u32, flags: u32, stream: *mut c_void) -> c_int;
     pub fn rsx_bin_caps(key_bytes: u32, max_edges: *mut u32, max_index_bins_lds: *mut u32, share: *mut u32) -> c_int;
+    // rows that pass a predicate, in input order (include/rsx.h, "rows that pass a predicate"): d_flags (may be null) one
+    // byte per row, d_lo / d_hi (may be null) ONE key each on the device; flags RSX_COMPACT_INVERT (1), _PARTITION (2);
+    // every output but d_out_num may be null; d_num (may be null) bounds n by a device word; not in place
+    pub fn rsx_compact_device(ctx: *mut RsxCtx, d_keys: *const c_void, n: usize, d_num: *const u64, key_bytes: u32,
+                              key_kind: u32, order: c_int, d_flags: *const u8, d_lo: *const c_void, d_hi: *const c_void,
+                              d_values: *const c_void, value_bytes: u32, flags: u32, d_out_keys: *mut c_void,
+                              d_out_values: *mut c_void, d_out_index: *mut c_void, index_bytes: u32, d_out_num: *mut u64,
+                              stream: *mut c_void) -> c_int;
+    pub fn rsx_ctx_reserve_compact(ctx: *mut RsxCtx, n: usize, key_bytes: u32, value_bytes: u32, index_bytes: u32) -> c_int;
+    pub fn rsx_compact_caps(key_bytes: u32, value_bytes: u32, index_bytes: u32, tile: *mut u32, scan_span: *mut u32) -> c_int;
     // scan by key (include/rsx.h, "scan by key"): op is RSX_REDUCE_SUM (0), _MIN (1), _MAX (2); flags RSX_SCAN_EXCLUSIVE (1)
     // and RSX_SCAN_RUNS (2); one result per row at the row's position; d_values null: every value is 1 (ranks);
     // `first` is what the first row of every group receives in an exclusive scan; d_out_num may be null
