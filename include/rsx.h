@@ -154,7 +154,10 @@ enum {
                                   those two digits, then every 16-bit bucket sorted by its remaining digits in LDS.
                                   0: never; 1 (default): by key width and size (8- and 16-byte keys above the middle sizes, 4-byte keys in
                                   8-byte elements from 1 GiB, in wider ones from 2 GiB), when the count says every bucket
-                                  fits; 2: always (any array of 65536+ such elements, buckets that do not fit go through
+                                  fits (a handful of larger ones is tolerated, unless 32768 elements of one lie so close
+                                  together in the input that one count workgroup meets them all: padding, a pre-sorted
+                                  block -- then, as after any refusal, the LSD passes run and RSX_INFO_LAST_PASSES
+                                  reports path 0); 2: always (any array of 65536+ such elements, buckets that do not fit go through
                                   memory); 3: as 1 without the size floor (above the middle sizes) */
     RSX_OPT_BUCKET_SKIP = 13,  /* the LDS passes of the bucket kernels: 1 (default) start at the digit that leaves them the
                                   bits an array of that size is, as a rule, told apart by (2 log2 m - 6 of its variable

@@ -374,12 +374,15 @@ int sort_wide(rsx_ctx* ctx, const EsLaunchers& K, void* d_data, void* d_tmp, siz
     const uint32_t* verdict = &plan->verdict;
     const RegionGeom geom = make_geom(ctx, n, es);
     // the count's workgroups: k per region of the sweeps' geometry where the scratch array holds their counters
-    // (128 KiB each) -- then the first sweep's count matrix is a marginal of those counters -- and no counter can
-    // overflow when the hybrid is taken (the device's verdict: every bucket fits LDS, so fewer than 0x8000 elements);
+    // (128 KiB each) -- then the first sweep's count matrix is a marginal of those counters, as long as none of them was
+    // parked in the per-bin overflow table.  A bucket that fits LDS cannot park (the assert below), but the verdict also
+    // keeps the hybrid with up to 8 buckets of up to medium_max elements, and 0x8000 of one of those inside one count
+    // chunk do: the count kernel then sets plan->parked and rsx_scan16_kernel gives the sort to the LSD passes --;
     // else flat shares, and a count kernel of its own for that sweep
     size_t parts = n * (size_t)es / (32768 * sizeof(uint32_t));
     if (parts > (size_t)ctx->num_cu) parts = (size_t)ctx->num_cu;
-    static_assert(bucket_cape(8, wide_kpt_for(8), 1024) < 0x8000u && bucket_cape(4, wide_kpt_for(4), 1024) < 0x8000u, "a bucket that fits LDS must not overflow a 16-bit counter");
+    static_assert(bucket_cape(8, wide_kpt_for(8), 1024) < 0x8000u && bucket_cape(4, wide_kpt_for(4), 1024) < 0x8000u,
+                  "buckets that fit LDS never park a 16-bit counter: uniform inputs must not lose the hybrid to WidePlan::parked");
     uint32_t k = ctx->wide_mode == 2 ? 0u : (uint32_t)(parts / geom.num_regions);
     if (k > 0) parts = (size_t)k * geom.num_regions;
     rc = K.wideplan(ctx, d_data, n, L, plan, st);

@@ -322,7 +322,11 @@ struct WidePlan {
     static constexpr uint32_t SCAN_LINE = 32;
     uint32_t scan_cnt[8 * SCAN_LINE];
     uint32_t scan_done;
-    uint32_t pad_done[SCAN_LINE - 1];
+    // rsx_count16top_kernel, k > 0: some workgroup moved 0x8000 of a 16-bit counter into the overflow table, so the
+    // marginal of the counters (rsx_marginal16_kernel) is short of the region's digit count: rsx_scan16_kernel refuses
+    // the hybrid.  Zeroed by the plan kernel with the accumulators above (a replayed graph starts clean).
+    uint32_t parked;
+    uint32_t pad_done[SCAN_LINE - 2];
     uint32_t scan_max;    // the largest bucket (saturated)
     uint32_t pad_max[SCAN_LINE - 1];
     unsigned long long scan_big;  // elements in buckets above what the largest workgroup holds

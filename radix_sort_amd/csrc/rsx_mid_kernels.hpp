@@ -271,6 +271,7 @@ __global__ __launch_bounds__(1024) void rsx_wideplan_kernel(const Elem<ES>* __re
     plan->violation = violation;
     for (int i = 0; i < 8; ++i) plan->scan_cnt[i * WidePlan::SCAN_LINE] = 0;
     plan->scan_done = 0;
+    plan->parked = 0;
     plan->scan_max = 0;
     plan->scan_big = 0;
 #pragma unroll
@@ -286,7 +287,8 @@ __global__ __launch_bounds__(1024) void rsx_wideplan_kernel(const Elem<ES>* __re
 // Workgroup b counts chunk b % k of region b / k (k chunks per region; k == 0: the array cut into gridDim.x flat
 // shares): a workgroup then stays inside ONE region of the sweeps' geometry, and the count matrix of the first sweep
 // (the window's low digit, per region) is a marginal of these counters -- rsx_marginal16_kernel reads
-// them back (32 MiB) instead of a count kernel reading the array again (1.37 ms of 21 on 2^30 u64).
+// them back (32 MiB) instead of a count kernel reading the array again (1.37 ms of 21 on 2^30 u64).  That holds while no
+// counter is parked; a workgroup that parks one (k > 0) says so in plan->parked, and the hybrid is refused.
 // 8- and 16-byte elements are read in 16-byte words, streaming from 256 MiB on (RSX_COUNT16_* in rsx_device.hpp).
 template <int ES, bool MAP>
 __global__ __launch_bounds__(1024) void rsx_count16top_kernel(const Elem<ES>* __restrict__ src, uint64_t n, WidePlan* __restrict__ plan, KeyXform xf,
@@ -326,9 +328,11 @@ __global__ __launch_bounds__(1024) void rsx_count16top_kernel(const Elem<ES>* __
         const uint32_t bin = (elem_digit_any<ES>(e, hi) << 8) | elem_digit_any<ES>(e, lo);
         const uint32_t sh = (bin & 1u) * 16u;
         const uint32_t old = atomicAdd(&cnt[bin >> 1], 1u << sh);
-        if (((old >> sh) & 0xFFFFu) == 0x7FFFu) {  // my add made it 0x8000: park that half in the overflow table
+        if (__builtin_expect(((old >> sh) & 0xFFFFu) == 0x7FFFu, 0)) {  // my add made it 0x8000: park that half in the overflow table (rare: kept off the loop's straight path)
             atomicSub(&cnt[bin >> 1], 0x8000u << sh);
             atomicAdd(&ovf[bin], 0x8000u);
+            // (the overflow table is per bin, not per workgroup: what is parked there is missing from this region's marginal)
+            if (k != 0) __hip_atomic_store(&plan->parked, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     };
     constexpr int UNR = ES <= 8 ? 8 : ES <= 16 ? 4 : 2;  // loads in flight per thread (one workgroup per CU: 16 waves)
@@ -401,10 +405,13 @@ __global__ __launch_bounds__(1024) void rsx_count16top_kernel(const Elem<ES>* __
 }
 
 // The first sweep's count matrix from the 16-bit counters: J[rep][r][v] += sum over the top byte h of P[b][h * 256 + v]
-// for workgroup b of rsx_count16top_kernel (region r = b / k).  Valid when no counter overflowed, which is the case
-// whenever the hybrid is taken on the device's verdict: a bucket that fits a workgroup's LDS holds fewer than 0x8000
-// elements.  Also does the jobs of a sort's first count kernel (count_side_jobs).  grid >= parts (the workgroups
-// beyond only help with those jobs), block = 256.  (A template only so that every element-size unit owns its copy.)
+// for workgroup b of rsx_count16top_kernel (region r = b / k).  Valid only when no counter was parked: the overflow table
+// is per bin, not per workgroup, so what a workgroup moved there cannot be given back to its region.  A bucket that the
+// verdict leaves to rsx_bucket16_medium_kernel may hold millions of elements, and 0x8000 of them inside one count chunk
+// (padding, a pre-sorted block) do park: the count kernel then sets WidePlan::parked and rsx_scan16_kernel refuses the
+// hybrid, so this kernel's gate stays shut.  Also does the jobs of a sort's first count kernel (count_side_jobs).
+// grid >= parts (the workgroups beyond only help with those jobs), block = 256.  (A template only so that every
+// element-size unit owns its copy.)
 template <int ES>
 __global__ __launch_bounds__(256) void rsx_marginal16_kernel(const uint32_t* __restrict__ P, uint32_t parts, uint32_t k, RegionGeom g,
                                                              unsigned long long* __restrict__ J, unsigned long long* __restrict__ jclear,

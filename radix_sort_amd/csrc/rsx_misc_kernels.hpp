@@ -315,7 +315,10 @@ __global__ __launch_bounds__(256) void rsx_scan16_kernel(const uint64_t* __restr
     const uint32_t biggest = __hip_atomic_load(&plan->scan_max, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     uint32_t v;
     const uint64_t crowded = __hip_atomic_load(&plan->scan_big, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (violation != 0 || (!forced && (n1024 > FEW || (n1024 != 0 && ((uint64_t)biggest > medium_max || crowded > crowd_max))))) v = VERDICT_LSD;
+    // A parked counter (rsx_count16top_kernel, k > 0: 0x8000 elements of one bucket inside one count chunk) leaves the
+    // first sweep's marginal counts short: the LSD passes run.  (The forced mode counts that sweep itself and parks freely.)
+    const uint32_t parked = __hip_atomic_load(&plan->parked, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (violation != 0 || (!forced && (parked != 0 || n1024 > FEW || (n1024 != 0 && ((uint64_t)biggest > medium_max || crowded > crowd_max))))) v = VERDICT_LSD;
     else if (gshift != 0 && n512 == 0) v = VERDICT_HYBRID | VERDICT_GROUPS;
     else if (n256 <= FEW) v = VERDICT_HYBRID | VERDICT_WG256 | (n256 ? VERDICT_MEDIUM : 0u);
     else if (n512 <= FEW) v = VERDICT_HYBRID | VERDICT_WG512 | (n512 ? VERDICT_MEDIUM : 0u);
