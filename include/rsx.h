@@ -216,6 +216,8 @@ enum {
                                  launched, every other bit is 0 -- a bin count has no route),
                                  17 rows that pass a predicate (rsx_compact_device: reported like 16, bits 24 and 28
                                  set; bits 0-7 are the kernels launched),
+                                 18 rows regrouped by bin (rsx_multisplit_device: reported like 16, bits 25 and 28
+                                 set; bits 0-7 are the kernels launched),
                                  bits 28-29 the route of a layout without kernels of its own: 0 direct, 1 packed
                                  re-layout, 2 key-index proxy (bits 0-27 then describe the sort of the re-laid-out
                                  elements / of the proxies) */
@@ -913,6 +915,58 @@ int rsx_ctx_reserve_compact(rsx_ctx *ctx, size_t n, uint32_t key_bytes, uint32_t
  * multiple of 256; a key, a value and a two-byte slot per row stay within 80 KiB of LDS, two workgroups per CU; a value
  * width without a typed kernel counts as none), *scan_span = the tiles one sweep of the scan takes. */
 int rsx_compact_caps(uint32_t key_bytes, uint32_t value_bytes, uint32_t index_bytes, uint32_t *tile, uint32_t *scan_span);
+
+/* -- rows regrouped by bin, in input order inside each bin ----------------------- */
+/* A stable multi-way partition: token -> expert dispatch, the bucketing step of a sample sort, range or hash partitioning
+ * of a table.  bin(key) and N are exactly those of rsx_bin_count_device: `mode` is RSX_BIN_UPPER, RSX_BIN_LOWER (m edges of
+ * key_bytes on the device, compared as mapped keys in the total order on bit patterns, complemented for descending
+ * `order`) or RSX_BIN_INDEX (integer keys, no edges, ascending; bin m is "outside": negative and too-large ids); N = n, or
+ * min(n, *d_num) read on the device.  Let p be the ONE permutation of 0 .. N-1 with bin(keys[p[t]]) non-decreasing in t
+ * and p increasing among equal bins: the stable argsort of the bins.
+ *     d_out_offsets[b] = #{ i < N : bin(keys[i]) < b }    b = 0 .. m + 1: m + 2 uint64, offsets[0] = 0, offsets[m+1] = N;
+ *                                                         required, always written; the layout the *_segments calls take
+ *     d_out_keys[t]    = keys[p[t]]      t < N   the raw key bytes, untouched
+ *     d_out_values[t]  = values[p[t]]    t < N
+ *     d_out_index[t]   = p[t]            t < N   integers of index_bytes (4 or 8)
+ * Each of the three row outputs is optional through NULL; all NULL: the offsets alone, the exclusive sums of
+ * rsx_bin_count_device's counts.  Nothing is written at N and beyond, the inputs are only read, and the call is not in
+ * place.  Equal edges give empty bins; m == 0 copies the first N rows and writes {0, N}; n == 0 or N == 0 writes the
+ * offsets (all 0) and nothing else.  Edges that are not sorted give an unspecified grouping, but both passes compute the
+ * same bin for a key: every one of the N rows is still written exactly once, no access leaves the arrays and
+ * offsets[m+1] == N.
+ * Keys of 1, 2, 4, 8, 16 bytes and every kind in the edge modes; integer keys of 1 to 8 bytes in the index mode.  Values
+ * of 1, 2, 4, 8, 16 bytes are moved by the write kernel; any other width up to RSX_MAX_ELEM_BYTES rides behind positions
+ * (d_out_index when given, else n u32 in the workspace) and rsx_compact_device's row gather, bounded by N on the device.
+ * d_values is looked at only when d_out_values is given.
+ * RSX_ERR_ARG: bad widths, kinds, mode, order or index_bytes; edges or a descending order in the index mode;
+ * d_out_offsets NULL; a needed pointer NULL; a pointer not aligned (keys and edges: key_bytes; values: as in
+ * rsx_sort_pairs_device; index: index_bytes; d_num and d_out_offsets: 8); an output that overlaps an input or another
+ * output.  RSX_ERR_UNSUPPORTED, with nothing enqueued: n >= 2^32; float or 16-byte keys in the index mode; m above
+ * max_edges (edge modes) or max_index_bins (index mode) of rsx_multisplit_caps.  All of these are answered before the
+ * context is looked at.
+ *
+ * Four launches over min(ceil(n / share), 2 * CUs) persistent workgroups, each owning one contiguous share of the rows:
+ * the bin count's body, flushed by plain stores into the workgroup's column of a workspace matrix; a scan of every bin's
+ * row of it; one workgroup that writes the offsets; and the write, which walks the share in tiles of `tile` rows, ranks
+ * every row among the rows of its bin in the wave's 64 (a wave match) and in the tile (LDS counters of the wave), and
+ * stores key, value and position.  A fifth launch gathers values of a width without a typed kernel; without a row output
+ * the write is left out.  No workgroup waits for another and there are no atomics on global memory: the same bytes on
+ * every call.  Stream-ordered, no synchronisation, the host reads nothing.  Workspace: 4 (m + 1) bytes per workgroup, plus
+ * n u32 positions on the wide-value route without d_out_index; made on first use or by rsx_ctx_reserve_multisplit
+ * (value_bytes, index_bytes: 0 for a column the calls will not have).  Under capture without a sufficient reserve the call
+ * returns RSX_ERR_WORKSPACE and enqueues nothing.  RSX_INFO_LAST_PASSES reports path 18 and, in bits 0-7, the kernels
+ * launched. */
+int rsx_multisplit_device(rsx_ctx *ctx, const void *d_keys, size_t n, const uint64_t *d_num, uint32_t key_bytes,
+                          uint32_t key_kind, const void *d_edges, uint32_t m, uint32_t mode, int order,
+                          const void *d_values, uint32_t value_bytes, void *d_out_keys, void *d_out_values,
+                          void *d_out_index, uint32_t index_bytes, uint64_t *d_out_offsets, void *stream);
+int rsx_ctx_reserve_multisplit(rsx_ctx *ctx, size_t n, uint32_t m, uint32_t key_bytes, uint32_t value_bytes,
+                               uint32_t index_bytes);
+/* Host-only, needs no device: *max_edges = the most edges of an edge mode, *max_index_bins = the largest m of the index
+ * mode -- what the write kernel's LDS holds beside m + 1 cursors and four waves' m + 1 counters, within 80 KiB so that two
+ * workgroups fit a CU --, *tile = the rows of one tile of the write launch, *share = the fewest rows worth a workgroup. */
+int rsx_multisplit_caps(uint32_t key_bytes, uint32_t *max_edges, uint32_t *max_index_bins, uint32_t *tile,
+                        uint32_t *share);
 
 /* -- several key columns ----------------------------------------------------- */
 /* Sorting a table by (a, b descending, c): ncols key columns of n keys each, column 0 the MOST significant (the opposite

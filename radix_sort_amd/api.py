@@ -334,6 +334,22 @@ class Context:
                                                d_out_keys or None, d_out_values or None, d_out_index or None, index_bytes, d_out_num or None,
                                                stream))
 
+    def reserve_multisplit(self, n: int, m: int, key_bytes: int, value_bytes: int = 0, index_bytes: int = 0):
+        """rsx_ctx_reserve_multisplit: the context's first-call set-up and the workspace of multisplit_device on up to n rows
+        and m edges (index mode: m values) with keys, values and indices of these widths (0: the calls have no such
+        column), so that the call allocates nothing and can be captured."""
+        self._check(self._L.rsx_ctx_reserve_multisplit(self._h, n, m, key_bytes, value_bytes, index_bytes))
+
+    def multisplit_device(self, d_keys: int, n: int, key_bytes: int, key_kind: int, d_edges: int, m: int, mode: int, d_values: int,
+                          value_bytes: int, d_out_keys: int, d_out_values: int, d_out_index: int, index_bytes: int, d_out_offsets: int,
+                          descending: bool = False, d_num: int = 0, stream: int = 0):
+        """rsx_multisplit_device: the first n (or min(n, *d_num)) rows regrouped by the bin of their key (`mode` and the m
+        edges at d_edges as in bin_count_device), in input order inside each bin -- keys, values and positions into the
+        outputs that are not 0, the m + 2 offsets of the bins (uint64) into d_out_offsets.  Not in place."""
+        self._check(self._L.rsx_multisplit_device(self._h, d_keys or None, n, d_num or None, key_bytes, key_kind, d_edges or None, m, mode,
+                                                  1 if descending else 0, d_values or None, value_bytes, d_out_keys or None,
+                                                  d_out_values or None, d_out_index or None, index_bytes, d_out_offsets or None, stream))
+
     def reserve_unique(self, n: int, key_bytes: int, with_positions: bool = True):
         """rsx_ctx_reserve_unique: the context's first-call set-up and the workspace of unique_device on up to n keys of this
         width, by the route with positions (perm or inverse asked for) or keys only, so that the call allocates nothing and
@@ -1684,6 +1700,164 @@ def radix_bincount(keys, num_bins: int, num=None, out=None, accumulate: bool = F
                            out.element_size(), False, num.data_ptr() if num is not None else 0,
                            _lib.BIN_ACCUMULATE if accumulate else 0, stream)
     return out
+
+
+def partition_caps(key_bytes: int):
+    """rsx_multisplit_caps -> (max_edges, max_index_bins, tile, share): the most edges and the largest num_bins
+    rsx_multisplit_device takes for this key width, the rows of one tile of its write launch and the fewest rows worth a
+    workgroup.  Needs no device."""
+    L = _lib.load()
+    out = [ctypes.c_uint32() for _ in range(4)]
+    _check_rc(L, L.rsx_multisplit_caps(key_bytes, *[ctypes.byref(o) for o in out]))
+    return tuple(int(o.value) for o in out)
+
+
+Partitioned = namedtuple("Partitioned", ["keys", "values", "index", "offsets"])
+
+
+def _partition_by_sort(keys, kb, n, edges, m, side, descending, values, num, key_kind, outs, ctx):
+    """radix_partition past partition_caps: the bin of every row (radix_searchsorted, or the id itself), a stable
+    radix_argsort of the bins, a gather per column, and the offsets from the bin counts.  With num= the rows from
+    min(n, num) on sort behind every bin and keep what the outputs held."""
+    import torch
+    out_keys, out_values, out_index, out_offsets = outs
+    small = m < (1 << 31) - 2
+    if edges is not None:
+        bins = radix_searchsorted(edges, keys, side=side, descending=descending, index_dtype=torch.int32 if small else torch.int64, ctx=ctx,
+                                  key_kind=key_kind)
+        counts = radix_histogram(keys, edges, side=side, descending=descending, num=num, ctx=ctx, key_kind=key_kind)
+    else:
+        wide = keys.to(torch.int64) if keys.dtype != torch.uint64 else keys.view(torch.int64)  # (uint64 ids of 2^63 or more: negative, outside)
+        bins = torch.where((wide < 0) | (wide >= m), m, wide).to(torch.int32 if small else torch.int64)
+        counts = radix_bincount(keys, m, num=num, ctx=ctx)
+    live = None
+    if num is not None:
+        live = torch.arange(n, device=keys.device) < num.reshape(())
+        bins = torch.where(live, bins, m + 1)
+    perm = radix_argsort(bins, ctx=ctx)
+    out_offsets[0] = 0
+    torch.cumsum(counts, 0, out=out_offsets[1:])
+    for src, dst in ((keys, out_keys), (values, out_values)):
+        if dst is not None:
+            got = src.index_select(0, perm)
+            dst.copy_(got if live is None else torch.where(live.reshape((n,) + (1,) * (src.dim() - 1)), got, dst))
+    if out_index is not None:
+        got = perm.to(out_index.dtype)
+        out_index.copy_(got if live is None else torch.where(live, got, out_index))
+
+
+def radix_partition(keys, edges=None, num_bins=None, values=None, side: str = "right", descending: bool = False,
+                    return_index: bool = False, index_dtype=None, num=None, out=None, ctx: Optional[Context] = None,
+                    key_kind: Optional[int] = None):
+    """A stable multi-way partition (rsx_multisplit_device): every row moved into the bin of its key, in input order
+    inside each bin, with the CSR offsets of the bins -- what `radix_searchsorted`, a stable `radix_argsort` of the bin
+    ids, a gather per column and a cumsum of `radix_histogram` give, in two reads of the keys and one write of each
+    column.  Token -> expert dispatch (num_bins=), range partitioning by the cuts radix_quantile leaves on the device
+    (edges=), bucketing for radix_sort_segments.
+
+    Exactly one of `edges` and `num_bins` is given.
+    edges: m cut points under the rules of radix_histogram (same dtype and device, sorted in the order
+       radix_sort(descending=descending) leaves, the total order on bit patterns; equal edges give empty bins; m = 0: one
+       bin); side="right" puts edges[b - 1] <= key < edges[b] into bin b, side="left" edges[b - 1] < key <= edges[b].
+       Unsorted edges give an unspecified grouping, still a permutation of the rows.
+    num_bins: m, for integer keys that are bin ids themselves: bin k holds the rows with key k for k < m, the last bin m
+       the rows outside (negative ids and those of m or more).
+
+    Returns Partitioned(keys, values, index, offsets): keys and values (None without values=) regrouped, index (only with
+    return_index=True; index_dtype torch.int64 or torch.int32) the input position of every output row -- `out.keys ==
+    keys[out.index]`, and scattering by it un-permutes a result --, and offsets, an int64 tensor of m + 2 values: bin b is
+    rows offsets[b] .. offsets[b + 1], offsets[m + 1] the number of rows.  It is the layout radix_group(...).offsets has
+    and radix_sort_segments takes.
+
+    keys: a contiguous 1-D GPU tensor of a dtype radix_sort knows, or (n, 16) uint8 128-bit keys (key_kind=, edge modes
+       only); it is not modified.
+    values: a contiguous tensor with one row per key; a row is one value of up to 32768 bytes, moved bitwise.  Widths of
+       1, 2, 4, 8, 16 bytes move in the write kernel, others behind positions.
+    num: a one-element int64 device tensor: only the first min(n, num) rows count; nothing is written behind them.
+    out: a Partitioned of preallocated tensors (keys, values, index of n rows -- None for an output that is not wanted --
+       and offsets of m + 2 int64): nothing is allocated, and after Context.reserve_multisplit the call can be captured.
+       No output may overlap an input.
+    More edges than partition_caps(key_bytes)[0], or a num_bins above partition_caps(key_bytes)[1], take the chain named
+    above, through this library's own calls: the same result, more passes over the data.  The host still reads nothing.
+    Enqueued on the current stream, not synchronised."""
+    import torch
+    if (edges is None) == (num_bins is None):
+        raise ValueError("exactly one of edges= and num_bins= must be given")
+    kb, kind, n = _pairs_keys(keys, key_kind)
+    if edges is not None:
+        if not isinstance(edges, torch.Tensor):
+            raise TypeError("edges must be a torch tensor")
+        if edges.dtype != keys.dtype:
+            raise TypeError(f"edges must have the dtype of keys ({keys.dtype}), not {edges.dtype}")
+        ekb, _ekind, m = _pairs_keys(edges, key_kind)
+        if ekb != kb:
+            raise ValueError("edges must be shaped like the keys: 1-D, or (m, 16) uint8 for 128-bit keys")
+        if side not in ("left", "right"):
+            raise ValueError(f'side must be "left" or "right", not {side!r}')
+        if edges.device != keys.device:
+            raise ValueError("keys and edges must live on the same device")
+        mode = _lib.BIN_UPPER if side == "right" else _lib.BIN_LOWER
+    else:
+        if kind == KEY_FLOAT or kb == 16:
+            raise TypeError(f"num_bins= takes integer keys, not {keys.dtype}")
+        if descending:
+            raise ValueError("num_bins= takes no order: descending must be False")
+        m = operator.index(num_bins)
+        if m < 0 or m >= (1 << 32) - 2:
+            raise ValueError(f"num_bins must be in 0 .. 2^32 - 3, not {m}")
+        mode = _lib.BIN_INDEX
+    vb = _value_bytes(values, (n,), "keys")
+    if values is not None and values.device != keys.device:
+        raise ValueError("keys and values must live on the same device")
+    _set_num(num, keys, "num")
+    if n >= 1 << 32:
+        raise ValueError("radix_partition takes fewer than 2^32 rows")
+    if out is not None:
+        if not isinstance(out, (tuple, list)) or len(out) != 4:
+            raise TypeError("out must be a Partitioned(keys, values, index, offsets)")
+        out_keys, out_values, out_index, out_offsets = out
+        if out_keys is not None:
+            _merge_out(out_keys, keys, n, "keys")
+        if out_values is not None:
+            if values is None:
+                raise ValueError("out.values needs values")
+            _merge_out(out_values, values, n, "values")
+        if out_index is not None:
+            _index_out(out_index, (n,), "the rows")
+            if out_index.device != keys.device:
+                raise ValueError("the keys and out (index) must live on the same device")
+            if index_dtype is not None and index_dtype != out_index.dtype:
+                raise TypeError(f"index_dtype ({index_dtype}) is not the dtype of out.index ({out_index.dtype})")
+        elif return_index:
+            raise ValueError("return_index=True with out= needs out.index")
+        if not isinstance(out_offsets, torch.Tensor) or out_offsets.dtype != torch.int64:
+            raise TypeError("out.offsets must be an int64 tensor")
+        if tuple(out_offsets.shape) != (m + 2,) or not out_offsets.is_contiguous():
+            raise ValueError(f"out.offsets must be a contiguous tensor of shape ({m + 2},)")
+        if out_offsets.device != keys.device:
+            raise ValueError("the keys and out (offsets) must live on the same device")
+    else:
+        index_dtype = _index_dtype(index_dtype)
+    _pairs_device(keys, None, "")
+    if out is None:
+        out_keys = torch.empty_like(keys)
+        out_values = torch.empty_like(values) if values is not None else None
+        out_index = torch.empty(n, dtype=index_dtype, device=keys.device) if return_index else None
+        out_offsets = torch.empty(m + 2, dtype=torch.int64, device=keys.device)
+    result = Partitioned(out_keys, out_values, out_index, out_offsets)
+    max_edges, max_index_bins, _tile, _share = partition_caps(kb)
+    if m > (max_edges if edges is not None else max_index_bins):
+        _partition_by_sort(keys, kb, n, edges, m, side, descending, values, num, key_kind, result, ctx)
+        return result
+    with _on_device(keys, ctx) as (c, stream):
+        c.multisplit_device(keys.data_ptr() if n else 0, n, kb, kind, edges.data_ptr() if edges is not None and m else 0, m, mode,
+                            values.data_ptr() if out_values is not None and n else 0, vb if out_values is not None and n else 0,
+                            out_keys.data_ptr() if out_keys is not None and n else 0,
+                            out_values.data_ptr() if out_values is not None and n else 0,
+                            out_index.data_ptr() if out_index is not None and n else 0,
+                            out_index.element_size() if out_index is not None else 8, out_offsets.data_ptr(), descending,
+                            num.data_ptr() if num is not None else 0, stream)
+    return result
 
 
 def compact_caps(key_bytes: int = 0, value_bytes: int = 0, index_bytes: int = 0):

@@ -8,6 +8,7 @@
 #include "rsx_any_kernels.hpp"
 #include "rsx_select_kernels.hpp"
 #include "rsx_bin_kernels.hpp"
+#include "rsx_msplit_kernels.hpp"
 
 #include <cmath>
 
@@ -1077,6 +1078,7 @@ int rsx_ctx_get_info(rsx_ctx* ctx, int what, uint64_t* out) try {
                 }
                 case PATH_BIN:      // bits 0-7 the kernels launched; the path takes bit 28, a bin count has no route
                 case PATH_COMPACT:  // the same: bits 0-7 the kernels launched, the path in bits 24-28
+                case PATH_MSPLIT:   // the same
                     *out = (uint64_t)(ctx->last_sort_passes & 0xFFu) | (uint64_t)ctx->last_path << 24;
                     return RSX_OK;
                 default: break;
@@ -2376,6 +2378,209 @@ int rsx_compact_caps(uint32_t key_bytes, uint32_t value_bytes, uint32_t index_by
         return RSX_ERR_ARG;
     *tile = compact_tile_elems(key_bytes, value_width_fused(value_bytes) ? value_bytes : 0u);
     *scan_span = unique_scan_span();
+    return RSX_OK;
+}
+
+// ---- rows regrouped by bin, in input order inside each bin (rsx_msplit_kernels.hpp, include/rsx.h) ----
+namespace {
+// The workspace of one rsx_multisplit_device call: the count matrix, one column per workgroup; the bins' totals; n u32
+// positions when the values have no typed kernel and the caller's own index cannot serve.
+struct MsplitPlan {
+    Carve ws;
+    bool wide;         // the values ride behind positions and a row gather
+    uint32_t kvb;      // the value width of the write kernel: 0 on that route
+    uint32_t groups;   // workgroups of the count and the write launch
+    size_t cnt_off;    // cnt [(m + 1) * groups] u32
+    size_t tot_off;    // tot [m + 1] u32
+    size_t pos_off;    // wide: pos [n] u32
+};
+MsplitPlan msplit_plan(const rsx_ctx* ctx, size_t n, uint32_t m, uint32_t vb) {
+    MsplitPlan P{};
+    P.wide = !value_width_fused(vb);
+    P.kvb = P.wide ? 0u : vb;
+    const uint64_t shares = ((uint64_t)n + SELECT_SHARE - 1) / SELECT_SHARE;
+    P.groups = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(shares, (uint64_t)ctx->num_cu * 2));
+    P.cnt_off = P.ws.take((size_t)(m + 1) * P.groups * sizeof(uint32_t));
+    P.tot_off = P.ws.take((size_t)(m + 1) * sizeof(uint32_t));
+    if (P.wide) P.pos_off = P.ws.take(n * sizeof(uint32_t));
+    return P;
+}
+struct MsplitCall {
+    const void* keys;
+    const void* values;
+    uint64_t n;
+    const uint64_t* num;
+    const void* edges;
+    uint32_t m, mode, kind, desc, vb, ib, groups;
+    uint32_t* cnt;
+    uint32_t* tot;
+    void* out_keys;
+    void* out_values;
+    void* out_index;
+    uint64_t* out_offsets;
+};
+extern "C++" template <int KB, int MODE>
+void msplit_typed(const MsplitCall& c, bool write, hipStream_t st) {
+    const uint32_t stream = c.n * KB >= (uint64_t)RSX_COUNT16_NT_BYTES && !write ? 1u : 0u;  // (a write launch reads the keys again)
+    const uint32_t bins = c.m + 1;
+    hipLaunchKernelGGL((rsx_msplit_count_kernel<KB, MODE>), dim3(c.groups), dim3(BIN_WG), 0, st, c.keys, c.n, c.num, c.edges, c.m, c.cnt, c.kind, c.desc,
+                       stream);
+    hipLaunchKernelGGL(rsx_msplit_scan_kernel, dim3((bins + MSPLIT_WAVES - 1) / MSPLIT_WAVES), dim3(MSPLIT_WG), 0, st, c.cnt, bins, c.groups, c.tot);
+    hipLaunchKernelGGL(rsx_msplit_offsets_kernel, dim3(1), dim3(MSPLIT_OFFSETS_WG), 0, st, c.tot, bins, c.out_offsets);
+    if (!write) return;
+    for_value_index_width(c.vb, 0u, [&](auto vb, auto) {
+        hipLaunchKernelGGL((rsx_msplit_write_kernel<KB, decltype(vb)::value, MODE>), dim3(c.groups), dim3(MSPLIT_WG), 0, st, c.keys,
+                           static_cast<const uint8_t*>(c.values), c.n, c.num, c.edges, c.m, c.cnt, c.out_offsets, c.kind, c.desc,
+                           static_cast<uint8_t*>(c.out_keys), static_cast<uint8_t*>(c.out_values), static_cast<uint8_t*>(c.out_index), c.ib);
+    });
+}
+extern "C++" template <int KB>
+int msplit_launch(rsx_ctx* ctx, const MsplitCall& c, bool write, hipStream_t st) {
+    if (c.mode == RSX_BIN_INDEX) {
+        if constexpr (KB <= 8) msplit_typed<KB, MSPLIT_INDEX>(c, write, st);
+        else return fail(ctx, RSX_ERR_INTERNAL, "no index form for this key width");
+    } else if (c.mode == RSX_BIN_UPPER) {
+        msplit_typed<KB, MSPLIT_UPPER>(c, write, st);
+    } else {
+        msplit_typed<KB, MSPLIT_LOWER>(c, write, st);
+    }
+    RSX_HIP(hipGetLastError());
+    return RSX_OK;
+}
+// Every check of rsx_multisplit_device that needs neither the context nor the device: 0, or the code with *what set.
+int msplit_check(const void* d_keys, size_t n, const uint64_t* d_num, uint32_t key_bytes, uint32_t key_kind, const void* d_edges, uint32_t m,
+                 uint32_t mode, int order, const void* d_values, uint32_t value_bytes, const void* d_out_keys, const void* d_out_values,
+                 const void* d_out_index, uint32_t index_bytes, const uint64_t* d_out_offsets, const char** what) {
+    *what = "invalid mode";
+    if (mode != RSX_BIN_UPPER && mode != RSX_BIN_LOWER && mode != RSX_BIN_INDEX) return RSX_ERR_ARG;
+    *what = "invalid key width or kind";
+    if (!key_widths_ok(key_bytes, key_kind)) return RSX_ERR_ARG;
+    *what = "invalid order";
+    if (order != RSX_ORDER_ASCENDING && order != RSX_ORDER_DESCENDING) return RSX_ERR_ARG;
+    *what = "the index mode takes no edges and no order";
+    if (mode == RSX_BIN_INDEX && (order != RSX_ORDER_ASCENDING || d_edges)) return RSX_ERR_ARG;
+    *what = "value wider than RSX_MAX_ELEM_BYTES";
+    if (value_bytes > RSX_MAX_ELEM_BYTES) return RSX_ERR_ARG;
+    *what = "index_bytes must be 4 or 8";
+    if (d_out_index && index_bytes != 4 && index_bytes != 8) return RSX_ERR_ARG;
+    *what = "d_out_offsets is null";
+    if (!d_out_offsets) return RSX_ERR_ARG;
+    *what = "value pointers and value_bytes disagree";
+    if ((value_bytes == 0 && (d_values || d_out_values)) || (d_out_values && !d_values)) return RSX_ERR_ARG;
+    *what = "null device pointer";
+    if ((n > 0 && !d_keys) || (mode != RSX_BIN_INDEX && m > 0 && !d_edges)) return RSX_ERR_ARG;
+    *what = "device pointer misaligned";
+    const uint32_t va = value_bytes ? value_align(value_bytes) : 1u, ia = d_out_index ? index_bytes : 1u;
+    if (!aligned(d_keys, key_bytes) || !aligned(d_edges, key_bytes) || !aligned(d_out_keys, key_bytes) || !aligned(d_values, va) ||
+        !aligned(d_out_values, va) || !aligned(d_out_index, ia) || !aligned(d_num, 8) || !aligned(d_out_offsets, 8))
+        return RSX_ERR_ARG;
+    *what = "an output overlaps an input or another output";
+    const uint64_t rows = (uint64_t)n;
+    const bool edged = mode != RSX_BIN_INDEX;
+    const ByteRange in[] = {{d_keys, rows * key_bytes}, {d_values, rows * value_bytes}, {d_num, 8}, {edged ? d_edges : nullptr, (uint64_t)m * key_bytes}};
+    const ByteRange out[] = {{d_out_keys, rows * key_bytes}, {d_out_values, rows * value_bytes}, {d_out_index, rows * ia}, {d_out_offsets, ((uint64_t)m + 2) * 8}};
+    for (const ByteRange* o = out; o != out + 4; ++o) {
+        for (const ByteRange& i : in)
+            if (ranges_overlap(o->p, o->bytes, i.p, i.bytes)) return RSX_ERR_ARG;
+        for (const ByteRange* p = o + 1; p != out + 4; ++p)
+            if (ranges_overlap(o->p, o->bytes, p->p, p->bytes)) return RSX_ERR_ARG;
+    }
+    *what = "2^32 or more rows";  // (what is wrong with the arguments themselves comes first)
+    if (rows >= (1ull << 32)) return RSX_ERR_UNSUPPORTED;
+    *what = "the index mode takes integer keys of 1, 2, 4 or 8 bytes";
+    if (mode == RSX_BIN_INDEX && (key_bytes == 16 || key_kind == RSX_KEY_FLOAT)) return RSX_ERR_UNSUPPORTED;
+    *what = "more edges or bins than rsx_multisplit_caps reports";
+    if (m > MSPLIT_MAX_EDGES) return RSX_ERR_UNSUPPORTED;
+    *what = "";
+    return RSX_OK;
+}
+}  // namespace
+
+int rsx_multisplit_device(rsx_ctx* ctx, const void* d_keys, size_t n, const uint64_t* d_num, uint32_t key_bytes, uint32_t key_kind, const void* d_edges,
+                          uint32_t m, uint32_t mode, int order, const void* d_values, uint32_t value_bytes, void* d_out_keys, void* d_out_values,
+                          void* d_out_index, uint32_t index_bytes, uint64_t* d_out_offsets, void* stream) try {
+    // the argument checks come first and need no context: a caller's mistake has the same answer with and without one
+    const char* what = "";
+    int rc = msplit_check(d_keys, n, d_num, key_bytes, key_kind, d_edges, m, mode, order, d_values, value_bytes, d_out_keys, d_out_values, d_out_index,
+                          index_bytes, d_out_offsets, &what);
+    if (rc) return fail(ctx, rc, what);
+    if (!ctx) return RSX_ERR_ARG;
+    const uint32_t desc = order == RSX_ORDER_DESCENDING ? 1u : 0u;
+    if (!d_out_values) value_bytes = 0;  // the values are not looked at
+    RSX_ENTER(stream);
+    const hipStream_t st = held.st;
+    rc = pending_error(ctx);
+    if (rc) return rc;
+    const MsplitPlan P = msplit_plan(ctx, n, m, value_bytes);
+    // the positions of the wide route: the index the caller asked for when there is one, else n u32 in the workspace
+    const bool ws_pos = P.wide && !d_out_index;
+    const size_t need = P.wide && !ws_pos ? P.pos_off : P.ws.bytes;  // (without them: the arrays in front of them)
+    rc = ensure_aux(ctx, st);
+    if (rc) return rc;
+    rc = ensure_any(ctx, need, st);
+    if (rc) return rc;
+    Enqueue enq(ctx, st);  // the workspace arrays belong to this call from the first launch on
+    char* w = reinterpret_cast<char*>(ctx->any_buf);
+    MsplitCall c{};
+    c.keys = d_keys;
+    c.values = d_values;
+    c.n = n;
+    c.num = d_num;
+    c.edges = d_edges;
+    c.m = m;
+    c.mode = mode;
+    c.kind = key_kind;
+    c.desc = desc;
+    c.vb = P.kvb;
+    c.ib = ws_pos ? 4u : (d_out_index ? index_bytes : 4u);
+    c.groups = P.groups;
+    c.cnt = reinterpret_cast<uint32_t*>(w + P.cnt_off);
+    c.tot = reinterpret_cast<uint32_t*>(w + P.tot_off);
+    c.out_keys = d_out_keys;
+    c.out_values = P.wide ? nullptr : d_out_values;
+    c.out_index = ws_pos ? static_cast<void*>(w + P.pos_off) : d_out_index;
+    c.out_offsets = d_out_offsets;
+    const bool write = n > 0 && (c.out_keys || c.out_values || c.out_index);
+    uint32_t launched = write ? 4u : 3u;
+    {
+        LaunchTimer lt(ctx, RSX_PROF_SCAN, st);  // (count, scan, write: the phases of one scan, timed as one)
+        for_key_width(key_bytes, [&](auto kb) { rc = msplit_launch<decltype(kb)::value>(ctx, c, write, st); });
+        if (rc) return rc;
+    }
+    if (P.wide && n > 0) {  // the compact call's row gather, over the first N rows
+        CompactCall g{};
+        g.values = d_values;
+        g.n = n;
+        g.num = d_num;
+        g.mode = RSX_COMPACT_PARTITION;
+        rc = launch_compact_gather(ctx, g, c.out_index, c.ib, value_bytes, d_out_values, st);
+        if (rc) return rc;
+        ++launched;
+    }
+    note_path(ctx, PATH_MSPLIT, launched);
+    return RSX_OK;
+} catch (...) {
+    return RSX_ERR_HIP;
+}
+
+int rsx_ctx_reserve_multisplit(rsx_ctx* ctx, size_t n, uint32_t m, uint32_t key_bytes, uint32_t value_bytes, uint32_t index_bytes) try {
+    if (!ctx) return RSX_ERR_ARG;
+    if (!key_widths_ok(key_bytes, RSX_KEY_UNSIGNED) || value_bytes > RSX_MAX_ELEM_BYTES || (index_bytes != 0 && index_bytes != 4 && index_bytes != 8))
+        return fail(ctx, RSX_ERR_ARG, "invalid key, value or index width");
+    if ((uint64_t)n >= (1ull << 32)) return fail(ctx, RSX_ERR_UNSUPPORTED, "2^32 or more rows");
+    if (m > MSPLIT_MAX_EDGES) return fail(ctx, RSX_ERR_UNSUPPORTED, "more edges or bins than rsx_multisplit_caps reports");
+    // enough with and without an index output: the positions of the wide route are counted in either way
+    return reserve_any_entry(ctx, msplit_plan(ctx, n, m, value_bytes).ws.bytes);
+} catch (...) {
+    return RSX_ERR_NOMEM;
+}
+
+int rsx_multisplit_caps(uint32_t key_bytes, uint32_t* max_edges, uint32_t* max_index_bins, uint32_t* tile, uint32_t* share) {
+    if (!max_edges || !max_index_bins || !tile || !share || !key_widths_ok(key_bytes, RSX_KEY_UNSIGNED)) return RSX_ERR_ARG;
+    *max_edges = MSPLIT_MAX_EDGES;
+    *max_index_bins = MSPLIT_MAX_EDGES;
+    *tile = MSPLIT_TILE;
+    *share = SELECT_SHARE;
     return RSX_OK;
 }
 

@@ -26,6 +26,7 @@
 //     rsx::select(const K* d_keys, size_t n, const uint64_t* ranks /* host */, uint32_t nranks, K* d_out_keys, I* d_out_index, bool descending, hipStream_t)   // order statistics, no sort
 //     rsx::bin_count(const K* d_keys, size_t n, const K* d_edges, uint32_t m, uint32_t mode, C* d_counts, bool descending, bool accumulate, const uint64_t* d_num, hipStream_t)   // RSX_BIN_*: histogram, bincount
 //     rsx::compact(const K* d_keys, size_t n, const uint8_t* d_flags, const K* d_lo, const K* d_hi, const V* d_values, K* d_out_keys, V* d_out_values, I* d_out_index, uint64_t* d_out_num, uint32_t flags, bool descending, const uint64_t* d_num, hipStream_t)   // RSX_COMPACT_*: select-if, partition, nonzero
+//     rsx::multisplit(const K* d_keys, size_t n, const K* d_edges, uint32_t m, uint32_t mode, const V* d_values, K* d_out_keys, V* d_out_values, I* d_out_index, uint64_t* d_out_offsets, bool descending, const uint64_t* d_num, hipStream_t)   // RSX_BIN_*: stable multi-way partition, CSR offsets
 //     rsx::lexsort({rsx::key_column(d_a), rsx::key_column(d_b, true)}, I* d_index, size_t n, hipStream_t)   // several key columns
 //     rsx::sort_columns({rsx::key_column(d_a), rsx::key_column(d_b, true)}, V* d_values, size_t n, hipStream_t)
 // Errors: the reference panics (mod.rs:68,106); here std::runtime_error is thrown.
@@ -492,6 +493,37 @@ void compact(const K* d_keys, size_t n, const uint8_t* d_flags, const K* d_lo, c
                                  d_flags, d_lo, d_hi, d_values, d_out_values ? (uint32_t)sizeof(V) : 0u, flags, d_out_keys, d_out_values,
                                  d_out_index, (uint32_t)sizeof(I), d_out_num, stream),
               "rsx_compact_device");
+}
+
+// Rows regrouped by bin (rsx_multisplit_device): the first n -- or min(n, *d_num) -- rows moved into the bin of their key,
+// in input order inside each bin; mode and the m edges as in bin_count (RSX_BIN_INDEX: d_edges nullptr, the last bin holds
+// the ids outside 0 .. m - 1).  Keys, values and input positions go to the outputs that are not nullptr; d_out_offsets
+// receives the m + 2 offsets of the bins, offsets[m + 1] the number of rows.  At most multisplit_caps<K>().max_edges
+// edges (index mode: max_index_bins).  Not in place.  Stream-ordered, never synchronised; Context::reserve is not enough
+// for a capture: rsx_ctx_reserve_multisplit.
+struct MultisplitCaps {
+    uint32_t max_edges, max_index_bins, tile, share;
+};
+template <typename K>
+MultisplitCaps multisplit_caps() {
+    MultisplitCaps c{};
+    const rsx_layout L = RadixDigits<K>::layout();
+    if (rsx_multisplit_caps(L.key_bytes, &c.max_edges, &c.max_index_bins, &c.tile, &c.share) != RSX_OK)
+        throw std::invalid_argument("multisplit_caps: no partition for this key width");
+    return c;
+}
+template <typename K, typename V = uint32_t, typename I = uint64_t>
+void multisplit(const K* d_keys, size_t n, const K* d_edges, uint32_t m, uint32_t mode, const V* d_values, K* d_out_keys, V* d_out_values,
+                I* d_out_index, uint64_t* d_out_offsets, bool descending = false, const uint64_t* d_num = nullptr, void* stream = nullptr,
+                Context& ctx = default_context()) {
+    static_assert(std::is_integral<I>::value && (sizeof(I) == 4 || sizeof(I) == 8), "indices are 4- or 8-byte integers");
+    static_assert(std::is_trivially_copyable<V>::value, "values are moved bitwise");
+    const rsx_layout L = RadixDigits<K>::layout();
+    if (L.key_offset != 0 || L.key_bytes != L.elem_bytes) throw std::invalid_argument("multisplit: the key type must be its own key");
+    ctx.check(rsx_multisplit_device(ctx.get(), d_keys, n, d_num, L.key_bytes, L.key_kind, d_edges, m, mode,
+                                    descending ? RSX_ORDER_DESCENDING : RSX_ORDER_ASCENDING, d_out_values ? d_values : nullptr,
+                                    d_out_values ? (uint32_t)sizeof(V) : 0u, d_out_keys, d_out_values, d_out_index, (uint32_t)sizeof(I), d_out_offsets, stream),
+              "rsx_multisplit_device");
 }
 
 // Several key columns (rsx_lexsort_device, rsx_sort_columns_device): rows sorted by (column 0, column 1, ...), column 0

@@ -131,6 +131,16 @@ extern "C" {
                               stream: *mut c_void) -> c_int;
     pub fn rsx_ctx_reserve_compact(ctx: *mut RsxCtx, n: usize, key_bytes: u32, value_bytes: u32, index_bytes: u32) -> c_int;
     pub fn rsx_compact_caps(key_bytes: u32, value_bytes: u32, index_bytes: u32, tile: *mut u32, scan_span: *mut u32) -> c_int;
+    // rows regrouped by bin, in input order inside each bin (include/rsx.h, "rows regrouped by bin"): mode and d_edges as
+    // in rsx_bin_count_device; every row output may be null; d_out_offsets holds m + 2 words; d_num (may be null) bounds n
+    // by a device word; not in place
+    pub fn rsx_multisplit_device(ctx: *mut RsxCtx, d_keys: *const c_void, n: usize, d_num: *const u64, key_bytes: u32,
+                                 key_kind: u32, d_edges: *const c_void, m: u32, mode: u32, order: c_int,
+                                 d_values: *const c_void, value_bytes: u32, d_out_keys: *mut c_void,
+                                 d_out_values: *mut c_void, d_out_index: *mut c_void, index_bytes: u32,
+                                 d_out_offsets: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn rsx_ctx_reserve_multisplit(ctx: *mut RsxCtx, n: usize, m: u32, key_bytes: u32, value_bytes: u32, index_bytes: u32) -> c_int;
+    pub fn rsx_multisplit_caps(key_bytes: u32, max_edges: *mut u32, max_index_bins: *mut u32, tile: *mut u32, share: *mut u32) -> c_int;
     // scan by key (include/rsx.h, "scan by key"): op is RSX_REDUCE_SUM (0), _MIN (1), _MAX (2); flags RSX_SCAN_EXCLUSIVE (1)
     // and RSX_SCAN_RUNS (2); one result per row at the row's position; d_values null: every value is 1 (ranks);
     // `first` is what the first row of every group receives in an exclusive scan; d_out_num may be null
