@@ -218,6 +218,8 @@ enum {
                                  set; bits 0-7 are the kernels launched),
                                  18 rows regrouped by bin (rsx_multisplit_device: reported like 16, bits 25 and 28
                                  set; bits 0-7 are the kernels launched),
+                                 19 a value column combined per bin (rsx_bin_reduce_device: reported like 16, bits
+                                 24, 25 and 28 set; bits 0-7 are the kernels launched),
                                  bits 28-29 the route of a layout without kernels of its own: 0 direct, 1 packed
                                  re-layout, 2 key-index proxy (bits 0-27 then describe the sort of the re-laid-out
                                  elements / of the proxies) */
@@ -967,6 +969,57 @@ int rsx_ctx_reserve_multisplit(rsx_ctx *ctx, size_t n, uint32_t m, uint32_t key_
  * workgroups fit a CU --, *tile = the rows of one tile of the write launch, *share = the fewest rows worth a workgroup. */
 int rsx_multisplit_caps(uint32_t key_bytes, uint32_t *max_edges, uint32_t *max_index_bins, uint32_t *tile,
                         uint32_t *share);
+
+/* -- a value column combined per bin, nothing sorted ----------------------------- */
+/* numpy.histogram(weights=), torch.bincount(weights=), zeros.index_add_(0, ids, w), scatter_reduce over a few hundred
+ * labels: per-expert load and score sums, per-class loss sums, sum, min and max of a measure per range of a key.
+ * bin(key), N, `mode`, `order`, the edges and the key widths and kinds are exactly those of rsx_bin_count_device and
+ * rsx_multisplit_device (RSX_BIN_INDEX: bin m is "outside"); values and operators are those of rsx_reduce_by_key_device:
+ * value_bytes 4 or 8, value_kind RSX_KEY_UNSIGNED, RSX_KEY_SIGNED or RSX_KEY_FLOAT; RSX_REDUCE_SUM (integers wrap, floats
+ * add by IEEE addition in their own type), RSX_REDUCE_MIN, RSX_REDUCE_MAX (floats by the total order on bit patterns: the
+ * result is the bit pattern of one of the bin's values).  For b = 0 .. m
+ *     d_out_values[b] = the (+) of values[i] over { i < N : bin(keys[i]) == b }     in the value's type; required
+ *     d_out_counts[b] = the size of that set, count_bytes (4 or 8) each             optional through NULL; byte for byte
+ *                                                                                   what rsx_bin_count_device writes
+ * An empty bin holds the operator's identity: SUM integer 0 or +0.0; MIN the highest value of the order (the integer
+ * type's maximum; the float bit pattern 0x7FFF...F, a +NaN); MAX the lowest (the integer type's minimum; 0xFFFF...F).  A
+ * float sum starts from +0.0, so a bin of -0.0 values holds +0.0.  The association of a float sum belongs to the kernels,
+ * but it is a function of the inputs' contents and sizes and of the grid alone -- never of which wave or workgroup ran
+ * first; there are no floating-point atomics: the same input gives the same bytes on every call and every context of one
+ * device.  Accuracy is the order-free bound of rsx_reduce_by_key_device: |result - exact| <= g(c - 1) * sum |v| for a
+ * bin of c values.
+ * With RSX_BIN_ACCUMULATE in `flags` the store becomes out[b] = out[b] (+) r[b], r the result without the flag, and the
+ * counts are added likewise; without it every one of the m + 1 entries of each given output is overwritten.  n == 0 or
+ * N == 0 still writes the identities -- or, accumulating, leaves the outputs alone.  m == 0 combines all N values into
+ * the one bin without reading a key (d_keys may be NULL).  Edges that are not sorted give an unspecified grouping, but no
+ * access leaves the arrays and the counts still sum to N.
+ * RSX_ERR_ARG: bad widths, kinds, mode, order, operator, flags or count_bytes; edges or a descending order in the index
+ * mode; d_out_values NULL; a needed pointer NULL; a pointer not aligned (keys and edges: key_bytes; values: value_bytes;
+ * counts: count_bytes; d_num: 8); an output that overlaps an input or the other output.  RSX_ERR_UNSUPPORTED, with
+ * nothing enqueued: n >= 2^32; float or 16-byte keys in the index mode; m above max_edges (edge modes) or max_index_bins
+ * (index mode) of rsx_bin_reduce_caps.  All of these are answered before the context is looked at.
+ *
+ * Two launches.  The first runs min(ceil(n / share), 2 * CUs) persistent workgroups, each owning one contiguous share of
+ * the rows: mapped edges, one row of m + 1 accumulators per wave and one row of counters in LDS; a wave takes 64
+ * consecutive rows per round, finds their bins, and either -- all 64 in one bin -- adds in registers, or matches equal bins
+ * (a wave match), combines the matched lanes' values along the peer mask in a fixed order and lets the group's first lane
+ * update the wave's own row by a plain read, combine and write; at the end the four rows are combined in wave order and
+ * stored into the workgroup's column of a workspace matrix.  The second gives every bin a wave that combines its row of
+ * partials in a fixed order, applies the flag and writes the outputs.  No zeroing launch, no workgroup waits for another.
+ * Stream-ordered, no synchronisation, the host reads nothing.  Workspace: (value_bytes + 4) (m + 1) bytes per workgroup;
+ * made on first use or by rsx_ctx_reserve_bin_reduce.  Under capture without a sufficient reserve the call returns
+ * RSX_ERR_WORKSPACE and enqueues nothing.  RSX_INFO_LAST_PASSES reports path 19 and, in bits 0-7, the kernels launched. */
+int rsx_bin_reduce_device(rsx_ctx *ctx, const void *d_keys, const void *d_values, size_t n, const uint64_t *d_num,
+                          uint32_t key_bytes, uint32_t key_kind, const void *d_edges, uint32_t m, uint32_t mode, int order,
+                          uint32_t value_bytes, uint32_t value_kind, int op, void *d_out_values,
+                          void *d_out_counts, uint32_t count_bytes, uint32_t flags, void *stream);
+int rsx_ctx_reserve_bin_reduce(rsx_ctx *ctx, size_t n, uint32_t m, uint32_t key_bytes, uint32_t value_bytes);
+/* Host-only, needs no device: *max_edges = the most edges of an edge mode, *max_index_bins = the largest m of the index
+ * mode -- what the first launch's LDS holds beside four waves' m + 1 accumulators of value_bytes and m + 1 counters, within
+ * 80 KiB so that two workgroups fit a CU, and at most 2047, the 11 bits of the wave match --, *tile = the rows of one tile
+ * of the first launch, *share = the fewest rows worth a workgroup. */
+int rsx_bin_reduce_caps(uint32_t key_bytes, uint32_t value_bytes, uint32_t *max_edges, uint32_t *max_index_bins,
+                        uint32_t *tile, uint32_t *share);
 
 /* -- several key columns ----------------------------------------------------- */
 /* Sorting a table by (a, b descending, c): ncols key columns of n keys each, column 0 the MOST significant (the opposite

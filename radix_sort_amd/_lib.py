@@ -32,6 +32,7 @@ SYMBOLS = [
     "rsx_bin_count_device", "rsx_bin_caps",
     "rsx_compact_device", "rsx_ctx_reserve_compact", "rsx_compact_caps",
     "rsx_multisplit_device", "rsx_ctx_reserve_multisplit", "rsx_multisplit_caps",
+    "rsx_bin_reduce_device", "rsx_ctx_reserve_bin_reduce", "rsx_bin_reduce_caps",
 ]
 SEG_CLASSES = 2  # RSX_SEG_CLASSES
 LEX_MAX_COLUMNS = 16  # RSX_LEX_MAX_COLUMNS
@@ -194,6 +195,9 @@ def load():
     L.rsx_multisplit_device.argtypes = [vp, vp, sz, vp, u32, u32, vp, u32, u32, i, vp, u32, vp, vp, vp, u32, vp, vp]
     L.rsx_ctx_reserve_multisplit.argtypes = [vp, sz, u32, u32, u32, u32]
     L.rsx_multisplit_caps.argtypes = [u32, pu32, pu32, pu32, pu32]
+    L.rsx_bin_reduce_device.argtypes = [vp, vp, vp, sz, vp, u32, u32, vp, u32, u32, i, u32, u32, i, vp, vp, u32, u32, vp]
+    L.rsx_ctx_reserve_bin_reduce.argtypes = [vp, sz, u32, u32, u32]
+    L.rsx_bin_reduce_caps.argtypes = [u32, u32, pu32, pu32, pu32, pu32]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("rsx_last_error", "rsx_strerror"):

@@ -350,6 +350,23 @@ class Context:
                                                   1 if descending else 0, d_values or None, value_bytes, d_out_keys or None,
                                                   d_out_values or None, d_out_index or None, index_bytes, d_out_offsets or None, stream))
 
+    def reserve_bin_reduce(self, n: int, m: int, key_bytes: int, value_bytes: int):
+        """rsx_ctx_reserve_bin_reduce: the context's first-call set-up and the workspace of bin_reduce_device on up to n rows
+        and m edges (index mode: m values) with keys and values of these widths, so that the call allocates nothing and
+        can be captured."""
+        self._check(self._L.rsx_ctx_reserve_bin_reduce(self._h, n, m, key_bytes, value_bytes))
+
+    def bin_reduce_device(self, d_keys: int, d_values: int, n: int, key_bytes: int, key_kind: int, d_edges: int, m: int, mode: int,
+                          value_bytes: int, value_kind: int, op: int, d_out_values: int, d_out_counts: int = 0, count_bytes: int = 8,
+                          descending: bool = False, d_num: int = 0, flags: int = 0, stream: int = 0):
+        """rsx_bin_reduce_device: the values of the first n (or min(n, *d_num)) rows combined by `op` (REDUCE_SUM / MIN / MAX)
+        per bin of their key (`mode` and the m edges at d_edges as in bin_count_device) into the m + 1 values at
+        d_out_values, an empty bin holding the operator's identity; the bins' sizes into the m + 1 counts of count_bytes at
+        d_out_counts unless it is 0.  flags BIN_ACCUMULATE: combined onto / added to what the outputs hold."""
+        self._check(self._L.rsx_bin_reduce_device(self._h, d_keys or None, d_values or None, n, d_num or None, key_bytes, key_kind,
+                                                  d_edges or None, m, mode, 1 if descending else 0, value_bytes, value_kind, op,
+                                                  d_out_values or None, d_out_counts or None, count_bytes, flags, stream))
+
     def reserve_unique(self, n: int, key_bytes: int, with_positions: bool = True):
         """rsx_ctx_reserve_unique: the context's first-call set-up and the workspace of unique_device on up to n keys of this
         width, by the route with positions (perm or inverse asked for) or keys only, so that the call allocates nothing and
@@ -1607,7 +1624,7 @@ def _bin_args(keys, bins: int, num, out, accumulate: bool, count_dtype):
 
 
 def radix_histogram(keys, edges, side: str = "right", descending: bool = False, num=None, out=None, accumulate: bool = False,
-                    count_dtype=None, ctx: Optional[Context] = None, key_kind: Optional[int] = None):
+                    count_dtype=None, ctx: Optional[Context] = None, key_kind: Optional[int] = None, weights=None):
     """How many keys fall between the cut points `edges` (rsx_bin_count_device): the m + 1 counts
     `torch.bincount(radix_searchsorted(edges, keys, side=side, descending=descending).flatten(), minlength=m + 1)` for
     m = len(edges), in one read of the keys and with no index array.  side="right" (the default, `torch.bucketize(keys,
@@ -1627,9 +1644,17 @@ def radix_histogram(keys, edges, side: str = "right", descending: bool = False, 
        read on the device.
     out: a contiguous int32 or int64 tensor of m + 1 counts to write (accumulate=True: to add to); otherwise a new
        tensor of count_dtype (torch.int64, the default, or torch.int32).
+    weights: a tensor with one entry per key: the m + 1 SUMS of the weights per bin instead of the counts, in
+       weights.dtype -- `numpy.histogram(keys, edges, weights=weights)`; the call is radix_bin_reduce(keys, weights,
+       edges=edges, op="sum", ...), whose rules for out=, accumulate= and the dtypes hold (count_dtype is not taken).
     More edges than bin_caps(key_bytes)[0] go through radix_searchsorted into an index array and the index form.
     Enqueued on the current stream, not synchronised; the host reads nothing."""
     import torch
+    if weights is not None:
+        if count_dtype is not None:
+            raise ValueError("count_dtype= has no meaning with weights=: the sums have the dtype of the weights")
+        return radix_bin_reduce(keys, weights, edges=edges, op="sum", side=side, descending=descending, num=num, out=out, accumulate=accumulate,
+                                ctx=ctx, key_kind=key_kind)
     if not isinstance(keys, torch.Tensor) or not isinstance(edges, torch.Tensor):
         raise TypeError("keys and edges must be torch tensors on a GPU")
     if edges.dtype != keys.dtype:
@@ -1668,7 +1693,8 @@ def radix_histogram(keys, edges, side: str = "right", descending: bool = False, 
     return out
 
 
-def radix_bincount(keys, num_bins: int, num=None, out=None, accumulate: bool = False, count_dtype=None, ctx: Optional[Context] = None):
+def radix_bincount(keys, num_bins: int, num=None, out=None, accumulate: bool = False, count_dtype=None, ctx: Optional[Context] = None,
+                   weights=None):
     """How often every value 0 .. num_bins - 1 occurs among integer `keys` (rsx_bin_count_device, index mode):
     num_bins + 1 counts, of which [:num_bins] equals `torch.bincount(in-range keys, minlength=num_bins)` and the last
     entry counts the keys outside -- negative ones and those of num_bins or more, which torch refuses or grows for.
@@ -1677,9 +1703,17 @@ def radix_bincount(keys, num_bins: int, num=None, out=None, accumulate: bool = F
        them, uint16, uint32, uint64); it is not modified.
     num, out, accumulate, count_dtype: as in radix_histogram; out holds num_bins + 1 counts.
     Up to bin_caps(key_bytes)[1] values are counted in LDS in one pass over the keys, up to 16 times as many in as many
-    passes, more by atomics straight into the counts.  Enqueued on the
+    passes, more by atomics straight into the counts.
+    weights: a tensor with one entry per key: the num_bins + 1 SUMS of the weights per value instead of the counts, in
+       weights.dtype -- `torch.bincount(keys, weights=weights)`; the call is radix_bin_reduce(keys, weights,
+       num_bins=num_bins, op="sum", ...), whose rules for out=, accumulate= and the dtypes hold (count_dtype is not taken).
+    Enqueued on the
     current stream, not synchronised; the host reads nothing."""
     import torch
+    if weights is not None:
+        if count_dtype is not None:
+            raise ValueError("count_dtype= has no meaning with weights=: the sums have the dtype of the weights")
+        return radix_bin_reduce(keys, weights, num_bins=num_bins, op="sum", num=num, out=out, accumulate=accumulate, ctx=ctx)
     if not isinstance(keys, torch.Tensor):
         raise TypeError("keys must be a torch tensor on a GPU")
     if not keys.is_contiguous():
@@ -1700,6 +1734,193 @@ def radix_bincount(keys, num_bins: int, num=None, out=None, accumulate: bool = F
                            out.element_size(), False, num.data_ptr() if num is not None else 0,
                            _lib.BIN_ACCUMULATE if accumulate else 0, stream)
     return out
+
+
+def bin_reduce_caps(key_bytes: int, value_bytes: int):
+    """rsx_bin_reduce_caps -> (max_edges, max_index_bins, tile, share): the most edges and the largest num_bins
+    rsx_bin_reduce_device takes for these key and value widths, the rows of one tile of its first launch and the fewest
+    rows worth a workgroup.  Needs no device."""
+    L = _lib.load()
+    out = [ctypes.c_uint32() for _ in range(4)]
+    _check_rc(L, L.rsx_bin_reduce_caps(key_bytes, value_bytes, *[ctypes.byref(o) for o in out]))
+    return tuple(int(o.value) for o in out)
+
+
+def _bin_reduce_bits(values):
+    """`values` as signed integers of its width: the bit patterns the operators are defined on."""
+    import torch
+    return values.view(torch.int32 if values.element_size() == 4 else torch.int64)
+
+
+def _bin_reduce_identity(vb: int, vkind: int, op: str) -> int:
+    """The bit pattern an empty bin holds, as a signed integer of vb bytes."""
+    top = 1 << (8 * vb - 1)
+    if op == "sum":
+        return 0
+    if op == "max":
+        return -1 if vkind == KEY_FLOAT else -top if vkind == KEY_SIGNED else 0  # the float of all ones; the signed minimum; 0
+    return -1 if vkind == KEY_UNSIGNED else top - 1  # the unsigned maximum; all ones below the sign: the signed maximum, a +NaN
+
+
+def _bin_reduce_join(a, b, vkind: int, op: str, float_dtype):
+    """a (+) b on bit patterns held as signed integers: a wrapping or IEEE sum, or min / max by the value's order."""
+    import torch
+    if op == "sum":
+        return (a.view(float_dtype) + b.view(float_dtype)).view(a.dtype) if vkind == KEY_FLOAT else a + b
+    top = -(1 << (8 * a.element_size() - 1))
+    if vkind == KEY_FLOAT:  # negative floats: the bits below the sign flipped, then signed order is the total order
+        ka, kb = a ^ ((a >> (8 * a.element_size() - 1)) & ~top), b ^ ((b >> (8 * b.element_size() - 1)) & ~top)
+    elif vkind == KEY_SIGNED:
+        ka, kb = a, b
+    else:
+        ka, kb = a ^ top, b ^ top
+    return torch.where((ka < kb) == (op == "min"), a, b)
+
+
+def _bin_reduce_by_sort(flat, n, edges, m, side, descending, values, vt, op, out, accumulate, counts, key_kind, ctx):
+    """radix_bin_reduce past bin_reduce_caps: the bin of every row (radix_searchsorted, or the id itself with the outside
+    ones set to m), radix_reduce_by_key on the bins, the first `num` group results copied into an identity-filled array
+    through a spare slot, the counts by radix_histogram / radix_bincount.  No host read."""
+    import torch
+    vb, vkind = vt
+    small = m < (1 << 31) - 2
+    if edges is not None:
+        bins = radix_searchsorted(edges, flat, side=side, descending=descending, index_dtype=torch.int32 if small else torch.int64, ctx=ctx,
+                                  key_kind=key_kind)
+        if counts is not None:
+            radix_histogram(flat, edges, side=side, descending=descending, out=counts, accumulate=accumulate, ctx=ctx, key_kind=key_kind)
+    else:
+        wide = flat.to(torch.int64) if flat.dtype != torch.uint64 else flat.view(torch.int64)  # (uint64 ids of 2^63 or more: negative, outside)
+        bins = torch.where((wide < 0) | (wide >= m), m, wide).to(torch.int32 if small else torch.int64)
+        if counts is not None:
+            radix_bincount(flat, m, out=counts, accumulate=accumulate, ctx=ctx)
+    int_dtype = torch.int32 if vb == 4 else torch.int64
+    full = torch.full((m + 2,), _bin_reduce_identity(vb, vkind, op), dtype=int_dtype, device=flat.device)
+    if n:
+        red = radix_reduce_by_key(bins, values.reshape(-1), op=op, ctx=ctx)
+        slot = torch.where(torch.arange(n, device=flat.device) < red.num, red.keys.to(torch.int64), m + 1)  # (the groups behind num: the spare slot)
+        full.scatter_(0, slot, _bin_reduce_bits(red.values))
+    res = full[:m + 1]
+    if op == "sum" and vkind == KEY_FLOAT:
+        res = (res.view(values.dtype) + 0.0).view(int_dtype)  # a sum starts from +0.0
+    bits = _bin_reduce_bits(out)
+    bits.copy_(_bin_reduce_join(bits, res, vkind, op, values.dtype) if accumulate else res)
+
+
+def radix_bin_reduce(keys, values, edges=None, num_bins=None, op: str = "sum", side: str = "right", descending: bool = False, num=None,
+                     out=None, accumulate: bool = False, return_counts: bool = False, count_dtype=None, ctx: Optional[Context] = None,
+                     key_kind: Optional[int] = None):
+    """A value column combined per bin, nothing sorted (rsx_bin_reduce_device): `numpy.histogram(keys, weights=values)`,
+    `torch.bincount(ids, weights=values)`, `zeros.index_add_(0, ids, values)`, `scatter_reduce` over a few hundred labels
+    -- the sum ("sum"), minimum ("min") or maximum ("max") of values[i] over the rows whose key falls into bin b, for
+    b = 0 .. m, in one read of the keys and the values.  Returns a tensor of m + 1 values of values.dtype, or
+    (values, counts) with return_counts=True, counts being what radix_histogram / radix_bincount give.
+
+    Exactly one of `edges` and `num_bins` is given, under the rules of radix_partition: edges= m cut points as in
+    radix_histogram (side=, descending=), num_bins= m for integer keys that are bin ids themselves, the last bin m holding
+    the rows outside 0 .. m - 1.
+    keys: a contiguous GPU tensor of any shape of a dtype radix_sort knows ((..., 16) uint8 128-bit keys with key_kind=, edge
+       modes only); it is not modified.
+    values: a contiguous tensor with one entry per key, of dtype int32, int64, float32 or float64 (uint32 / uint64 where
+       torch has them); anything else raises TypeError.  Integer sums wrap; float minima and maxima follow the total order
+       on bit patterns (-0.0 below +0.0, +NaN the largest) and return one of the bin's values bit for bit; a float sum is
+       IEEE addition in values.dtype, associated in an order fixed by the input's contents and size and the device's grid
+       alone -- there are no atomics, so the same input gives the same bits on every call.
+    An empty bin holds the operator's identity: 0 or +0.0 for "sum"; the largest value of the order for "min" (the integer
+       maximum; for floats the +NaN of all ones below the sign); the smallest for "max" (the integer minimum; the float of
+       all ones).  Divide by the counts for a mean.
+    num: a one-element int64 device tensor: only the first min(n, num) rows count.
+    out: a contiguous tensor of m + 1 values of values.dtype to write; accumulate=True combines onto it instead (and adds
+       to the counts of a (values, counts) pair given as out=).
+    More edges than bin_reduce_caps(key_bytes, value_bytes)[0], or a num_bins above [1], take the sorted route through
+    this library's own calls (radix_searchsorted, radix_reduce_by_key): the same result for integers, minima and maxima,
+    another association for float sums; with num= they raise ValueError instead.  The host reads nothing.
+    Enqueued on the current stream, not synchronised."""
+    import torch
+    if (edges is None) == (num_bins is None):
+        raise ValueError("exactly one of edges= and num_bins= must be given")
+    if not isinstance(keys, torch.Tensor) or not isinstance(values, torch.Tensor):
+        raise TypeError("keys and values must be torch tensors on a GPU")
+    if op not in _REDUCE_OPS:
+        raise ValueError(f"op must be 'sum', 'min' or 'max', not {op!r}")
+    vt = _reduce_value_types().get(values.dtype)
+    if vt is None:
+        raise TypeError(f"values must be int32, int64, float32, float64, uint32 or uint64, not {values.dtype}")
+    if not keys.is_contiguous():
+        raise ValueError("keys must be contiguous")
+    if edges is not None:
+        if not isinstance(edges, torch.Tensor):
+            raise TypeError("edges must be a torch tensor")
+        if edges.dtype != keys.dtype:
+            raise TypeError(f"edges must have the dtype of keys ({keys.dtype}), not {edges.dtype}")
+        kb, kind, m = _pairs_keys(edges, key_kind)
+        if side not in ("left", "right"):
+            raise ValueError(f'side must be "left" or "right", not {side!r}')
+        if edges.device != keys.device:
+            raise ValueError("keys and edges must live on the same device")
+        mode = _lib.BIN_UPPER if side == "right" else _lib.BIN_LOWER
+    else:
+        d = _torch_digits(keys, None)
+        if d.key_kind == KEY_FLOAT or d.key_bytes != d.elem_bytes or key_kind is not None:
+            raise TypeError(f"num_bins= takes integer keys, not {keys.dtype}")
+        if descending:
+            raise ValueError("num_bins= takes no order: descending must be False")
+        kb, kind = d.key_bytes, d.key_kind
+        m = operator.index(num_bins)
+        if m < 0 or m >= (1 << 32) - 2:
+            raise ValueError(f"num_bins must be in 0 .. 2^32 - 3, not {m}")
+        mode = _lib.BIN_INDEX
+    if kb == 16:
+        if keys.dim() < 1 or keys.shape[-1] != 16:
+            raise ValueError("128-bit keys must have shape (..., 16)")
+        n = keys.numel() // 16
+    else:
+        n = keys.numel()
+    if values.numel() != n:
+        raise ValueError(f"values must have one entry per key ({n}), not {values.numel()}")
+    if not values.is_contiguous():
+        raise ValueError("values must be contiguous")
+    if values.device != keys.device:
+        raise ValueError("keys and values must live on the same device")
+    if n >= 1 << 32:
+        raise ValueError("radix_bin_reduce takes fewer than 2^32 rows")
+    out_counts = None
+    if out is not None and isinstance(out, (tuple, list)):
+        if len(out) != 2:
+            raise TypeError("out must be a tensor of values or a (values, counts) pair")
+        out, out_counts = out
+    if out_counts is not None and not return_counts:
+        raise ValueError("out=(values, counts) needs return_counts=True")
+    if accumulate and (out is None or (return_counts and out_counts is None)):
+        raise ValueError("accumulate=True combines onto out=, which must be given (with return_counts=True: a (values, counts) pair)")
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.dtype != values.dtype:
+            raise TypeError(f"out must be a tensor of the dtype of values ({values.dtype})")
+        if tuple(out.shape) != (m + 1,) or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous tensor of shape ({m + 1},)")
+        if out.device != keys.device:
+            raise ValueError("keys and out must live on the same device")
+    count_dtype = _bin_args(keys, m + 1, num, out_counts, accumulate and out_counts is not None, count_dtype)
+    max_edges, max_index_bins, _tile, _share = bin_reduce_caps(kb, vt[0])
+    sorted_route = m > (max_edges if edges is not None else max_index_bins)
+    if sorted_route and num is not None:
+        raise ValueError(f"num= needs at most {max_edges} edges or {max_index_bins} bins for these widths (bin_reduce_caps), not {m}")
+    _pairs_device(keys, None, "")
+    if out is None:
+        out = torch.empty(m + 1, dtype=values.dtype, device=keys.device)
+    if return_counts and out_counts is None:
+        out_counts = torch.empty(m + 1, dtype=count_dtype, device=keys.device)
+    if sorted_route:
+        flat = keys.reshape(-1, 16) if kb == 16 else keys.reshape(-1)
+        _bin_reduce_by_sort(flat, n, edges, m, side, descending, values, vt, op, out, accumulate, out_counts, key_kind, ctx)
+    else:
+        with _on_device(keys, ctx) as (c, stream):
+            c.bin_reduce_device(keys.data_ptr() if n else 0, values.data_ptr() if n else 0, n, kb, kind,
+                                edges.data_ptr() if edges is not None and m else 0, m, mode, vt[0], vt[1], _REDUCE_OPS[op], out.data_ptr(),
+                                out_counts.data_ptr() if out_counts is not None else 0,
+                                out_counts.element_size() if out_counts is not None else 8, descending,
+                                num.data_ptr() if num is not None else 0, _lib.BIN_ACCUMULATE if accumulate else 0, stream)
+    return (out, out_counts) if return_counts else out
 
 
 def partition_caps(key_bytes: int):

@@ -9,6 +9,7 @@
 #include "rsx_select_kernels.hpp"
 #include "rsx_bin_kernels.hpp"
 #include "rsx_msplit_kernels.hpp"
+#include "rsx_binred_kernels.hpp"
 
 #include <cmath>
 
@@ -1079,6 +1080,7 @@ int rsx_ctx_get_info(rsx_ctx* ctx, int what, uint64_t* out) try {
                 case PATH_BIN:      // bits 0-7 the kernels launched; the path takes bit 28, a bin count has no route
                 case PATH_COMPACT:  // the same: bits 0-7 the kernels launched, the path in bits 24-28
                 case PATH_MSPLIT:   // the same
+                case PATH_BINRED:   // the same
                     *out = (uint64_t)(ctx->last_sort_passes & 0xFFu) | (uint64_t)ctx->last_path << 24;
                     return RSX_OK;
                 default: break;
@@ -2808,6 +2810,194 @@ int rsx_reduce_caps(uint32_t key_bytes, uint32_t value_bytes, uint32_t* tile, ui
     if (!tile || !scan_span || !key_widths_ok(key_bytes, RSX_KEY_UNSIGNED) || !reduce_value_ok(value_bytes, RSX_KEY_UNSIGNED)) return RSX_ERR_ARG;
     *tile = reduce_tile_elems(key_bytes, value_bytes);
     *scan_span = reduce_scan_span();
+    return RSX_OK;
+}
+
+// ---- a value column combined per bin (rsx_binred_kernels.hpp, include/rsx.h) ----
+namespace {
+// The workspace of one rsx_bin_reduce_device call: the matrix of partial values and the matrix of partial counts, one
+// column per workgroup.
+struct BinredPlan {
+    Carve ws;
+    uint32_t groups;   // workgroups of the first launch (0: no rows)
+    size_t part_off;   // part [(m + 1) * groups] values
+    size_t cnt_off;    // cnt  [(m + 1) * groups] u32
+};
+BinredPlan binred_plan(const rsx_ctx* ctx, size_t n, uint32_t m, uint32_t vb) {
+    BinredPlan P{};
+    const uint64_t shares = ((uint64_t)n + SELECT_SHARE - 1) / SELECT_SHARE;
+    P.groups = (uint32_t)std::min<uint64_t>(shares, (uint64_t)ctx->num_cu * 2);
+    P.part_off = P.ws.take((size_t)(m + 1) * std::max(P.groups, 1u) * vb);
+    P.cnt_off = P.ws.take((size_t)(m + 1) * std::max(P.groups, 1u) * sizeof(uint32_t));
+    return P;
+}
+uint32_t binred_cap(uint32_t mode, uint32_t kb, uint32_t vb) { return mode == RSX_BIN_INDEX ? binred_max_index(vb) : binred_max_edges(kb, vb); }
+struct BinredCall {
+    const void* keys;
+    const void* values;
+    uint64_t n;
+    const uint64_t* num;
+    const void* edges;
+    uint32_t m, mode, kind, desc, op, groups, accumulate, cb;
+    uint64_t flip;     // the sign bit of a signed integer value under MIN and MAX, else 0 (rsx_binred_kernels.hpp)
+    void* part;
+    uint32_t* cnt;
+    void* out_values;
+    void* out_counts;
+};
+extern "C++" template <int KB, int VB, bool FLT>
+int binred_launch(rsx_ctx* ctx, const BinredCall& c, hipStream_t st) {
+    uint32_t* cnt = c.out_counts ? c.cnt : nullptr;
+    if (c.groups != 0) {
+        const auto part = [&](auto idx) {
+            hipLaunchKernelGGL((rsx_binred_part_kernel<KB, VB, FLT, decltype(idx)::value>), dim3(c.groups), dim3(BINRED_WG), 0, st, c.keys, c.values, c.n,
+                               c.num, c.edges, c.m, c.mode == RSX_BIN_UPPER ? 1u : 0u, c.kind, c.desc, c.op, c.flip, c.part, cnt);
+        };
+        if (c.mode == RSX_BIN_INDEX) {
+            if constexpr (KB <= 8) part(std::true_type{});
+            else return fail(ctx, RSX_ERR_INTERNAL, "no index form for this key width");
+        } else {
+            part(std::false_type{});
+        }
+        RSX_HIP(hipGetLastError());
+    }
+    const uint32_t bins = c.m + 1;
+    hipLaunchKernelGGL((rsx_binred_final_kernel<VB, FLT>), dim3((bins + BINRED_WAVES - 1) / BINRED_WAVES), dim3(BINRED_WG), 0, st, c.part, c.cnt, bins,
+                       c.groups, c.n, c.num, c.op, c.flip, c.accumulate, c.out_values, c.out_counts, c.cb);
+    RSX_HIP(hipGetLastError());
+    return RSX_OK;
+}
+extern "C++" template <int KB>
+int binred_value(rsx_ctx* ctx, const BinredCall& c, uint32_t vb, uint32_t vkind, hipStream_t st) {
+    const auto kind = [&](auto w) -> int {
+        constexpr int VB = decltype(w)::value;
+        return vkind == RSX_KEY_FLOAT ? binred_launch<KB, VB, true>(ctx, c, st) : binred_launch<KB, VB, false>(ctx, c, st);
+    };
+    return vb == 8 ? kind(Width<8>{}) : kind(Width<4>{});
+}
+// Every check of rsx_bin_reduce_device that needs neither the context nor the device: 0, or the code with *what set.
+int binred_check(const void* d_keys, const void* d_values, size_t n, const uint64_t* d_num, uint32_t key_bytes, uint32_t key_kind, const void* d_edges,
+                 uint32_t m, uint32_t mode, int order, uint32_t value_bytes, uint32_t value_kind, int op, const void* d_out_values,
+                 const void* d_out_counts, uint32_t count_bytes, uint32_t flags, const char** what) {
+    *what = "invalid mode";
+    if (mode != RSX_BIN_UPPER && mode != RSX_BIN_LOWER && mode != RSX_BIN_INDEX) return RSX_ERR_ARG;
+    *what = "unknown flag bits";
+    if (flags & ~(uint32_t)RSX_BIN_ACCUMULATE) return RSX_ERR_ARG;
+    *what = "invalid key width or kind";
+    if (!key_widths_ok(key_bytes, key_kind)) return RSX_ERR_ARG;
+    *what = "invalid value width or kind";
+    if (!reduce_value_ok(value_bytes, value_kind)) return RSX_ERR_ARG;
+    *what = "invalid operator";
+    if (op != RSX_REDUCE_SUM && op != RSX_REDUCE_MIN && op != RSX_REDUCE_MAX) return RSX_ERR_ARG;
+    *what = "invalid order";
+    if (order != RSX_ORDER_ASCENDING && order != RSX_ORDER_DESCENDING) return RSX_ERR_ARG;
+    *what = "the index mode takes no edges and no order";
+    if (mode == RSX_BIN_INDEX && (order != RSX_ORDER_ASCENDING || d_edges)) return RSX_ERR_ARG;
+    *what = "count_bytes must be 4 or 8";
+    if (d_out_counts && count_bytes != 4 && count_bytes != 8) return RSX_ERR_ARG;
+    *what = "d_out_values is null";
+    if (!d_out_values) return RSX_ERR_ARG;
+    *what = "null device pointer";
+    if ((n > 0 && !d_values) || (n > 0 && m > 0 && !d_keys) || (mode != RSX_BIN_INDEX && m > 0 && !d_edges)) return RSX_ERR_ARG;
+    *what = "device pointer misaligned";
+    const uint32_t ca = d_out_counts ? count_bytes : 1u;
+    if (!aligned(d_keys, key_bytes) || !aligned(d_edges, key_bytes) || !aligned(d_values, value_bytes) || !aligned(d_out_values, value_bytes) ||
+        !aligned(d_out_counts, ca) || !aligned(d_num, 8))
+        return RSX_ERR_ARG;
+    *what = "an output overlaps an input or the other output";
+    const uint64_t rows = (uint64_t)n, bins = (uint64_t)m + 1;
+    const bool edged = mode != RSX_BIN_INDEX;
+    const ByteRange in[] = {{d_keys, rows * key_bytes}, {d_values, rows * value_bytes}, {d_num, 8}, {edged ? d_edges : nullptr, (uint64_t)m * key_bytes}};
+    const ByteRange out[] = {{d_out_values, bins * value_bytes}, {d_out_counts, bins * ca}};
+    for (const ByteRange& o : out)
+        for (const ByteRange& i : in)
+            if (ranges_overlap(o.p, o.bytes, i.p, i.bytes)) return RSX_ERR_ARG;
+    if (ranges_overlap(out[0].p, out[0].bytes, out[1].p, out[1].bytes)) return RSX_ERR_ARG;
+    *what = "2^32 or more rows";  // (what is wrong with the arguments themselves comes first)
+    if (rows >= (1ull << 32)) return RSX_ERR_UNSUPPORTED;
+    *what = "the index mode takes integer keys of 1, 2, 4 or 8 bytes";
+    if (mode == RSX_BIN_INDEX && (key_bytes == 16 || key_kind == RSX_KEY_FLOAT)) return RSX_ERR_UNSUPPORTED;
+    *what = "more edges or bins than rsx_bin_reduce_caps reports";
+    if (m > binred_cap(mode, key_bytes, value_bytes)) return RSX_ERR_UNSUPPORTED;
+    *what = "";
+    return RSX_OK;
+}
+}  // namespace
+
+int rsx_bin_reduce_device(rsx_ctx* ctx, const void* d_keys, const void* d_values, size_t n, const uint64_t* d_num, uint32_t key_bytes, uint32_t key_kind,
+                          const void* d_edges, uint32_t m, uint32_t mode, int order, uint32_t value_bytes, uint32_t value_kind, int op,
+                          void* d_out_values, void* d_out_counts, uint32_t count_bytes, uint32_t flags, void* stream) try {
+    // the argument checks come first and need no context: a caller's mistake has the same answer with and without one
+    const char* what = "";
+    int rc = binred_check(d_keys, d_values, n, d_num, key_bytes, key_kind, d_edges, m, mode, order, value_bytes, value_kind, op, d_out_values,
+                          d_out_counts, count_bytes, flags, &what);
+    if (rc) return fail(ctx, rc, what);
+    if (!ctx) return RSX_ERR_ARG;
+    RSX_ENTER(stream);
+    const hipStream_t st = held.st;
+    rc = pending_error(ctx);
+    if (rc) return rc;
+    const bool accumulate = (flags & RSX_BIN_ACCUMULATE) != 0;
+    if (n == 0 && accumulate) {  // nothing to add: the outputs stay as they are
+        note_path(ctx, PATH_BINRED, 0);
+        return RSX_OK;
+    }
+    const BinredPlan P = binred_plan(ctx, n, m, value_bytes);
+    rc = ensure_aux(ctx, st);
+    if (rc) return rc;
+    rc = ensure_any(ctx, P.ws.bytes, st);
+    if (rc) return rc;
+    Enqueue enq(ctx, st);  // the workspace arrays belong to this call from the first launch on
+    char* w = reinterpret_cast<char*>(ctx->any_buf);
+    BinredCall c{};
+    c.keys = d_keys;
+    c.values = d_values;
+    c.n = n;
+    c.num = d_num;
+    c.edges = d_edges;
+    c.m = m;
+    c.mode = mode;
+    c.kind = key_kind;
+    c.desc = order == RSX_ORDER_DESCENDING ? 1u : 0u;
+    c.op = (uint32_t)op;
+    c.flip = value_kind == RSX_KEY_SIGNED && op != RSX_REDUCE_SUM ? 1ull << (8 * value_bytes - 1) : 0ull;
+    c.groups = P.groups;
+    c.accumulate = accumulate ? 1u : 0u;
+    c.cb = count_bytes;
+    c.part = w + P.part_off;
+    c.cnt = reinterpret_cast<uint32_t*>(w + P.cnt_off);
+    c.out_values = d_out_values;
+    c.out_counts = d_out_counts;
+    {
+        LaunchTimer lt(ctx, RSX_PROF_OTHER, st);
+        for_key_width(key_bytes, [&](auto kb) { rc = binred_value<decltype(kb)::value>(ctx, c, value_bytes, value_kind, st); });
+        if (rc) return rc;
+    }
+    note_path(ctx, PATH_BINRED, P.groups != 0 ? 2u : 1u);
+    return RSX_OK;
+} catch (...) {
+    return RSX_ERR_HIP;
+}
+
+int rsx_ctx_reserve_bin_reduce(rsx_ctx* ctx, size_t n, uint32_t m, uint32_t key_bytes, uint32_t value_bytes) try {
+    if (!ctx) return RSX_ERR_ARG;
+    if (!key_widths_ok(key_bytes, RSX_KEY_UNSIGNED) || !reduce_value_ok(value_bytes, RSX_KEY_UNSIGNED))
+        return fail(ctx, RSX_ERR_ARG, "invalid key or value width");
+    if ((uint64_t)n >= (1ull << 32)) return fail(ctx, RSX_ERR_UNSUPPORTED, "2^32 or more rows");
+    // (the index mode's cap is the larger one: a reserve does not know the mode)
+    if (m > binred_max_index(value_bytes)) return fail(ctx, RSX_ERR_UNSUPPORTED, "more edges or bins than rsx_bin_reduce_caps reports");
+    return reserve_any_entry(ctx, binred_plan(ctx, n, m, value_bytes).ws.bytes);
+} catch (...) {
+    return RSX_ERR_NOMEM;
+}
+
+int rsx_bin_reduce_caps(uint32_t key_bytes, uint32_t value_bytes, uint32_t* max_edges, uint32_t* max_index_bins, uint32_t* tile, uint32_t* share) {
+    if (!max_edges || !max_index_bins || !tile || !share || !key_widths_ok(key_bytes, RSX_KEY_UNSIGNED) || !reduce_value_ok(value_bytes, RSX_KEY_UNSIGNED))
+        return RSX_ERR_ARG;
+    *max_edges = binred_max_edges(key_bytes, value_bytes);
+    *max_index_bins = binred_max_index(value_bytes);
+    *tile = binred_tile((int)key_bytes, (int)value_bytes);
+    *share = SELECT_SHARE;
     return RSX_OK;
 }
 

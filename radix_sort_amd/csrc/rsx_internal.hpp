@@ -70,7 +70,7 @@ constexpr int HOST_RING = 4;
 // every array carved out of a workspace starts on a 256-byte boundary
 constexpr size_t round256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
-// rsx_ctx::last_path, what the last call ran.  The values are frozen: RSX_INFO_LAST_PASSES reports them in bits 24..27 (PATH_BIN, PATH_COMPACT, PATH_MSPLIT: 24..28).
+// rsx_ctx::last_path, what the last call ran.  The values are frozen: RSX_INFO_LAST_PASSES reports them in bits 24..27 (PATH_BIN, PATH_COMPACT, PATH_MSPLIT, PATH_BINRED: 24..28).
 enum : uint32_t {
     PATH_LSD = 0,        // general passes
     PATH_SMALL = 1,      // one-launch sort
@@ -91,6 +91,7 @@ enum : uint32_t {
     PATH_BIN = 16,       // keys per bin: it takes bit 28 with it, where the sorts report their route (it has none)
     PATH_COMPACT = 17,   // rows that pass a predicate: bits 24 and 28, as PATH_BIN
     PATH_MSPLIT = 18,    // rows regrouped by bin: bits 25 and 28
+    PATH_BINRED = 19,    // a value column combined per bin: bits 24, 25 and 28
 };
 
 // option bits (rsx_ctx_set_option): alternative kernel paths, all bit-exact

@@ -27,6 +27,7 @@
 //     rsx::bin_count(const K* d_keys, size_t n, const K* d_edges, uint32_t m, uint32_t mode, C* d_counts, bool descending, bool accumulate, const uint64_t* d_num, hipStream_t)   // RSX_BIN_*: histogram, bincount
 //     rsx::compact(const K* d_keys, size_t n, const uint8_t* d_flags, const K* d_lo, const K* d_hi, const V* d_values, K* d_out_keys, V* d_out_values, I* d_out_index, uint64_t* d_out_num, uint32_t flags, bool descending, const uint64_t* d_num, hipStream_t)   // RSX_COMPACT_*: select-if, partition, nonzero
 //     rsx::multisplit(const K* d_keys, size_t n, const K* d_edges, uint32_t m, uint32_t mode, const V* d_values, K* d_out_keys, V* d_out_values, I* d_out_index, uint64_t* d_out_offsets, bool descending, const uint64_t* d_num, hipStream_t)   // RSX_BIN_*: stable multi-way partition, CSR offsets
+//     rsx::bin_reduce(const K* d_keys, const V* d_values, size_t n, const K* d_edges, uint32_t m, uint32_t mode, int op, V* d_out_values, C* d_out_counts, bool descending, bool accumulate, const uint64_t* d_num, hipStream_t)   // RSX_BIN_* x RSX_REDUCE_*: weighted histogram, bincount(weights=)
 //     rsx::lexsort({rsx::key_column(d_a), rsx::key_column(d_b, true)}, I* d_index, size_t n, hipStream_t)   // several key columns
 //     rsx::sort_columns({rsx::key_column(d_a), rsx::key_column(d_b, true)}, V* d_values, size_t n, hipStream_t)
 // Errors: the reference panics (mod.rs:68,106); here std::runtime_error is thrown.
@@ -524,6 +525,41 @@ void multisplit(const K* d_keys, size_t n, const K* d_edges, uint32_t m, uint32_
                                     descending ? RSX_ORDER_DESCENDING : RSX_ORDER_ASCENDING, d_out_values ? d_values : nullptr,
                                     d_out_values ? (uint32_t)sizeof(V) : 0u, d_out_keys, d_out_values, d_out_index, (uint32_t)sizeof(I), d_out_offsets, stream),
               "rsx_multisplit_device");
+}
+
+// A value column combined per bin, nothing sorted (rsx_bin_reduce_device): d_out_values[b], b = 0 .. m, the sum
+// (RSX_REDUCE_SUM), minimum or maximum of the values of the first n -- or min(n, *d_num) -- rows whose key's bin is b; mode
+// and the m edges as in bin_count (RSX_BIN_INDEX: d_edges nullptr, the last bin holds the ids outside 0 .. m - 1); V and the
+// operators as in reduce_by_key.  An empty bin holds the operator's identity (0 / +0.0; the highest / lowest value of the
+// order).  d_out_counts (may be nullptr) receives the bins' sizes, what bin_count writes.  accumulate: combined onto /
+// added to what the outputs hold.  No atomics on floats: the same input gives the same bits on every call.  At most
+// bin_reduce_caps<K, V>().max_edges edges (index mode: max_index_bins).  Stream-ordered, never synchronised;
+// Context::reserve is not enough for a capture: rsx_ctx_reserve_bin_reduce.
+struct BinReduceCaps {
+    uint32_t max_edges, max_index_bins, tile, share;
+};
+template <typename K, typename V>
+BinReduceCaps bin_reduce_caps() {
+    BinReduceCaps c{};
+    const rsx_layout L = RadixDigits<K>::layout();
+    if (rsx_bin_reduce_caps(L.key_bytes, (uint32_t)sizeof(V), &c.max_edges, &c.max_index_bins, &c.tile, &c.share) != RSX_OK)
+        throw std::invalid_argument("bin_reduce_caps: no per-bin reduction for these key and value widths");
+    return c;
+}
+template <typename K, typename V, typename C = uint64_t>
+void bin_reduce(const K* d_keys, const V* d_values, size_t n, const K* d_edges, uint32_t m, uint32_t mode, int op, V* d_out_values,
+                C* d_out_counts = nullptr, bool descending = false, bool accumulate = false, const uint64_t* d_num = nullptr,
+                void* stream = nullptr, Context& ctx = default_context()) {
+    static_assert(std::is_arithmetic<V>::value && !std::is_same<V, bool>::value && (sizeof(V) == 4 || sizeof(V) == 8),
+                  "values are 4- or 8-byte integers or floats");
+    static_assert(std::is_integral<C>::value && (sizeof(C) == 4 || sizeof(C) == 8), "counts are 4- or 8-byte integers");
+    const rsx_layout L = RadixDigits<K>::layout();
+    if (L.key_offset != 0 || L.key_bytes != L.elem_bytes) throw std::invalid_argument("bin_reduce: the key type must be its own key");
+    const uint32_t vkind = std::is_floating_point<V>::value ? RSX_KEY_FLOAT : std::is_signed<V>::value ? RSX_KEY_SIGNED : RSX_KEY_UNSIGNED;
+    ctx.check(rsx_bin_reduce_device(ctx.get(), d_keys, d_values, n, d_num, L.key_bytes, L.key_kind, d_edges, m, mode,
+                                    descending ? RSX_ORDER_DESCENDING : RSX_ORDER_ASCENDING, (uint32_t)sizeof(V), vkind, op, d_out_values,
+                                    d_out_counts, (uint32_t)sizeof(C), accumulate ? RSX_BIN_ACCUMULATE : 0u, stream),
+              "rsx_bin_reduce_device");
 }
 
 // Several key columns (rsx_lexsort_device, rsx_sort_columns_device): rows sorted by (column 0, column 1, ...), column 0

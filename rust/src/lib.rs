@@ -141,6 +141,16 @@ extern "C" {
                                  d_out_offsets: *mut u64, stream: *mut c_void) -> c_int;
     pub fn rsx_ctx_reserve_multisplit(ctx: *mut RsxCtx, n: usize, m: u32, key_bytes: u32, value_bytes: u32, index_bytes: u32) -> c_int;
     pub fn rsx_multisplit_caps(key_bytes: u32, max_edges: *mut u32, max_index_bins: *mut u32, tile: *mut u32, share: *mut u32) -> c_int;
+    // a value column combined per bin, nothing sorted (include/rsx.h, "a value column combined per bin"): mode and d_edges
+    // as in rsx_bin_count_device; op is RSX_REDUCE_SUM (0), _MIN (1), _MAX (2); d_out_values holds m + 1 values,
+    // d_out_counts (may be null) m + 1 counts of count_bytes; flags RSX_BIN_ACCUMULATE (1); d_num (may be null) bounds n
+    pub fn rsx_bin_reduce_device(ctx: *mut RsxCtx, d_keys: *const c_void, d_values: *const c_void, n: usize, d_num: *const u64,
+                                 key_bytes: u32, key_kind: u32, d_edges: *const c_void, m: u32, mode: u32, order: c_int,
+                                 value_bytes: u32, value_kind: u32, op: c_int, d_out_values: *mut c_void,
+                                 d_out_counts: *mut c_void, count_bytes: u32, flags: u32, stream: *mut c_void) -> c_int;
+    pub fn rsx_ctx_reserve_bin_reduce(ctx: *mut RsxCtx, n: usize, m: u32, key_bytes: u32, value_bytes: u32) -> c_int;
+    pub fn rsx_bin_reduce_caps(key_bytes: u32, value_bytes: u32, max_edges: *mut u32, max_index_bins: *mut u32, tile: *mut u32,
+                               share: *mut u32) -> c_int;
     // scan by key (include/rsx.h, "scan by key"): op is RSX_REDUCE_SUM (0), _MIN (1), _MAX (2); flags RSX_SCAN_EXCLUSIVE (1)
     // and RSX_SCAN_RUNS (2); one result per row at the row's position; d_values null: every value is 1 (ranks);
     // `first` is what the first row of every group receives in an exclusive scan; d_out_num may be null
